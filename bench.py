@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- alignments/s of the fixed-shape Smith-Waterman scorer on N MI355X GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs P] [--lanes L]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs P] [--lanes L] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch of synthetic pairs that are already resident in HBM when the timed
 region starts.
@@ -56,6 +56,8 @@ VALU_PEAK_TOPS = 256 * 4 * 32 * 2.4e9 / 1e12   # 78.6 T full-rate 32-bit lane-op
 HBM_PEAK_GBS = 8000.0
 REFERENCE_PUBLISHED_ALIGN_PER_S = 1e6 / 4.4    # README.md:4 of the reference: simd4 ~4.4 s / 1M on one EPYC 7501 core
 CONFIG3_PAIRS_PER_GPU = 1 << 26                # BASELINE.json configs[3]: 512M pairs over 8 GPUs
+DUMP_BYTES = 60 * 1000 * 1000                  # --dump-outputs writes at most this much data: under 64 MB with the headers
+DUMP_SAMPLE_SEED = 0                           # rows kept of an output too large to write whole (independent of --seed)
 
 
 def issue_bound(kernel_regex, trips, waves, kernel_ms, marker=None, conditional_share=1.0, pick="innermost", second=None):
@@ -142,6 +144,28 @@ def stamped_profile(kernel_code_sha256):
     return tr, tr.get("source")
 
 
+def dump_outputs(np, torch, outdir, outputs):
+    """--dump-outputs DIR: the arrays the timed path returned in its last step, as DIR/<name>.npy in float64 (every output
+    is an integer array, exact in float64), at most DUMP_BYTES in all.  `outputs` holds (name, tensor) or (name, tensor,
+    lengths): row k of such a tensor holds lengths[k] entries, and the rest of the row, which is no output, is written as -1.
+    An output larger than its share of the bytes left keeps a sample of its rows (seeded, sorted: the same in every run)."""
+    os.makedirs(outdir, exist_ok=True)
+    left = DUMP_BYTES
+    for k, (name, t, *lengths) in enumerate(outputs):
+        n = t.shape[0]
+        keep = left // (len(outputs) - k) // (8 * (t.numel() // n))
+        if keep < n:
+            rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, keep, replace=False))
+            rows = torch.from_numpy(rows).to(t.device)
+            t = t[rows]
+            lengths = [ln[rows] for ln in lengths]
+        a = t.cpu().numpy().astype(np.float64)
+        if lengths:
+            a[np.arange(a.shape[1])[None, :] >= lengths[0].cpu().numpy()[:, None]] = -1
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        left -= a.nbytes
+
+
 def effective_cores():
     """Cores the container may actually use: the cgroup CPU quota (cpu.max), else the affinity mask."""
     try:
@@ -166,7 +190,7 @@ def effective_cores():
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 200; 10 in the semiglobal mode)")
     ap.add_argument("--warmup", type=int, default=30, help="untimed steps (the clock takes ~10 launches to settle after idle)")
     ap.add_argument("--len", type=int, default=1024, help="sequence length of the banded-affine mode")
     ap.add_argument("--gap-open", type=int, default=5)
@@ -190,7 +214,14 @@ def parse():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL over xGMI; "
                     "gloo only to rehearse the multi-rank path on a box with fewer GPUs than ranks)")
     ap.add_argument("--cpu-sample", type=int, default=0, help="pairs in the CPU baseline sample (0 = auto, ~10-15 s)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                    "(float64, under 64 MB in all: a fixed sample of the rows of a larger output)")
+    args = ap.parse_args()
+    if args.steps is None:
+        args.steps = 10 if args.mode == "semiglobal" else 200
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def respawn_under_torchrun(args):
@@ -307,7 +338,9 @@ def bench_banded(args, swmi, np, torch, local_rank, steps=None, warmup=None):
     d2 = torch.empty(P * length, dtype=torch.uint8, device=dev)
     swmi.generate_pairs_device(d1.data_ptr(), d2.data_ptr(), npairs128, args.seed, 0, stream.cuda_stream)
     # make seq2 a mutated copy of seq1 (~8 % substitutions) so that alignments are long: random-vs-random would idle in H = 0
-    mut = torch.rand(P * length, device=dev) < 0.08
+    # (from --seed: torch's default generator starts from a different seed in every process)
+    g = torch.Generator(device=dev); g.manual_seed(args.seed)
+    mut = torch.rand(P * length, device=dev, generator=g) < 0.08
     d2 = torch.where(mut, d2, d1).contiguous()
     scores = torch.empty(P, dtype=torch.int32, device=dev)
     sm = swmi.match_matrix(2, -3)
@@ -325,6 +358,8 @@ def bench_banded(args, swmi, np, torch, local_rank, steps=None, warmup=None):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     kernel_ms = sum(a.elapsed_time(b) for a, b in ev) / steps
+    if args.dump_outputs and args.mode == "banded-affine":       # (not as a row of the headline)
+        dump_outputs(np, torch, args.dump_outputs, [("scores", scores)])
     band_cells = sum(min(length, i + 63) - max(1, i - 64) + 1 for i in range(1, length + 1))
     value = P * steps / elapsed
     # main loop = `length` iterations of two anti-diagonal steps; one wavefront per alignment (sw_banded_affine_kernel, int32
@@ -424,7 +459,7 @@ def bench_semiglobal(args, swmi, np, torch, local_rank, steps=None, warmup=None)
     def launch():
         swmi.semiglobal_xdrop_device(d1.data_ptr(), d2.data_ptr(), P, scores.data_ptr(), tb.data_ptr(), cap, lengths.data_ptr(),
                                      stream.cuda_stream)
-    steps = min(args.steps, 10) if steps is None else steps
+    steps = args.steps if steps is None else steps
     warm = min(args.warmup, 2) if warmup is None else warmup
     for _ in range(warm):
         launch()
@@ -434,6 +469,8 @@ def bench_semiglobal(args, swmi, np, torch, local_rank, steps=None, warmup=None)
         launch()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and args.mode == "semiglobal":          # (not as a row of the headline)
+        dump_outputs(np, torch, args.dump_outputs, [("scores", scores), ("traceback_lengths", lengths), ("tracebacks", tb, lengths)])
     value = P * steps / elapsed
     line = {"metric": "alignments/sec, semi-global adaptive-band X-drop with traceback (SURVEY 8f N4)", "value": round(value, 1),
             "unit": "alignments/s", "n_gpus": 1, "steps": steps, "warmup": warm, "ms_per_step": round(elapsed * 1e3 / steps, 3),
@@ -711,6 +748,8 @@ def single_gpu(args, swmi, np, torch, local_rank):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     kernel_ms = sum(a.elapsed_time(b) for a, b in events) / args.steps     # HIP events on the launch stream
+    if args.dump_outputs:                       # before the rows below reuse `scores`
+        dump_outputs(np, torch, args.dump_outputs, [("scores", scores)])
     value = P * args.steps / elapsed
     roof = sw128_roofline(swmi, P, args.lanes, flags, args.mode, kernel_ms, args.match, args.mismatch, args.gap)
     prof, prof_src = stamped_profile(roof.get("kernel_code_sha256"))
@@ -991,6 +1030,8 @@ def multi_gpu(args, swmi, np, torch, dist, rank, world, local_rank):
     ranks_agree = int(cmin.item()) == int(cmax.item())
     line = None
     if rank == 0:
+        if args.dump_outputs:                   # the gathered scores of the headline leg's last step
+            dump_outputs(np, torch, args.dump_outputs, [("scores", full)])
         # a sample of EVERY shard of the gathered vector against the CPU checker: head, middle and tail of each shard
         per = 1024
         checked = mism = 0
