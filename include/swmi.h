@@ -298,6 +298,48 @@ SWMI_API int swmi_semiglobal_kernels_for_batch(size_t n, char *sweep, size_t swe
 SWMI_API int swmi_semiglobal_time_device(const void *d_seq1s, const void *d_seq2s, size_t n, void *d_scores,
                                          void *d_tracebacks, size_t cap, void *d_lengths, void *stream, float phase_ms[2]);
 
+/* ---- local alignment with end cell, start cell and traceback ---------------------------
+ * Replaces SmithWaterman_111_long (source.cpp:1526-1576: a seq1 of any length against a 128-mer -> (score, path of (i, j)))
+ * for a batch of n alignments, with any int8 matrix and gap in [0, 127] (the reference's own function is score_matrix =
+ * match 1 / mismatch -1, gap 1).  seq1 k = the len1 bytes at seq1s + len1 * k (1 <= len1 <= 16384, one length per call),
+ * seq2 k = the 128 bytes at seq2s + 128 * k; bases are taken modulo 4 as in swmi_score_batch.
+ *     H(i,j) = max(0, H(i-1,j-1) + sm[seq1[i-1]*4 + seq2[j-1]], H(i-1,j) - gap, H(i,j-1) - gap),  i = 1..len1, j = 1..128
+ * scores[k] = max H.  ends[k] = (end_i, end_j, start_i, start_j): the end cell is the first cell in row-major order that
+ * holds the score ((0, 0) when it is 0, source.cpp:1545); the walk from it takes a diagonal step when H(i,j) = H(i-1,j-1) + s,
+ * else an up step (i - 1) when H(i,j) = H(i-1,j) - gap, else a left step (j - 1), until it reaches a cell holding 0, the start
+ * cell (source.cpp:1553-1569).  moves + k * SWMI_LOCAL_MOVE_WORDS(len1) receives the steps in WALKING order (step 0 leaves the
+ * end cell), step t at bits 2 (t % 32) of word t / 32: 3 = diagonal, 2 = up, 1 = left (the encoding of
+ * swmi_semiglobal_xdrop_moves); steps[k] = their number, so the reference's list has steps[k] + 1 positions; words past the
+ * last step are unspecified.  moves and steps both NULL: ENDS-ONLY -- no traceback is stored or walked, the score and the end
+ * cell are the same, the start cell is reported as (-1, -1).  The score is at most 127 * 128.
+ * Host buffers.  The batch runs in SLICES (swmi_local_slices_for) on two sets of device buffers, one slice's copies beside
+ * the other's kernel.  Errors: SWMI_ERR_INVALID_ARGUMENT for len1 outside [1, 16384], a NULL buffer, or only one of
+ * moves / steps; SWMI_ERR_DOMAIN for gap_penalty < 0. */
+#define SWMI_LOCAL_SEQ2_LEN 128
+#define SWMI_LOCAL_MAX_LEN 16384
+#define SWMI_LOCAL_MOVE_WORDS(len1) (((((size_t)(len1)) + 128 + 31) / 32 + 1) & ~(size_t)1)   /* 16-byte rows */
+SWMI_API int swmi_local_align(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t n, const int8_t score_matrix[16],
+                              int8_t gap_penalty, int32_t *scores, int32_t *ends, uint64_t *moves, uint32_t *steps);
+/* The slices a swmi_local_align call of n alignments cuts its batch into (traceback = 0: ends-only), in order; returns how
+ * many there are and writes the first `cap` sizes (NULL to count).  Every slice's device buffers stay within 256 MiB.
+ * Needs no device.  0 for len1 outside [1, 16384]. */
+SWMI_API size_t swmi_local_slices_for(size_t n, size_t len1, int traceback, size_t *sizes, size_t cap);
+/* Same with every buffer in device memory (16-byte aligned), asynchronous on `stream`.  The traceback codes (32 * len1
+ * bytes per alignment) go to a workspace of the library's per (GPU, stream), grown on demand up to one slice and kept until
+ * swmi_shutdown(): calls on one stream serialise by themselves, calls on different streams may be in flight together. */
+SWMI_API int swmi_local_align_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t n,
+                                     const int8_t score_matrix[16], int8_t gap_penalty, void *d_scores, void *d_ends,
+                                     void *d_moves, void *d_steps, void *stream);
+/* One alignment's moves -> the reference's list of (i, j) positions from the start cell to the end cell (steps + 1 of them;
+ * at most `cap` are written), on the host.  No device. */
+SWMI_API int swmi_local_expand_moves(const uint64_t *moves, uint32_t steps, int32_t end_i, int32_t end_j, int32_t *positions,
+                                     size_t cap);
+/* Measurement helper: `iters` swmi_local_align_device calls back to back on `stream`, bracketed by HIP events; *avg_ms = the
+ * average time of one call.  Synchronous. */
+SWMI_API int swmi_local_time_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t n,
+                                    const int8_t score_matrix[16], int8_t gap_penalty, void *d_scores, void *d_ends,
+                                    void *d_moves, void *d_steps, void *stream, int iters, float *avg_ms);
+
 /* unpack() itself (source.cpp:1580-1583) for n packed sequences, on the GPU. Host buffers. */
 SWMI_API int swmi_unpack(const uint8_t *packed, size_t n_seqs, uint8_t *unpacked);
 

@@ -8,6 +8,7 @@
 // SmithWaterman_mi355x(...) where they called SmithWaterman_simd4(...) -- or, to keep the 1M-call loop
 // shape AND get batch throughput, submits through swmi::PairQueue (same arguments per call).
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <stdexcept>
@@ -33,7 +34,60 @@ inline int SmithWaterman_mi355x(const std::array<uint8_t, 128> &seq1, const std:
 inline std::pair<int, std::vector<std::pair<int, int>>> SemiGlobal_AdaptiveBanded_XDrop_mi355x(const std::array<uint8_t, 16384> &seq1,
                                                                                               const std::array<uint8_t, 16384> &seq2);
 
+// Same arguments, same return value as SmithWaterman_111_long (source.cpp:1526-1576): (score, path of (i, j) from the start
+// cell to the end cell).  One synchronous call per alignment; SmithWaterman_local_mi355x_batch below is the throughput form.
+inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_111_long_mi355x(const std::vector<uint8_t> &seq1,
+                                                                                     const std::array<uint8_t, 128> &seq2);
+// The same local alignment with any score matrix and gap (swmi_local_align: no reference counterpart beyond (1, -1, 1)).
+inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_local_mi355x(const std::vector<uint8_t> &seq1,
+                                                                                  const std::array<uint8_t, 128> &seq2,
+                                                                                  const std::array<int8_t, 16> &score_matrix,
+                                                                                  const int8_t gap_penalty);
+
 namespace swmi {
+
+// One local alignment's moves (swmi_local_align) -> the reference's path vector (source.cpp:1571-1575).
+inline std::vector<std::pair<int, int>> expand_local_moves(const uint64_t *moves, uint32_t steps, int32_t end_i, int32_t end_j)
+{
+    static_assert(sizeof(std::pair<int, int>) == 2 * sizeof(int32_t), "std::pair<int,int> must be two packed ints");
+    std::vector<std::pair<int, int>> path(size_t(steps) + 1);
+    if (swmi_local_expand_moves(moves, steps, end_i, end_j, reinterpret_cast<int32_t *>(path.data()), path.size()) != SWMI_OK)
+        throw std::runtime_error(std::string("swmi_local_expand_moves: ") + swmi_last_error());
+    return path;
+}
+
+// Local alignment of seq1s[k] (every one of the same length) against seq2s[k]: result[k] == SmithWaterman_local_mi355x(seq1s[k],
+// seq2s[k], score_matrix, gap_penalty).  The batch goes to the GPU in pieces of at most `piece` alignments, so only one piece's
+// inputs and moves are staged at a time (not n rows of moves up front); each piece's paths are built on the host.
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SmithWaterman_local_mi355x_batch(
+    const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::array<uint8_t, 128>> &seq2s,
+    const std::array<int8_t, 16> &score_matrix, const int8_t gap_penalty, size_t piece = 65536)
+{
+    if (seq1s.size() != seq2s.size()) throw std::invalid_argument("SmithWaterman_local_mi355x_batch: seq1s and seq2s differ in length");
+    const size_t n = seq1s.size();
+    std::vector<std::pair<int, std::vector<std::pair<int, int>>>> out(n);
+    if (n == 0) return out;
+    const size_t len1 = seq1s[0].size();
+    for (const auto &s : seq1s)
+        if (s.size() != len1) throw std::invalid_argument("SmithWaterman_local_mi355x_batch: every seq1 must have the same length");
+    if (piece == 0) piece = 1;
+    const size_t mw = SWMI_LOCAL_MOVE_WORDS(len1);
+    const size_t m_max = n < piece ? n : piece;
+    std::vector<uint8_t> a(m_max * len1);
+    std::vector<int32_t> scores(m_max), ends(4 * m_max);
+    std::vector<uint64_t> moves(m_max * mw);
+    std::vector<uint32_t> steps(m_max);
+    for (size_t off = 0; off < n; off += piece) {
+        const size_t m = n - off < piece ? n - off : piece;
+        for (size_t k = 0; k < m; ++k) std::copy(seq1s[off + k].begin(), seq1s[off + k].end(), a.begin() + k * len1);
+        if (swmi_local_align(a.data(), len1, seq2s[off].data(), m, score_matrix.data(), gap_penalty, scores.data(), ends.data(),
+                             moves.data(), steps.data()) != SWMI_OK)
+            throw std::runtime_error(std::string("swmi_local_align: ") + swmi_last_error());
+        for (size_t k = 0; k < m; ++k)
+            out[off + k] = {scores[k], expand_local_moves(moves.data() + k * mw, steps[k], ends[4 * k], ends[4 * k + 1])};
+    }
+    return out;
+}
 
 // One alignment's moves (swmi_semiglobal_xdrop_moves) -> the reference's traceback vector (source.cpp:1962-1975).
 inline std::vector<std::pair<int, int>> expand_moves(const uint64_t *moves, uint32_t length)
@@ -150,4 +204,25 @@ inline std::pair<int, std::vector<std::pair<int, int>>> SemiGlobal_AdaptiveBande
     if (swmi_semiglobal_xdrop_moves(seq1.data(), seq2.data(), 1, &score, moves.data(), &length) != SWMI_OK)
         throw std::runtime_error(std::string("swmi_semiglobal_xdrop_moves: ") + swmi_last_error());
     return {score, swmi::expand_moves(moves.data(), length)};
+}
+
+inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_local_mi355x(const std::vector<uint8_t> &seq1,
+                                                                                  const std::array<uint8_t, 128> &seq2,
+                                                                                  const std::array<int8_t, 16> &score_matrix,
+                                                                                  const int8_t gap_penalty)
+{
+    int32_t score = 0, ends[4] = {0, 0, 0, 0};
+    uint32_t steps = 0;
+    std::vector<uint64_t> moves(SWMI_LOCAL_MOVE_WORDS(seq1.size()));
+    if (swmi_local_align(seq1.data(), seq1.size(), seq2.data(), 1, score_matrix.data(), gap_penalty, &score, ends, moves.data(),
+                         &steps) != SWMI_OK)
+        throw std::runtime_error(std::string("swmi_local_align: ") + swmi_last_error());
+    return {score, swmi::expand_local_moves(moves.data(), steps, ends[0], ends[1])};
+}
+
+inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_111_long_mi355x(const std::vector<uint8_t> &seq1,
+                                                                                     const std::array<uint8_t, 128> &seq2)
+{
+    static const std::array<int8_t, 16> k111 = {1, -1, -1, -1, -1, 1, -1, -1, -1, -1, 1, -1, -1, -1, -1, 1};
+    return SmithWaterman_local_mi355x(seq1, seq2, k111, 1);
 }

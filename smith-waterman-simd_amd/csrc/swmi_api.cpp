@@ -657,6 +657,7 @@ void destroy_context(Context &c)
         (void)hipFree(g.d_moves);
         g = SgSet{};
     }
+    c.local_state.reset();              // (after the synchronisation above: its deleter frees device memory)
     if (c.pin) (void)hipHostFree(c.pin);
     c.pin = nullptr;
     c.pin_dev = nullptr;

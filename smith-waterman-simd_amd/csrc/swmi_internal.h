@@ -74,3 +74,13 @@ void semiglobal_kernel_names(size_t n, int compute_units, char *sweep_name, size
                              SgTuning tuning = SgTuning());
 
 }  // namespace swmi
+
+namespace swmi {
+// Local aligner with end / start cell and traceback (local_kernels.hip).  n alignments of seq1 (len1 bytes each, at
+// d_seq1s + len1 * k) against a 128-mer (d_seq2s + 128 k); d_codes holds local_code_words(len1) dwords per alignment of the
+// launch.  d_moves NULL: the ends-only kernel (no codes, no walk; d_codes and d_steps unused).
+size_t local_code_words(int len1);
+hipError_t launch_local(const uint8_t *d_seq1s, const uint8_t *d_seq2s, int len1, size_t n, const int8_t *sm, int gap,
+                        int32_t *d_scores, int32_t *d_ends, uint32_t *d_codes, unsigned long long *d_moves, uint32_t *d_steps,
+                        size_t move_words, hipStream_t stream);
+}  // namespace swmi

@@ -1,0 +1,65 @@
+#!/usr/bin/env python3
+"""Alignments per second of the local aligner with traceback (swmi_local_align*); prints ONE JSON line.
+
+Resident buffers (swmi_local_time_device: HIP events around back-to-back device calls): len1 = 128 ends-only and traceback,
+len1 = 1024 and 16384 (both modes); the host entry (swmi_local_align, host arrays in and out) at len1 = 128 with traceback.
+Inputs: the library's pair generator; for len1 > 128 each seq1 is its generated 128-mer repeated.
+Parameters (1, -1, 1), those of the reference's SmithWaterman_111_long.
+
+    python tools/local_rate.py [--n128 1048576] [--iters 10]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "smith-waterman-simd_amd"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402,F401  (before libswmi.so: INTEGRATION.md 3)
+
+import swmi  # noqa: E402
+
+
+def device_rate(len1, n, traceback, iters, sm):
+    dev = torch.device("cuda:0")
+    a, b = swmi.generate_pairs_host(n, 123, 0)
+    s1 = np.ascontiguousarray(np.tile(a, (1, (len1 + 127) // 128))[:, :len1])     # seq1 k = seq1 k of the generator, repeated
+    d1 = torch.from_numpy(np.ascontiguousarray(s1)).to(dev)
+    d2 = torch.from_numpy(b).to(dev)
+    sc = torch.zeros(n, dtype=torch.int32, device=dev)
+    ends = torch.zeros((n, 4), dtype=torch.int32, device=dev)
+    mv = torch.zeros((n, swmi.local_move_words(len1)), dtype=torch.int64, device=dev) if traceback else None
+    st = torch.zeros(n, dtype=torch.int32, device=dev) if traceback else None
+    torch.cuda.synchronize()
+    ms = swmi.local_time_device(d1.data_ptr(), len1, d2.data_ptr(), n, sm, 1, sc.data_ptr(), ends.data_ptr(),
+                                mv.data_ptr() if traceback else None, st.data_ptr() if traceback else None, 0, iters)
+    return n / (ms * 1e-3), ms
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n128", type=int, default=1 << 20)
+    ap.add_argument("--iters", type=int, default=10)
+    args = ap.parse_args()
+    swmi.init(0)
+    sm = swmi.match_matrix(1, -1)
+    out = {"metric": "local_align_alignments_per_s", "params": [1, -1, 1], "device": swmi.device_info()["arch"]}
+    for len1, n in ((128, args.n128), (1024, max(args.n128 // 8, 1)), (16384, max(args.n128 // 128, 1))):
+        for tb in (False, True):
+            rate, ms = device_rate(len1, n, tb, args.iters, sm)
+            key = "len%d_%s" % (len1, "traceback" if tb else "ends_only")
+            out[key] = {"n": n, "ms_per_call": round(ms, 4), "alignments_per_s": round(rate)}
+    a, b = swmi.generate_pairs_host(args.n128, 321, 0)
+    swmi.local_align(a[:1024], b[:1024], sm, 1)                          # buffers and streams set up outside the timing
+    t0 = time.perf_counter()
+    swmi.local_align(a, b, sm, 1)
+    dt = time.perf_counter() - t0
+    out["len128_host_traceback"] = {"n": args.n128, "ms_per_call": round(dt * 1e3, 3), "alignments_per_s": round(args.n128 / dt)}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
