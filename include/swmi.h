@@ -340,6 +340,51 @@ SWMI_API int swmi_local_time_device(const void *d_seq1s, size_t len1, const void
                                     const int8_t score_matrix[16], int8_t gap_penalty, void *d_scores, void *d_ends,
                                     void *d_moves, void *d_steps, void *stream, int iters, float *avg_ms);
 
+/* ---- exact semi-global aligner with traceback (SemiGlobal_111, source.cpp:1776-1834) ------------------------------------
+ * The full table of the reference's SemiGlobal_111, with no band and no X-drop: the exact answer that
+ * swmi_semiglobal_xdrop approximates.  n alignments of seq1 (len1 bytes, alignment k at seq1s + len1 * k) against seq2
+ * (len2 bytes, at seq2s + len2 * k), one (len1, len2) per call, 1 <= len1, len2 <= 16384; any int8 matrix, gap in
+ * [0, 127]; bases are taken modulo 4.  The reference's own parameters are match 1, mismatch -1, gap 1 at 16384 x 16384:
+ *     H(0,0) = 0,  H(0,j) = -j gap,  H(i,0) = -i gap,
+ *     H(i,j) = max(H(i-1,j-1) + sm[seq1[i-1]*4 + seq2[j-1]], H(i-1,j) - gap, H(i,j-1) - gap)      (no zero floor)
+ * The BEST CELL is the first cell in row-major order over i = 0..len1, j = 0..len2 whose H is strictly greater than every
+ * earlier one, starting from 0 at (0,0); scores[k] = H there (>= 0), ends[2k], ends[2k+1] = its (i, j).  When no cell is
+ * above 0 the best cell is (0,0).  The walk goes from the best cell to (0,0): a diagonal step if i && j and
+ * H = H(i-1,j-1) + s, else an up step if i and H = H(i-1,j) - gap, else a left step (source.cpp:1815-1827).
+ * moves + k * SWMI_SGFULL_MOVE_WORDS(len1, len2) receives it in WALKING order, step t at bits 2 (t % 32) of word t / 32:
+ * 3 = diagonal, 2 = up, 1 = left (the encoding of swmi_semiglobal_xdrop_moves); lengths[k] = positions of the reference's
+ * list = steps + 1, so swmi_semiglobal_expand_moves(moves_k, lengths[k], ...) rebuilds that list, from (0,0) to the best
+ * cell; words past the last step are unspecified.  moves and lengths both NULL: ENDS-ONLY, no codes are stored or walked.
+ * H lies in [-(len1 + len2) 127, 127 min(len1, len2)].
+ * Host buffers.  The batch runs in SLICES (swmi_semiglobal_full_slices_for) on two sets of device buffers, one slice's
+ * copies beside the other's kernel.  Errors: SWMI_ERR_INVALID_ARGUMENT for a length outside [1, 16384], a NULL buffer, or
+ * only one of moves / lengths; SWMI_ERR_DOMAIN for gap_penalty < 0. */
+#define SWMI_SGFULL_MAX_LEN 16384
+#define SWMI_SGFULL_MOVE_WORDS(len1, len2) ((((((size_t)(len1)) + ((size_t)(len2)) + 31) / 32) + 1) & ~(size_t)1)   /* 16-byte rows */
+SWMI_API int swmi_semiglobal_full(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t len2, size_t n,
+                                  const int8_t score_matrix[16], int8_t gap_penalty, int32_t *scores, int32_t *ends,
+                                  uint64_t *moves, uint32_t *lengths);
+/* The slices a swmi_semiglobal_full call of n alignments cuts its batch into (traceback = 0: ends-only), in order; returns
+ * how many there are and writes the first `cap` sizes (NULL to count).  With a traceback a slice's device buffers stay
+ * within what 256 alignments of 16384 x 16384 take (about 16.1 GiB: 64.25 MiB of codes each), so that a full-size slice
+ * gives every CU of an MI355X a workgroup; ends-only slices stay within 256 MiB of inputs and results.  At most 2^20
+ * alignments per slice.  Needs no device.  0 for a length outside [1, 16384]. */
+SWMI_API size_t swmi_semiglobal_full_slices_for(size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap);
+/* Same with every buffer in device memory (16-byte aligned), asynchronous on `stream`.  The traceback codes (2 bits per
+ * cell) go to a workspace of the library's per (GPU, stream), grown on demand up to one slice and kept until
+ * swmi_semiglobal_full_release_workspaces() / swmi_shutdown(): calls on one stream serialise by themselves, calls on
+ * different streams may be in flight together. */
+SWMI_API int swmi_semiglobal_full_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
+                                         const int8_t score_matrix[16], int8_t gap_penalty, void *d_scores, void *d_ends,
+                                         void *d_moves, void *d_lengths, void *stream);
+/* Free the device buffers of both entries above on the current GPU (synchronises the device first). */
+SWMI_API int swmi_semiglobal_full_release_workspaces(void);
+/* Measurement helper: `iters` swmi_semiglobal_full_device calls back to back on `stream`, bracketed by HIP events;
+ * *avg_ms = the average time of one call.  Synchronous. */
+SWMI_API int swmi_semiglobal_full_time_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
+                                              const int8_t score_matrix[16], int8_t gap_penalty, void *d_scores, void *d_ends,
+                                              void *d_moves, void *d_lengths, void *stream, int iters, float *avg_ms);
+
 /* unpack() itself (source.cpp:1580-1583) for n packed sequences, on the GPU. Host buffers. */
 SWMI_API int swmi_unpack(const uint8_t *packed, size_t n_seqs, uint8_t *unpacked);
 

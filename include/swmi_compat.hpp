@@ -11,6 +11,8 @@
 #include <algorithm>
 #include <array>
 #include <cstdint>
+#include <exception>
+#include <mutex>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -44,7 +46,20 @@ inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_local_mi35
                                                                                   const std::array<int8_t, 16> &score_matrix,
                                                                                   const int8_t gap_penalty);
 
+// Same arguments, same return value as SemiGlobal_111 (source.cpp:1776-1834): (score, path of (i, j) from (0,0) to the best
+// cell) of the exact semi-global alignment, the full table with no band and no X-drop (swmi_semiglobal_full).  One
+// synchronous call per alignment; swmi::SemiGlobal_111_mi355x_batch below is the throughput form.
+inline std::pair<int, std::vector<std::pair<int, int>>> SemiGlobal_111_mi355x(const std::array<uint8_t, 16384> &seq1,
+                                                                             const std::array<uint8_t, 16384> &seq2);
+
 namespace swmi {
+
+// match 1, mismatch -1 (source.cpp:1786)
+inline const std::array<int8_t, 16> &semiglobal_111_matrix()
+{
+    static const std::array<int8_t, 16> m = {1, -1, -1, -1, -1, 1, -1, -1, -1, -1, 1, -1, -1, -1, -1, 1};
+    return m;
+}
 
 // One local alignment's moves (swmi_local_align) -> the reference's path vector (source.cpp:1571-1575).
 inline std::vector<std::pair<int, int>> expand_local_moves(const uint64_t *moves, uint32_t steps, int32_t end_i, int32_t end_j)
@@ -225,4 +240,93 @@ inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_111_long_m
 {
     static const std::array<int8_t, 16> k111 = {1, -1, -1, -1, -1, 1, -1, -1, -1, -1, 1, -1, -1, -1, -1, 1};
     return SmithWaterman_local_mi355x(seq1, seq2, k111, 1);
+}
+
+namespace swmi {
+
+// The reference's SemiGlobal_111 (source.cpp:1776-1834) over arrays of pairs: result[k] == SemiGlobal_111(seq1s[k], seq2s[k]).
+// The batch goes to the GPU in pieces of `piece` alignments (256 = one full-size slice of swmi_semiglobal_full); only two
+// pieces' moves are held at a time (8 KiB per alignment), and the paths of one piece are rebuilt on `threads` host threads
+// (0 = as many as the machine reports, at most 64) while the GPU aligns the next.  A failure in an expander thread is
+// recorded, every thread is joined, and then it is thrown.
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SemiGlobal_111_mi355x_batch(
+    const std::vector<std::array<uint8_t, 16384>> &seq1s, const std::vector<std::array<uint8_t, 16384>> &seq2s,
+    unsigned threads = 0, size_t piece = 256)
+{
+    static_assert(sizeof(std::array<uint8_t, 16384>) == 16384, "std::array<uint8_t,16384> must be 16384 contiguous bytes");
+    if (seq1s.size() != seq2s.size()) throw std::invalid_argument("SemiGlobal_111_mi355x_batch: seq1s and seq2s differ in length");
+    const size_t n = seq1s.size();
+    std::vector<std::pair<int, std::vector<std::pair<int, int>>>> out(n);
+    if (n == 0) return out;
+    if (threads == 0) threads = std::thread::hardware_concurrency();
+    threads = threads < 1 ? 1 : threads > 64 ? 64 : threads;
+    if (piece == 0) piece = 1;
+    const size_t mw = SWMI_SGFULL_MOVE_WORDS(16384, 16384), m_max = n < piece ? n : piece;
+    std::vector<int32_t> scores[2], ends[2];
+    std::vector<uint32_t> lengths[2];
+    std::vector<uint64_t> moves[2];
+    for (int b = 0; b < 2; ++b) {
+        scores[b].resize(m_max);
+        ends[b].resize(2 * m_max);
+        lengths[b].resize(m_max);
+        moves[b].resize(m_max * mw);
+    }
+    std::vector<std::thread> pool;                     // the expanders of the piece before the one the GPU works on
+    std::mutex mu;
+    std::string failed;                                // the first failure, GPU or expander
+    auto join_all = [&] {
+        for (auto &th : pool) th.join();
+        pool.clear();
+    };
+    auto record = [&](const std::string &what) {
+        std::lock_guard<std::mutex> lock(mu);
+        if (failed.empty()) failed = what;
+    };
+    auto has_failed = [&] {
+        std::lock_guard<std::mutex> lock(mu);
+        return !failed.empty();
+    };
+    int buf = 0;
+    for (size_t off = 0; off < n && !has_failed(); off += piece, buf ^= 1) {
+        const size_t m = n - off < piece ? n - off : piece;
+        if (swmi_semiglobal_full(seq1s[off].data(), 16384, seq2s[off].data(), 16384, m, semiglobal_111_matrix().data(), 1, scores[buf].data(),
+                                 ends[buf].data(), moves[buf].data(), lengths[buf].data()) != SWMI_OK)
+            record(std::string("swmi_semiglobal_full: ") + swmi_last_error());
+        join_all();                                    // (the previous piece's expanders, which used the other buffer)
+        if (has_failed()) break;
+        const unsigned use = threads > m ? unsigned(m) : threads;
+        try {
+            for (unsigned t = 0; t < use; ++t)
+                pool.emplace_back([&, off, m, t, use, buf] {
+                    try {
+                        for (size_t k = m * t / use; k < m * (t + 1) / use; ++k)
+                            out[off + k] = {scores[buf][k], expand_moves(moves[buf].data() + k * mw, lengths[buf][k])};
+                    } catch (const std::exception &e) {
+                        record(e.what());
+                    } catch (...) {
+                        record("SemiGlobal_111_mi355x_batch: expander failed");
+                    }
+                });
+        } catch (...) {
+            join_all();
+            throw;
+        }
+    }
+    join_all();
+    if (!failed.empty()) throw std::runtime_error(failed);
+    return out;
+}
+
+}  // namespace swmi
+
+inline std::pair<int, std::vector<std::pair<int, int>>> SemiGlobal_111_mi355x(const std::array<uint8_t, 16384> &seq1,
+                                                                             const std::array<uint8_t, 16384> &seq2)
+{
+    int32_t score = 0, ends[2] = {0, 0};
+    uint32_t length = 0;
+    std::vector<uint64_t> moves(SWMI_SGFULL_MOVE_WORDS(16384, 16384));
+    if (swmi_semiglobal_full(seq1.data(), 16384, seq2.data(), 16384, 1, swmi::semiglobal_111_matrix().data(), 1, &score, ends, moves.data(),
+                             &length) != SWMI_OK)
+        throw std::runtime_error(std::string("swmi_semiglobal_full: ") + swmi_last_error());
+    return {score, swmi::expand_moves(moves.data(), length)};
 }

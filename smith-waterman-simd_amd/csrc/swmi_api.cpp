@@ -658,6 +658,7 @@ void destroy_context(Context &c)
         g = SgSet{};
     }
     c.local_state.reset();              // (after the synchronisation above: its deleter frees device memory)
+    c.sgfull_state.reset();
     if (c.pin) (void)hipHostFree(c.pin);
     c.pin = nullptr;
     c.pin_dev = nullptr;

@@ -84,3 +84,16 @@ hipError_t launch_local(const uint8_t *d_seq1s, const uint8_t *d_seq2s, int len1
                         int32_t *d_scores, int32_t *d_ends, uint32_t *d_codes, unsigned long long *d_moves, uint32_t *d_steps,
                         size_t move_words, hipStream_t stream);
 }  // namespace swmi
+
+namespace swmi {
+// Exact semi-global aligner with traceback (sgfull_kernels.hip).  n alignments of seq1 (len1 bytes each, at d_seq1s +
+// len1 * k) against seq2 (len2 bytes each, at d_seq2s + len2 * k), one workgroup of sgfull_waves(len2) wavefronts each;
+// d_codes holds sgfull_code_words(len1, len2) dwords per alignment of the launch; d_ends two int32 per alignment.
+// d_moves NULL: the ends-only kernel (no codes, no walk; d_codes and d_lengths unused).
+int sgfull_waves(int len2);
+size_t sgfull_trips(int len1);
+size_t sgfull_code_words(int len1, int len2);
+hipError_t launch_sgfull(const uint8_t *d_seq1s, const uint8_t *d_seq2s, int len1, int len2, size_t n, const int8_t *sm, int gap,
+                         int32_t *d_scores, int32_t *d_ends, uint32_t *d_codes, unsigned long long *d_moves, uint32_t *d_lengths,
+                         size_t move_words, hipStream_t stream);
+}  // namespace swmi

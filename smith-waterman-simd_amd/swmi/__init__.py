@@ -124,6 +124,12 @@ def load():
     lib.swmi_local_slices_for.restype = sz
     lib.swmi_local_expand_moves.argtypes = [vp, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32, vp, sz]
     lib.swmi_local_time_device.argtypes = [vp, sz, vp, sz, vp, i8, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
+    lib.swmi_semiglobal_full.argtypes = [vp, sz, vp, sz, sz, vp, i8, vp, vp, vp, vp]
+    lib.swmi_semiglobal_full_device.argtypes = [vp, sz, vp, sz, sz, vp, i8, vp, vp, vp, vp, vp]
+    lib.swmi_semiglobal_full_slices_for.argtypes = [sz, sz, sz, ctypes.c_int, vp, sz]
+    lib.swmi_semiglobal_full_slices_for.restype = sz
+    lib.swmi_semiglobal_full_time_device.argtypes = [vp, sz, vp, sz, sz, vp, i8, vp, vp, vp, vp, vp, ctypes.c_int,
+                                                     ctypes.POINTER(ctypes.c_float)]
     _lib = lib
     return lib
 
@@ -570,6 +576,73 @@ def local_slices_for(n, len1, traceback=True):
     buf = (ctypes.c_size_t * max(count, 1))()
     load().swmi_local_slices_for(n, len1, 1 if traceback else 0, buf, count)
     return [int(buf[k]) for k in range(count)]
+
+
+SGFULL_MAX_LEN = 16384
+
+
+def semiglobal_full_move_words(len1, len2):
+    """64-bit words of moves per alignment of swmi_semiglobal_full (SWMI_SGFULL_MOVE_WORDS)."""
+    return (((int(len1) + int(len2) + 31) // 32) + 1) & ~1
+
+
+def semiglobal_full(seq1s, seq2s, score_matrix, gap_penalty, traceback=True):
+    """Exact semi-global alignment with traceback (swmi_semiglobal_full): the reference's SemiGlobal_111
+    (source.cpp:1776-1834) for n pairs, any lengths in [1, 16384] (one (len1, len2) per call), any int8 matrix and gap.
+    seq1s: (n, len1) bases, seq2s: (n, len2).
+
+    Returns (scores[n] int32, ends[n, 2] int32 = the best cell, moves[n, semiglobal_full_move_words(len1, len2)] uint64,
+    lengths[n] uint32); move t of alignment k = (moves[k, t // 32] >> 2 * (t % 32)) & 3 in walking order from the best
+    cell to (0,0) (3 diagonal, 2 up, 1 left), lengths = steps + 1; semiglobal_expand_moves(moves[k], lengths[k]) gives the
+    reference's list.  traceback=False: ends-only (moves and lengths are None)."""
+    a = np.ascontiguousarray(seq1s, dtype=np.uint8)
+    b = np.ascontiguousarray(seq2s, dtype=np.uint8)
+    if a.ndim != 2 or b.ndim != 2:
+        raise ValueError("seq1s and seq2s must be (n, len1) and (n, len2)")
+    n, len1 = a.shape
+    len2 = b.shape[1]
+    if b.shape[0] != n:
+        raise ValueError("seq1s and seq2s hold different numbers of sequences")
+    sm, gap = _sm(score_matrix), _gap(gap_penalty)
+    scores = np.zeros(n, np.int32)
+    ends = np.zeros((n, 2), np.int32)
+    moves = np.zeros((n, semiglobal_full_move_words(len1, len2)), np.uint64) if traceback else None
+    lengths = np.zeros(n, np.uint32) if traceback else None
+    _check(load().swmi_semiglobal_full(a.ctypes.data, len1, b.ctypes.data, len2, n, sm.ctypes.data, gap, scores.ctypes.data,
+                                       ends.ctypes.data, moves.ctypes.data if traceback else None,
+                                       lengths.ctypes.data if traceback else None))
+    return scores, ends, moves, lengths
+
+
+def semiglobal_full_device(d_seq1s, len1, d_seq2s, len2, n, score_matrix, gap_penalty, d_scores, d_ends, d_moves=None,
+                           d_lengths=None, stream=0):
+    """swmi_semiglobal_full_device on device pointers (asynchronous on `stream`); d_moves = d_lengths = None: ends-only."""
+    sm = _sm(score_matrix)
+    _check(load().swmi_semiglobal_full_device(d_seq1s, len1, d_seq2s, len2, n, sm.ctypes.data, _gap(gap_penalty), d_scores,
+                                              d_ends, d_moves, d_lengths, stream))
+
+
+def semiglobal_full_time_device(d_seq1s, len1, d_seq2s, len2, n, score_matrix, gap_penalty, d_scores, d_ends, d_moves=None,
+                                d_lengths=None, stream=0, iters=10):
+    """Average ms of one swmi_semiglobal_full_device call over `iters` back-to-back calls (HIP events on `stream`)."""
+    sm = _sm(score_matrix)
+    ms = ctypes.c_float()
+    _check(load().swmi_semiglobal_full_time_device(d_seq1s, len1, d_seq2s, len2, n, sm.ctypes.data, _gap(gap_penalty), d_scores,
+                                                   d_ends, d_moves, d_lengths, stream, int(iters), ctypes.byref(ms)))
+    return float(ms.value)
+
+
+def semiglobal_full_slices_for(n, len1, len2, traceback=True):
+    """The slices swmi_semiglobal_full cuts n alignments into (needs no device)."""
+    count = load().swmi_semiglobal_full_slices_for(n, len1, len2, 1 if traceback else 0, None, 0)
+    buf = (ctypes.c_size_t * max(count, 1))()
+    load().swmi_semiglobal_full_slices_for(n, len1, len2, 1 if traceback else 0, buf, count)
+    return [int(buf[k]) for k in range(count)]
+
+
+def semiglobal_full_release_workspaces():
+    """Free the exact semi-global aligner's device buffers on the current GPU."""
+    _check(load().swmi_semiglobal_full_release_workspaces())
 
 
 def unpack(packed):
