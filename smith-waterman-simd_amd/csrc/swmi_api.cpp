@@ -438,11 +438,23 @@ int score_host_batch(Context &ctx, const uint8_t *s1, const uint8_t *s2, size_t 
     const bool serial = knobs().host_serial;             // round 2's order of issue, for the A/B
     const size_t score_group = knobs().score_group;
     const size_t first_group = n < score_group ? n : score_group;
+    // The slots hold the largest granule of ANY group.  A batch has at most two group sizes, the full group and the ragged
+    // tail, but the tail's granules can be the larger: the balanced schedule cuts its middle at multiples of 4096 and gives
+    // the rest to the last middle granule, so a tail group can carry one of up to steady + 4095 pairs where a full group
+    // divides evenly (2^24 + 655359 pairs: 131072 in the first group, 135167 in the tail).
     std::vector<size_t> sizes;
-    granule_list(first_group, per_pair, &sizes);                      // no later group is larger, so none has a larger granule
+    const size_t tail = n > score_group ? n % score_group : 0;
     size_t largest = 0;
+    if (tail) {
+        granule_list(tail, per_pair, &sizes);
+        for (size_t g : sizes) largest = g > largest ? g : largest;
+    }
+    granule_list(first_group, per_pair, &sizes);
     for (size_t g : sizes) largest = g > largest ? g : largest;
     const size_t first_count = sizes.size();
+    // (A tail group can also have MORE granules than a full one -- 8 just below 4 x steady against 6 at 4 x steady -- which
+    // the rest does not depend on: with several groups the slot count is fixed, every group splits its own early copy, and
+    // a first group of one granule leaves a tail of one.)
     // issuing threads: two where copy and kernel are level (the 2-bit packed entry) and there is more than one granule; where
     // the link alone is the bound (256 / 128 bytes per pair) a second thread only makes the two threads' copies and kernels
     // compete (measured: profiles/r04_host_pipeline_experiment.txt)

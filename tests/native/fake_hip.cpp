@@ -6,12 +6,17 @@
 // scores here, as it would on hardware -- streams and events that only carry an id, and swmi::launch_* stand-ins that write, as the "score" of a pair, the 32-bit number found in the first four
 // bytes of its seq1 -- tests/native/multi_fake.cpp stores the global pair index there, so a gathered score vector must read
 // 0, 1, 2, ... whatever the sharding, the gather backend and the order of the calls.  Nothing here is linked into libswmi.so.
+// Every hipMalloc / hipHostMalloc block is registered, and the DEVICE side of every copy and every launcher stand-in's reads
+// and writes must lie inside ONE live block, or the process aborts with the call, the range and the block it started in:
+// malloc'ed "device" memory under ASan alone can hide a large overflow that lands inside a neighbouring allocation.
 #include <hip/hip_runtime_api.h>
 
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <iterator>
+#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -49,6 +54,66 @@ void drain_all()
     { std::lock_guard<std::mutex> l(g_mu); all = g_streams; }
     for (Handle *h : all) drain(h);
 }
+// live device blocks (hipMalloc, and hipHostMalloc's mapped pinned blocks): base -> bytes
+std::mutex g_blocks_mu;
+std::map<uintptr_t, size_t> g_blocks;
+void *add_block(size_t n)
+{
+    void *p = malloc(n ? n : 1);
+    if (p) {
+        std::lock_guard<std::mutex> l(g_blocks_mu);
+        g_blocks[reinterpret_cast<uintptr_t>(p)] = n;
+    }
+    return p;
+}
+void drop_block(const char *call, void *p)
+{
+    if (!p) return;
+    {
+        std::lock_guard<std::mutex> l(g_blocks_mu);
+        if (g_blocks.erase(reinterpret_cast<uintptr_t>(p)) == 0) {
+            fprintf(stderr, "fake_hip: %s(%p): not a live block\n", call, p);
+            abort();
+        }
+    }
+    free(p);
+}
+// [p, p + n) must lie inside one live block; `what` names the call and the operand
+void check_range(const char *what, const void *p, size_t n)
+{
+    if (n == 0) return;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+    std::lock_guard<std::mutex> l(g_blocks_mu);
+    auto it = g_blocks.upper_bound(a);
+    if (it != g_blocks.begin()) {
+        --it;
+        if (a - it->first < it->second && n <= it->second - (a - it->first)) return;
+        if (a - it->first < it->second) {
+            fprintf(stderr, "fake_hip: BOUNDS %s: [%p, +%zu) ends %zu bytes past its block [%p, +%zu)\n", what, p, n,
+                    n - (it->second - (a - it->first)), reinterpret_cast<void *>(it->first), it->second);
+            abort();
+        }
+    }
+    fprintf(stderr, "fake_hip: BOUNDS %s: [%p, +%zu) starts in no live device block\n", what, p, n);
+    abort();
+}
+// the device side(s) of a copy of this kind
+void check_copy(const char *call, void *dst, const void *src, size_t n, hipMemcpyKind kind)
+{
+    char what[96];
+    if (kind == hipMemcpyHostToDevice || kind == hipMemcpyDeviceToDevice) {
+        snprintf(what, sizeof what, "%s destination (kind %d)", call, (int)kind);
+        check_range(what, dst, n);
+    }
+    if (kind == hipMemcpyDeviceToHost || kind == hipMemcpyDeviceToDevice) {
+        snprintf(what, sizeof what, "%s source (kind %d)", call, (int)kind);
+        check_range(what, src, n);
+    }
+    if (kind != hipMemcpyHostToDevice && kind != hipMemcpyDeviceToDevice && kind != hipMemcpyDeviceToHost) {
+        fprintf(stderr, "fake_hip: %s with kind %d: the fake knows no device side for it\n", call, (int)kind);
+        abort();
+    }
+}
 int device_count()
 {
     const char *e = getenv("FAKE_HIP_DEVICES");
@@ -74,10 +139,15 @@ hipError_t hipGetDevicePropertiesR0600(hipDeviceProp_t *p, int d)
 }
 const char *hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : "fake HIP error"; }
 hipError_t hipGetLastError() { return hipSuccess; }
-hipError_t hipMalloc(void **p, size_t n) { *p = malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
-hipError_t hipFree(void *p) { free(p); return hipSuccess; }
-hipError_t hipHostMalloc(void **p, size_t n, unsigned) { *p = malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
-hipError_t hipHostFree(void *p) { free(p); return hipSuccess; }
+hipError_t hipMalloc(void **p, size_t n)
+{
+    *p = add_block(n);
+    log("dev%d malloc bytes%zu", t_device, n);
+    return *p ? hipSuccess : hipErrorOutOfMemory;
+}
+hipError_t hipFree(void *p) { drop_block("hipFree", p); return hipSuccess; }
+hipError_t hipHostMalloc(void **p, size_t n, unsigned) { *p = add_block(n); return *p ? hipSuccess : hipErrorOutOfMemory; }
+hipError_t hipHostFree(void *p) { drop_block("hipHostFree", p); return hipSuccess; }
 hipError_t hipHostGetDevicePointer(void **d, void *h, unsigned) { *d = h; return hipSuccess; }
 hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned)
 {
@@ -121,6 +191,7 @@ hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) { log("dev%
 hipError_t hipMemcpyAsync(void *dst, const void *src, size_t n, hipMemcpyKind kind, hipStream_t s)
 {
     log("dev%d memcpy kind%d bytes%zu stream%d", t_device, (int)kind, n, stream_id(s));
+    check_copy(s ? "hipMemcpyAsync" : "hipMemcpy", dst, src, n, kind);
     if (kind == hipMemcpyDeviceToHost && s) reinterpret_cast<Handle *>(s)->pending.push_back(Pending{dst, src, n});
     else memmove(dst, src, n);
     return hipSuccess;
@@ -128,12 +199,20 @@ hipError_t hipMemcpyAsync(void *dst, const void *src, size_t n, hipMemcpyKind ki
 hipError_t hipMemcpy(void *dst, const void *src, size_t n, hipMemcpyKind kind) { return hipMemcpyAsync(dst, src, n, kind, nullptr); }
 hipError_t hipMemcpyPeerAsync(void *dst, int dst_dev, const void *src, int src_dev, size_t n, hipStream_t s)
 {
+    check_range("hipMemcpyPeerAsync destination", dst, n);
+    check_range("hipMemcpyPeerAsync source", src, n);
     memmove(dst, src, n);
     log("dev%d memcpy_peer dst_dev%d src_dev%d bytes%zu stream%d", t_device, dst_dev, src_dev, n, stream_id(s));
     return hipSuccess;
 }
-hipError_t hipMemcpy2DAsync(void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t height, hipMemcpyKind, hipStream_t)
+hipError_t hipMemcpy2DAsync(void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t height, hipMemcpyKind kind, hipStream_t)
 {
+    if (height) {   // each side spans (height - 1) pitches + one row
+        const size_t dst_n = (height - 1) * dpitch + width, src_n = (height - 1) * spitch + width;
+        if (kind != hipMemcpyHostToDevice && kind != hipMemcpyDeviceToDevice && kind != hipMemcpyDeviceToHost) check_copy("hipMemcpy2DAsync", dst, src, 0, kind);
+        if (kind != hipMemcpyDeviceToHost) check_range("hipMemcpy2DAsync destination", dst, dst_n);
+        if (kind != hipMemcpyHostToDevice) check_range("hipMemcpy2DAsync source", src, src_n);
+    }
     for (size_t r = 0; r < height; ++r) memmove(static_cast<char *>(dst) + r * dpitch, static_cast<const char *>(src) + r * spitch, width);
     return hipSuccess;
 }
@@ -148,22 +227,31 @@ static void fake_scores(const uint8_t *s1, size_t stride, int32_t *out, size_t n
 {
     for (size_t k = 0; k < n; ++k) memcpy(&out[k], s1 + k * stride, 4);       // "score" = the number in the pair's first four bytes
 }
-hipError_t launch_score(const LaunchConfig &cfg, const uint8_t *s1, const uint8_t *, int32_t *out, size_t n, const SmRows &, int,
+hipError_t launch_score(const LaunchConfig &cfg, const uint8_t *s1, const uint8_t *s2, int32_t *out, size_t n, const SmRows &, int,
                         bool packed, hipStream_t st)
 {
     log("dev%d launch_score n%zu lanes%d stream%d", t_device, n, cfg.lanes_per_alignment, stream_id(st));
-    fake_scores(s1, packed ? 32 : 128, out, n);
+    const size_t stride = packed ? 32 : 128;
+    check_range("launch_score seq1 reads", s1, n * stride);
+    check_range("launch_score seq2 reads", s2, n * stride);
+    check_range("launch_score score writes", out, n * sizeof(int32_t));
+    fake_scores(s1, stride, out, n);
     return hipSuccess;
 }
-hipError_t launch_score_one_vs_many(const LaunchConfig &, const uint8_t *s1, const uint8_t *, int32_t *out, size_t n, const SmRows &, int, hipStream_t st)
+hipError_t launch_score_one_vs_many(const LaunchConfig &, const uint8_t *s1, const uint8_t *s2, int32_t *out, size_t n, const SmRows &, int, hipStream_t st)
 {
     log("dev%d launch_one_vs_many n%zu stream%d", t_device, n, stream_id(st));
+    check_range("launch_score_one_vs_many seq1 reads", s1, n * 128);
+    check_range("launch_score_one_vs_many seq2 reads", s2, n ? 128 : 0);
+    check_range("launch_score_one_vs_many score writes", out, n * sizeof(int32_t));
     fake_scores(s1, 128, out, n);
     return hipSuccess;
 }
 hipError_t launch_generate(uint8_t *s1, uint8_t *s2, size_t n, uint64_t, uint64_t first_pair, hipStream_t st)
 {
     log("dev%d launch_generate n%zu first%llu stream%d", t_device, n, (unsigned long long)first_pair, stream_id(st));
+    check_range("launch_generate seq1 writes", s1, n * 128);
+    check_range("launch_generate seq2 writes", s2, n * 128);
     for (size_t k = 0; k < n; ++k) {
         const uint32_t id = (uint32_t)(first_pair + k);
         memset(s1 + 128 * k, 0, 128); memset(s2 + 128 * k, 0, 128);

@@ -147,3 +147,113 @@ def test_host_batch_above_one_production_score_group(gpu, oracle):
         assert np.array_equal(got[lo:hi], oracle.batch(a[lo:hi], b[lo:hi], sm, 15)), lo
     got_packed = gpu.score_batch_packed(gpu.pack(a), gpu.pack(b), sm, 15)
     assert np.array_equal(got_packed, want)
+
+
+def _resident_pairs(gpu, n, seed, sm, gap):
+    """n generated pairs as host arrays, and their scores from ONE resident launch (swmi_score_batch_device: no host slicing),
+    plus the one-vs-many scores (every seq1 against seq2[0]) the same way."""
+    d1 = torch.empty(n * 128, dtype=torch.uint8, device="cuda")
+    d2 = torch.empty(n * 128, dtype=torch.uint8, device="cuda")
+    gpu.generate_pairs_device(d1.data_ptr(), d2.data_ptr(), n, seed, 0, torch.cuda.current_stream().cuda_stream)
+    want = _score(gpu, d1, d2, sm, gap, n).cpu().numpy()
+    a = d1.cpu().numpy().reshape(n, 128)
+    b = d2.cpu().numpy().reshape(n, 128)
+    d2 = d2.view(n, 128)[:1].expand(n, 128).contiguous().view(-1)
+    want_ovm = _score(gpu, d1, d2, sm, gap, n).cpu().numpy()
+    del d1, d2
+    torch.cuda.empty_cache()
+    return a, b, want, want_ovm
+
+
+def _oversized_window_starts(gpu, n, group):
+    """1200-pair windows: the head, both ends of the packed schedule's largest granule, the first group boundary, the tail."""
+    g = gpu.host_granules(n, gpu.ENTRY_PACKED)
+    ends = np.cumsum(g)
+    k = int(np.argmax(g))
+    assert k >= len(gpu.host_granules(group, gpu.ENTRY_PACKED)) and g[k] > 131072     # it lies in the tail group
+    return [0, int(ends[k] - g[k]) - 600, int(ends[k]) - 600, group - 600, n - 1200]
+
+
+def test_host_batch_score_group_tail_with_an_oversized_granule(gpu, oracle):
+    """score_host_batch sizes its slot buffers from the largest granule of ANY score group: at SWMI_TEST_SCORE_GROUP = 1M pairs
+    and n = 1 703 935 the packed entry's tail group carries a granule of 135 167 pairs, above the full group's 131 072.  Each
+    entry runs on a FRESH context (no buffer grown by an earlier call), and every score must equal the same pairs scored
+    resident in one launch; the oracle checks windows around the oversized granule, the group boundary and the tail."""
+    import os
+    group, n = 1 << 20, 1703935
+    sm = match_matrix(10, -30)
+    a, b, want, want_ovm = _resident_pairs(gpu, n, 2718, sm, 15)
+    gpu.shutdown()
+    os.environ["SWMI_TEST_SCORE_GROUP"] = str(group)            # knobs are read at swmi_init
+    try:
+        gpu.init(0)
+        starts = _oversized_window_starts(gpu, n, group)
+        got = {}
+        for entry in ("packed", "pairs", "one_vs_many"):
+            gpu.shutdown()
+            gpu.init(0)
+            if entry == "packed":
+                got[entry] = gpu.score_batch_packed(gpu.pack(a), gpu.pack(b), sm, 15)
+            elif entry == "pairs":
+                got[entry] = gpu.score_batch(a, b, sm, 15)
+            else:
+                got[entry] = gpu.score_one_vs_many(a, b[0], sm, 15)
+        assert np.array_equal(got["packed"], want)
+        assert np.array_equal(got["pairs"], want)
+        assert np.array_equal(got["one_vs_many"], want_ovm)
+        for lo in starts:
+            hi = lo + 1200
+            assert np.array_equal(got["packed"][lo:hi], oracle.batch(a[lo:hi], b[lo:hi], sm, 15)), lo
+            assert np.array_equal(got["one_vs_many"][lo:hi], oracle.batch(a[lo:hi], np.repeat(b[:1], hi - lo, 0), sm, 15)), lo
+    finally:
+        del os.environ["SWMI_TEST_SCORE_GROUP"]
+        gpu.shutdown()
+        gpu.init(0)
+        gpu.set_schedule(0, 0)
+
+
+def test_host_batch_packed_production_score_group_tail_with_an_oversized_granule(gpu, oracle):
+    """The production score group (2^24 pairs): a packed host batch of 2^24 + 655 359 pairs, whose tail group carries a granule
+    of 135 167 pairs, on a fresh context -- every score against the resident scores, the oracle on windows."""
+    n = (1 << 24) + 655359
+    sm = match_matrix(10, -30)
+    a, b, want, _ = _resident_pairs(gpu, n, 1618, sm, 15)
+    pa, pb = gpu.pack(a), gpu.pack(b)
+    starts = _oversized_window_starts(gpu, n, 1 << 24)
+    gpu.shutdown()
+    try:
+        gpu.init(0)
+        got = gpu.score_batch_packed(pa, pb, sm, 15)
+        assert np.array_equal(got, want)
+        for lo in starts:
+            assert np.array_equal(got[lo:lo + 1200], oracle.batch(a[lo:lo + 1200], b[lo:lo + 1200], sm, 15)), lo
+    finally:
+        gpu.shutdown()
+        gpu.init(0)
+        gpu.set_schedule(0, 0)
+
+
+def test_host_batch_packed_multi_with_an_oversized_granule_per_shard(gpu):
+    """swmi_score_batch_packed_multi over every GPU present, on fresh contexts, at SWMI_TEST_SCORE_GROUP = 1M pairs: each shard
+    is 1 703 935 pairs, so every GPU's host batch has the oversized tail granule."""
+    import os
+    sm = match_matrix(2, -3)
+    gpu.shutdown()
+    os.environ["SWMI_TEST_SCORE_GROUP"] = str(1 << 20)
+    try:
+        G = gpu.init_all(0)
+        n = G * 1703935
+        gpu.use_gpu(0)
+        a, b, want, _ = _resident_pairs(gpu, n, 31415, sm, 5)
+        gpu.shutdown()
+        assert gpu.init_all(0) == G                             # fresh contexts for the multi call
+        for g in range(G):
+            lo, hi = gpu.shard_bounds(n, g, G)
+            assert hi - lo == 1703935
+        got = gpu.score_batch_multi(gpu.pack(a), gpu.pack(b), sm, 5, packed=True)
+        assert np.array_equal(got, want)
+    finally:
+        del os.environ["SWMI_TEST_SCORE_GROUP"]
+        gpu.shutdown()
+        gpu.init(0)
+        gpu.set_schedule(0, 0)
