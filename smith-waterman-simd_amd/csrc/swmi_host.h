@@ -166,9 +166,9 @@ struct Context {
     uint8_t *pin = nullptr;             // [kPinPairs * 128] seq1s, [kPinPairs * 128] seq2s, [kPinPairs] int32 scores
     void *pin_dev = nullptr;            // the same memory as the device sees it
     unsigned extra_lds = 0;             // SWMI_EXTRA_LDS: occupancy sweep knob (BASELINE config 3)
-    // Device buffers of entry points that live in other translation units (swmi_local.cpp, swmi_sgfull.cpp), created by
-    // them on first use under ws_mu.  destroy_context drops the last reference after synchronising the device, and the
-    // owner's deleter frees what it holds -- so this file needs no symbol of theirs.
+    // Device buffers of the local and the exact semi-global aligner, one state each, which live in another translation
+    // unit (swmi_table.cpp) and are created there on first use under ws_mu.  destroy_context drops the last reference after
+    // synchronising the device, and the owner's deleter frees what it holds -- so this file needs no symbol of that one.
     std::shared_ptr<void> local_state;
     std::shared_ptr<void> sgfull_state;
     std::mutex mu;                      // serialises use of the slots, the sg sets and the pinned buffer

@@ -1,0 +1,410 @@
+// swmi_table.cpp -- host side of the two aligners that fill the whole table, write 2-bit codes and walk them (include/swmi.h):
+// the local aligner with end cell, start cell and traceback (swmi_local_*) and the exact semi-global
+// aligner with traceback (swmi_semiglobal_full*, section 13).  What differs between the two is data (struct Table).
+//
+// Their device buffers hang off Context::local_state and Context::sgfull_state, which destroy_context (swmi_api.cpp) drops
+// at swmi_shutdown: that file names no symbol of this one, so the host-only builds of swmi_api.cpp / swmi_multi.cpp
+// (tests/test_multi_fake.py, tests/test_sanitizers.py) link without these kernels.
+#include "swmi_host.h"
+
+#include <initializer_list>
+
+namespace swmi {
+namespace host {
+namespace {
+
+constexpr size_t kSliceBytes = size_t(256) << 20;   // device memory of one slice's buffers (but an exact semi-global traceback's)
+constexpr size_t kMaxSlice = size_t(1) << 20;       // alignments per slice (and per launch)
+
+// One call of either aligner, its lengths checked
+struct Table {
+    bool local;                 // launch_local, else launch_sgfull
+    const char *count;          // name of the per-alignment count array: "steps" (= moves) or "lengths" (= moves + 1)
+    size_t len1, len2;          // len2 = SWMI_LOCAL_SEQ2_LEN for the local aligner
+    size_t ends;                // int32 of `ends` per alignment
+    size_t code_words, move_words;
+    uint32_t count_offset;      // count = moves + count_offset
+};
+
+Table local_table(size_t len1)
+{
+    return {true, "steps", len1, SWMI_LOCAL_SEQ2_LEN, 4, swmi::local_code_words((int)len1), SWMI_LOCAL_MOVE_WORDS(len1), 0};
+}
+
+Table sgfull_table(size_t len1, size_t len2)
+{
+    return {false, "lengths", len1, len2, 2, swmi::sgfull_code_words((int)len1, (int)len2), SWMI_SGFULL_MOVE_WORDS(len1, len2), 1};
+}
+
+// device bytes one alignment of a slice takes: inputs, results, and with a traceback the codes, the moves and the count
+size_t bytes_per_alignment(const Table &t, bool tb)
+{
+    size_t b = t.len1 + t.len2 + sizeof(int32_t) + t.ends * sizeof(int32_t);
+    if (tb) b += t.code_words * sizeof(uint32_t) + t.move_words * sizeof(uint64_t) + sizeof(uint32_t);
+    return b;
+}
+
+// An exact semi-global traceback slice holds as many alignments as 256 of 16384 x 16384 (about 16.1 GiB): one workgroup per
+// alignment, so that a full-size batch occupies every CU of an MI355X.  Every other slice holds 256 MiB.
+size_t slice_size(const Table &t, size_t n, bool tb)
+{
+    const size_t budget =
+        tb && !t.local ? 256 * bytes_per_alignment(sgfull_table(SWMI_SGFULL_MAX_LEN, SWMI_SGFULL_MAX_LEN), true) : kSliceBytes;
+    size_t s = budget / bytes_per_alignment(t, tb);
+    if (s > kMaxSlice) s = kMaxSlice;
+    if (s < 1) s = 1;
+    return n < s ? n : s;
+}
+
+hipError_t launch(const Table &t, const uint8_t *s1, const uint8_t *s2, size_t n, const int8_t *sm, int gap, int32_t *scores,
+                  int32_t *ends, uint32_t *codes, unsigned long long *moves, uint32_t *counts, hipStream_t st)
+{
+    if (t.local) return swmi::launch_local(s1, s2, (int)t.len1, n, sm, gap, scores, ends, codes, moves, counts, t.move_words, st);
+    return swmi::launch_sgfull(s1, s2, (int)t.len1, (int)t.len2, n, sm, gap, scores, ends, codes, moves, counts, t.move_words, st);
+}
+
+// p holds `have` elements: reallocated for `need` if that is more
+template <class T> int grow(T *&p, size_t &have, size_t need)
+{
+    if (have >= need) return SWMI_OK;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    have = 0;
+    SWMI_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&p), need * sizeof(T)));
+    have = need;
+    return SWMI_OK;
+}
+
+// one set of device buffers of the host entry (two slices in flight)
+struct HostSet {
+    uint8_t *d1 = nullptr, *d2 = nullptr;
+    int32_t *d_scores = nullptr, *d_ends = nullptr;
+    uint32_t *d_codes = nullptr, *d_counts = nullptr;
+    unsigned long long *d_moves = nullptr;
+    struct { size_t d1, d2, scores, ends, codes, counts, moves; } have{};     // capacity in elements
+    size_t off = 0, m = 0;                                                   // slice in flight
+    void release()
+    {
+        for (void *p : std::initializer_list<void *>{d1, d2, d_scores, d_ends, d_codes, d_counts, d_moves})
+            if (p) (void)hipFree(p);
+        *this = HostSet{};
+    }
+};
+
+// the device buffers of one aligner on one context
+struct TableState {
+    std::mutex mu;                                   // the device-entry workspaces
+    std::map<hipStream_t, Workspace> workspaces;     // codes of one slice per caller stream
+    HostSet sets[2];                                 // host entry, used under Context::mu
+    void release()
+    {
+        for (auto &w : workspaces)
+            if (w.second.ptr) (void)hipFree(w.second.ptr);
+        workspaces.clear();
+        for (auto &s : sets) s.release();
+    }
+    ~TableState() { release(); }
+};
+
+TableState &state(Context &ctx, bool local)
+{
+    std::lock_guard<std::mutex> lock(ctx.ws_mu);
+    std::shared_ptr<void> &p = local ? ctx.local_state : ctx.sgfull_state;
+    if (!p) p = std::make_shared<TableState>();
+    return *static_cast<TableState *>(p.get());
+}
+
+bool len_ok(size_t len, size_t max) { return len >= 1 && len <= max; }
+
+int check_local(size_t len1, const int8_t *sm, int gap)
+{
+    if (!len_ok(len1, SWMI_LOCAL_MAX_LEN)) return fail(SWMI_ERR_INVALID_ARGUMENT, "len1 %zu outside [1, %d]", len1, SWMI_LOCAL_MAX_LEN);
+    return check_params(sm, gap);
+}
+
+int check_sgfull(size_t len1, size_t len2, const int8_t *sm, int gap)
+{
+    if (!len_ok(len1, SWMI_SGFULL_MAX_LEN) || !len_ok(len2, SWMI_SGFULL_MAX_LEN))
+        return fail(SWMI_ERR_INVALID_ARGUMENT, "lengths (%zu, %zu) outside [1, %d]", len1, len2, SWMI_SGFULL_MAX_LEN);
+    return check_params(sm, gap);
+}
+
+// what the timers check before their first call
+int check_timer(size_t n, int iters, const float *avg_ms)
+{
+    if (!avg_ms || iters < 1) return fail(SWMI_ERR_INVALID_ARGUMENT, "avg_ms is NULL or iters %d < 1", iters);
+    if (n == 0) return fail(SWMI_ERR_INVALID_ARGUMENT, "n is 0");
+    return current() ? SWMI_OK : last_status();
+}
+
+size_t slices_for(const Table &t, size_t n, bool tb, size_t *sizes, size_t cap)
+{
+    const size_t s = slice_size(t, n, tb);
+    size_t count = 0;
+    for (size_t off = 0; off < n; off += s, ++count)
+        if (sizes && count < cap) sizes[count] = n - off < s ? n - off : s;
+    return count;
+}
+
+int device(const Table &t, const void *d_seq1s, const void *d_seq2s, size_t n, const int8_t *sm, int gap, void *d_scores, void *d_ends,
+           void *d_moves, void *d_counts, void *stream)
+{
+    if (!d_moves != !d_counts)
+        return fail(SWMI_ERR_INVALID_ARGUMENT, "moves and %s must both be given (traceback) or both be NULL (ends-only)", t.count);
+    if (n == 0) return SWMI_OK;
+    if (!d_seq1s || !d_seq2s || !d_scores || !d_ends) return fail(SWMI_ERR_INVALID_ARGUMENT, "NULL device buffer with n = %zu", n);
+    if ((reinterpret_cast<uintptr_t>(d_seq1s) | reinterpret_cast<uintptr_t>(d_seq2s) | reinterpret_cast<uintptr_t>(d_scores) |
+         reinterpret_cast<uintptr_t>(d_ends) | reinterpret_cast<uintptr_t>(d_moves) | reinterpret_cast<uintptr_t>(d_counts)) & 15)
+        return fail(SWMI_ERR_ALIGNMENT, "device pointers must be 16-byte aligned");
+    Context *ctx = current();
+    if (!ctx) return last_status();
+    const bool tb = d_moves != nullptr;
+    const size_t slice = slice_size(t, n, tb), mw = t.move_words;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    TableState &ts = state(*ctx, t.local);
+    // one workspace per (context, stream), looked up, grown and handed to the launches under one lock (growing waits for
+    // this stream only: earlier launches on it may still use the old one)
+    std::lock_guard<std::mutex> lock(ts.mu);
+    uint32_t *codes = nullptr;
+    if (tb) {
+        Workspace &ws = ts.workspaces[st];
+        const size_t need = slice * t.code_words * sizeof(uint32_t);
+        if (need > ws.bytes) {
+            SWMI_HIP_TRY(hipStreamSynchronize(st));
+            if (ws.ptr) (void)hipFree(ws.ptr);
+            ws.ptr = nullptr;
+            ws.bytes = 0;
+            SWMI_HIP_TRY(hipMalloc(&ws.ptr, need));
+            ws.bytes = need;
+        }
+        codes = static_cast<uint32_t *>(ws.ptr);
+    }
+    const uint8_t *s1 = static_cast<const uint8_t *>(d_seq1s), *s2 = static_cast<const uint8_t *>(d_seq2s);
+    for (size_t off = 0; off < n; off += slice) {
+        const size_t m = n - off < slice ? n - off : slice;
+        SWMI_HIP_TRY(launch(t, s1 + off * t.len1, s2 + off * t.len2, m, sm, gap, static_cast<int32_t *>(d_scores) + off,
+                            static_cast<int32_t *>(d_ends) + t.ends * off, codes,
+                            tb ? static_cast<unsigned long long *>(d_moves) + off * mw : nullptr,
+                            tb ? static_cast<uint32_t *>(d_counts) + off : nullptr, st));
+    }
+    return SWMI_OK;
+}
+
+int host(const Table &t, const char *entry, const uint8_t *seq1s, const uint8_t *seq2s, size_t n, const int8_t *sm, int gap,
+         int32_t *scores, int32_t *ends, uint64_t *moves, uint32_t *counts)
+{
+    if (!moves != !counts)
+        return fail(SWMI_ERR_INVALID_ARGUMENT, "moves and %s must both be given (traceback) or both be NULL (ends-only)", t.count);
+    if (n == 0) return SWMI_OK;
+    if (!seq1s || !seq2s || !scores || !ends) return fail(SWMI_ERR_INVALID_ARGUMENT, "NULL buffer with n = %zu", n);
+    Context *ctx = current();
+    if (!ctx) return last_status();
+    const bool tb = moves != nullptr;
+    const size_t slice = slice_size(t, n, tb), mw = t.move_words, len1 = t.len1, len2 = t.len2;
+    TableState &ts = state(*ctx, t.local);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    HostSet *sets = ts.sets;
+    const int n_sets = n > slice ? 2 : 1;
+    hipStream_t streams[2] = {ctx->slots[0].stream, ctx->slots[1].stream};
+    for (int k = 0; k < n_sets; ++k) {
+        HostSet &s = sets[k];
+        s.off = s.m = 0;
+        int rc = grow(s.d1, s.have.d1, slice * len1);
+        if (rc == SWMI_OK) rc = grow(s.d2, s.have.d2, slice * len2);
+        if (rc == SWMI_OK) rc = grow(s.d_scores, s.have.scores, slice);
+        if (rc == SWMI_OK) rc = grow(s.d_ends, s.have.ends, slice * t.ends);
+        if (rc == SWMI_OK) rc = grow(s.d_counts, s.have.counts, slice);
+        if (rc == SWMI_OK && tb) rc = grow(s.d_codes, s.have.codes, slice * t.code_words);
+        if (rc == SWMI_OK && tb) rc = grow(s.d_moves, s.have.moves, slice * mw);
+        if (rc != SWMI_OK) return rc;
+    }
+    // results of the slice a set holds -> host; only as many move words per alignment as the slice's longest walk needs
+    auto drain = [&](int which) -> hipError_t {
+        HostSet &s = sets[which];
+        hipStream_t st = streams[which];
+        if (s.m == 0) return hipSuccess;
+        hipError_t r = hipMemcpyAsync(scores + s.off, s.d_scores, s.m * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+        if (r == hipSuccess) r = hipMemcpyAsync(ends + t.ends * s.off, s.d_ends, s.m * t.ends * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+        if (r == hipSuccess && tb) r = hipMemcpyAsync(counts + s.off, s.d_counts, s.m * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+        if (r == hipSuccess) r = hipStreamSynchronize(st);
+        if (r == hipSuccess && tb) {
+            uint32_t longest = 0;
+            for (size_t k = 0; k < s.m; ++k) longest = counts[s.off + k] > longest ? counts[s.off + k] : longest;
+            if (longest > t.count_offset) {
+                const size_t pitch = mw * sizeof(uint64_t), words = (longest - t.count_offset + 31) / 32;
+                r = hipMemcpy2DAsync(moves + s.off * mw, pitch, s.d_moves, pitch, words * sizeof(uint64_t), s.m, hipMemcpyDeviceToHost, st);
+                if (r == hipSuccess) r = hipStreamSynchronize(st);
+            }
+        }
+        s.m = 0;
+        return r;
+    };
+    hipError_t e = hipSuccess;
+    int turn = 0;
+    for (size_t off = 0; e == hipSuccess && off < n; off += slice, turn ^= 1) {
+        const int which = n_sets == 2 ? turn : 0;
+        HostSet &s = sets[which];
+        hipStream_t st = streams[which];
+        e = drain(which);                                   // (two slices ago; normally already empty)
+        if (e != hipSuccess) break;
+        s.off = off;
+        s.m = n - off < slice ? n - off : slice;
+        e = hipMemcpyAsync(s.d1, seq1s + off * len1, s.m * len1, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(s.d2, seq2s + off * len2, s.m * len2, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            e = launch(t, s.d1, s.d2, s.m, sm, gap, s.d_scores, s.d_ends, tb ? s.d_codes : nullptr, tb ? s.d_moves : nullptr,
+                       tb ? s.d_counts : nullptr, st);
+        if (e == hipSuccess && n_sets == 2) e = drain(turn ^ 1);         // the previous slice, while this one computes
+    }
+    for (int k = 0; k < n_sets; ++k) {
+        if (e == hipSuccess) e = drain(k);
+        if (e != hipSuccess) (void)hipStreamSynchronize(streams[k]);
+        sets[k].m = 0;
+    }
+    if (e != hipSuccess) return fail(SWMI_ERR_HIP, "%s: %s", entry, hipGetErrorString(e));
+    return SWMI_OK;
+}
+
+// one untimed device call first (it grows the workspace, which synchronises the stream), then HIP events around `iters`
+int time_device(const Table &t, const char *entry, const void *d_seq1s, const void *d_seq2s, size_t n, const int8_t *sm, int gap,
+                void *d_scores, void *d_ends, void *d_moves, void *d_counts, void *stream, int iters, float *avg_ms)
+{
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int rc = device(t, d_seq1s, d_seq2s, n, sm, gap, d_scores, d_ends, d_moves, d_counts, stream);
+    if (rc != SWMI_OK) return rc;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    hipError_t he = hipEventCreate(&ev[0]);
+    if (he == hipSuccess) he = hipEventCreate(&ev[1]);
+    if (he == hipSuccess) he = hipEventRecord(ev[0], st);
+    for (int k = 0; k < iters && he == hipSuccess && rc == SWMI_OK; ++k)
+        rc = device(t, d_seq1s, d_seq2s, n, sm, gap, d_scores, d_ends, d_moves, d_counts, stream);
+    if (he == hipSuccess && rc == SWMI_OK) he = hipEventRecord(ev[1], st);
+    if (he == hipSuccess && rc == SWMI_OK) he = hipEventSynchronize(ev[1]);
+    float ms = 0.f;
+    if (he == hipSuccess && rc == SWMI_OK) he = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    for (auto &x : ev)
+        if (x) (void)hipEventDestroy(x);
+    if (he != hipSuccess) return fail(SWMI_ERR_HIP, "%s: %s", entry, hipGetErrorString(he));
+    if (rc == SWMI_OK) *avg_ms = ms / iters;
+    return rc;
+}
+
+}  // namespace
+}  // namespace host
+}  // namespace swmi
+
+using namespace swmi::host;
+
+extern "C" {
+
+size_t swmi_local_slices_for(size_t n, size_t len1, int traceback, size_t *sizes, size_t cap)
+{
+    return len_ok(len1, SWMI_LOCAL_MAX_LEN) ? slices_for(local_table(len1), n, traceback != 0, sizes, cap) : 0;
+}
+
+int swmi_local_align_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t n, const int8_t score_matrix[16],
+                            int8_t gap_penalty, void *d_scores, void *d_ends, void *d_moves, void *d_steps, void *stream)
+{
+    const int rc = check_local(len1, score_matrix, gap_penalty);
+    if (rc != SWMI_OK) return rc;
+    return device(local_table(len1), d_seq1s, d_seq2s, n, score_matrix, gap_penalty, d_scores, d_ends, d_moves, d_steps, stream);
+}
+
+int swmi_local_align(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t n, const int8_t score_matrix[16],
+                     int8_t gap_penalty, int32_t *scores, int32_t *ends, uint64_t *moves, uint32_t *steps)
+{
+    const int rc = check_local(len1, score_matrix, gap_penalty);
+    if (rc != SWMI_OK) return rc;
+    return host(local_table(len1), __func__, seq1s, seq2s, n, score_matrix, gap_penalty, scores, ends, moves, steps);
+}
+
+int swmi_local_time_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t n, const int8_t score_matrix[16],
+                           int8_t gap_penalty, void *d_scores, void *d_ends, void *d_moves, void *d_steps, void *stream, int iters,
+                           float *avg_ms)
+{
+    int rc = check_timer(n, iters, avg_ms);
+    if (rc == SWMI_OK) rc = check_local(len1, score_matrix, gap_penalty);
+    if (rc != SWMI_OK) return rc;
+    return time_device(local_table(len1), __func__, d_seq1s, d_seq2s, n, score_matrix, gap_penalty, d_scores, d_ends, d_moves,
+                       d_steps, stream, iters, avg_ms);
+}
+
+// The reference's list (source.cpp:1571-1572: from the start cell to the end cell) from the walk's moves: the start cell is
+// the end cell less the moves' row / column steps, and the list applies the moves last to first.
+int swmi_local_expand_moves(const uint64_t *moves, uint32_t steps, int32_t end_i, int32_t end_j, int32_t *positions, size_t cap)
+{
+    if ((!moves && steps) || (!positions && cap)) return fail(SWMI_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (end_i < 0 || end_j < 0 || end_i > SWMI_LOCAL_MAX_LEN || end_j > SWMI_LOCAL_SEQ2_LEN)
+        return fail(SWMI_ERR_INVALID_ARGUMENT, "end cell (%d, %d) outside the matrix", end_i, end_j);
+    if (steps > (uint32_t)end_i + (uint32_t)end_j) return fail(SWMI_ERR_INVALID_ARGUMENT, "%u steps cannot start inside the matrix from (%d, %d)", steps, end_i, end_j);
+    int32_t i = end_i, j = end_j;
+    for (uint32_t t = 0; t < steps; ++t) {
+        const unsigned c = unsigned(moves[t >> 5] >> (2 * (t & 31))) & 3u;
+        if (c == 0) return fail(SWMI_ERR_INVALID_ARGUMENT, "move %u is 0", t);
+        i -= c != 1;
+        j -= c != 2;
+    }
+    if (i < 0 || j < 0) return fail(SWMI_ERR_INVALID_ARGUMENT, "the moves leave the matrix");
+    const size_t count = size_t(steps) + 1 < cap ? size_t(steps) + 1 : cap;
+    for (size_t k = 0; k < count; ++k) {
+        positions[2 * k] = i;
+        positions[2 * k + 1] = j;
+        if (k + 1 < count) {
+            const uint32_t t = steps - 1 - uint32_t(k);          // the move that leads from list position k to k + 1
+            const unsigned c = unsigned(moves[t >> 5] >> (2 * (t & 31))) & 3u;
+            i += c != 1;
+            j += c != 2;
+        }
+    }
+    return SWMI_OK;
+}
+
+size_t swmi_semiglobal_full_slices_for(size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap)
+{
+    if (!len_ok(len1, SWMI_SGFULL_MAX_LEN) || !len_ok(len2, SWMI_SGFULL_MAX_LEN)) return 0;
+    return slices_for(sgfull_table(len1, len2), n, traceback != 0, sizes, cap);
+}
+
+int swmi_semiglobal_full_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
+                                const int8_t score_matrix[16], int8_t gap_penalty, void *d_scores, void *d_ends, void *d_moves,
+                                void *d_lengths, void *stream)
+{
+    const int rc = check_sgfull(len1, len2, score_matrix, gap_penalty);
+    if (rc != SWMI_OK) return rc;
+    return device(sgfull_table(len1, len2), d_seq1s, d_seq2s, n, score_matrix, gap_penalty, d_scores, d_ends,
+                  d_moves, d_lengths, stream);
+}
+
+int swmi_semiglobal_full(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t len2, size_t n,
+                         const int8_t score_matrix[16], int8_t gap_penalty, int32_t *scores, int32_t *ends, uint64_t *moves,
+                         uint32_t *lengths)
+{
+    const int rc = check_sgfull(len1, len2, score_matrix, gap_penalty);
+    if (rc != SWMI_OK) return rc;
+    return host(sgfull_table(len1, len2), __func__, seq1s, seq2s, n, score_matrix, gap_penalty, scores, ends, moves, lengths);
+}
+
+int swmi_semiglobal_full_release_workspaces(void)
+{
+    Context *ctx = current();
+    if (!ctx) return last_status();
+    SWMI_HIP_TRY(hipDeviceSynchronize());
+    TableState &ts = state(*ctx, false);
+    std::lock_guard<std::mutex> host_lock(ctx->mu);
+    std::lock_guard<std::mutex> lock(ts.mu);
+    ts.release();
+    return SWMI_OK;
+}
+
+int swmi_semiglobal_full_time_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
+                                     const int8_t score_matrix[16], int8_t gap_penalty, void *d_scores, void *d_ends, void *d_moves,
+                                     void *d_lengths, void *stream, int iters, float *avg_ms)
+{
+    int rc = check_timer(n, iters, avg_ms);
+    if (rc == SWMI_OK) rc = check_sgfull(len1, len2, score_matrix, gap_penalty);
+    if (rc != SWMI_OK) return rc;
+    return time_device(sgfull_table(len1, len2), __func__, d_seq1s, d_seq2s, n, score_matrix, gap_penalty, d_scores, d_ends,
+                       d_moves, d_lengths, stream, iters, avg_ms);
+}
+
+}  // extern "C"

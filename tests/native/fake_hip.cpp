@@ -1,7 +1,8 @@
 // fake_hip.cpp -- TEST INFRASTRUCTURE ONLY: a recording stand-in for the HIP runtime and for the kernel launchers, so that the
-// product's HOST code (swmi_api.cpp, swmi_multi.cpp) can run its multi-GPU logic on a machine with no GPU at all:
+// product's HOST code (swmi_api.cpp, swmi_multi.cpp, swmi_table.cpp) can run on a machine with no GPU at all:
 // FAKE_HIP_DEVICES "gfx950" devices whose memory is host memory, copies that happen at once -- EXCEPT device-to-host copies on
-// a stream, which are held back until that stream (or the device, or an event) is synchronised and read the device buffer
+// a stream (hipMemcpyAsync and hipMemcpy2DAsync), which are held back until that stream (or the device, or an event) is
+// synchronised and read the device buffer
 // THEN: a host pipeline that lets later kernels overwrite a score buffer before its copy-back has drained hands back wrong
 // scores here, as it would on hardware -- streams and events that only carry an id, and swmi::launch_* stand-ins that write, as the "score" of a pair, the 32-bit number found in the first four
 // bytes of its seq1 -- tests/native/multi_fake.cpp stores the global pair index there, so a gathered score vector must read
@@ -205,22 +206,28 @@ hipError_t hipMemcpyPeerAsync(void *dst, int dst_dev, const void *src, int src_d
     log("dev%d memcpy_peer dst_dev%d src_dev%d bytes%zu stream%d", t_device, dst_dev, src_dev, n, stream_id(s));
     return hipSuccess;
 }
-hipError_t hipMemcpy2DAsync(void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t height, hipMemcpyKind kind, hipStream_t)
+hipError_t hipMemcpy2DAsync(void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t height, hipMemcpyKind kind, hipStream_t s)
 {
+    log("dev%d memcpy2d kind%d width%zu height%zu stream%d", t_device, (int)kind, width, height, stream_id(s));
     if (height) {   // each side spans (height - 1) pitches + one row
         const size_t dst_n = (height - 1) * dpitch + width, src_n = (height - 1) * spitch + width;
         if (kind != hipMemcpyHostToDevice && kind != hipMemcpyDeviceToDevice && kind != hipMemcpyDeviceToHost) check_copy("hipMemcpy2DAsync", dst, src, 0, kind);
         if (kind != hipMemcpyDeviceToHost) check_range("hipMemcpy2DAsync destination", dst, dst_n);
         if (kind != hipMemcpyHostToDevice) check_range("hipMemcpy2DAsync source", src, src_n);
     }
-    for (size_t r = 0; r < height; ++r) memmove(static_cast<char *>(dst) + r * dpitch, static_cast<const char *>(src) + r * spitch, width);
+    for (size_t r = 0; r < height; ++r) {          // (held back like hipMemcpyAsync's device-to-host copies, row by row)
+        char *d = static_cast<char *>(dst) + r * dpitch;
+        const char *from = static_cast<const char *>(src) + r * spitch;
+        if (kind == hipMemcpyDeviceToHost && s) reinterpret_cast<Handle *>(s)->pending.push_back(Pending{d, from, width});
+        else memmove(d, from, width);
+    }
     return hipSuccess;
 }
 hipError_t hipDeviceCanAccessPeer(int *can, int a, int b) { *can = a != b; return hipSuccess; }
 hipError_t hipDeviceEnablePeerAccess(int peer, unsigned) { log("dev%d enable_peer dev%d", t_device, peer); return hipSuccess; }
 }  // extern "C"
 
-// ---- stand-ins for the kernel launchers (sw_kernels.hip / sg_kernels.hip) ----------------------------------------------
+// ---- stand-ins for the kernel launchers (sw_kernels.hip, sg_kernels.hip, local_kernels.hip, sgfull_kernels.hip) -------------
 namespace swmi {
 bool schedule_supported(int L) { return L == 64 || L == 32 || L == 16 || L == 8 || L == 4 || L == 2; }
 static void fake_scores(const uint8_t *s1, size_t stride, int32_t *out, size_t n)
@@ -267,4 +274,55 @@ size_t semiglobal_workspace_bytes(size_t n) { return 64 * (n + 1); }
 hipError_t launch_semiglobal(const uint8_t *, const uint8_t *, size_t, void *, int32_t *, int32_t *, size_t, uint32_t *, hipStream_t, hipEvent_t, int, SgTuning, unsigned long long *) { return hipSuccess; }
 size_t semiglobal_move_words() { return 1040; }
 void semiglobal_kernel_names(size_t, int, char *a, size_t an, char *b, size_t bn, SgTuning) { if (a && an) a[0] = 0; if (b && bn) b[0] = 0; }
+
+// The table aligners (local_kernels.hip, sgfull_kernels.hip).  Their code workspaces take a constant kFakeCodeWords dwords per
+// alignment, not the kernels' formula: a slice is then a few thousand alignments (the exact semi-global traceback budget,
+// 256 alignments of 16384 x 16384, about 11 MiB), so multi-slice batches stay small.  Alignment k of a launch reads its
+// index `id` from the first (up to) four bytes of its seq1 and writes score 2 id + 1, ends[e] = 8 id + e + 3, and with a
+// traceback (id >> 20) % (32 move_words + 1) moves, reported as that + count_offset (local steps: 0, semi-global lengths: 1),
+// and move word w = 0xC0DE << 48 | id << 16 | w in EVERY word of its row.  tests/native/table_host_fake.cpp states the same.
+constexpr size_t kFakeCodeWords = 1024;
+static void fake_table(const char *name, const uint8_t *s1, size_t len1, const uint8_t *s2, size_t len2, size_t n, int32_t *scores,
+                       int32_t *ends, size_t n_ends, uint32_t *codes, unsigned long long *moves, uint32_t *counts, uint32_t count_offset,
+                       size_t move_words, hipStream_t st)
+{
+    log("dev%d %s n%zu stream%d", t_device, name, n, stream_id(st));
+    char what[96];
+    const auto check = [&](const char *operand, const void *p, size_t bytes) {
+        snprintf(what, sizeof what, "%s %s", name, operand);
+        check_range(what, p, bytes);
+    };
+    check("seq1 reads", s1, n * len1);
+    check("seq2 reads", s2, n * len2);
+    check("score writes", scores, n * sizeof(int32_t));
+    check("end writes", ends, n * n_ends * sizeof(int32_t));
+    if (moves) {
+        check("code writes", codes, n * kFakeCodeWords * sizeof(uint32_t));
+        check("move writes", moves, n * move_words * sizeof(uint64_t));
+        check("count writes", counts, n * sizeof(uint32_t));
+    }
+    for (size_t k = 0; k < n; ++k) {
+        uint32_t id = 0;
+        memcpy(&id, s1 + k * len1, len1 < 4 ? len1 : 4);
+        scores[k] = int32_t(2 * id + 1);
+        for (size_t e = 0; e < n_ends; ++e) ends[k * n_ends + e] = int32_t(8 * id + e + 3);
+        if (!moves) continue;
+        counts[k] = uint32_t((id >> 20) % (32 * move_words + 1)) + count_offset;
+        for (size_t w = 0; w < move_words; ++w) moves[k * move_words + w] = 0xC0DEull << 48 | uint64_t(id) << 16 | w;
+    }
+}
+size_t local_code_words(int) { return kFakeCodeWords; }
+hipError_t launch_local(const uint8_t *s1, const uint8_t *s2, int len1, size_t n, const int8_t *, int, int32_t *scores, int32_t *ends,
+                        uint32_t *codes, unsigned long long *moves, uint32_t *steps, size_t move_words, hipStream_t st)
+{
+    fake_table("launch_local", s1, len1, s2, 128, n, scores, ends, 4, codes, moves, steps, 0, move_words, st);
+    return hipSuccess;
+}
+size_t sgfull_code_words(int, int) { return kFakeCodeWords; }
+hipError_t launch_sgfull(const uint8_t *s1, const uint8_t *s2, int len1, int len2, size_t n, const int8_t *, int, int32_t *scores,
+                         int32_t *ends, uint32_t *codes, unsigned long long *moves, uint32_t *lengths, size_t move_words, hipStream_t st)
+{
+    fake_table("launch_sgfull", s1, len1, s2, len2, n, scores, ends, 2, codes, moves, lengths, 1, move_words, st);
+    return hipSuccess;
+}
 }  // namespace swmi
