@@ -7,7 +7,9 @@ the reference's own TestSimdSmithWaterman idea (source.cpp:2943-2982: fresh rand
 Every round generates a fresh batch on the device (counter-based generator, new seed), scores it through the C ABI,
 copies the inputs back and scores them with oracle/liboracle.so on all host cores (OpenMP); any mismatch is dumped.
 A second phase does the same for the semi-global aligner against the reference's simd_mark4 (full tracebacks); a third
-one for the banded affine extension against the oracle's scalar Gotoh (random lengths, matrices, open / extend)."""
+one for the banded affine extension against the oracle's scalar Gotoh (random lengths, matrices, open / extend); a fourth
+and a fifth for the local aligner and the exact semi-global aligner against their C restatements (tests/native/
+local_oracle.c, sgfull_oracle.c): shapes from the grids of tests/table_edges.py and the inputs built there, every field."""
 import argparse, ctypes, os, sys, time
 from concurrent.futures import ThreadPoolExecutor
 import numpy as np
@@ -20,6 +22,8 @@ ap.add_argument("--seconds", type=float, default=120)
 ap.add_argument("--batch", type=int, default=1 << 22)
 ap.add_argument("--sg-seconds", type=float, default=60)
 ap.add_argument("--ba-seconds", type=float, default=30)
+ap.add_argument("--local-seconds", type=float, default=30)
+ap.add_argument("--sgfull-seconds", type=float, default=60)
 args = ap.parse_args()
 swmi.init(0)
 vp = ctypes.c_void_p
@@ -145,3 +149,93 @@ while time.time() < t_end:
     ba_total += m; ba_bad += int((got != want).sum())
 print("banded affine fuzz vs oracle: %d alignments, %d mismatches (11 lengths 64..1792, random matrices, open/extend 0..127 either order); per kernel: %s" % (
     ba_total, ba_bad, ", ".join("%s %d" % kv for kv in sorted(ba_kernels.items()))), flush=True)
+
+# ---- the table aligners vs their C restatements: grid shapes, random shapes, the constructed edge inputs ---------------
+import tempfile
+import table_edges as te
+from local_support import LocalOracle
+from sgfull_support import SgFullOracle
+_tmp = tempfile.mkdtemp()
+lorc, sorc = LocalOracle(_tmp), SgFullOracle(_tmp)
+
+
+def table_params():
+    kind = int(rng.integers(0, 4))
+    if kind == 0:
+        return rng.integers(-128, 128, 16).astype(np.int8), int(rng.integers(0, 128))
+    if kind == 1:
+        return rng.integers(-12, 13, 16).astype(np.int8), int(rng.integers(0, 9))
+    if kind == 2:                        # ties are common
+        return rng.integers(-1, 2, 16).astype(np.int8), int(rng.integers(0, 2))
+    return swmi.match_matrix(int(rng.integers(1, 128)), -int(rng.integers(0, 129))), int(rng.integers(0, 128))
+
+
+def table_round(kind, cases, draw, count_offset):
+    """one batch: a constructed case (its own parameters, or random ones) every third round, else a drawn shape; returns
+    (alignments, mismatching alignments)"""
+    global table_iter
+    table_iter += 1
+    if table_iter % 3 == 0:
+        case = cases[int(rng.integers(0, len(cases)))]
+        a, b = case.a, case.b
+        sm, gap = (case.sm, case.gap) if rng.random() < 0.5 else table_params()
+    else:
+        (a, b), (sm, gap) = draw(), table_params()
+    tb = bool(rng.random() < 0.75)
+    if kind == "local":
+        got, want = swmi.local_align(a, b, sm, gap, traceback=tb), lorc.align(a, b, sm, gap)
+        if not tb:
+            got, want = (got[0], got[1][:, :2], None, None), (want[0], want[1][:, :2], None, None)
+    else:
+        got, want = swmi.semiglobal_full(a, b, sm, gap, traceback=tb), sorc.align(a, b, sm, gap, traceback=tb)
+    bad = 0
+    while True:                          # count every mismatching alignment, report the first
+        diff = te.first_difference(got, want, count_offset, tb)
+        if diff is None:
+            break
+        field, k = diff
+        if bad == 0:
+            print("MISMATCH %s %dx%d gap %d sm %s traceback %d: alignment %d %s" % (kind, a.shape[1], b.shape[1], gap, np.asarray(sm).tolist(),
+                                                                                 tb, k, field), flush=True)
+        bad += 1
+        keep = np.arange(len(got[0])) != k
+        got = tuple(None if x is None else x[keep] for x in got)
+        want = tuple(None if x is None else x[keep] for x in want)
+        a, b = a[keep], b[keep]
+    return len(a) + bad, bad
+
+
+def draw_local():
+    len1 = int(rng.choice(te.LOC_LEN1)) if rng.random() < 0.6 else int(rng.integers(1, te.LOC_MAX_LEN + 1))
+    n = int(rng.choice(te.LOC_N)) if len1 > 4096 else int(rng.integers(1, 300))
+    return te.local_mixed_pairs(n, len1, int(rng.integers(0, 2**62)))
+
+
+def draw_sgfull():
+    if rng.random() < 0.5:
+        len1, len2, n = te.sg_shape_grid()[int(rng.integers(0, len(te.sg_shape_grid())))]
+    else:
+        len1, len2 = int(rng.integers(1, te.SG_MAX_LEN + 1)), int(rng.integers(1, te.SG_MAX_LEN + 1))
+        while len1 * len2 > 1 << 26:
+            len1, len2 = max(1, len1 // 2), max(1, len2 // 2)
+        n = max(1, min(16, (1 << 25) // (len1 * len2)))
+    return te.sg_mixed_pairs(n, len1, len2, int(rng.integers(0, 2**62)))
+
+
+table_iter = 0
+for kind, seconds, cases, draw, offset in (
+        ("local", args.local_seconds, lambda: te.local_insertion_cases() + te.local_tie_cases() + te.local_extreme_cases(), draw_local, 0),
+        ("sgfull", args.sgfull_seconds, lambda: (te.sg_gap_run_cases() + te.sg_staircase_cases() + te.sg_corner_cases()
+                                                 + te.sg_wave_edge_end_cases() + te.sg_tie_cases() + te.sg_pad_cases()), draw_sgfull, 1)):
+    if seconds <= 0:
+        continue
+    built = cases()
+    t_end = time.time() + seconds
+    total = bad = rounds = 0
+    while time.time() < t_end:
+        m, b_ = table_round(kind, built, draw, offset)
+        total += m
+        bad += b_
+        rounds += 1
+    print("%s fuzz vs C restatement: %d rounds, %d alignments (grid and random shapes, random matrices and gaps, constructed "
+          "edge inputs; traceback and ends-only), %d mismatches" % (kind, rounds, total, bad), flush=True)
