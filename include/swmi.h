@@ -340,6 +340,44 @@ SWMI_API int swmi_local_time_device(const void *d_seq1s, size_t len1, const void
                                     const int8_t score_matrix[16], int8_t gap_penalty, void *d_scores, void *d_ends,
                                     void *d_moves, void *d_steps, void *stream, int iters, float *avg_ms);
 
+/* ---- local alignment with AFFINE gaps, end cell, start cell and traceback ---------------------
+ * No reference counterpart: swmi_local_align with Gotoh's gaps, a gap of length k costing gap_open + (k-1) gap_extend (the
+ * convention of swmi_score_banded_affine).  Same inputs, outputs, move encoding and slicing as swmi_local_align; any int8
+ * matrix, gap_open and gap_extend each in [0, 127] in either order, bases taken modulo 4, 1 <= len1 <= 16384.  With
+ * H(0,.) = H(.,0) = 0 and E(0,.) = F(.,0) = -inf, for i = 1..len1, j = 1..128:
+ *     E(i,j) = max(H(i-1,j) - gap_open, E(i-1,j) - gap_extend)      vertical gap: consumes seq1, an up move
+ *     F(i,j) = max(H(i,j-1) - gap_open, F(i,j-1) - gap_extend)      horizontal gap: consumes seq2, a left move
+ *     H(i,j) = max(0, H(i-1,j-1) + sm[seq1[i-1]*4 + seq2[j-1]], E(i,j), F(i,j))
+ * scores[k] = max H; the end cell is the first cell in row-major order holding it ((0, 0) when it is 0).  The walk starts at
+ * the end cell in state H.  State H at (i,j): stop if H = 0 (the start cell); else a diagonal step if H = H(i-1,j-1) + s;
+ * else state E if H = E(i,j); else state F.  State E at (i,j): an up step to (i-1,j), after which the state is H if
+ * E(i,j) = H(i-1,j) - gap_open (opening wins a tie) and stays E otherwise; state F likewise with left steps.  moves +
+ * k * SWMI_LOCAL_MOVE_WORDS(len1) receives the steps in walking order, 3 = diagonal, 2 = up, 1 = left; steps[k] = their
+ * number, so swmi_local_expand_moves rebuilds the (i, j) list.  moves and steps both NULL: ENDS-ONLY (start cell (-1, -1)).
+ * With gap_open == gap_extend == g every field equals swmi_local_align's with gap g.  The score is at most 127 * 128.
+ * Host buffers, in SLICES on two sets of device buffers.  Errors: SWMI_ERR_INVALID_ARGUMENT for len1 outside [1, 16384], a
+ * NULL buffer, or only one of moves / steps; SWMI_ERR_DOMAIN for gap_open or gap_extend outside [0, 127]; n = 0 is a no-op
+ * that needs no device. */
+SWMI_API int swmi_local_align_affine(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t n,
+                                     const int8_t score_matrix[16], int gap_open, int gap_extend, int32_t *scores, int32_t *ends,
+                                     uint64_t *moves, uint32_t *steps);
+/* The slices a swmi_local_align_affine call of n alignments cuts its batch into (traceback = 0: ends-only), in order; returns
+ * how many there are and writes the first `cap` sizes (NULL to count).  With a traceback a slice's device buffers stay within
+ * what 4096 alignments of len1 = 16384 take (about 4.1 GiB: 1 MiB of codes each, 4 bits per cell), so that a full-length slice
+ * gives every CU of an MI355X a workgroup; ends-only slices stay within 256 MiB.  At most 2^20 alignments per slice.  Needs
+ * no device.  0 for len1 outside [1, 16384]. */
+SWMI_API size_t swmi_local_affine_slices_for(size_t n, size_t len1, int traceback, size_t *sizes, size_t cap);
+/* Same with every buffer in device memory (16-byte aligned), asynchronous on `stream`.  The traceback codes go to a workspace
+ * of the library's per (GPU, stream), grown on demand up to one slice and kept until swmi_shutdown(). */
+SWMI_API int swmi_local_align_affine_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t n,
+                                            const int8_t score_matrix[16], int gap_open, int gap_extend, void *d_scores,
+                                            void *d_ends, void *d_moves, void *d_steps, void *stream);
+/* Measurement helper: `iters` swmi_local_align_affine_device calls back to back on `stream`, bracketed by HIP events;
+ * *avg_ms = the average time of one call.  Synchronous. */
+SWMI_API int swmi_local_affine_time_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t n,
+                                           const int8_t score_matrix[16], int gap_open, int gap_extend, void *d_scores,
+                                           void *d_ends, void *d_moves, void *d_steps, void *stream, int iters, float *avg_ms);
+
 /* ---- exact semi-global aligner with traceback (SemiGlobal_111, source.cpp:1776-1834) ------------------------------------
  * The full table of the reference's SemiGlobal_111, with no band and no X-drop: the exact answer that
  * swmi_semiglobal_xdrop approximates.  n alignments of seq1 (len1 bytes, alignment k at seq1s + len1 * k) against seq2

@@ -45,6 +45,12 @@ inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_local_mi35
                                                                                   const std::array<uint8_t, 128> &seq2,
                                                                                   const std::array<int8_t, 16> &score_matrix,
                                                                                   const int8_t gap_penalty);
+// The same local alignment with affine gaps, a gap of length k costing gap_open + (k-1) gap_extend (swmi_local_align_affine:
+// no reference counterpart; open = extend = 1 with (1, -1) is SmithWaterman_111_long).
+inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_affine_mi355x(const std::vector<uint8_t> &seq1,
+                                                                                   const std::array<uint8_t, 128> &seq2,
+                                                                                   const std::array<int8_t, 16> &score_matrix,
+                                                                                   int gap_open, int gap_extend);
 
 // Same arguments, same return value as SemiGlobal_111 (source.cpp:1776-1834): (score, path of (i, j) from (0,0) to the best
 // cell) of the exact semi-global alignment, the full table with no band and no X-drop (swmi_semiglobal_full).  One
@@ -98,6 +104,39 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SmithWaterm
         if (swmi_local_align(a.data(), len1, seq2s[off].data(), m, score_matrix.data(), gap_penalty, scores.data(), ends.data(),
                              moves.data(), steps.data()) != SWMI_OK)
             throw std::runtime_error(std::string("swmi_local_align: ") + swmi_last_error());
+        for (size_t k = 0; k < m; ++k)
+            out[off + k] = {scores[k], expand_local_moves(moves.data() + k * mw, steps[k], ends[4 * k], ends[4 * k + 1])};
+    }
+    return out;
+}
+
+// Affine local alignment of seq1s[k] (every one of the same length) against seq2s[k]: result[k] ==
+// SmithWaterman_affine_mi355x(seq1s[k], seq2s[k], score_matrix, gap_open, gap_extend), in pieces of at most `piece` alignments
+// as SmithWaterman_local_mi355x_batch.
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SmithWaterman_affine_mi355x_batch(
+    const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::array<uint8_t, 128>> &seq2s,
+    const std::array<int8_t, 16> &score_matrix, int gap_open, int gap_extend, size_t piece = 65536)
+{
+    if (seq1s.size() != seq2s.size()) throw std::invalid_argument("SmithWaterman_affine_mi355x_batch: seq1s and seq2s differ in length");
+    const size_t n = seq1s.size();
+    std::vector<std::pair<int, std::vector<std::pair<int, int>>>> out(n);
+    if (n == 0) return out;
+    const size_t len1 = seq1s[0].size();
+    for (const auto &s : seq1s)
+        if (s.size() != len1) throw std::invalid_argument("SmithWaterman_affine_mi355x_batch: every seq1 must have the same length");
+    if (piece == 0) piece = 1;
+    const size_t mw = SWMI_LOCAL_MOVE_WORDS(len1);
+    const size_t m_max = n < piece ? n : piece;
+    std::vector<uint8_t> a(m_max * len1);
+    std::vector<int32_t> scores(m_max), ends(4 * m_max);
+    std::vector<uint64_t> moves(m_max * mw);
+    std::vector<uint32_t> steps(m_max);
+    for (size_t off = 0; off < n; off += piece) {
+        const size_t m = n - off < piece ? n - off : piece;
+        for (size_t k = 0; k < m; ++k) std::copy(seq1s[off + k].begin(), seq1s[off + k].end(), a.begin() + k * len1);
+        if (swmi_local_align_affine(a.data(), len1, seq2s[off].data(), m, score_matrix.data(), gap_open, gap_extend, scores.data(),
+                                    ends.data(), moves.data(), steps.data()) != SWMI_OK)
+            throw std::runtime_error(std::string("swmi_local_align_affine: ") + swmi_last_error());
         for (size_t k = 0; k < m; ++k)
             out[off + k] = {scores[k], expand_local_moves(moves.data() + k * mw, steps[k], ends[4 * k], ends[4 * k + 1])};
     }
@@ -232,6 +271,20 @@ inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_local_mi35
     if (swmi_local_align(seq1.data(), seq1.size(), seq2.data(), 1, score_matrix.data(), gap_penalty, &score, ends, moves.data(),
                          &steps) != SWMI_OK)
         throw std::runtime_error(std::string("swmi_local_align: ") + swmi_last_error());
+    return {score, swmi::expand_local_moves(moves.data(), steps, ends[0], ends[1])};
+}
+
+inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_affine_mi355x(const std::vector<uint8_t> &seq1,
+                                                                                   const std::array<uint8_t, 128> &seq2,
+                                                                                   const std::array<int8_t, 16> &score_matrix,
+                                                                                   int gap_open, int gap_extend)
+{
+    int32_t score = 0, ends[4] = {0, 0, 0, 0};
+    uint32_t steps = 0;
+    std::vector<uint64_t> moves(SWMI_LOCAL_MOVE_WORDS(seq1.size()));
+    if (swmi_local_align_affine(seq1.data(), seq1.size(), seq2.data(), 1, score_matrix.data(), gap_open, gap_extend, &score, ends,
+                                moves.data(), &steps) != SWMI_OK)
+        throw std::runtime_error(std::string("swmi_local_align_affine: ") + swmi_last_error());
     return {score, swmi::expand_local_moves(moves.data(), steps, ends[0], ends[1])};
 }
 

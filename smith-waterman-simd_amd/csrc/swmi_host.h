@@ -171,6 +171,7 @@ struct Context {
     // synchronising the device, and the owner's deleter frees what it holds -- so this file needs no symbol of that one.
     std::shared_ptr<void> local_state;
     std::shared_ptr<void> sgfull_state;
+    std::shared_ptr<void> local_affine_state;   // the affine local aligner's (local_affine_api.cpp through the same pipeline)
     std::mutex mu;                      // serialises use of the slots, the sg sets and the pinned buffer
 };
 
@@ -194,6 +195,37 @@ int launch_device(Context &ctx, const void *d1, const void *d2, size_t n, const 
 // host arrays -> scores through ctx's buffer sets (the body of swmi_score_batch and its relatives); takes ctx.mu
 int score_host_batch(Context &ctx, const uint8_t *s1, const uint8_t *s2, size_t n, const int8_t *sm, int gap,
                      int32_t *out, bool packed, bool one_vs_many);
+
+// ---- the table aligners' slice pipeline (swmi_table.cpp) ----
+// One call of an aligner that fills the whole table, writes codes and walks them: its lengths and parameters checked, and
+// what differs between the aligners as data -- how a slice launches, which Context member holds its device buffers, and
+// how much device memory a traceback slice may take.  Ends-only slices always take at most kTableSliceBytes.
+struct Table;
+using TableLaunch = hipError_t (*)(const Table &t, const uint8_t *s1, const uint8_t *s2, size_t n, int32_t *scores, int32_t *ends,
+                                   uint32_t *codes, unsigned long long *moves, uint32_t *counts, hipStream_t st);
+struct Table {
+    TableLaunch launch;
+    std::shared_ptr<void> Context::*state;      // created on first use under Context::ws_mu, dropped by destroy_context
+    size_t tb_slice_bytes;      // device bytes of one traceback slice's buffers
+    const char *count;          // name of the per-alignment count array: "steps" (= moves) or "lengths" (= moves + 1)
+    size_t len1, len2;          // len2 = SWMI_LOCAL_SEQ2_LEN for the local aligners
+    size_t ends;                // int32 of `ends` per alignment
+    size_t code_words, move_words;
+    uint32_t count_offset;      // count = moves + count_offset
+    const int8_t *sm;
+    int gap, gap_extend;        // gap_extend: the affine aligner's (gap is then the open cost)
+};
+constexpr size_t kTableSliceBytes = size_t(256) << 20;
+constexpr size_t kTableMaxSlice = size_t(1) << 20;     // alignments per slice (and per launch)
+size_t table_slice_bytes(const Table &t, bool tb);     // device bytes of one alignment of a slice
+size_t table_slices_for(const Table &t, size_t n, bool tb, size_t *sizes, size_t cap);
+int table_device(const Table &t, const void *d_seq1s, const void *d_seq2s, size_t n, void *d_scores, void *d_ends, void *d_moves,
+                 void *d_counts, void *stream);
+int table_host(const Table &t, const char *entry, const uint8_t *seq1s, const uint8_t *seq2s, size_t n, int32_t *scores,
+               int32_t *ends, uint64_t *moves, uint32_t *counts);
+int table_time_device(const Table &t, const char *entry, const void *d_seq1s, const void *d_seq2s, size_t n, void *d_scores,
+                      void *d_ends, void *d_moves, void *d_counts, void *stream, int iters, float *avg_ms);
+int table_check_timer(size_t n, int iters, const float *avg_ms);   // what the timers check before their first call
 
 #define SWMI_HIP_TRY(expr)                                                                                          \
     do {                                                                                                            \

@@ -86,6 +86,15 @@ hipError_t launch_local(const uint8_t *d_seq1s, const uint8_t *d_seq2s, int len1
 }  // namespace swmi
 
 namespace swmi {
+// Affine-gap local aligner with end / start cell and traceback (local_affine_kernels.hip): launch_local's shapes, with
+// local_affine_code_words(len1) dwords of codes per alignment of the launch.
+size_t local_affine_code_words(int len1);
+hipError_t launch_local_affine(const uint8_t *d_seq1s, const uint8_t *d_seq2s, int len1, size_t n, const int8_t *sm, int gap_open,
+                               int gap_extend, int32_t *d_scores, int32_t *d_ends, uint32_t *d_codes, unsigned long long *d_moves,
+                               uint32_t *d_steps, size_t move_words, hipStream_t stream);
+}  // namespace swmi
+
+namespace swmi {
 // Exact semi-global aligner with traceback (sgfull_kernels.hip).  n alignments of seq1 (len1 bytes each, at d_seq1s +
 // len1 * k) against seq2 (len2 bytes each, at d_seq2s + len2 * k), one workgroup of sgfull_waves(len2) wavefronts each;
 // d_codes holds sgfull_code_words(len1, len2) dwords per alignment of the launch; d_ends two int32 per alignment.

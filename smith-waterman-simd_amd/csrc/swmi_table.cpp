@@ -1,10 +1,13 @@
-// swmi_table.cpp -- host side of the two aligners that fill the whole table, write 2-bit codes and walk them (include/swmi.h):
-// the local aligner with end cell, start cell and traceback (swmi_local_*) and the exact semi-global
-// aligner with traceback (swmi_semiglobal_full*, section 13).  What differs between the two is data (struct Table).
+// swmi_table.cpp -- host side of the aligners that fill the whole table, write codes and walk them (include/swmi.h): the local
+// aligner with end cell, start cell and traceback (swmi_local_*) and the exact semi-global aligner with
+// traceback (swmi_semiglobal_full*, section 13) here, and the one slice pipeline that they and the affine local aligner
+// (local_affine_api.cpp, section 14) run through.  What differs between them is data (struct Table, swmi_host.h).
 //
-// Their device buffers hang off Context::local_state and Context::sgfull_state, which destroy_context (swmi_api.cpp) drops
-// at swmi_shutdown: that file names no symbol of this one, so the host-only builds of swmi_api.cpp / swmi_multi.cpp
-// (tests/test_multi_fake.py, tests/test_sanitizers.py) link without these kernels.
+// Their device buffers hang off Context::local_state, sgfull_state and local_affine_state, which destroy_context
+// (swmi_api.cpp) drops at swmi_shutdown: that file names no symbol of this one, so the host-only builds of swmi_api.cpp /
+// swmi_multi.cpp (tests/test_multi_fake.py, tests/test_sanitizers.py) link without these kernels -- and this file names no
+// launcher but launch_local and launch_sgfull, so that the fake-GPU build of every swmi_*.cpp (tests/test_table_host_fake.py)
+// links without the affine kernels.
 #include "swmi_host.h"
 
 #include <initializer_list>
@@ -13,54 +16,44 @@ namespace swmi {
 namespace host {
 namespace {
 
-constexpr size_t kSliceBytes = size_t(256) << 20;   // device memory of one slice's buffers (but an exact semi-global traceback's)
-constexpr size_t kMaxSlice = size_t(1) << 20;       // alignments per slice (and per launch)
-
-// One call of either aligner, its lengths checked
-struct Table {
-    bool local;                 // launch_local, else launch_sgfull
-    const char *count;          // name of the per-alignment count array: "steps" (= moves) or "lengths" (= moves + 1)
-    size_t len1, len2;          // len2 = SWMI_LOCAL_SEQ2_LEN for the local aligner
-    size_t ends;                // int32 of `ends` per alignment
-    size_t code_words, move_words;
-    uint32_t count_offset;      // count = moves + count_offset
-};
-
-Table local_table(size_t len1)
+hipError_t launch_local_slice(const Table &t, const uint8_t *s1, const uint8_t *s2, size_t n, int32_t *scores, int32_t *ends,
+                              uint32_t *codes, unsigned long long *moves, uint32_t *counts, hipStream_t st)
 {
-    return {true, "steps", len1, SWMI_LOCAL_SEQ2_LEN, 4, swmi::local_code_words((int)len1), SWMI_LOCAL_MOVE_WORDS(len1), 0};
+    return swmi::launch_local(s1, s2, (int)t.len1, n, t.sm, t.gap, scores, ends, codes, moves, counts, t.move_words, st);
 }
 
-Table sgfull_table(size_t len1, size_t len2)
+hipError_t launch_sgfull_slice(const Table &t, const uint8_t *s1, const uint8_t *s2, size_t n, int32_t *scores, int32_t *ends,
+                               uint32_t *codes, unsigned long long *moves, uint32_t *counts, hipStream_t st)
 {
-    return {false, "lengths", len1, len2, 2, swmi::sgfull_code_words((int)len1, (int)len2), SWMI_SGFULL_MOVE_WORDS(len1, len2), 1};
+    return swmi::launch_sgfull(s1, s2, (int)t.len1, (int)t.len2, n, t.sm, t.gap, scores, ends, codes, moves, counts, t.move_words, st);
 }
 
-// device bytes one alignment of a slice takes: inputs, results, and with a traceback the codes, the moves and the count
-size_t bytes_per_alignment(const Table &t, bool tb)
+Table local_table(size_t len1, const int8_t *sm, int gap)
 {
-    size_t b = t.len1 + t.len2 + sizeof(int32_t) + t.ends * sizeof(int32_t);
-    if (tb) b += t.code_words * sizeof(uint32_t) + t.move_words * sizeof(uint64_t) + sizeof(uint32_t);
-    return b;
+    return {launch_local_slice, &Context::local_state, kTableSliceBytes, "steps", len1, SWMI_LOCAL_SEQ2_LEN, 4,
+            swmi::local_code_words((int)len1), SWMI_LOCAL_MOVE_WORDS(len1), 0, sm, gap, 0};
 }
 
 // An exact semi-global traceback slice holds as many alignments as 256 of 16384 x 16384 (about 16.1 GiB): one workgroup per
-// alignment, so that a full-size batch occupies every CU of an MI355X.  Every other slice holds 256 MiB.
-size_t slice_size(const Table &t, size_t n, bool tb)
+// alignment, so that a full-size batch occupies every CU of an MI355X.
+Table sgfull_table(size_t len1, size_t len2, const int8_t *sm, int gap)
 {
-    const size_t budget =
-        tb && !t.local ? 256 * bytes_per_alignment(sgfull_table(SWMI_SGFULL_MAX_LEN, SWMI_SGFULL_MAX_LEN), true) : kSliceBytes;
-    size_t s = budget / bytes_per_alignment(t, tb);
-    if (s > kMaxSlice) s = kMaxSlice;
-    if (s < 1) s = 1;
-    return n < s ? n : s;
+    Table t{launch_sgfull_slice, &Context::sgfull_state, 0, "lengths", len1, len2, 2, swmi::sgfull_code_words((int)len1, (int)len2),
+            SWMI_SGFULL_MOVE_WORDS(len1, len2), 1, sm, gap, 0};
+    Table full = t;
+    full.len1 = full.len2 = SWMI_SGFULL_MAX_LEN;
+    full.code_words = swmi::sgfull_code_words(SWMI_SGFULL_MAX_LEN, SWMI_SGFULL_MAX_LEN);
+    full.move_words = SWMI_SGFULL_MOVE_WORDS(SWMI_SGFULL_MAX_LEN, SWMI_SGFULL_MAX_LEN);
+    t.tb_slice_bytes = 256 * table_slice_bytes(full, true);
+    return t;
 }
 
-hipError_t launch(const Table &t, const uint8_t *s1, const uint8_t *s2, size_t n, const int8_t *sm, int gap, int32_t *scores,
-                  int32_t *ends, uint32_t *codes, unsigned long long *moves, uint32_t *counts, hipStream_t st)
+size_t slice_size(const Table &t, size_t n, bool tb)
 {
-    if (t.local) return swmi::launch_local(s1, s2, (int)t.len1, n, sm, gap, scores, ends, codes, moves, counts, t.move_words, st);
-    return swmi::launch_sgfull(s1, s2, (int)t.len1, (int)t.len2, n, sm, gap, scores, ends, codes, moves, counts, t.move_words, st);
+    size_t s = (tb ? t.tb_slice_bytes : kTableSliceBytes) / table_slice_bytes(t, tb);
+    if (s > kTableMaxSlice) s = kTableMaxSlice;
+    if (s < 1) s = 1;
+    return n < s ? n : s;
 }
 
 // p holds `have` elements: reallocated for `need` if that is more
@@ -106,10 +99,10 @@ struct TableState {
     ~TableState() { release(); }
 };
 
-TableState &state(Context &ctx, bool local)
+TableState &state(Context &ctx, std::shared_ptr<void> Context::*member)
 {
     std::lock_guard<std::mutex> lock(ctx.ws_mu);
-    std::shared_ptr<void> &p = local ? ctx.local_state : ctx.sgfull_state;
+    std::shared_ptr<void> &p = ctx.*member;
     if (!p) p = std::make_shared<TableState>();
     return *static_cast<TableState *>(p.get());
 }
@@ -129,15 +122,24 @@ int check_sgfull(size_t len1, size_t len2, const int8_t *sm, int gap)
     return check_params(sm, gap);
 }
 
-// what the timers check before their first call
-int check_timer(size_t n, int iters, const float *avg_ms)
+}  // namespace
+
+// device bytes one alignment of a slice takes: inputs, results, and with a traceback the codes, the moves and the count
+size_t table_slice_bytes(const Table &t, bool tb)
+{
+    size_t b = t.len1 + t.len2 + sizeof(int32_t) + t.ends * sizeof(int32_t);
+    if (tb) b += t.code_words * sizeof(uint32_t) + t.move_words * sizeof(uint64_t) + sizeof(uint32_t);
+    return b;
+}
+
+int table_check_timer(size_t n, int iters, const float *avg_ms)
 {
     if (!avg_ms || iters < 1) return fail(SWMI_ERR_INVALID_ARGUMENT, "avg_ms is NULL or iters %d < 1", iters);
     if (n == 0) return fail(SWMI_ERR_INVALID_ARGUMENT, "n is 0");
     return current() ? SWMI_OK : last_status();
 }
 
-size_t slices_for(const Table &t, size_t n, bool tb, size_t *sizes, size_t cap)
+size_t table_slices_for(const Table &t, size_t n, bool tb, size_t *sizes, size_t cap)
 {
     const size_t s = slice_size(t, n, tb);
     size_t count = 0;
@@ -146,8 +148,8 @@ size_t slices_for(const Table &t, size_t n, bool tb, size_t *sizes, size_t cap)
     return count;
 }
 
-int device(const Table &t, const void *d_seq1s, const void *d_seq2s, size_t n, const int8_t *sm, int gap, void *d_scores, void *d_ends,
-           void *d_moves, void *d_counts, void *stream)
+int table_device(const Table &t, const void *d_seq1s, const void *d_seq2s, size_t n, void *d_scores, void *d_ends, void *d_moves,
+                 void *d_counts, void *stream)
 {
     if (!d_moves != !d_counts)
         return fail(SWMI_ERR_INVALID_ARGUMENT, "moves and %s must both be given (traceback) or both be NULL (ends-only)", t.count);
@@ -161,7 +163,7 @@ int device(const Table &t, const void *d_seq1s, const void *d_seq2s, size_t n, c
     const bool tb = d_moves != nullptr;
     const size_t slice = slice_size(t, n, tb), mw = t.move_words;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    TableState &ts = state(*ctx, t.local);
+    TableState &ts = state(*ctx, t.state);
     // one workspace per (context, stream), looked up, grown and handed to the launches under one lock (growing waits for
     // this stream only: earlier launches on it may still use the old one)
     std::lock_guard<std::mutex> lock(ts.mu);
@@ -182,16 +184,16 @@ int device(const Table &t, const void *d_seq1s, const void *d_seq2s, size_t n, c
     const uint8_t *s1 = static_cast<const uint8_t *>(d_seq1s), *s2 = static_cast<const uint8_t *>(d_seq2s);
     for (size_t off = 0; off < n; off += slice) {
         const size_t m = n - off < slice ? n - off : slice;
-        SWMI_HIP_TRY(launch(t, s1 + off * t.len1, s2 + off * t.len2, m, sm, gap, static_cast<int32_t *>(d_scores) + off,
-                            static_cast<int32_t *>(d_ends) + t.ends * off, codes,
-                            tb ? static_cast<unsigned long long *>(d_moves) + off * mw : nullptr,
-                            tb ? static_cast<uint32_t *>(d_counts) + off : nullptr, st));
+        SWMI_HIP_TRY(t.launch(t, s1 + off * t.len1, s2 + off * t.len2, m, static_cast<int32_t *>(d_scores) + off,
+                              static_cast<int32_t *>(d_ends) + t.ends * off, codes,
+                              tb ? static_cast<unsigned long long *>(d_moves) + off * mw : nullptr,
+                              tb ? static_cast<uint32_t *>(d_counts) + off : nullptr, st));
     }
     return SWMI_OK;
 }
 
-int host(const Table &t, const char *entry, const uint8_t *seq1s, const uint8_t *seq2s, size_t n, const int8_t *sm, int gap,
-         int32_t *scores, int32_t *ends, uint64_t *moves, uint32_t *counts)
+int table_host(const Table &t, const char *entry, const uint8_t *seq1s, const uint8_t *seq2s, size_t n, int32_t *scores,
+               int32_t *ends, uint64_t *moves, uint32_t *counts)
 {
     if (!moves != !counts)
         return fail(SWMI_ERR_INVALID_ARGUMENT, "moves and %s must both be given (traceback) or both be NULL (ends-only)", t.count);
@@ -201,7 +203,7 @@ int host(const Table &t, const char *entry, const uint8_t *seq1s, const uint8_t 
     if (!ctx) return last_status();
     const bool tb = moves != nullptr;
     const size_t slice = slice_size(t, n, tb), mw = t.move_words, len1 = t.len1, len2 = t.len2;
-    TableState &ts = state(*ctx, t.local);
+    TableState &ts = state(*ctx, t.state);
     std::lock_guard<std::mutex> lock(ctx->mu);
     HostSet *sets = ts.sets;
     const int n_sets = n > slice ? 2 : 1;
@@ -252,8 +254,8 @@ int host(const Table &t, const char *entry, const uint8_t *seq1s, const uint8_t 
         e = hipMemcpyAsync(s.d1, seq1s + off * len1, s.m * len1, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(s.d2, seq2s + off * len2, s.m * len2, hipMemcpyHostToDevice, st);
         if (e == hipSuccess)
-            e = launch(t, s.d1, s.d2, s.m, sm, gap, s.d_scores, s.d_ends, tb ? s.d_codes : nullptr, tb ? s.d_moves : nullptr,
-                       tb ? s.d_counts : nullptr, st);
+            e = t.launch(t, s.d1, s.d2, s.m, s.d_scores, s.d_ends, tb ? s.d_codes : nullptr, tb ? s.d_moves : nullptr,
+                         tb ? s.d_counts : nullptr, st);
         if (e == hipSuccess && n_sets == 2) e = drain(turn ^ 1);         // the previous slice, while this one computes
     }
     for (int k = 0; k < n_sets; ++k) {
@@ -266,18 +268,18 @@ int host(const Table &t, const char *entry, const uint8_t *seq1s, const uint8_t 
 }
 
 // one untimed device call first (it grows the workspace, which synchronises the stream), then HIP events around `iters`
-int time_device(const Table &t, const char *entry, const void *d_seq1s, const void *d_seq2s, size_t n, const int8_t *sm, int gap,
-                void *d_scores, void *d_ends, void *d_moves, void *d_counts, void *stream, int iters, float *avg_ms)
+int table_time_device(const Table &t, const char *entry, const void *d_seq1s, const void *d_seq2s, size_t n, void *d_scores,
+                      void *d_ends, void *d_moves, void *d_counts, void *stream, int iters, float *avg_ms)
 {
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int rc = device(t, d_seq1s, d_seq2s, n, sm, gap, d_scores, d_ends, d_moves, d_counts, stream);
+    int rc = table_device(t, d_seq1s, d_seq2s, n, d_scores, d_ends, d_moves, d_counts, stream);
     if (rc != SWMI_OK) return rc;
     hipEvent_t ev[2] = {nullptr, nullptr};
     hipError_t he = hipEventCreate(&ev[0]);
     if (he == hipSuccess) he = hipEventCreate(&ev[1]);
     if (he == hipSuccess) he = hipEventRecord(ev[0], st);
     for (int k = 0; k < iters && he == hipSuccess && rc == SWMI_OK; ++k)
-        rc = device(t, d_seq1s, d_seq2s, n, sm, gap, d_scores, d_ends, d_moves, d_counts, stream);
+        rc = table_device(t, d_seq1s, d_seq2s, n, d_scores, d_ends, d_moves, d_counts, stream);
     if (he == hipSuccess && rc == SWMI_OK) he = hipEventRecord(ev[1], st);
     if (he == hipSuccess && rc == SWMI_OK) he = hipEventSynchronize(ev[1]);
     float ms = 0.f;
@@ -289,7 +291,6 @@ int time_device(const Table &t, const char *entry, const void *d_seq1s, const vo
     return rc;
 }
 
-}  // namespace
 }  // namespace host
 }  // namespace swmi
 
@@ -299,7 +300,7 @@ extern "C" {
 
 size_t swmi_local_slices_for(size_t n, size_t len1, int traceback, size_t *sizes, size_t cap)
 {
-    return len_ok(len1, SWMI_LOCAL_MAX_LEN) ? slices_for(local_table(len1), n, traceback != 0, sizes, cap) : 0;
+    return len_ok(len1, SWMI_LOCAL_MAX_LEN) ? table_slices_for(local_table(len1, nullptr, 0), n, traceback != 0, sizes, cap) : 0;
 }
 
 int swmi_local_align_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t n, const int8_t score_matrix[16],
@@ -307,7 +308,7 @@ int swmi_local_align_device(const void *d_seq1s, size_t len1, const void *d_seq2
 {
     const int rc = check_local(len1, score_matrix, gap_penalty);
     if (rc != SWMI_OK) return rc;
-    return device(local_table(len1), d_seq1s, d_seq2s, n, score_matrix, gap_penalty, d_scores, d_ends, d_moves, d_steps, stream);
+    return table_device(local_table(len1, score_matrix, gap_penalty), d_seq1s, d_seq2s, n, d_scores, d_ends, d_moves, d_steps, stream);
 }
 
 int swmi_local_align(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t n, const int8_t score_matrix[16],
@@ -315,18 +316,18 @@ int swmi_local_align(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, si
 {
     const int rc = check_local(len1, score_matrix, gap_penalty);
     if (rc != SWMI_OK) return rc;
-    return host(local_table(len1), __func__, seq1s, seq2s, n, score_matrix, gap_penalty, scores, ends, moves, steps);
+    return table_host(local_table(len1, score_matrix, gap_penalty), __func__, seq1s, seq2s, n, scores, ends, moves, steps);
 }
 
 int swmi_local_time_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t n, const int8_t score_matrix[16],
                            int8_t gap_penalty, void *d_scores, void *d_ends, void *d_moves, void *d_steps, void *stream, int iters,
                            float *avg_ms)
 {
-    int rc = check_timer(n, iters, avg_ms);
+    int rc = table_check_timer(n, iters, avg_ms);
     if (rc == SWMI_OK) rc = check_local(len1, score_matrix, gap_penalty);
     if (rc != SWMI_OK) return rc;
-    return time_device(local_table(len1), __func__, d_seq1s, d_seq2s, n, score_matrix, gap_penalty, d_scores, d_ends, d_moves,
-                       d_steps, stream, iters, avg_ms);
+    return table_time_device(local_table(len1, score_matrix, gap_penalty), __func__, d_seq1s, d_seq2s, n, d_scores, d_ends, d_moves,
+                             d_steps, stream, iters, avg_ms);
 }
 
 // The reference's list (source.cpp:1571-1572: from the start cell to the end cell) from the walk's moves: the start cell is
@@ -362,7 +363,7 @@ int swmi_local_expand_moves(const uint64_t *moves, uint32_t steps, int32_t end_i
 size_t swmi_semiglobal_full_slices_for(size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap)
 {
     if (!len_ok(len1, SWMI_SGFULL_MAX_LEN) || !len_ok(len2, SWMI_SGFULL_MAX_LEN)) return 0;
-    return slices_for(sgfull_table(len1, len2), n, traceback != 0, sizes, cap);
+    return table_slices_for(sgfull_table(len1, len2, nullptr, 0), n, traceback != 0, sizes, cap);
 }
 
 int swmi_semiglobal_full_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
@@ -371,8 +372,8 @@ int swmi_semiglobal_full_device(const void *d_seq1s, size_t len1, const void *d_
 {
     const int rc = check_sgfull(len1, len2, score_matrix, gap_penalty);
     if (rc != SWMI_OK) return rc;
-    return device(sgfull_table(len1, len2), d_seq1s, d_seq2s, n, score_matrix, gap_penalty, d_scores, d_ends,
-                  d_moves, d_lengths, stream);
+    return table_device(sgfull_table(len1, len2, score_matrix, gap_penalty), d_seq1s, d_seq2s, n, d_scores, d_ends, d_moves,
+                        d_lengths, stream);
 }
 
 int swmi_semiglobal_full(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t len2, size_t n,
@@ -381,7 +382,7 @@ int swmi_semiglobal_full(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s
 {
     const int rc = check_sgfull(len1, len2, score_matrix, gap_penalty);
     if (rc != SWMI_OK) return rc;
-    return host(sgfull_table(len1, len2), __func__, seq1s, seq2s, n, score_matrix, gap_penalty, scores, ends, moves, lengths);
+    return table_host(sgfull_table(len1, len2, score_matrix, gap_penalty), __func__, seq1s, seq2s, n, scores, ends, moves, lengths);
 }
 
 int swmi_semiglobal_full_release_workspaces(void)
@@ -389,7 +390,7 @@ int swmi_semiglobal_full_release_workspaces(void)
     Context *ctx = current();
     if (!ctx) return last_status();
     SWMI_HIP_TRY(hipDeviceSynchronize());
-    TableState &ts = state(*ctx, false);
+    TableState &ts = state(*ctx, &Context::sgfull_state);
     std::lock_guard<std::mutex> host_lock(ctx->mu);
     std::lock_guard<std::mutex> lock(ts.mu);
     ts.release();
@@ -400,11 +401,11 @@ int swmi_semiglobal_full_time_device(const void *d_seq1s, size_t len1, const voi
                                      const int8_t score_matrix[16], int8_t gap_penalty, void *d_scores, void *d_ends, void *d_moves,
                                      void *d_lengths, void *stream, int iters, float *avg_ms)
 {
-    int rc = check_timer(n, iters, avg_ms);
+    int rc = table_check_timer(n, iters, avg_ms);
     if (rc == SWMI_OK) rc = check_sgfull(len1, len2, score_matrix, gap_penalty);
     if (rc != SWMI_OK) return rc;
-    return time_device(sgfull_table(len1, len2), __func__, d_seq1s, d_seq2s, n, score_matrix, gap_penalty, d_scores, d_ends,
-                       d_moves, d_lengths, stream, iters, avg_ms);
+    return table_time_device(sgfull_table(len1, len2, score_matrix, gap_penalty), __func__, d_seq1s, d_seq2s, n, d_scores, d_ends,
+                             d_moves, d_lengths, stream, iters, avg_ms);
 }
 
 }  // extern "C"

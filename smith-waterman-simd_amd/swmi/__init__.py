@@ -124,6 +124,12 @@ def load():
     lib.swmi_local_slices_for.restype = sz
     lib.swmi_local_expand_moves.argtypes = [vp, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32, vp, sz]
     lib.swmi_local_time_device.argtypes = [vp, sz, vp, sz, vp, i8, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
+    ci = ctypes.c_int
+    lib.swmi_local_align_affine.argtypes = [vp, sz, vp, sz, vp, ci, ci, vp, vp, vp, vp]
+    lib.swmi_local_align_affine_device.argtypes = [vp, sz, vp, sz, vp, ci, ci, vp, vp, vp, vp, vp]
+    lib.swmi_local_affine_slices_for.argtypes = [sz, sz, ci, vp, sz]
+    lib.swmi_local_affine_slices_for.restype = sz
+    lib.swmi_local_affine_time_device.argtypes = [vp, sz, vp, sz, vp, ci, ci, vp, vp, vp, vp, vp, ci, ctypes.POINTER(ctypes.c_float)]
     lib.swmi_semiglobal_full.argtypes = [vp, sz, vp, sz, sz, vp, i8, vp, vp, vp, vp]
     lib.swmi_semiglobal_full_device.argtypes = [vp, sz, vp, sz, sz, vp, i8, vp, vp, vp, vp, vp]
     lib.swmi_semiglobal_full_slices_for.argtypes = [sz, sz, sz, ctypes.c_int, vp, sz]
@@ -575,6 +581,53 @@ def local_slices_for(n, len1, traceback=True):
     count = load().swmi_local_slices_for(n, len1, 1 if traceback else 0, None, 0)
     buf = (ctypes.c_size_t * max(count, 1))()
     load().swmi_local_slices_for(n, len1, 1 if traceback else 0, buf, count)
+    return [int(buf[k]) for k in range(count)]
+
+
+def local_align_affine(seq1s, seq2s, score_matrix, gap_open, gap_extend, traceback=True):
+    """Local alignment with affine gaps, end cell, start cell and traceback (swmi_local_align_affine): a gap of length k costs
+    gap_open + (k-1) gap_extend.  Same arguments and return value as local_align, with (gap_open, gap_extend) for the gap."""
+    a = np.ascontiguousarray(seq1s, dtype=np.uint8)
+    if a.ndim != 2:
+        raise ValueError("seq1s must be (n, len1)")
+    b = _u8(seq2s, LOCAL_SEQ2_LEN).reshape(-1, LOCAL_SEQ2_LEN)
+    n, len1 = a.shape
+    if b.shape[0] != n:
+        raise ValueError("seq1s and seq2s hold different numbers of sequences")
+    sm = _sm(score_matrix)
+    scores = np.zeros(n, np.int32)
+    ends = np.zeros((n, 4), np.int32)
+    moves = np.zeros((n, local_move_words(max(len1, 1))), np.uint64) if traceback else None
+    steps = np.zeros(n, np.uint32) if traceback else None
+    _check(load().swmi_local_align_affine(a.ctypes.data, len1, b.ctypes.data, n, sm.ctypes.data, int(gap_open), int(gap_extend),
+                                          scores.ctypes.data, ends.ctypes.data, moves.ctypes.data if traceback else None,
+                                          steps.ctypes.data if traceback else None))
+    return scores, ends, moves, steps
+
+
+def local_align_affine_device(d_seq1s, len1, d_seq2s, n, score_matrix, gap_open, gap_extend, d_scores, d_ends, d_moves=None,
+                              d_steps=None, stream=0):
+    """swmi_local_align_affine_device on device pointers (asynchronous on `stream`); d_moves = d_steps = None: ends-only."""
+    sm = _sm(score_matrix)
+    _check(load().swmi_local_align_affine_device(d_seq1s, len1, d_seq2s, n, sm.ctypes.data, int(gap_open), int(gap_extend), d_scores,
+                                                 d_ends, d_moves, d_steps, stream))
+
+
+def local_affine_time_device(d_seq1s, len1, d_seq2s, n, score_matrix, gap_open, gap_extend, d_scores, d_ends, d_moves=None,
+                             d_steps=None, stream=0, iters=10):
+    """Average ms of one swmi_local_align_affine_device call over `iters` back-to-back calls (HIP events on `stream`)."""
+    sm = _sm(score_matrix)
+    ms = ctypes.c_float()
+    _check(load().swmi_local_affine_time_device(d_seq1s, len1, d_seq2s, n, sm.ctypes.data, int(gap_open), int(gap_extend), d_scores,
+                                                d_ends, d_moves, d_steps, stream, int(iters), ctypes.byref(ms)))
+    return float(ms.value)
+
+
+def local_affine_slices_for(n, len1, traceback=True):
+    """The slices swmi_local_align_affine cuts n alignments into (needs no device)."""
+    count = load().swmi_local_affine_slices_for(n, len1, 1 if traceback else 0, None, 0)
+    buf = (ctypes.c_size_t * max(count, 1))()
+    load().swmi_local_affine_slices_for(n, len1, 1 if traceback else 0, buf, count)
     return [int(buf[k]) for k in range(count)]
 
 
