@@ -378,6 +378,45 @@ SWMI_API int swmi_local_affine_time_device(const void *d_seq1s, size_t len1, con
                                            const int8_t score_matrix[16], int gap_open, int gap_extend, void *d_scores,
                                            void *d_ends, void *d_moves, void *d_steps, void *stream, int iters, float *avg_ms);
 
+/* ---- the local aligners on a batch of MIXED seq1 lengths --------------------------------------------
+ * swmi_local_align and swmi_local_align_affine with one seq1 length per alignment, as the reference's SmithWaterman_111_long
+ * (source.cpp:1526) takes a seq1 of any length.  Alignment k is seq1 = bytes [seq1_offsets[k], seq1_offsets[k+1]) of seq1s
+ * against the 128-mer at seq2s + 128 k; seq1_offsets holds n + 1 non-decreasing entries, and every length is in [0, 16384].
+ * A length of 0 gives score 0, ends (0, 0, 0, 0) and 0 steps (ends-only: (0, 0, -1, -1)), and reads no seq1 byte.  scores,
+ * ends and steps are those of the fixed-length entries, in caller order, with the same semantics, tie rules and move
+ * encoding.  Alignment k's moves start at word move_offsets[k] = the sum over m < k of SWMI_LOCAL_MOVE_WORDS(length m)
+ * (swmi_local_ragged_move_offsets), so swmi_local_expand_moves(moves + move_offsets[k], ...) rebuilds its path.  moves and
+ * steps both NULL: ends-only.
+ * Host buffers.  The batch runs in slices (swmi_local_ragged_slices_for) on two sets of device buffers, the slots of a slice
+ * ordered longest first so that the alignments sharing a wavefront have similar lengths; results go to caller positions.
+ * Errors: SWMI_ERR_INVALID_ARGUMENT for decreasing offsets, a length above 16384, a NULL buffer, or only one of moves /
+ * steps; SWMI_ERR_DOMAIN for parameters out of range (those of the fixed-length entries).  n = 0 is a no-op.  Every argument
+ * is checked before any device is touched. */
+SWMI_API int swmi_local_align_ragged(const uint8_t *seq1s, const uint64_t *seq1_offsets, const uint8_t *seq2s, size_t n,
+                                     const int8_t score_matrix[16], int8_t gap_penalty, int32_t *scores, int32_t *ends,
+                                     uint64_t *moves, uint32_t *steps);
+SWMI_API int swmi_local_align_affine_ragged(const uint8_t *seq1s, const uint64_t *seq1_offsets, const uint8_t *seq2s, size_t n,
+                                            const int8_t score_matrix[16], int gap_open, int gap_extend, int32_t *scores,
+                                            int32_t *ends, uint64_t *moves, uint32_t *steps);
+/* move_offsets[0 .. n] of a ragged batch (the layout of its moves).  Needs no device.  SWMI_ERR_INVALID_ARGUMENT as above. */
+SWMI_API int swmi_local_ragged_move_offsets(const uint64_t *seq1_offsets, size_t n, uint64_t *move_offsets);
+/* The slices a ragged call of n alignments cuts its batch into (affine = 0: swmi_local_align_ragged, else the affine one;
+ * traceback = 0: ends-only), in order; returns how many there are and writes the first `cap` sizes (NULL to count).  Each is
+ * the longest run of the alignments left, in caller order, whose device buffers fit the fixed-length aligner's budget for one
+ * slice (256 MiB; the affine aligner with a traceback: swmi_local_affine_slices_for's), at most 2^20 alignments and at least
+ * one.  Needs no device.  0 for invalid offsets. */
+SWMI_API size_t swmi_local_ragged_slices_for(const uint64_t *seq1_offsets, size_t n, int affine, int traceback, size_t *sizes,
+                                             size_t cap);
+/* Same with every data buffer in device memory (16-byte aligned), asynchronous on `stream`; d_moves uses the move_offsets
+ * layout.  seq1_offsets stays a HOST array, read during the call only (it sizes the workspace and orders the work).  The
+ * codes and slots go to the workspace of the fixed-length entry per (GPU, stream). */
+SWMI_API int swmi_local_align_ragged_device(const void *d_seq1s, const uint64_t *seq1_offsets, const void *d_seq2s, size_t n,
+                                            const int8_t score_matrix[16], int8_t gap_penalty, void *d_scores, void *d_ends,
+                                            void *d_moves, void *d_steps, void *stream);
+SWMI_API int swmi_local_align_affine_ragged_device(const void *d_seq1s, const uint64_t *seq1_offsets, const void *d_seq2s,
+                                                   size_t n, const int8_t score_matrix[16], int gap_open, int gap_extend,
+                                                   void *d_scores, void *d_ends, void *d_moves, void *d_steps, void *stream);
+
 /* ---- exact semi-global aligner with traceback (SemiGlobal_111, source.cpp:1776-1834) ------------------------------------
  * The full table of the reference's SemiGlobal_111, with no band and no X-drop: the exact answer that
  * swmi_semiglobal_xdrop approximates.  n alignments of seq1 (len1 bytes, alignment k at seq1s + len1 * k) against seq2

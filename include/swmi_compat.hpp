@@ -143,6 +143,77 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SmithWaterm
     return out;
 }
 
+// Ragged local alignments (swmi_local_align_ragged and its affine twin): seq1s[k] of any length in [0, 16384] against
+// seq2s[k], in pieces of at most `piece` alignments, each one call, so only one piece's inputs and moves are staged at a time.
+// call(seq1 bytes, offsets, seq2s, m, scores, ends, moves, steps) is the C entry with its parameters bound.
+template <class Call>
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> local_ragged_batch(
+    const char *name, const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::array<uint8_t, 128>> &seq2s,
+    size_t piece, Call call)
+{
+    if (seq1s.size() != seq2s.size()) throw std::invalid_argument(std::string(name) + ": seq1s and seq2s differ in length");
+    const size_t n = seq1s.size();
+    std::vector<std::pair<int, std::vector<std::pair<int, int>>>> out(n);
+    if (piece == 0) piece = 1;
+    std::vector<uint8_t> a;
+    std::vector<uint64_t> offsets, move_offsets, moves;
+    std::vector<int32_t> scores, ends;
+    std::vector<uint32_t> steps;
+    for (size_t off = 0; off < n; off += piece) {
+        const size_t m = n - off < piece ? n - off : piece;
+        a.clear();
+        offsets.assign(1, 0);
+        for (size_t k = 0; k < m; ++k) {
+            a.insert(a.end(), seq1s[off + k].begin(), seq1s[off + k].end());
+            offsets.push_back(a.size());
+        }
+        if (a.empty()) a.push_back(0);                  // (every seq1 of the piece is empty: a pointer that is never read)
+        move_offsets.resize(m + 1);
+        if (swmi_local_ragged_move_offsets(offsets.data(), m, move_offsets.data()) != SWMI_OK)
+            throw std::invalid_argument(std::string(name) + ": " + swmi_last_error());
+        moves.resize(move_offsets[m]);
+        scores.resize(m);
+        ends.resize(4 * m);
+        steps.resize(m);
+        if (call(a.data(), offsets.data(), seq2s[off].data(), m, scores.data(), ends.data(), moves.data(), steps.data()) != SWMI_OK)
+            throw std::runtime_error(std::string(name) + ": " + swmi_last_error());
+        for (size_t k = 0; k < m; ++k)
+            out[off + k] = {scores[k], expand_local_moves(moves.data() + move_offsets[k], steps[k], ends[4 * k], ends[4 * k + 1])};
+    }
+    return out;
+}
+
+// Local alignment of seq1s[k] (any lengths, 0 .. 16384) against seq2s[k]: result[k] == SmithWaterman_local_mi355x(seq1s[k],
+// seq2s[k], score_matrix, gap_penalty), in ragged calls of at most `piece` alignments (an empty seq1 gives (0, {(0, 0)})).
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SmithWaterman_local_mi355x_ragged_batch(
+    const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::array<uint8_t, 128>> &seq2s,
+    const std::array<int8_t, 16> &score_matrix, const int8_t gap_penalty, size_t piece = 65536)
+{
+    return local_ragged_batch("SmithWaterman_local_mi355x_ragged_batch", seq1s, seq2s, piece,
+                              [&](const uint8_t *a, const uint64_t *o, const uint8_t *b, size_t m, int32_t *sc, int32_t *e, uint64_t *mv,
+                                  uint32_t *st) { return swmi_local_align_ragged(a, o, b, m, score_matrix.data(), gap_penalty, sc, e, mv, st); });
+}
+
+// The same with affine gaps: result[k] == SmithWaterman_affine_mi355x(seq1s[k], seq2s[k], score_matrix, gap_open, gap_extend).
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SmithWaterman_affine_mi355x_ragged_batch(
+    const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::array<uint8_t, 128>> &seq2s,
+    const std::array<int8_t, 16> &score_matrix, int gap_open, int gap_extend, size_t piece = 65536)
+{
+    return local_ragged_batch("SmithWaterman_affine_mi355x_ragged_batch", seq1s, seq2s, piece,
+                              [&](const uint8_t *a, const uint64_t *o, const uint8_t *b, size_t m, int32_t *sc, int32_t *e, uint64_t *mv,
+                                  uint32_t *st) {
+                                  return swmi_local_align_affine_ragged(a, o, b, m, score_matrix.data(), gap_open, gap_extend, sc, e, mv, st);
+                              });
+}
+
+// The reference's SmithWaterman_111_long (source.cpp:1526-1576) over a batch of any seq1 lengths: result[k] ==
+// SmithWaterman_111_long(seq1s[k], seq2s[k]).
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SmithWaterman_111_long_mi355x_batch(
+    const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::array<uint8_t, 128>> &seq2s, size_t piece = 65536)
+{
+    return SmithWaterman_local_mi355x_ragged_batch(seq1s, seq2s, semiglobal_111_matrix(), 1, piece);
+}
+
 // One alignment's moves (swmi_semiglobal_xdrop_moves) -> the reference's traceback vector (source.cpp:1962-1975).
 inline std::vector<std::pair<int, int>> expand_moves(const uint64_t *moves, uint32_t length)
 {

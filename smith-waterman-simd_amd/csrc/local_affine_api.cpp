@@ -19,17 +19,6 @@ hipError_t launch_affine_slice(const Table &t, const uint8_t *s1, const uint8_t 
                                      t.move_words, st);
 }
 
-Table affine_table(size_t len1, const int8_t *sm, int gap_open, int gap_extend)
-{
-    Table t{launch_affine_slice, &Context::local_affine_state, 0, "steps", len1, SWMI_LOCAL_SEQ2_LEN, 4,
-            swmi::local_affine_code_words((int)len1), SWMI_LOCAL_MOVE_WORDS(len1), 0, sm, gap_open, gap_extend};
-    Table full = t;
-    full.len1 = SWMI_LOCAL_MAX_LEN;
-    full.code_words = swmi::local_affine_code_words(SWMI_LOCAL_MAX_LEN);
-    full.move_words = SWMI_LOCAL_MOVE_WORDS(SWMI_LOCAL_MAX_LEN);
-    t.tb_slice_bytes = kAffineSliceAlignments * table_slice_bytes(full, true);
-    return t;
-}
 
 bool len1_ok(size_t len1) { return len1 >= 1 && len1 <= SWMI_LOCAL_MAX_LEN; }
 
@@ -43,6 +32,19 @@ int check_affine(size_t len1, const int8_t *sm, int gap_open, int gap_extend)
 }
 
 }  // namespace
+
+Table affine_table(size_t len1, const int8_t *sm, int gap_open, int gap_extend)
+{
+    Table t{launch_affine_slice, &Context::local_affine_state, 0, "steps", len1, SWMI_LOCAL_SEQ2_LEN, 4,
+            swmi::local_affine_code_words((int)len1), SWMI_LOCAL_MOVE_WORDS(len1), 0, sm, gap_open, gap_extend};
+    Table full = t;
+    full.len1 = SWMI_LOCAL_MAX_LEN;
+    full.code_words = swmi::local_affine_code_words(SWMI_LOCAL_MAX_LEN);
+    full.move_words = SWMI_LOCAL_MOVE_WORDS(SWMI_LOCAL_MAX_LEN);
+    t.tb_slice_bytes = kAffineSliceAlignments * table_slice_bytes(full, true);
+    return t;
+}
+
 }  // namespace host
 }  // namespace swmi
 

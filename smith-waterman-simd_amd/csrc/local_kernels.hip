@@ -67,24 +67,47 @@ __device__ __forceinline__ int base_shift(const uint8_t *s1, int idx, int len1)
     return (idx >= 0 && idx < len1) ? 8 * (b & 3) : 0;
 }
 
+// base_shift for a length that may be 0 (ragged launches): the load is clamped to s1[0] then, which the caller points at a
+// readable byte that is not seq1
+__device__ __forceinline__ int base_shift_any(const uint8_t *s1, int idx, int len1)
+{
+    const int c = idx >= len1 ? len1 - 1 : idx;
+    const int b = s1[c < 0 ? 0 : c];
+    return (idx >= 0 && idx < len1) ? 8 * (b & 3) : 0;
+}
+
 // cols[b] = bytes a = 0..3: sm[a*4 + b] -- the column of the score matrix that a seq2 base b selects
 struct SmCols {
     uint32_t c[4];
 };
 
-template <bool TB>
+// RAGGED: slot k of the launch computes the alignment work[k] names (its own length, seq1, codes and moves, results at
+// work[k].k); otherwise alignment k of len1 bytes at seq1s + len1 k, codes and moves at k code_words / k move_words.
+template <bool TB, bool RAGGED>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void sw_local_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ seq2s,
                                                                        int len1, uint32_t n, SmCols cols, int gap, int32_t *__restrict__ scores,
                                                                        int32_t *__restrict__ ends, uint32_t *__restrict__ codes,
                                                                        unsigned long long *__restrict__ moves, uint32_t *__restrict__ steps,
-                                                                       uint32_t move_words, uint32_t code_words)
+                                                                       uint32_t move_words, uint32_t code_words,
+                                                                       const LocalWork *__restrict__ work)
 {
     const int lane = threadIdx.x & 63;
     const int l = lane & (kLanes - 1);
-    const uint32_t k = blockIdx.x * kAlnPerBlock + (threadIdx.x >> 6) * kAlnPerWave + (lane >> 4);
+    uint32_t k = blockIdx.x * kAlnPerBlock + (threadIdx.x >> 6) * kAlnPerWave + (lane >> 4);
     if (k >= n) return;                                 // uniform over the 16 lanes of an alignment
 
-    const uint8_t *s1 = seq1s + (size_t)k * (size_t)len1;
+    const uint8_t *s1;
+    uint32_t code_base = 0, move_base = 0;             // RAGGED only (the fixed layout computes its offsets where it uses them)
+    if constexpr (RAGGED) {
+        const LocalWork w = work[k];
+        k = w.k;
+        len1 = (int)w.len1;
+        s1 = len1 ? seq1s + w.s1_off : seq2s + (size_t)k * 128;     // length 0: the clamped loads read the seq2, never seq1
+        code_base = w.code_base;
+        move_base = w.move_base;
+    } else {
+        s1 = seq1s + (size_t)k * (size_t)len1;
+    }
     // the lane's 8 columns of seq2 (8-byte aligned: seq2 k starts at 128 k) -> 8 query-profile dwords
     const uint2 b8 = *reinterpret_cast<const uint2 *>(seq2s + (size_t)k * 128 + kCols * l);
     uint32_t prof[kCols];
@@ -103,21 +126,21 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void sw_local_kernel(const uin
         best[jj] = 0;
     }
     int diag_in = kBoundary;                            // key(i-1, 8l) of the lane's current row i
-    uint32_t *cw_out = TB ? codes + (size_t)k * code_words + l : nullptr;
+    uint32_t *cw_out = TB ? codes + (RAGGED ? code_base : (size_t)k * code_words) + l : nullptr;
 
     const int n_steps = len1 + kLanes - 1;
     // seq1 bases of the lane's rows for the next trip, as bit offsets 8 * base into a profile dword (0 past either end)
     int sh_next[kUnroll];
 #pragma unroll
     for (int t = 0; t < kUnroll; ++t) {
-        sh_next[t] = base_shift(s1, t - l, len1);       // row t - l + 1 at step t
+        sh_next[t] = RAGGED ? base_shift_any(s1, t - l, len1) : base_shift(s1, t - l, len1);   // row t - l + 1 at step t
     }
     for (int s0 = 0; s0 < n_steps; s0 += kUnroll) {
         int sh[kUnroll];
 #pragma unroll
         for (int t = 0; t < kUnroll; ++t) {
             sh[t] = sh_next[t];
-            sh_next[t] = base_shift(s1, s0 + kUnroll + t - l, len1);
+            sh_next[t] = RAGGED ? base_shift_any(s1, s0 + kUnroll + t - l, len1) : base_shift(s1, s0 + kUnroll + t - l, len1);
         }
         uint32_t cw[kUnroll / 2] = {0, 0, 0, 0};
 #pragma unroll
@@ -183,8 +206,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void sw_local_kernel(const uin
         // s_waitcnt vmcnt(0) is that guarantee (a workgroup-scope fence lowers to nothing here); the "memory" clobber keeps
         // the compiler from moving a walk load above it.
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const uint32_t *cd = codes + (size_t)k * code_words;
-        unsigned long long *mv = moves + (size_t)k * move_words;
+        const uint32_t *cd = codes + (RAGGED ? code_base : (size_t)k * code_words);
+        unsigned long long *mv = moves + (RAGGED ? move_base : (size_t)k * move_words);
         int i = end_i, j = end_j;
         uint32_t t = 0;
         unsigned long long acc = 0;
@@ -219,25 +242,47 @@ size_t local_code_words(int len1)
     return (size_t)trips * (kUnroll / 2) * kLanes;
 }
 
-hipError_t launch_local(const uint8_t *d_seq1s, const uint8_t *d_seq2s, int len1, size_t n, const int8_t *sm, int gap,
-                        int32_t *d_scores, int32_t *d_ends, uint32_t *d_codes, unsigned long long *d_moves, uint32_t *d_steps,
-                        size_t move_words, hipStream_t stream)
+static SmCols sm_cols(const int8_t *sm)
 {
-    if (n == 0) return hipSuccess;
     SmCols cols;
     for (int b = 0; b < 4; ++b) {
         uint32_t c = 0;
         for (int a = 0; a < 4; ++a) c |= uint32_t(uint8_t(sm[4 * a + b])) << (8 * a);
         cols.c[b] = c;
     }
+    return cols;
+}
+
+hipError_t launch_local(const uint8_t *d_seq1s, const uint8_t *d_seq2s, int len1, size_t n, const int8_t *sm, int gap,
+                        int32_t *d_scores, int32_t *d_ends, uint32_t *d_codes, unsigned long long *d_moves, uint32_t *d_steps,
+                        size_t move_words, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    const SmCols cols = sm_cols(sm);
     const dim3 grid((unsigned)((n + kAlnPerBlock - 1) / kAlnPerBlock)), block(64 * kWavesPerBlock);
     const uint32_t cw = (uint32_t)local_code_words(len1);
     if (d_moves)
-        hipLaunchKernelGGL(sw_local_kernel<true>, grid, block, 0, stream, d_seq1s, d_seq2s, len1, (uint32_t)n, cols, gap, d_scores,
-                           d_ends, d_codes, d_moves, d_steps, (uint32_t)move_words, cw);
+        hipLaunchKernelGGL((sw_local_kernel<true, false>), grid, block, 0, stream, d_seq1s, d_seq2s, len1, (uint32_t)n, cols, gap,
+                           d_scores, d_ends, d_codes, d_moves, d_steps, (uint32_t)move_words, cw, nullptr);
     else
-        hipLaunchKernelGGL(sw_local_kernel<false>, grid, block, 0, stream, d_seq1s, d_seq2s, len1, (uint32_t)n, cols, gap, d_scores,
-                           d_ends, nullptr, nullptr, nullptr, 0u, cw);
+        hipLaunchKernelGGL((sw_local_kernel<false, false>), grid, block, 0, stream, d_seq1s, d_seq2s, len1, (uint32_t)n, cols, gap,
+                           d_scores, d_ends, nullptr, nullptr, nullptr, 0u, cw, nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_local_ragged(const uint8_t *d_seq1s, const uint8_t *d_seq2s, const LocalWork *d_work, size_t n, const int8_t *sm,
+                               int gap, int32_t *d_scores, int32_t *d_ends, uint32_t *d_codes, unsigned long long *d_moves,
+                               uint32_t *d_steps, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    const SmCols cols = sm_cols(sm);
+    const dim3 grid((unsigned)((n + kAlnPerBlock - 1) / kAlnPerBlock)), block(64 * kWavesPerBlock);
+    if (d_moves)
+        hipLaunchKernelGGL((sw_local_kernel<true, true>), grid, block, 0, stream, d_seq1s, d_seq2s, 0, (uint32_t)n, cols, gap, d_scores,
+                           d_ends, d_codes, d_moves, d_steps, 0u, 0u, d_work);
+    else
+        hipLaunchKernelGGL((sw_local_kernel<false, true>), grid, block, 0, stream, d_seq1s, d_seq2s, 0, (uint32_t)n, cols, gap, d_scores,
+                           d_ends, nullptr, nullptr, nullptr, 0u, 0u, d_work);
     return hipGetLastError();
 }
 

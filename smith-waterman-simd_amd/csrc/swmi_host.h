@@ -203,6 +203,20 @@ int score_host_batch(Context &ctx, const uint8_t *s1, const uint8_t *s2, size_t 
 struct Table;
 using TableLaunch = hipError_t (*)(const Table &t, const uint8_t *s1, const uint8_t *s2, size_t n, int32_t *scores, int32_t *ends,
                                    uint32_t *codes, unsigned long long *moves, uint32_t *counts, hipStream_t st);
+using RaggedLaunch = hipError_t (*)(const Table &t, const uint8_t *s1, const uint8_t *s2, const LocalWork *work, size_t n,
+                                    int32_t *scores, int32_t *ends, uint32_t *codes, unsigned long long *moves, uint32_t *counts,
+                                    hipStream_t st);
+// A batch of the local aligners with a seq1 length of its own per alignment (local_ragged_api.cpp): its slices, contiguous in
+// caller order, and one LocalWork per alignment, slice-relative, the slots of each slice ordered longest first.
+struct RaggedPlan {
+    RaggedLaunch launch;
+    const uint64_t *seq1_offsets;               // the caller's n + 1
+    std::vector<uint64_t> move_offsets;         // n + 1: moves of alignment k at word move_offsets[k] (SWMI_LOCAL_MOVE_WORDS)
+    std::vector<size_t> first;                  // slice s = alignments [first[s], first[s + 1]); first.back() = n
+    std::vector<size_t> code_words;             // per slice: dwords of codes (0 ends-only)
+    std::vector<LocalWork> work;                // [n]: slice s's slots at [first[s], first[s + 1])
+    size_t max_m = 0, max_seq1 = 0, max_codes = 0, max_moves = 0;  // the largest slice's alignments, seq1 bytes, codes, moves
+};
 struct Table {
     TableLaunch launch;
     std::shared_ptr<void> Context::*state;      // created on first use under Context::ws_mu, dropped by destroy_context
@@ -214,6 +228,7 @@ struct Table {
     uint32_t count_offset;      // count = moves + count_offset
     const int8_t *sm;
     int gap, gap_extend;        // gap_extend: the affine aligner's (gap is then the open cost)
+    const RaggedPlan *plan = nullptr;   // a ragged batch: len1, code_words and move_words unused, slices as the plan says
 };
 constexpr size_t kTableSliceBytes = size_t(256) << 20;
 constexpr size_t kTableMaxSlice = size_t(1) << 20;     // alignments per slice (and per launch)
@@ -226,6 +241,8 @@ int table_host(const Table &t, const char *entry, const uint8_t *seq1s, const ui
 int table_time_device(const Table &t, const char *entry, const void *d_seq1s, const void *d_seq2s, size_t n, void *d_scores,
                       void *d_ends, void *d_moves, void *d_counts, void *stream, int iters, float *avg_ms);
 int table_check_timer(size_t n, int iters, const float *avg_ms);   // what the timers check before their first call
+Table local_table(size_t len1, const int8_t *sm, int gap);                               // swmi_table.cpp
+Table affine_table(size_t len1, const int8_t *sm, int gap_open, int gap_extend);         // local_affine_api.cpp
 
 #define SWMI_HIP_TRY(expr)                                                                                          \
     do {                                                                                                            \

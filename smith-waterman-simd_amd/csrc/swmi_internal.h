@@ -76,6 +76,16 @@ void semiglobal_kernel_names(size_t n, int compute_units, char *sweep_name, size
 }  // namespace swmi
 
 namespace swmi {
+// One slot of a ragged launch of the local aligners (launch_local_ragged, launch_local_affine_ragged): the alignment it
+// computes, every field relative to the launch's buffers.  The slots of a wavefront may have different lengths.
+struct LocalWork {
+    uint32_t k;             // results at index k, seq2 at d_seq2s + 128 k
+    uint32_t s1_off;        // seq1 = the len1 bytes at d_seq1s + s1_off (not read when len1 is 0)
+    uint32_t len1;          // 0 .. 16384
+    uint32_t code_base;     // codes at d_codes + code_base: local_code_words(len1) / local_affine_code_words(len1) dwords
+    uint32_t move_base;     // moves at d_moves + move_base: SWMI_LOCAL_MOVE_WORDS(len1) words
+};
+
 // Local aligner with end / start cell and traceback (local_kernels.hip).  n alignments of seq1 (len1 bytes each, at
 // d_seq1s + len1 * k) against a 128-mer (d_seq2s + 128 k); d_codes holds local_code_words(len1) dwords per alignment of the
 // launch.  d_moves NULL: the ends-only kernel (no codes, no walk; d_codes and d_steps unused).
@@ -83,6 +93,10 @@ size_t local_code_words(int len1);
 hipError_t launch_local(const uint8_t *d_seq1s, const uint8_t *d_seq2s, int len1, size_t n, const int8_t *sm, int gap,
                         int32_t *d_scores, int32_t *d_ends, uint32_t *d_codes, unsigned long long *d_moves, uint32_t *d_steps,
                         size_t move_words, hipStream_t stream);
+// The same for n slots of d_work (device memory), each of its own length: results at d_scores[work.k] etc.
+hipError_t launch_local_ragged(const uint8_t *d_seq1s, const uint8_t *d_seq2s, const LocalWork *d_work, size_t n, const int8_t *sm,
+                               int gap, int32_t *d_scores, int32_t *d_ends, uint32_t *d_codes, unsigned long long *d_moves,
+                               uint32_t *d_steps, hipStream_t stream);
 }  // namespace swmi
 
 namespace swmi {
@@ -92,6 +106,9 @@ size_t local_affine_code_words(int len1);
 hipError_t launch_local_affine(const uint8_t *d_seq1s, const uint8_t *d_seq2s, int len1, size_t n, const int8_t *sm, int gap_open,
                                int gap_extend, int32_t *d_scores, int32_t *d_ends, uint32_t *d_codes, unsigned long long *d_moves,
                                uint32_t *d_steps, size_t move_words, hipStream_t stream);
+hipError_t launch_local_affine_ragged(const uint8_t *d_seq1s, const uint8_t *d_seq2s, const LocalWork *d_work, size_t n,
+                                      const int8_t *sm, int gap_open, int gap_extend, int32_t *d_scores, int32_t *d_ends,
+                                      uint32_t *d_codes, unsigned long long *d_moves, uint32_t *d_steps, hipStream_t stream);
 }  // namespace swmi
 
 namespace swmi {

@@ -10,6 +10,7 @@
 // links without the affine kernels.
 #include "swmi_host.h"
 
+#include <algorithm>
 #include <initializer_list>
 
 namespace swmi {
@@ -26,12 +27,6 @@ hipError_t launch_sgfull_slice(const Table &t, const uint8_t *s1, const uint8_t 
                                uint32_t *codes, unsigned long long *moves, uint32_t *counts, hipStream_t st)
 {
     return swmi::launch_sgfull(s1, s2, (int)t.len1, (int)t.len2, n, t.sm, t.gap, scores, ends, codes, moves, counts, t.move_words, st);
-}
-
-Table local_table(size_t len1, const int8_t *sm, int gap)
-{
-    return {launch_local_slice, &Context::local_state, kTableSliceBytes, "steps", len1, SWMI_LOCAL_SEQ2_LEN, 4,
-            swmi::local_code_words((int)len1), SWMI_LOCAL_MOVE_WORDS(len1), 0, sm, gap, 0};
 }
 
 // An exact semi-global traceback slice holds as many alignments as 256 of 16384 x 16384 (about 16.1 GiB): one workgroup per
@@ -74,26 +69,40 @@ struct HostSet {
     int32_t *d_scores = nullptr, *d_ends = nullptr;
     uint32_t *d_codes = nullptr, *d_counts = nullptr;
     unsigned long long *d_moves = nullptr;
-    struct { size_t d1, d2, scores, ends, codes, counts, moves; } have{};     // capacity in elements
+    LocalWork *d_work = nullptr;                                             // a ragged batch's slots
+    struct { size_t d1, d2, scores, ends, codes, counts, moves, work; } have{};   // capacity in elements
     size_t off = 0, m = 0;                                                   // slice in flight
     void release()
     {
-        for (void *p : std::initializer_list<void *>{d1, d2, d_scores, d_ends, d_codes, d_counts, d_moves})
+        for (void *p : std::initializer_list<void *>{d1, d2, d_scores, d_ends, d_codes, d_counts, d_moves, d_work})
             if (p) (void)hipFree(p);
         *this = HostSet{};
     }
 };
 
+// pinned copy of a ragged device call's slots, read by that call's upload; `done` is recorded behind the upload
+struct Staging {
+    LocalWork *host = nullptr;
+    size_t cap = 0;
+    hipEvent_t done = nullptr;
+};
+
 // the device buffers of one aligner on one context
 struct TableState {
     std::mutex mu;                                   // the device-entry workspaces
-    std::map<hipStream_t, Workspace> workspaces;     // codes of one slice per caller stream
+    std::map<hipStream_t, Workspace> workspaces;     // codes of one slice (and a ragged batch's slots) per caller stream
+    std::map<hipStream_t, Staging> staging;          // ragged slots on their way to a stream's workspace
     HostSet sets[2];                                 // host entry, used under Context::mu
     void release()
     {
         for (auto &w : workspaces)
             if (w.second.ptr) (void)hipFree(w.second.ptr);
         workspaces.clear();
+        for (auto &g : staging) {
+            if (g.second.host) (void)hipHostFree(g.second.host);
+            if (g.second.done) (void)hipEventDestroy(g.second.done);
+        }
+        staging.clear();
         for (auto &s : sets) s.release();
     }
     ~TableState() { release(); }
@@ -109,6 +118,31 @@ TableState &state(Context &ctx, std::shared_ptr<void> Context::*member)
 
 bool len_ok(size_t len, size_t max) { return len >= 1 && len <= max; }
 
+// Where slice by slice a batch's data lie: evenly cut for one length, as the plan says for a ragged batch.  Offsets count
+// alignments (first), seq1 bytes (seq1) and move words (moves) from the start of the caller's arrays.
+struct Slices {
+    const Table &t;
+    size_t n, slice;            // slice: alignments per slice of a fixed-length batch
+    size_t count() const { return t.plan ? t.plan->first.size() - 1 : (n + slice - 1) / slice; }
+    size_t first(size_t s) const { return t.plan ? t.plan->first[s] : s * slice; }
+    size_t size(size_t s) const { return t.plan ? t.plan->first[s + 1] - t.plan->first[s] : n - s * slice < slice ? n - s * slice : slice; }
+    size_t seq1(size_t k) const { return t.plan ? size_t(t.plan->seq1_offsets[k]) : k * t.len1; }
+    size_t moves(size_t k) const { return t.plan ? size_t(t.plan->move_offsets[k]) : k * t.move_words; }
+    size_t codes(size_t s) const { return t.plan ? t.plan->code_words[s] : size(s) * t.code_words; }
+    // capacity one set of buffers needs: alignments, seq1 bytes, code dwords, move words
+    size_t max_m() const { return t.plan ? t.plan->max_m : slice; }
+    size_t max_seq1() const { return t.plan ? t.plan->max_seq1 : slice * t.len1; }
+    size_t max_codes() const { return t.plan ? t.plan->max_codes : slice * t.code_words; }
+    size_t max_moves() const { return t.plan ? t.plan->max_moves : slice * t.move_words; }
+};
+
+hipError_t launch_table(const Table &t, const uint8_t *s1, const uint8_t *s2, const LocalWork *work, size_t m,
+                        int32_t *scores, int32_t *ends, uint32_t *codes, unsigned long long *moves, uint32_t *counts, hipStream_t st)
+{
+    if (t.plan) return t.plan->launch(t, s1, s2, work, m, scores, ends, codes, moves, counts, st);
+    return t.launch(t, s1, s2, m, scores, ends, codes, moves, counts, st);
+}
+
 int check_local(size_t len1, const int8_t *sm, int gap)
 {
     if (!len_ok(len1, SWMI_LOCAL_MAX_LEN)) return fail(SWMI_ERR_INVALID_ARGUMENT, "len1 %zu outside [1, %d]", len1, SWMI_LOCAL_MAX_LEN);
@@ -123,6 +157,12 @@ int check_sgfull(size_t len1, size_t len2, const int8_t *sm, int gap)
 }
 
 }  // namespace
+
+Table local_table(size_t len1, const int8_t *sm, int gap)
+{
+    return {launch_local_slice, &Context::local_state, kTableSliceBytes, "steps", len1, SWMI_LOCAL_SEQ2_LEN, 4,
+            swmi::local_code_words((int)len1), SWMI_LOCAL_MOVE_WORDS(len1), 0, sm, gap, 0};
+}
 
 // device bytes one alignment of a slice takes: inputs, results, and with a traceback the codes, the moves and the count
 size_t table_slice_bytes(const Table &t, bool tb)
@@ -161,16 +201,18 @@ int table_device(const Table &t, const void *d_seq1s, const void *d_seq2s, size_
     Context *ctx = current();
     if (!ctx) return last_status();
     const bool tb = d_moves != nullptr;
-    const size_t slice = slice_size(t, n, tb), mw = t.move_words;
+    const Slices sl{t, n, t.plan ? 0 : slice_size(t, n, tb)};
     hipStream_t st = static_cast<hipStream_t>(stream);
     TableState &ts = state(*ctx, t.state);
     // one workspace per (context, stream), looked up, grown and handed to the launches under one lock (growing waits for
-    // this stream only: earlier launches on it may still use the old one)
+    // this stream only: earlier launches on it may still use the old one).  A ragged batch's slots follow the codes.
     std::lock_guard<std::mutex> lock(ts.mu);
     uint32_t *codes = nullptr;
-    if (tb) {
+    LocalWork *work = nullptr;
+    const size_t code_bytes = ((tb ? sl.max_codes() * sizeof(uint32_t) : 0) + 15) & ~size_t(15);
+    const size_t need = code_bytes + (t.plan ? n * sizeof(LocalWork) : 0);
+    if (need) {
         Workspace &ws = ts.workspaces[st];
-        const size_t need = slice * t.code_words * sizeof(uint32_t);
         if (need > ws.bytes) {
             SWMI_HIP_TRY(hipStreamSynchronize(st));
             if (ws.ptr) (void)hipFree(ws.ptr);
@@ -179,15 +221,32 @@ int table_device(const Table &t, const void *d_seq1s, const void *d_seq2s, size_
             SWMI_HIP_TRY(hipMalloc(&ws.ptr, need));
             ws.bytes = need;
         }
-        codes = static_cast<uint32_t *>(ws.ptr);
+        codes = tb ? static_cast<uint32_t *>(ws.ptr) : nullptr;
+        if (t.plan) {
+            // the slots go up from pinned memory that the stream's last ragged upload has finished reading
+            work = reinterpret_cast<LocalWork *>(static_cast<char *>(ws.ptr) + code_bytes);
+            Staging &g = ts.staging[st];
+            if (g.done) SWMI_HIP_TRY(hipEventSynchronize(g.done));
+            else SWMI_HIP_TRY(hipEventCreateWithFlags(&g.done, hipEventDisableTiming));
+            if (g.cap < n) {
+                if (g.host) (void)hipHostFree(g.host);
+                g.host = nullptr;
+                g.cap = 0;
+                SWMI_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&g.host), n * sizeof(LocalWork), 0));
+                g.cap = n;
+            }
+            std::copy(t.plan->work.begin(), t.plan->work.end(), g.host);
+            SWMI_HIP_TRY(hipMemcpyAsync(work, g.host, n * sizeof(LocalWork), hipMemcpyHostToDevice, st));
+            SWMI_HIP_TRY(hipEventRecord(g.done, st));
+        }
     }
     const uint8_t *s1 = static_cast<const uint8_t *>(d_seq1s), *s2 = static_cast<const uint8_t *>(d_seq2s);
-    for (size_t off = 0; off < n; off += slice) {
-        const size_t m = n - off < slice ? n - off : slice;
-        SWMI_HIP_TRY(t.launch(t, s1 + off * t.len1, s2 + off * t.len2, m, static_cast<int32_t *>(d_scores) + off,
-                              static_cast<int32_t *>(d_ends) + t.ends * off, codes,
-                              tb ? static_cast<unsigned long long *>(d_moves) + off * mw : nullptr,
-                              tb ? static_cast<uint32_t *>(d_counts) + off : nullptr, st));
+    for (size_t s = 0; s < sl.count(); ++s) {
+        const size_t off = sl.first(s);
+        SWMI_HIP_TRY(launch_table(t, s1 + sl.seq1(off), s2 + off * t.len2, work ? work + off : nullptr, sl.size(s),
+                                  static_cast<int32_t *>(d_scores) + off, static_cast<int32_t *>(d_ends) + t.ends * off, codes,
+                                  tb ? static_cast<unsigned long long *>(d_moves) + sl.moves(off) : nullptr,
+                                  tb ? static_cast<uint32_t *>(d_counts) + off : nullptr, st));
     }
     return SWMI_OK;
 }
@@ -202,25 +261,29 @@ int table_host(const Table &t, const char *entry, const uint8_t *seq1s, const ui
     Context *ctx = current();
     if (!ctx) return last_status();
     const bool tb = moves != nullptr;
-    const size_t slice = slice_size(t, n, tb), mw = t.move_words, len1 = t.len1, len2 = t.len2;
+    const Slices sl{t, n, t.plan ? 0 : slice_size(t, n, tb)};
+    const size_t mw = t.move_words, len2 = t.len2;
     TableState &ts = state(*ctx, t.state);
     std::lock_guard<std::mutex> lock(ctx->mu);
     HostSet *sets = ts.sets;
-    const int n_sets = n > slice ? 2 : 1;
+    const int n_sets = sl.count() > 1 ? 2 : 1;
     hipStream_t streams[2] = {ctx->slots[0].stream, ctx->slots[1].stream};
     for (int k = 0; k < n_sets; ++k) {
         HostSet &s = sets[k];
         s.off = s.m = 0;
-        int rc = grow(s.d1, s.have.d1, slice * len1);
+        const size_t slice = sl.max_m();
+        int rc = grow(s.d1, s.have.d1, sl.max_seq1());
         if (rc == SWMI_OK) rc = grow(s.d2, s.have.d2, slice * len2);
         if (rc == SWMI_OK) rc = grow(s.d_scores, s.have.scores, slice);
         if (rc == SWMI_OK) rc = grow(s.d_ends, s.have.ends, slice * t.ends);
         if (rc == SWMI_OK) rc = grow(s.d_counts, s.have.counts, slice);
-        if (rc == SWMI_OK && tb) rc = grow(s.d_codes, s.have.codes, slice * t.code_words);
-        if (rc == SWMI_OK && tb) rc = grow(s.d_moves, s.have.moves, slice * mw);
+        if (rc == SWMI_OK && tb) rc = grow(s.d_codes, s.have.codes, sl.max_codes());
+        if (rc == SWMI_OK && tb) rc = grow(s.d_moves, s.have.moves, sl.max_moves());
+        if (rc == SWMI_OK && t.plan) rc = grow(s.d_work, s.have.work, slice);
         if (rc != SWMI_OK) return rc;
     }
-    // results of the slice a set holds -> host; only as many move words per alignment as the slice's longest walk needs
+    // results of the slice a set holds -> host; only as many move words per alignment as the slice's longest walk needs (a
+    // ragged slice: its alignments' move words, one run in the caller's layout)
     auto drain = [&](int which) -> hipError_t {
         HostSet &s = sets[which];
         hipStream_t st = streams[which];
@@ -228,8 +291,12 @@ int table_host(const Table &t, const char *entry, const uint8_t *seq1s, const ui
         hipError_t r = hipMemcpyAsync(scores + s.off, s.d_scores, s.m * sizeof(int32_t), hipMemcpyDeviceToHost, st);
         if (r == hipSuccess) r = hipMemcpyAsync(ends + t.ends * s.off, s.d_ends, s.m * t.ends * sizeof(int32_t), hipMemcpyDeviceToHost, st);
         if (r == hipSuccess && tb) r = hipMemcpyAsync(counts + s.off, s.d_counts, s.m * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+        if (r == hipSuccess && tb && t.plan) {
+            const size_t w0 = sl.moves(s.off), words = sl.moves(s.off + s.m) - w0;
+            if (words) r = hipMemcpyAsync(moves + w0, s.d_moves, words * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
+        }
         if (r == hipSuccess) r = hipStreamSynchronize(st);
-        if (r == hipSuccess && tb) {
+        if (r == hipSuccess && tb && !t.plan) {
             uint32_t longest = 0;
             for (size_t k = 0; k < s.m; ++k) longest = counts[s.off + k] > longest ? counts[s.off + k] : longest;
             if (longest > t.count_offset) {
@@ -243,19 +310,24 @@ int table_host(const Table &t, const char *entry, const uint8_t *seq1s, const ui
     };
     hipError_t e = hipSuccess;
     int turn = 0;
-    for (size_t off = 0; e == hipSuccess && off < n; off += slice, turn ^= 1) {
+    for (size_t sc = 0; e == hipSuccess && sc < sl.count(); ++sc, turn ^= 1) {
         const int which = n_sets == 2 ? turn : 0;
         HostSet &s = sets[which];
         hipStream_t st = streams[which];
         e = drain(which);                                   // (two slices ago; normally already empty)
         if (e != hipSuccess) break;
+        const size_t off = sl.first(sc);
         s.off = off;
-        s.m = n - off < slice ? n - off : slice;
-        e = hipMemcpyAsync(s.d1, seq1s + off * len1, s.m * len1, hipMemcpyHostToDevice, st);
+        s.m = sl.size(sc);
+        const size_t seq1_bytes = sl.seq1(off + s.m) - sl.seq1(off);     // (0 for a ragged slice of empty seq1s only)
+        if (seq1_bytes)
+            e = hipMemcpyAsync(s.d1, seq1s + sl.seq1(off), seq1_bytes, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(s.d2, seq2s + off * len2, s.m * len2, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && t.plan)
+            e = hipMemcpyAsync(s.d_work, t.plan->work.data() + off, s.m * sizeof(LocalWork), hipMemcpyHostToDevice, st);
         if (e == hipSuccess)
-            e = t.launch(t, s.d1, s.d2, s.m, s.d_scores, s.d_ends, tb ? s.d_codes : nullptr, tb ? s.d_moves : nullptr,
-                         tb ? s.d_counts : nullptr, st);
+            e = launch_table(t, s.d1, s.d2, s.d_work, s.m, s.d_scores, s.d_ends, tb ? s.d_codes : nullptr, tb ? s.d_moves : nullptr,
+                             tb ? s.d_counts : nullptr, st);
         if (e == hipSuccess && n_sets == 2) e = drain(turn ^ 1);         // the previous slice, while this one computes
     }
     for (int k = 0; k < n_sets; ++k) {

@@ -130,6 +130,13 @@ def load():
     lib.swmi_local_affine_slices_for.argtypes = [sz, sz, ci, vp, sz]
     lib.swmi_local_affine_slices_for.restype = sz
     lib.swmi_local_affine_time_device.argtypes = [vp, sz, vp, sz, vp, ci, ci, vp, vp, vp, vp, vp, ci, ctypes.POINTER(ctypes.c_float)]
+    lib.swmi_local_align_ragged.argtypes = [vp, vp, vp, sz, vp, i8, vp, vp, vp, vp]
+    lib.swmi_local_align_affine_ragged.argtypes = [vp, vp, vp, sz, vp, ci, ci, vp, vp, vp, vp]
+    lib.swmi_local_align_ragged_device.argtypes = [vp, vp, vp, sz, vp, i8, vp, vp, vp, vp, vp]
+    lib.swmi_local_align_affine_ragged_device.argtypes = [vp, vp, vp, sz, vp, ci, ci, vp, vp, vp, vp, vp]
+    lib.swmi_local_ragged_move_offsets.argtypes = [vp, sz, vp]
+    lib.swmi_local_ragged_slices_for.argtypes = [vp, sz, ci, ci, vp, sz]
+    lib.swmi_local_ragged_slices_for.restype = sz
     lib.swmi_semiglobal_full.argtypes = [vp, sz, vp, sz, sz, vp, i8, vp, vp, vp, vp]
     lib.swmi_semiglobal_full_device.argtypes = [vp, sz, vp, sz, sz, vp, i8, vp, vp, vp, vp, vp]
     lib.swmi_semiglobal_full_slices_for.argtypes = [sz, sz, sz, ctypes.c_int, vp, sz]
@@ -629,6 +636,96 @@ def local_affine_slices_for(n, len1, traceback=True):
     buf = (ctypes.c_size_t * max(count, 1))()
     load().swmi_local_affine_slices_for(n, len1, 1 if traceback else 0, buf, count)
     return [int(buf[k]) for k in range(count)]
+
+
+def _ragged_seq1s(seq1s):
+    """(concatenated uint8, offsets uint64[n + 1]) from a list of 1-D arrays or from such a pair."""
+    if isinstance(seq1s, tuple):
+        cat, off = seq1s
+        cat = np.ascontiguousarray(cat, dtype=np.uint8).reshape(-1)
+        off = np.ascontiguousarray(off, dtype=np.uint64).reshape(-1)
+        if len(off) < 1:
+            raise ValueError("offsets must hold n + 1 entries")
+        if int(off[-1]) > len(cat):
+            raise ValueError("offsets point past the concatenated seq1s")
+        return cat, off
+    parts = [np.ascontiguousarray(x, dtype=np.uint8).reshape(-1) for x in seq1s]
+    off = np.zeros(len(parts) + 1, np.uint64)
+    if parts:
+        off[1:] = np.cumsum([len(x) for x in parts], dtype=np.uint64)
+    cat = np.concatenate(parts) if parts else np.zeros(0, np.uint8)
+    return cat, off
+
+
+def local_ragged_move_offsets(seq1_offsets):
+    """move_offsets[n + 1] of a ragged batch (swmi_local_ragged_move_offsets; needs no device)."""
+    off = np.ascontiguousarray(seq1_offsets, dtype=np.uint64).reshape(-1)
+    out = np.zeros(len(off), np.uint64)
+    _check(load().swmi_local_ragged_move_offsets(off.ctypes.data, len(off) - 1, out.ctypes.data))
+    return out
+
+
+def local_ragged_slices_for(seq1_offsets, affine=False, traceback=True):
+    """The slices a ragged call cuts its batch into (swmi_local_ragged_slices_for; needs no device)."""
+    off = np.ascontiguousarray(seq1_offsets, dtype=np.uint64).reshape(-1)
+    lib = load()
+    count = lib.swmi_local_ragged_slices_for(off.ctypes.data, len(off) - 1, 1 if affine else 0, 1 if traceback else 0, None, 0)
+    buf = (ctypes.c_size_t * max(count, 1))()
+    lib.swmi_local_ragged_slices_for(off.ctypes.data, len(off) - 1, 1 if affine else 0, 1 if traceback else 0, buf, count)
+    return [int(buf[k]) for k in range(count)]
+
+
+def _ragged_call(entry, seq1s, seq2s, params, traceback):
+    cat, off = _ragged_seq1s(seq1s)
+    n = len(off) - 1
+    b = _u8(seq2s, LOCAL_SEQ2_LEN).reshape(-1, LOCAL_SEQ2_LEN) if n else np.zeros((0, LOCAL_SEQ2_LEN), np.uint8)
+    if b.shape[0] != n:
+        raise ValueError("seq1s and seq2s hold different numbers of sequences")
+    mo = local_ragged_move_offsets(off) if traceback else None
+    scores = np.zeros(n, np.int32)
+    ends = np.zeros((n, 4), np.int32)
+    moves = np.zeros(int(mo[-1]), np.uint64) if traceback else None
+    steps = np.zeros(n, np.uint32) if traceback else None
+    if len(cat) == 0:
+        cat = np.zeros(16, np.uint8)        # every seq1 is empty: a valid pointer the library never reads
+    _check(entry(cat.ctypes.data, off.ctypes.data, b.ctypes.data, n, *params, scores.ctypes.data, ends.ctypes.data,
+                 moves.ctypes.data if traceback else None, steps.ctypes.data if traceback else None))
+    return scores, ends, moves, mo, steps
+
+
+def local_align_ragged(seq1s, seq2s, score_matrix, gap_penalty, traceback=True):
+    """swmi_local_align_ragged: local_align with a seq1 length of its own (0 .. 16384) per alignment.  seq1s: a list of 1-D
+    uint8 arrays, or a (concatenated, offsets[n + 1]) pair; seq2s: (n, 128).
+
+    Returns (scores[n] int32, ends[n, 4] int32, moves uint64 (flat: alignment k's at move_offsets[k] ..), move_offsets[n + 1],
+    steps[n] uint32); traceback=False: moves, move_offsets and steps are None."""
+    sm = _sm(score_matrix)
+    return _ragged_call(load().swmi_local_align_ragged, seq1s, seq2s, (sm.ctypes.data, _gap(gap_penalty)), traceback)
+
+
+def local_align_affine_ragged(seq1s, seq2s, score_matrix, gap_open, gap_extend, traceback=True):
+    """swmi_local_align_affine_ragged: local_align_affine on a ragged batch; arguments and result as local_align_ragged."""
+    sm = _sm(score_matrix)
+    return _ragged_call(load().swmi_local_align_affine_ragged, seq1s, seq2s, (sm.ctypes.data, int(gap_open), int(gap_extend)),
+                        traceback)
+
+
+def local_align_ragged_device(d_seq1s, seq1_offsets, d_seq2s, score_matrix, gap_penalty, d_scores, d_ends, d_moves=None,
+                              d_steps=None, stream=0):
+    """swmi_local_align_ragged_device: device pointers, seq1_offsets a host array of n + 1 (asynchronous on `stream`)."""
+    sm = _sm(score_matrix)
+    off = np.ascontiguousarray(seq1_offsets, dtype=np.uint64).reshape(-1)
+    _check(load().swmi_local_align_ragged_device(d_seq1s, off.ctypes.data, d_seq2s, len(off) - 1, sm.ctypes.data, _gap(gap_penalty),
+                                                 d_scores, d_ends, d_moves, d_steps, stream))
+
+
+def local_align_affine_ragged_device(d_seq1s, seq1_offsets, d_seq2s, score_matrix, gap_open, gap_extend, d_scores, d_ends,
+                                     d_moves=None, d_steps=None, stream=0):
+    """swmi_local_align_affine_ragged_device: as local_align_ragged_device with (gap_open, gap_extend)."""
+    sm = _sm(score_matrix)
+    off = np.ascontiguousarray(seq1_offsets, dtype=np.uint64).reshape(-1)
+    _check(load().swmi_local_align_affine_ragged_device(d_seq1s, off.ctypes.data, d_seq2s, len(off) - 1, sm.ctypes.data, int(gap_open),
+                                                        int(gap_extend), d_scores, d_ends, d_moves, d_steps, stream))
 
 
 SGFULL_MAX_LEN = 16384
