@@ -67,13 +67,90 @@ inline const std::array<int8_t, 16> &semiglobal_111_matrix()
     return m;
 }
 
+namespace detail {
+
+using Result = std::pair<int, std::vector<std::pair<int, int>>>;
+
+// Throws std::runtime_error("<what>: <the library's last error>") unless rc is SWMI_OK.
+inline void check(int rc, const char *what)
+{
+    if (rc != SWMI_OK) throw std::runtime_error(std::string(what) + ": " + swmi_last_error());
+}
+
+// One piece's inputs and outputs; each batch overload sizes and fills the ones its C entry takes.
+struct PieceBuffers {
+    std::vector<uint8_t> seq1s;                        // seq1s staged back to back
+    std::vector<uint64_t> seq1_offsets, move_offsets;  // a ragged piece's layouts
+    std::vector<int32_t> scores, ends;
+    std::vector<uint64_t> moves;
+    std::vector<uint32_t> counts;                      // steps or lengths
+};
+
+// Aligns alignments [0, n) in pieces of at most `piece` (0 counts as 1).  align(buf, off, m) runs the C entry for
+// [off, off + m) into piece buffers `buf` and throws on failure; expand(buf, k) returns piece-relative result k of the piece
+// that `buf` holds.  threads == 0: each piece is expanded on the calling thread before the next is aligned (one set of
+// buffers).  threads >= 1: piece p is expanded on min(threads, m) threads while piece p + 1 is aligned (two sets, taken in
+// turn).  The first failure -- of align, of an expander or of creating a thread -- is recorded, no piece starts after it,
+// every started thread is joined, and then it is rethrown as it was thrown.
+template <class Align, class Expand>
+std::vector<Result> run_in_pieces(size_t n, size_t piece, unsigned threads, Align align, Expand expand)
+{
+    if (piece == 0) piece = 1;
+    std::vector<Result> out(n);
+    PieceBuffers bufs[2];
+    std::vector<std::thread> pool;                     // the expanders of the piece before the one being aligned
+    std::mutex mu;
+    std::exception_ptr failed;
+    auto record = [&] {                                // (called in a handler)
+        std::lock_guard<std::mutex> lock(mu);
+        if (!failed) failed = std::current_exception();
+    };
+    auto has_failed = [&] {
+        std::lock_guard<std::mutex> lock(mu);
+        return bool(failed);
+    };
+    auto join_all = [&] {
+        for (auto &th : pool) th.join();
+        pool.clear();
+    };
+    auto expand_range = [&](int buf, size_t off, size_t lo, size_t hi) {
+        try {
+            for (size_t k = lo; k < hi; ++k) out[off + k] = expand(bufs[buf], k);
+        } catch (...) {
+            record();
+        }
+    };
+    int b = 0;
+    try {
+        for (size_t off = 0; off < n && !has_failed(); off += piece) {
+            const size_t m = std::min(piece, n - off);
+            align(bufs[b], off, m);
+            join_all();                                // (the previous piece's expanders, which read the other buffers)
+            if (threads == 0) {
+                expand_range(b, off, 0, m);
+            } else if (!has_failed()) {
+                const unsigned use = threads > m ? unsigned(m) : threads;
+                for (unsigned t = 0; t < use; ++t) pool.emplace_back(expand_range, b, off, m * t / use, m * (t + 1) / use);
+                b ^= 1;
+            }
+        }
+    } catch (...) {
+        record();                                      // (align failed, or a thread could not be created)
+    }
+    join_all();
+    if (failed) std::rethrow_exception(failed);
+    return out;
+}
+
+}  // namespace detail
+
 // One local alignment's moves (swmi_local_align) -> the reference's path vector (source.cpp:1571-1575).
 inline std::vector<std::pair<int, int>> expand_local_moves(const uint64_t *moves, uint32_t steps, int32_t end_i, int32_t end_j)
 {
     static_assert(sizeof(std::pair<int, int>) == 2 * sizeof(int32_t), "std::pair<int,int> must be two packed ints");
     std::vector<std::pair<int, int>> path(size_t(steps) + 1);
-    if (swmi_local_expand_moves(moves, steps, end_i, end_j, reinterpret_cast<int32_t *>(path.data()), path.size()) != SWMI_OK)
-        throw std::runtime_error(std::string("swmi_local_expand_moves: ") + swmi_last_error());
+    detail::check(swmi_local_expand_moves(moves, steps, end_i, end_j, reinterpret_cast<int32_t *>(path.data()), path.size()),
+                  "swmi_local_expand_moves");
     return path;
 }
 
@@ -85,29 +162,23 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SmithWaterm
     const std::array<int8_t, 16> &score_matrix, const int8_t gap_penalty, size_t piece = 65536)
 {
     if (seq1s.size() != seq2s.size()) throw std::invalid_argument("SmithWaterman_local_mi355x_batch: seq1s and seq2s differ in length");
-    const size_t n = seq1s.size();
-    std::vector<std::pair<int, std::vector<std::pair<int, int>>>> out(n);
-    if (n == 0) return out;
-    const size_t len1 = seq1s[0].size();
+    const size_t len1 = seq1s.empty() ? 0 : seq1s[0].size(), mw = SWMI_LOCAL_MOVE_WORDS(len1);
     for (const auto &s : seq1s)
         if (s.size() != len1) throw std::invalid_argument("SmithWaterman_local_mi355x_batch: every seq1 must have the same length");
-    if (piece == 0) piece = 1;
-    const size_t mw = SWMI_LOCAL_MOVE_WORDS(len1);
-    const size_t m_max = n < piece ? n : piece;
-    std::vector<uint8_t> a(m_max * len1);
-    std::vector<int32_t> scores(m_max), ends(4 * m_max);
-    std::vector<uint64_t> moves(m_max * mw);
-    std::vector<uint32_t> steps(m_max);
-    for (size_t off = 0; off < n; off += piece) {
-        const size_t m = n - off < piece ? n - off : piece;
-        for (size_t k = 0; k < m; ++k) std::copy(seq1s[off + k].begin(), seq1s[off + k].end(), a.begin() + k * len1);
-        if (swmi_local_align(a.data(), len1, seq2s[off].data(), m, score_matrix.data(), gap_penalty, scores.data(), ends.data(),
-                             moves.data(), steps.data()) != SWMI_OK)
-            throw std::runtime_error(std::string("swmi_local_align: ") + swmi_last_error());
-        for (size_t k = 0; k < m; ++k)
-            out[off + k] = {scores[k], expand_local_moves(moves.data() + k * mw, steps[k], ends[4 * k], ends[4 * k + 1])};
-    }
-    return out;
+    auto align = [&](detail::PieceBuffers &p, size_t off, size_t m) {
+        p.seq1s.resize(m * len1);
+        for (size_t k = 0; k < m; ++k) std::copy(seq1s[off + k].begin(), seq1s[off + k].end(), p.seq1s.begin() + k * len1);
+        p.scores.resize(m);
+        p.ends.resize(4 * m);
+        p.moves.resize(m * mw);
+        p.counts.resize(m);
+        detail::check(swmi_local_align(p.seq1s.data(), len1, seq2s[off].data(), m, score_matrix.data(), gap_penalty, p.scores.data(),
+                                       p.ends.data(), p.moves.data(), p.counts.data()),
+                      "swmi_local_align");
+    };
+    return detail::run_in_pieces(seq1s.size(), piece, 0, align, [&](const detail::PieceBuffers &p, size_t k) {
+        return detail::Result{p.scores[k], expand_local_moves(p.moves.data() + k * mw, p.counts[k], p.ends[4 * k], p.ends[4 * k + 1])};
+    });
 }
 
 // Affine local alignment of seq1s[k] (every one of the same length) against seq2s[k]: result[k] ==
@@ -118,29 +189,23 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SmithWaterm
     const std::array<int8_t, 16> &score_matrix, int gap_open, int gap_extend, size_t piece = 65536)
 {
     if (seq1s.size() != seq2s.size()) throw std::invalid_argument("SmithWaterman_affine_mi355x_batch: seq1s and seq2s differ in length");
-    const size_t n = seq1s.size();
-    std::vector<std::pair<int, std::vector<std::pair<int, int>>>> out(n);
-    if (n == 0) return out;
-    const size_t len1 = seq1s[0].size();
+    const size_t len1 = seq1s.empty() ? 0 : seq1s[0].size(), mw = SWMI_LOCAL_MOVE_WORDS(len1);
     for (const auto &s : seq1s)
         if (s.size() != len1) throw std::invalid_argument("SmithWaterman_affine_mi355x_batch: every seq1 must have the same length");
-    if (piece == 0) piece = 1;
-    const size_t mw = SWMI_LOCAL_MOVE_WORDS(len1);
-    const size_t m_max = n < piece ? n : piece;
-    std::vector<uint8_t> a(m_max * len1);
-    std::vector<int32_t> scores(m_max), ends(4 * m_max);
-    std::vector<uint64_t> moves(m_max * mw);
-    std::vector<uint32_t> steps(m_max);
-    for (size_t off = 0; off < n; off += piece) {
-        const size_t m = n - off < piece ? n - off : piece;
-        for (size_t k = 0; k < m; ++k) std::copy(seq1s[off + k].begin(), seq1s[off + k].end(), a.begin() + k * len1);
-        if (swmi_local_align_affine(a.data(), len1, seq2s[off].data(), m, score_matrix.data(), gap_open, gap_extend, scores.data(),
-                                    ends.data(), moves.data(), steps.data()) != SWMI_OK)
-            throw std::runtime_error(std::string("swmi_local_align_affine: ") + swmi_last_error());
-        for (size_t k = 0; k < m; ++k)
-            out[off + k] = {scores[k], expand_local_moves(moves.data() + k * mw, steps[k], ends[4 * k], ends[4 * k + 1])};
-    }
-    return out;
+    auto align = [&](detail::PieceBuffers &p, size_t off, size_t m) {
+        p.seq1s.resize(m * len1);
+        for (size_t k = 0; k < m; ++k) std::copy(seq1s[off + k].begin(), seq1s[off + k].end(), p.seq1s.begin() + k * len1);
+        p.scores.resize(m);
+        p.ends.resize(4 * m);
+        p.moves.resize(m * mw);
+        p.counts.resize(m);
+        detail::check(swmi_local_align_affine(p.seq1s.data(), len1, seq2s[off].data(), m, score_matrix.data(), gap_open, gap_extend,
+                                              p.scores.data(), p.ends.data(), p.moves.data(), p.counts.data()),
+                      "swmi_local_align_affine");
+    };
+    return detail::run_in_pieces(seq1s.size(), piece, 0, align, [&](const detail::PieceBuffers &p, size_t k) {
+        return detail::Result{p.scores[k], expand_local_moves(p.moves.data() + k * mw, p.counts[k], p.ends[4 * k], p.ends[4 * k + 1])};
+    });
 }
 
 // Ragged local alignments (swmi_local_align_ragged and its affine twin): seq1s[k] of any length in [0, 16384] against
@@ -152,35 +217,29 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> local_ragge
     size_t piece, Call call)
 {
     if (seq1s.size() != seq2s.size()) throw std::invalid_argument(std::string(name) + ": seq1s and seq2s differ in length");
-    const size_t n = seq1s.size();
-    std::vector<std::pair<int, std::vector<std::pair<int, int>>>> out(n);
-    if (piece == 0) piece = 1;
-    std::vector<uint8_t> a;
-    std::vector<uint64_t> offsets, move_offsets, moves;
-    std::vector<int32_t> scores, ends;
-    std::vector<uint32_t> steps;
-    for (size_t off = 0; off < n; off += piece) {
-        const size_t m = n - off < piece ? n - off : piece;
-        a.clear();
-        offsets.assign(1, 0);
+    auto align = [&](detail::PieceBuffers &p, size_t off, size_t m) {
+        p.seq1s.clear();
+        p.seq1_offsets.assign(1, 0);
         for (size_t k = 0; k < m; ++k) {
-            a.insert(a.end(), seq1s[off + k].begin(), seq1s[off + k].end());
-            offsets.push_back(a.size());
+            p.seq1s.insert(p.seq1s.end(), seq1s[off + k].begin(), seq1s[off + k].end());
+            p.seq1_offsets.push_back(p.seq1s.size());
         }
-        if (a.empty()) a.push_back(0);                  // (every seq1 of the piece is empty: a pointer that is never read)
-        move_offsets.resize(m + 1);
-        if (swmi_local_ragged_move_offsets(offsets.data(), m, move_offsets.data()) != SWMI_OK)
+        if (p.seq1s.empty()) p.seq1s.push_back(0);      // (every seq1 of the piece is empty: a pointer that is never read)
+        p.move_offsets.resize(m + 1);
+        if (swmi_local_ragged_move_offsets(p.seq1_offsets.data(), m, p.move_offsets.data()) != SWMI_OK)
             throw std::invalid_argument(std::string(name) + ": " + swmi_last_error());
-        moves.resize(move_offsets[m]);
-        scores.resize(m);
-        ends.resize(4 * m);
-        steps.resize(m);
-        if (call(a.data(), offsets.data(), seq2s[off].data(), m, scores.data(), ends.data(), moves.data(), steps.data()) != SWMI_OK)
-            throw std::runtime_error(std::string(name) + ": " + swmi_last_error());
-        for (size_t k = 0; k < m; ++k)
-            out[off + k] = {scores[k], expand_local_moves(moves.data() + move_offsets[k], steps[k], ends[4 * k], ends[4 * k + 1])};
-    }
-    return out;
+        p.scores.resize(m);
+        p.ends.resize(4 * m);
+        p.moves.resize(p.move_offsets[m]);
+        p.counts.resize(m);
+        detail::check(call(p.seq1s.data(), p.seq1_offsets.data(), seq2s[off].data(), m, p.scores.data(), p.ends.data(), p.moves.data(),
+                           p.counts.data()),
+                      name);
+    };
+    return detail::run_in_pieces(seq1s.size(), piece, 0, align, [](const detail::PieceBuffers &p, size_t k) {
+        return detail::Result{p.scores[k],
+                              expand_local_moves(p.moves.data() + p.move_offsets[k], p.counts[k], p.ends[4 * k], p.ends[4 * k + 1])};
+    });
 }
 
 // Local alignment of seq1s[k] (any lengths, 0 .. 16384) against seq2s[k]: result[k] == SmithWaterman_local_mi355x(seq1s[k],
@@ -219,52 +278,64 @@ inline std::vector<std::pair<int, int>> expand_moves(const uint64_t *moves, uint
 {
     static_assert(sizeof(std::pair<int, int>) == 2 * sizeof(int32_t), "std::pair<int,int> must be two packed ints");
     std::vector<std::pair<int, int>> tb(length);
-    if (swmi_semiglobal_expand_moves(moves, length, reinterpret_cast<int32_t *>(tb.data()), length) != SWMI_OK)
-        throw std::runtime_error(std::string("swmi_semiglobal_expand_moves: ") + swmi_last_error());
+    detail::check(swmi_semiglobal_expand_moves(moves, length, reinterpret_cast<int32_t *>(tb.data()), length), "swmi_semiglobal_expand_moves");
     return tb;
 }
 
 // The reference's SpeedtestSemiGlobal loop (source.cpp:2818-2856) over arrays of pairs: result[k] ==
 // SemiGlobal_AdaptiveBanded_XDrop_111_32_70(seq1s[k], seq2s[k]).  The GPU returns 2 bits per traceback step (8 KB per
-// alignment over PCIe instead of the 262 KB its positions take); the positions are rebuilt here, on `threads` host threads
-// (0 = as many as the machine reports, at most 64), one slice of 65536 alignments while the GPU works on the next.
+// alignment over PCIe instead of the 262 KB its positions take).  The batch goes to the GPU in pieces of `piece` alignments
+// (65536 = two of the library's internal chunks: its copies and kernels overlap inside a call); only two pieces' moves are
+// held at a time, and the positions of one piece are rebuilt on `threads` host threads (0 = as many as the machine reports,
+// at most 64) while the GPU aligns the next.  A failure in an expander thread is recorded, every thread is joined, and then
+// it is thrown.
 inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SemiGlobal_mi355x_batch(
-    const std::vector<std::array<uint8_t, 16384>> &seq1s, const std::vector<std::array<uint8_t, 16384>> &seq2s, unsigned threads = 0)
+    const std::vector<std::array<uint8_t, 16384>> &seq1s, const std::vector<std::array<uint8_t, 16384>> &seq2s, unsigned threads = 0,
+    size_t piece = 65536)
 {
     static_assert(sizeof(std::array<uint8_t, 16384>) == 16384, "std::array<uint8_t,16384> must be 16384 contiguous bytes");
     if (seq1s.size() != seq2s.size()) throw std::invalid_argument("SemiGlobal_mi355x_batch: seq1s and seq2s differ in length");
-    const size_t n = seq1s.size();
-    std::vector<std::pair<int, std::vector<std::pair<int, int>>>> out(n);
-    if (n == 0) return out;
     if (threads == 0) threads = std::thread::hardware_concurrency();
     threads = threads < 1 ? 1 : threads > 64 ? 64 : threads;
-    constexpr size_t kSlice = 65536;                   // two of the library's internal chunks: its copies and kernels overlap inside a call
-    std::vector<int32_t> scores(n);
-    std::vector<uint32_t> lengths(n);
-    std::vector<uint64_t> moves(n * size_t(SWMI_SG_MOVE_WORDS));
-    std::vector<std::thread> pool;                     // the expanders of the slice before the one the GPU works on
-    std::string failed;
-    auto join_all = [&] {
-        for (auto &th : pool) th.join();
-        pool.clear();
+    const size_t mw = SWMI_SG_MOVE_WORDS;
+    auto align = [&](detail::PieceBuffers &p, size_t off, size_t m) {
+        p.scores.resize(m);
+        p.moves.resize(m * mw);
+        p.counts.resize(m);
+        detail::check(swmi_semiglobal_xdrop_moves(seq1s[off].data(), seq2s[off].data(), m, p.scores.data(), p.moves.data(), p.counts.data()),
+                      "swmi_semiglobal_xdrop_moves");
     };
-    for (size_t off = 0; off < n && failed.empty(); off += kSlice) {
-        const size_t m = n - off < kSlice ? n - off : kSlice;
-        if (swmi_semiglobal_xdrop_moves(seq1s[off].data(), seq2s[off].data(), m, scores.data() + off,
-                                        moves.data() + off * size_t(SWMI_SG_MOVE_WORDS), lengths.data() + off) != SWMI_OK)
-            failed = swmi_last_error();
-        join_all();
-        if (!failed.empty()) break;
-        const unsigned use = threads > m ? unsigned(m) : threads;
-        for (unsigned t = 0; t < use; ++t)
-            pool.emplace_back([&, off, m, t, use] {
-                for (size_t k = off + m * t / use; k < off + m * (t + 1) / use; ++k)
-                    out[k] = {scores[k], expand_moves(moves.data() + k * size_t(SWMI_SG_MOVE_WORDS), lengths[k])};
-            });
-    }
-    join_all();
-    if (!failed.empty()) throw std::runtime_error("swmi_semiglobal_xdrop_moves: " + failed);
-    return out;
+    return detail::run_in_pieces(seq1s.size(), piece, threads, align, [&](const detail::PieceBuffers &p, size_t k) {
+        return detail::Result{p.scores[k], expand_moves(p.moves.data() + k * mw, p.counts[k])};
+    });
+}
+
+// The reference's SemiGlobal_111 (source.cpp:1776-1834) over arrays of pairs: result[k] == SemiGlobal_111(seq1s[k], seq2s[k]).
+// The batch goes to the GPU in pieces of `piece` alignments (256 = one full-size slice of swmi_semiglobal_full); only two
+// pieces' moves are held at a time (8 KiB per alignment), and the paths of one piece are rebuilt on `threads` host threads
+// (0 = as many as the machine reports, at most 64) while the GPU aligns the next.  A failure in an expander thread is
+// recorded, every thread is joined, and then it is thrown.
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SemiGlobal_111_mi355x_batch(
+    const std::vector<std::array<uint8_t, 16384>> &seq1s, const std::vector<std::array<uint8_t, 16384>> &seq2s,
+    unsigned threads = 0, size_t piece = 256)
+{
+    static_assert(sizeof(std::array<uint8_t, 16384>) == 16384, "std::array<uint8_t,16384> must be 16384 contiguous bytes");
+    if (seq1s.size() != seq2s.size()) throw std::invalid_argument("SemiGlobal_111_mi355x_batch: seq1s and seq2s differ in length");
+    if (threads == 0) threads = std::thread::hardware_concurrency();
+    threads = threads < 1 ? 1 : threads > 64 ? 64 : threads;
+    const size_t mw = SWMI_SGFULL_MOVE_WORDS(16384, 16384);
+    auto align = [&](detail::PieceBuffers &p, size_t off, size_t m) {
+        p.scores.resize(m);
+        p.ends.resize(2 * m);
+        p.moves.resize(m * mw);
+        p.counts.resize(m);
+        detail::check(swmi_semiglobal_full(seq1s[off].data(), 16384, seq2s[off].data(), 16384, m, semiglobal_111_matrix().data(), 1,
+                                           p.scores.data(), p.ends.data(), p.moves.data(), p.counts.data()),
+                      "swmi_semiglobal_full");
+    };
+    return detail::run_in_pieces(seq1s.size(), piece, threads, align, [&](const detail::PieceBuffers &p, size_t k) {
+        return detail::Result{p.scores[k], expand_moves(p.moves.data() + k * mw, p.counts[k])};
+    });
 }
 
 // The reference's 1M-call loop (source.cpp:3074-3082) over arrays of pairs, on every GPU the library is bound to:
@@ -282,7 +353,7 @@ inline std::vector<int32_t> SmithWaterman_mi355x_batch(const std::vector<std::ar
     const int rc = swmi_num_gpus() > 1
                        ? swmi_score_batch_multi(a, b, seq1s.size(), score_matrix.data(), gap_penalty, scores.data())
                        : swmi_score_batch(a, b, seq1s.size(), score_matrix.data(), gap_penalty, scores.data());
-    if (rc != SWMI_OK) throw std::runtime_error(std::string("SmithWaterman_mi355x_batch: ") + swmi_last_error());
+    detail::check(rc, "SmithWaterman_mi355x_batch");
     return scores;
 }
 
@@ -291,8 +362,7 @@ class PairQueue {
 public:
     PairQueue(size_t max_pairs, const std::array<int8_t, 16> &score_matrix, int8_t gap_penalty)
     {
-        if (swmi_queue_create(max_pairs, score_matrix.data(), gap_penalty, &q_) != SWMI_OK)
-            throw std::runtime_error(std::string("swmi_queue_create: ") + swmi_last_error());
+        detail::check(swmi_queue_create(max_pairs, score_matrix.data(), gap_penalty, &q_), "swmi_queue_create");
     }
     ~PairQueue() { swmi_queue_destroy(q_); }
     PairQueue(const PairQueue &) = delete;
@@ -309,7 +379,7 @@ public:
     {
         const int32_t *p = nullptr;
         size_t n = 0;
-        if (swmi_queue_wait(q_, &p, &n) != SWMI_OK) throw std::runtime_error(std::string("swmi_queue_wait: ") + swmi_last_error());
+        detail::check(swmi_queue_wait(q_, &p, &n), "swmi_queue_wait");
         return std::vector<int32_t>(p, p + n);
     }
     void reset() { swmi_queue_reset(q_); }
@@ -326,8 +396,7 @@ inline std::pair<int, std::vector<std::pair<int, int>>> SemiGlobal_AdaptiveBande
     int32_t score = 0;
     uint32_t length = 0;
     std::vector<uint64_t> moves(SWMI_SG_MOVE_WORDS);
-    if (swmi_semiglobal_xdrop_moves(seq1.data(), seq2.data(), 1, &score, moves.data(), &length) != SWMI_OK)
-        throw std::runtime_error(std::string("swmi_semiglobal_xdrop_moves: ") + swmi_last_error());
+    swmi::detail::check(swmi_semiglobal_xdrop_moves(seq1.data(), seq2.data(), 1, &score, moves.data(), &length), "swmi_semiglobal_xdrop_moves");
     return {score, swmi::expand_moves(moves.data(), length)};
 }
 
@@ -339,9 +408,9 @@ inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_local_mi35
     int32_t score = 0, ends[4] = {0, 0, 0, 0};
     uint32_t steps = 0;
     std::vector<uint64_t> moves(SWMI_LOCAL_MOVE_WORDS(seq1.size()));
-    if (swmi_local_align(seq1.data(), seq1.size(), seq2.data(), 1, score_matrix.data(), gap_penalty, &score, ends, moves.data(),
-                         &steps) != SWMI_OK)
-        throw std::runtime_error(std::string("swmi_local_align: ") + swmi_last_error());
+    swmi::detail::check(swmi_local_align(seq1.data(), seq1.size(), seq2.data(), 1, score_matrix.data(), gap_penalty, &score, ends,
+                                         moves.data(), &steps),
+                        "swmi_local_align");
     return {score, swmi::expand_local_moves(moves.data(), steps, ends[0], ends[1])};
 }
 
@@ -353,95 +422,17 @@ inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_affine_mi3
     int32_t score = 0, ends[4] = {0, 0, 0, 0};
     uint32_t steps = 0;
     std::vector<uint64_t> moves(SWMI_LOCAL_MOVE_WORDS(seq1.size()));
-    if (swmi_local_align_affine(seq1.data(), seq1.size(), seq2.data(), 1, score_matrix.data(), gap_open, gap_extend, &score, ends,
-                                moves.data(), &steps) != SWMI_OK)
-        throw std::runtime_error(std::string("swmi_local_align_affine: ") + swmi_last_error());
+    swmi::detail::check(swmi_local_align_affine(seq1.data(), seq1.size(), seq2.data(), 1, score_matrix.data(), gap_open, gap_extend, &score,
+                                                ends, moves.data(), &steps),
+                        "swmi_local_align_affine");
     return {score, swmi::expand_local_moves(moves.data(), steps, ends[0], ends[1])};
 }
 
 inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_111_long_mi355x(const std::vector<uint8_t> &seq1,
                                                                                      const std::array<uint8_t, 128> &seq2)
 {
-    static const std::array<int8_t, 16> k111 = {1, -1, -1, -1, -1, 1, -1, -1, -1, -1, 1, -1, -1, -1, -1, 1};
-    return SmithWaterman_local_mi355x(seq1, seq2, k111, 1);
+    return SmithWaterman_local_mi355x(seq1, seq2, swmi::semiglobal_111_matrix(), 1);
 }
-
-namespace swmi {
-
-// The reference's SemiGlobal_111 (source.cpp:1776-1834) over arrays of pairs: result[k] == SemiGlobal_111(seq1s[k], seq2s[k]).
-// The batch goes to the GPU in pieces of `piece` alignments (256 = one full-size slice of swmi_semiglobal_full); only two
-// pieces' moves are held at a time (8 KiB per alignment), and the paths of one piece are rebuilt on `threads` host threads
-// (0 = as many as the machine reports, at most 64) while the GPU aligns the next.  A failure in an expander thread is
-// recorded, every thread is joined, and then it is thrown.
-inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SemiGlobal_111_mi355x_batch(
-    const std::vector<std::array<uint8_t, 16384>> &seq1s, const std::vector<std::array<uint8_t, 16384>> &seq2s,
-    unsigned threads = 0, size_t piece = 256)
-{
-    static_assert(sizeof(std::array<uint8_t, 16384>) == 16384, "std::array<uint8_t,16384> must be 16384 contiguous bytes");
-    if (seq1s.size() != seq2s.size()) throw std::invalid_argument("SemiGlobal_111_mi355x_batch: seq1s and seq2s differ in length");
-    const size_t n = seq1s.size();
-    std::vector<std::pair<int, std::vector<std::pair<int, int>>>> out(n);
-    if (n == 0) return out;
-    if (threads == 0) threads = std::thread::hardware_concurrency();
-    threads = threads < 1 ? 1 : threads > 64 ? 64 : threads;
-    if (piece == 0) piece = 1;
-    const size_t mw = SWMI_SGFULL_MOVE_WORDS(16384, 16384), m_max = n < piece ? n : piece;
-    std::vector<int32_t> scores[2], ends[2];
-    std::vector<uint32_t> lengths[2];
-    std::vector<uint64_t> moves[2];
-    for (int b = 0; b < 2; ++b) {
-        scores[b].resize(m_max);
-        ends[b].resize(2 * m_max);
-        lengths[b].resize(m_max);
-        moves[b].resize(m_max * mw);
-    }
-    std::vector<std::thread> pool;                     // the expanders of the piece before the one the GPU works on
-    std::mutex mu;
-    std::string failed;                                // the first failure, GPU or expander
-    auto join_all = [&] {
-        for (auto &th : pool) th.join();
-        pool.clear();
-    };
-    auto record = [&](const std::string &what) {
-        std::lock_guard<std::mutex> lock(mu);
-        if (failed.empty()) failed = what;
-    };
-    auto has_failed = [&] {
-        std::lock_guard<std::mutex> lock(mu);
-        return !failed.empty();
-    };
-    int buf = 0;
-    for (size_t off = 0; off < n && !has_failed(); off += piece, buf ^= 1) {
-        const size_t m = n - off < piece ? n - off : piece;
-        if (swmi_semiglobal_full(seq1s[off].data(), 16384, seq2s[off].data(), 16384, m, semiglobal_111_matrix().data(), 1, scores[buf].data(),
-                                 ends[buf].data(), moves[buf].data(), lengths[buf].data()) != SWMI_OK)
-            record(std::string("swmi_semiglobal_full: ") + swmi_last_error());
-        join_all();                                    // (the previous piece's expanders, which used the other buffer)
-        if (has_failed()) break;
-        const unsigned use = threads > m ? unsigned(m) : threads;
-        try {
-            for (unsigned t = 0; t < use; ++t)
-                pool.emplace_back([&, off, m, t, use, buf] {
-                    try {
-                        for (size_t k = m * t / use; k < m * (t + 1) / use; ++k)
-                            out[off + k] = {scores[buf][k], expand_moves(moves[buf].data() + k * mw, lengths[buf][k])};
-                    } catch (const std::exception &e) {
-                        record(e.what());
-                    } catch (...) {
-                        record("SemiGlobal_111_mi355x_batch: expander failed");
-                    }
-                });
-        } catch (...) {
-            join_all();
-            throw;
-        }
-    }
-    join_all();
-    if (!failed.empty()) throw std::runtime_error(failed);
-    return out;
-}
-
-}  // namespace swmi
 
 inline std::pair<int, std::vector<std::pair<int, int>>> SemiGlobal_111_mi355x(const std::array<uint8_t, 16384> &seq1,
                                                                              const std::array<uint8_t, 16384> &seq2)
@@ -449,8 +440,8 @@ inline std::pair<int, std::vector<std::pair<int, int>>> SemiGlobal_111_mi355x(co
     int32_t score = 0, ends[2] = {0, 0};
     uint32_t length = 0;
     std::vector<uint64_t> moves(SWMI_SGFULL_MOVE_WORDS(16384, 16384));
-    if (swmi_semiglobal_full(seq1.data(), 16384, seq2.data(), 16384, 1, swmi::semiglobal_111_matrix().data(), 1, &score, ends, moves.data(),
-                             &length) != SWMI_OK)
-        throw std::runtime_error(std::string("swmi_semiglobal_full: ") + swmi_last_error());
+    swmi::detail::check(swmi_semiglobal_full(seq1.data(), 16384, seq2.data(), 16384, 1, swmi::semiglobal_111_matrix().data(), 1, &score, ends,
+                                             moves.data(), &length),
+                        "swmi_semiglobal_full");
     return {score, swmi::expand_moves(moves.data(), length)};
 }
