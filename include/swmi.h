@@ -462,6 +462,57 @@ SWMI_API int swmi_semiglobal_full_time_device(const void *d_seq1s, size_t len1, 
                                               const int8_t score_matrix[16], int8_t gap_penalty, void *d_scores, void *d_ends,
                                               void *d_moves, void *d_lengths, void *stream, int iters, float *avg_ms);
 
+/* ---- exact semi-global aligner with AFFINE gaps and traceback ----------------------------------
+ * No reference counterpart: swmi_semiglobal_full with Gotoh's gaps, a gap of length k costing gap_open + (k-1) gap_extend
+ * (the convention of swmi_score_banded_affine and swmi_local_align_affine).  n alignments; seq1 k = the len1 bytes at
+ * seq1s + len1 * k, seq2 k = the len2 bytes at seq2s + len2 * k, one (len1, len2) per call, 1 <= len1, len2 <= 16384; any
+ * int8 matrix; gap_open and gap_extend each in [0, 127], in either order; bases are taken modulo 4.
+ *     H(0,0) = 0;  H(0,j) = -(open + (j-1) extend)  (j >= 1);  H(i,0) = -(open + (i-1) extend)  (i >= 1)
+ *     E(0,j) = -inf;  F(i,0) = -inf
+ *     E(i,j) = max(H(i-1,j) - open, E(i-1,j) - extend)        vertical gap: consumes seq1, an up move
+ *     F(i,j) = max(H(i,j-1) - open, F(i,j-1) - extend)        horizontal gap: consumes seq2, a left move
+ *     H(i,j) = max(H(i-1,j-1) + sm[seq1[i-1]*4 + seq2[j-1]], E(i,j), F(i,j))          (no zero floor)
+ * The BEST CELL is swmi_semiglobal_full's: the first cell in row-major order over i = 0..len1, j = 0..len2 whose H is
+ * strictly greater than every earlier one, starting from 0 at (0,0); (0,0) when no cell is above 0.  scores[k] = H there,
+ * ends[2k], ends[2k+1] = its (i, j).  The walk starts at the best cell in state H.  State H at (i,j), i > 0 and j > 0: a
+ * diagonal step if H = H(i-1,j-1) + s, else state E if H = E(i,j), else state F.  State E: an up step, after which the state
+ * is H if E(i,j) = H(i-1,j) - open (opening wins a tie) and stays E otherwise; state F likewise with left steps.  On row 0
+ * and column 0 the walk is forced: up along column 0, left along row 0.  moves + k * SWMI_SGFULL_MOVE_WORDS(len1, len2)
+ * receives the steps in WALKING order, 3 = diagonal, 2 = up, 1 = left (every step decreases i or j); lengths[k] = steps + 1,
+ * so swmi_semiglobal_expand_moves(moves_k, lengths[k], ...) rebuilds the (i, j) list from (0,0) to the best cell.  moves
+ * and lengths both NULL: ENDS-ONLY, no codes are stored or walked.
+ * Every H, E and F that can be reached lies in [-127 (len1 + len2), 127 min(len1, len2)], within +-2^22 (what sizes the
+ * kernel's keys).  With gap_open == gap_extend == g, E(i,j) = H(i-1,j) - g exactly and opening wins the tie, so H is
+ * swmi_semiglobal_full's table and the walk its walk: every field equals swmi_semiglobal_full's with gap g.
+ * Host buffers, in SLICES (swmi_semiglobal_full_affine_slices_for) on two sets of device buffers.  Errors:
+ * SWMI_ERR_INVALID_ARGUMENT for a length outside [1, 16384], a NULL buffer, or only one of moves / lengths; SWMI_ERR_DOMAIN
+ * for gap_open or gap_extend outside [0, 127]; n = 0 is a no-op that needs no device.  Every argument is checked before any
+ * device is touched. */
+SWMI_API int swmi_semiglobal_full_affine(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t len2, size_t n,
+                                         const int8_t score_matrix[16], int gap_open, int gap_extend, int32_t *scores,
+                                         int32_t *ends, uint64_t *moves, uint32_t *lengths);
+/* The slices a swmi_semiglobal_full_affine call of n alignments cuts its batch into (traceback = 0: ends-only), in order;
+ * returns how many there are and writes the first `cap` sizes (NULL to count).  With a traceback a slice's device buffers
+ * stay within what 256 alignments of 16384 x 16384 take (about 32.1 GiB: 128.5 MiB of codes each, 4 bits per cell), so that
+ * a full-size slice gives every CU of an MI355X a workgroup; ends-only slices stay within 256 MiB.  At most 2^20 alignments
+ * per slice.  Needs no device.  0 for a length outside [1, 16384]. */
+SWMI_API size_t swmi_semiglobal_full_affine_slices_for(size_t n, size_t len1, size_t len2, int traceback, size_t *sizes,
+                                                       size_t cap);
+/* Same with every buffer in device memory (16-byte aligned), asynchronous on `stream`.  The traceback codes go to a workspace
+ * of the library's per (GPU, stream), grown on demand up to one slice and kept until
+ * swmi_semiglobal_full_affine_release_workspaces() / swmi_shutdown(). */
+SWMI_API int swmi_semiglobal_full_affine_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
+                                                const int8_t score_matrix[16], int gap_open, int gap_extend, void *d_scores,
+                                                void *d_ends, void *d_moves, void *d_lengths, void *stream);
+/* Free the device buffers of both entries above on the current GPU (synchronises the device first). */
+SWMI_API int swmi_semiglobal_full_affine_release_workspaces(void);
+/* Measurement helper: `iters` swmi_semiglobal_full_affine_device calls back to back on `stream`, bracketed by HIP events;
+ * *avg_ms = the average time of one call.  Synchronous. */
+SWMI_API int swmi_semiglobal_full_affine_time_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2,
+                                                     size_t n, const int8_t score_matrix[16], int gap_open, int gap_extend,
+                                                     void *d_scores, void *d_ends, void *d_moves, void *d_lengths, void *stream,
+                                                     int iters, float *avg_ms);
+
 /* unpack() itself (source.cpp:1580-1583) for n packed sequences, on the GPU. Host buffers. */
 SWMI_API int swmi_unpack(const uint8_t *packed, size_t n_seqs, uint8_t *unpacked);
 

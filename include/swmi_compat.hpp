@@ -57,6 +57,13 @@ inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_affine_mi3
 // synchronous call per alignment; swmi::SemiGlobal_111_mi355x_batch below is the throughput form.
 inline std::pair<int, std::vector<std::pair<int, int>>> SemiGlobal_111_mi355x(const std::array<uint8_t, 16384> &seq1,
                                                                              const std::array<uint8_t, 16384> &seq2);
+// The same exact semi-global alignment of any lengths in [1, 16384] with affine gaps, a gap of length k costing gap_open +
+// (k-1) gap_extend (swmi_semiglobal_full_affine: no reference counterpart; open = extend = 1 with (1, -1) at 16384 x 16384
+// is SemiGlobal_111).  One synchronous call per alignment; swmi::SemiGlobal_affine_mi355x_batch is the throughput form.
+inline std::pair<int, std::vector<std::pair<int, int>>> SemiGlobal_affine_mi355x(const std::vector<uint8_t> &seq1,
+                                                                                const std::vector<uint8_t> &seq2,
+                                                                                const std::array<int8_t, 16> &score_matrix,
+                                                                                int gap_open, int gap_extend);
 
 namespace swmi {
 
@@ -338,6 +345,51 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SemiGlobal_
     });
 }
 
+// Affine exact semi-global alignment of seq1s[k] against seq2s[k], every seq1 of one length and every seq2 of one length:
+// result[k] == SemiGlobal_affine_mi355x(seq1s[k], seq2s[k], score_matrix, gap_open, gap_extend).  The batch goes to the GPU
+// in pieces of `piece` alignments, at most one traceback slice of swmi_semiglobal_full_affine (0 = one slice: 256 at
+// 16384 x 16384); only two pieces' moves are held at a time, and the paths of one piece are rebuilt on `threads` host
+// threads (0 = as many as the machine reports, at most 64) while the GPU aligns the next.
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SemiGlobal_affine_mi355x_batch(
+    const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::vector<uint8_t>> &seq2s,
+    const std::array<int8_t, 16> &score_matrix, int gap_open, int gap_extend, unsigned threads = 0, size_t piece = 0)
+{
+    if (seq1s.size() != seq2s.size()) throw std::invalid_argument("SemiGlobal_affine_mi355x_batch: seq1s and seq2s differ in length");
+    const size_t len1 = seq1s.empty() ? 0 : seq1s[0].size(), len2 = seq2s.empty() ? 0 : seq2s[0].size();
+    for (const auto &s : seq1s)
+        if (s.size() != len1) throw std::invalid_argument("SemiGlobal_affine_mi355x_batch: every seq1 must have the same length");
+    for (const auto &s : seq2s)
+        if (s.size() != len2) throw std::invalid_argument("SemiGlobal_affine_mi355x_batch: every seq2 must have the same length");
+    if (seq1s.empty()) return {};
+    size_t slice = 0;
+    if (swmi_semiglobal_full_affine_slices_for(seq1s.size(), len1, len2, 1, &slice, 1) == 0)
+        detail::check(swmi_semiglobal_full_affine(nullptr, len1, nullptr, len2, 1, score_matrix.data(), gap_open, gap_extend, nullptr,
+                                                  nullptr, nullptr, nullptr),
+                      "swmi_semiglobal_full_affine");       // (a length out of range: throws the library's error)
+    if (piece == 0 || piece > slice) piece = slice;
+    if (threads == 0) threads = std::thread::hardware_concurrency();
+    threads = threads < 1 ? 1 : threads > 64 ? 64 : threads;
+    const size_t mw = SWMI_SGFULL_MOVE_WORDS(len1, len2);
+    auto align = [&](detail::PieceBuffers &p, size_t off, size_t m) {
+        p.seq1s.resize(m * (len1 + len2));
+        uint8_t *s2 = p.seq1s.data() + m * len1;
+        for (size_t k = 0; k < m; ++k) {
+            std::copy(seq1s[off + k].begin(), seq1s[off + k].end(), p.seq1s.begin() + k * len1);
+            std::copy(seq2s[off + k].begin(), seq2s[off + k].end(), s2 + k * len2);
+        }
+        p.scores.resize(m);
+        p.ends.resize(2 * m);
+        p.moves.resize(m * mw);
+        p.counts.resize(m);
+        detail::check(swmi_semiglobal_full_affine(p.seq1s.data(), len1, s2, len2, m, score_matrix.data(), gap_open, gap_extend,
+                                                  p.scores.data(), p.ends.data(), p.moves.data(), p.counts.data()),
+                      "swmi_semiglobal_full_affine");
+    };
+    return detail::run_in_pieces(seq1s.size(), piece, threads, align, [&](const detail::PieceBuffers &p, size_t k) {
+        return detail::Result{p.scores[k], expand_moves(p.moves.data() + k * mw, p.counts[k])};
+    });
+}
+
 // The reference's 1M-call loop (source.cpp:3074-3082) over arrays of pairs, on every GPU the library is bound to:
 // scores[k] == SmithWaterman(seq1s[k], seq2s[k], score_matrix, gap_penalty).  std::array<uint8_t,128> has no padding, so a
 // vector of them IS the concatenated layout the C ABI takes.  With swmi_init(device) it runs on that one GPU, with
@@ -443,5 +495,19 @@ inline std::pair<int, std::vector<std::pair<int, int>>> SemiGlobal_111_mi355x(co
     swmi::detail::check(swmi_semiglobal_full(seq1.data(), 16384, seq2.data(), 16384, 1, swmi::semiglobal_111_matrix().data(), 1, &score, ends,
                                              moves.data(), &length),
                         "swmi_semiglobal_full");
+    return {score, swmi::expand_moves(moves.data(), length)};
+}
+
+inline std::pair<int, std::vector<std::pair<int, int>>> SemiGlobal_affine_mi355x(const std::vector<uint8_t> &seq1,
+                                                                                const std::vector<uint8_t> &seq2,
+                                                                                const std::array<int8_t, 16> &score_matrix,
+                                                                                int gap_open, int gap_extend)
+{
+    int32_t score = 0, ends[2] = {0, 0};
+    uint32_t length = 0;
+    std::vector<uint64_t> moves(SWMI_SGFULL_MOVE_WORDS(seq1.size(), seq2.size()));
+    swmi::detail::check(swmi_semiglobal_full_affine(seq1.data(), seq1.size(), seq2.data(), seq2.size(), 1, score_matrix.data(), gap_open,
+                                                    gap_extend, &score, ends, moves.data(), &length),
+                        "swmi_semiglobal_full_affine");
     return {score, swmi::expand_moves(moves.data(), length)};
 }

@@ -672,6 +672,7 @@ void destroy_context(Context &c)
     c.local_state.reset();              // (after the synchronisation above: its deleter frees device memory)
     c.sgfull_state.reset();
     c.local_affine_state.reset();
+    c.sgfull_affine_state.reset();
     if (c.pin) (void)hipHostFree(c.pin);
     c.pin = nullptr;
     c.pin_dev = nullptr;

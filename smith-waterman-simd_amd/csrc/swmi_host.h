@@ -172,6 +172,7 @@ struct Context {
     std::shared_ptr<void> local_state;
     std::shared_ptr<void> sgfull_state;
     std::shared_ptr<void> local_affine_state;   // the affine local aligner's (local_affine_api.cpp through the same pipeline)
+    std::shared_ptr<void> sgfull_affine_state;  // the affine exact semi-global aligner's (sgfull_affine_api.cpp, likewise)
     std::mutex mu;                      // serialises use of the slots, the sg sets and the pinned buffer
 };
 
@@ -243,6 +244,8 @@ int table_time_device(const Table &t, const char *entry, const void *d_seq1s, co
 int table_check_timer(size_t n, int iters, const float *avg_ms);   // what the timers check before their first call
 Table local_table(size_t len1, const int8_t *sm, int gap);                               // swmi_table.cpp
 Table affine_table(size_t len1, const int8_t *sm, int gap_open, int gap_extend);         // local_affine_api.cpp
+// Free one aligner's device buffers on the current GPU (synchronises the device first): the body of the *_release_workspaces entries
+int table_release_workspaces(std::shared_ptr<void> Context::*member);
 
 #define SWMI_HIP_TRY(expr)                                                                                          \
     do {                                                                                                            \

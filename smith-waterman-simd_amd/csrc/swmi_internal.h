@@ -123,3 +123,12 @@ hipError_t launch_sgfull(const uint8_t *d_seq1s, const uint8_t *d_seq2s, int len
                          int32_t *d_scores, int32_t *d_ends, uint32_t *d_codes, unsigned long long *d_moves, uint32_t *d_lengths,
                          size_t move_words, hipStream_t stream);
 }  // namespace swmi
+
+namespace swmi {
+// Exact semi-global aligner with AFFINE gaps and traceback (sgfull_affine_kernels.hip): launch_sgfull's shapes and
+// workgroups, with sgfull_affine_code_qwords(len1, len2) qwords of codes per alignment of the launch (4 bits per cell).
+size_t sgfull_affine_code_qwords(int len1, int len2);
+hipError_t launch_sgfull_affine(const uint8_t *d_seq1s, const uint8_t *d_seq2s, int len1, int len2, size_t n, const int8_t *sm,
+                                int gap_open, int gap_extend, int32_t *d_scores, int32_t *d_ends, unsigned long long *d_codes,
+                                unsigned long long *d_moves, uint32_t *d_lengths, size_t move_words, hipStream_t stream);
+}  // namespace swmi

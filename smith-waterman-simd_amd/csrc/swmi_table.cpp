@@ -1,10 +1,11 @@
 // swmi_table.cpp -- host side of the aligners that fill the whole table, write codes and walk them (include/swmi.h): the local
 // aligner with end cell, start cell and traceback (swmi_local_*) and the exact semi-global aligner with
-// traceback (swmi_semiglobal_full*, section 13) here, and the one slice pipeline that they and the affine local aligner
-// (local_affine_api.cpp, section 14) run through.  What differs between them is data (struct Table, swmi_host.h).
+// traceback (swmi_semiglobal_full*, section 13) here, and the one slice pipeline that they and the affine aligners
+// (local_affine_api.cpp, section 14; sgfull_affine_api.cpp, section 16) run through.  What differs between them is data
+// (struct Table, swmi_host.h).
 //
-// Their device buffers hang off Context::local_state, sgfull_state and local_affine_state, which destroy_context
-// (swmi_api.cpp) drops at swmi_shutdown: that file names no symbol of this one, so the host-only builds of swmi_api.cpp /
+// Their device buffers hang off Context::local_state, sgfull_state, local_affine_state and sgfull_affine_state, which
+// destroy_context (swmi_api.cpp) drops at swmi_shutdown: that file names no symbol of this one, so the host-only builds of swmi_api.cpp /
 // swmi_multi.cpp (tests/test_multi_fake.py, tests/test_sanitizers.py) link without these kernels -- and this file names no
 // launcher but launch_local and launch_sgfull, so that the fake-GPU build of every swmi_*.cpp (tests/test_table_host_fake.py)
 // links without the affine kernels.
@@ -363,6 +364,18 @@ int table_time_device(const Table &t, const char *entry, const void *d_seq1s, co
     return rc;
 }
 
+int table_release_workspaces(std::shared_ptr<void> Context::*member)
+{
+    Context *ctx = current();
+    if (!ctx) return last_status();
+    SWMI_HIP_TRY(hipDeviceSynchronize());
+    TableState &ts = state(*ctx, member);
+    std::lock_guard<std::mutex> host_lock(ctx->mu);
+    std::lock_guard<std::mutex> lock(ts.mu);
+    ts.release();
+    return SWMI_OK;
+}
+
 }  // namespace host
 }  // namespace swmi
 
@@ -457,17 +470,7 @@ int swmi_semiglobal_full(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s
     return table_host(sgfull_table(len1, len2, score_matrix, gap_penalty), __func__, seq1s, seq2s, n, scores, ends, moves, lengths);
 }
 
-int swmi_semiglobal_full_release_workspaces(void)
-{
-    Context *ctx = current();
-    if (!ctx) return last_status();
-    SWMI_HIP_TRY(hipDeviceSynchronize());
-    TableState &ts = state(*ctx, &Context::sgfull_state);
-    std::lock_guard<std::mutex> host_lock(ctx->mu);
-    std::lock_guard<std::mutex> lock(ts.mu);
-    ts.release();
-    return SWMI_OK;
-}
+int swmi_semiglobal_full_release_workspaces(void) { return table_release_workspaces(&Context::sgfull_state); }
 
 int swmi_semiglobal_full_time_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
                                      const int8_t score_matrix[16], int8_t gap_penalty, void *d_scores, void *d_ends, void *d_moves,

@@ -143,6 +143,12 @@ def load():
     lib.swmi_semiglobal_full_slices_for.restype = sz
     lib.swmi_semiglobal_full_time_device.argtypes = [vp, sz, vp, sz, sz, vp, i8, vp, vp, vp, vp, vp, ctypes.c_int,
                                                      ctypes.POINTER(ctypes.c_float)]
+    lib.swmi_semiglobal_full_affine.argtypes = [vp, sz, vp, sz, sz, vp, ci, ci, vp, vp, vp, vp]
+    lib.swmi_semiglobal_full_affine_device.argtypes = [vp, sz, vp, sz, sz, vp, ci, ci, vp, vp, vp, vp, vp]
+    lib.swmi_semiglobal_full_affine_slices_for.argtypes = [sz, sz, sz, ci, vp, sz]
+    lib.swmi_semiglobal_full_affine_slices_for.restype = sz
+    lib.swmi_semiglobal_full_affine_time_device.argtypes = [vp, sz, vp, sz, sz, vp, ci, ci, vp, vp, vp, vp, vp, ci,
+                                                            ctypes.POINTER(ctypes.c_float)]
     _lib = lib
     return lib
 
@@ -793,6 +799,61 @@ def semiglobal_full_slices_for(n, len1, len2, traceback=True):
 def semiglobal_full_release_workspaces():
     """Free the exact semi-global aligner's device buffers on the current GPU."""
     _check(load().swmi_semiglobal_full_release_workspaces())
+
+
+def semiglobal_full_affine(seq1s, seq2s, score_matrix, gap_open, gap_extend, traceback=True):
+    """Exact semi-global alignment with affine gaps and traceback (swmi_semiglobal_full_affine): semiglobal_full with a gap of
+    length k costing gap_open + (k-1) gap_extend.  Same arguments and return value as semiglobal_full, with (gap_open,
+    gap_extend) for the gap."""
+    a = np.ascontiguousarray(seq1s, dtype=np.uint8)
+    b = np.ascontiguousarray(seq2s, dtype=np.uint8)
+    if a.ndim != 2 or b.ndim != 2:
+        raise ValueError("seq1s and seq2s must be (n, len1) and (n, len2)")
+    n, len1 = a.shape
+    len2 = b.shape[1]
+    if b.shape[0] != n:
+        raise ValueError("seq1s and seq2s hold different numbers of sequences")
+    sm = _sm(score_matrix)
+    scores = np.zeros(n, np.int32)
+    ends = np.zeros((n, 2), np.int32)
+    moves = np.zeros((n, semiglobal_full_move_words(len1, len2)), np.uint64) if traceback else None
+    lengths = np.zeros(n, np.uint32) if traceback else None
+    _check(load().swmi_semiglobal_full_affine(a.ctypes.data, len1, b.ctypes.data, len2, n, sm.ctypes.data, int(gap_open),
+                                              int(gap_extend), scores.ctypes.data, ends.ctypes.data,
+                                              moves.ctypes.data if traceback else None, lengths.ctypes.data if traceback else None))
+    return scores, ends, moves, lengths
+
+
+def semiglobal_full_affine_device(d_seq1s, len1, d_seq2s, len2, n, score_matrix, gap_open, gap_extend, d_scores, d_ends,
+                                  d_moves=None, d_lengths=None, stream=0):
+    """swmi_semiglobal_full_affine_device on device pointers (asynchronous on `stream`); d_moves = d_lengths = None: ends-only."""
+    sm = _sm(score_matrix)
+    _check(load().swmi_semiglobal_full_affine_device(d_seq1s, len1, d_seq2s, len2, n, sm.ctypes.data, int(gap_open), int(gap_extend),
+                                                     d_scores, d_ends, d_moves, d_lengths, stream))
+
+
+def semiglobal_full_affine_time_device(d_seq1s, len1, d_seq2s, len2, n, score_matrix, gap_open, gap_extend, d_scores, d_ends,
+                                       d_moves=None, d_lengths=None, stream=0, iters=10):
+    """Average ms of one swmi_semiglobal_full_affine_device call over `iters` back-to-back calls (HIP events on `stream`)."""
+    sm = _sm(score_matrix)
+    ms = ctypes.c_float()
+    _check(load().swmi_semiglobal_full_affine_time_device(d_seq1s, len1, d_seq2s, len2, n, sm.ctypes.data, int(gap_open),
+                                                          int(gap_extend), d_scores, d_ends, d_moves, d_lengths, stream, int(iters),
+                                                          ctypes.byref(ms)))
+    return float(ms.value)
+
+
+def semiglobal_full_affine_slices_for(n, len1, len2, traceback=True):
+    """The slices swmi_semiglobal_full_affine cuts n alignments into (needs no device)."""
+    count = load().swmi_semiglobal_full_affine_slices_for(n, len1, len2, 1 if traceback else 0, None, 0)
+    buf = (ctypes.c_size_t * max(count, 1))()
+    load().swmi_semiglobal_full_affine_slices_for(n, len1, len2, 1 if traceback else 0, buf, count)
+    return [int(buf[k]) for k in range(count)]
+
+
+def semiglobal_full_affine_release_workspaces():
+    """Free the affine exact semi-global aligner's device buffers on the current GPU."""
+    _check(load().swmi_semiglobal_full_affine_release_workspaces())
 
 
 def unpack(packed):
