@@ -9,7 +9,10 @@ copies the inputs back and scores them with oracle/liboracle.so on all host core
 A second phase does the same for the semi-global aligner against the reference's simd_mark4 (full tracebacks); a third
 one for the banded affine extension against the oracle's scalar Gotoh (random lengths, matrices, open / extend); a fourth
 and a fifth for the local aligner and the exact semi-global aligner against their C restatements (tests/native/
-local_oracle.c, sgfull_oracle.c): shapes from the grids of tests/table_edges.py and the inputs built there, every field."""
+local_oracle.c, sgfull_oracle.c): shapes from the grids of tests/table_edges.py and the inputs built there, every field;
+a sixth and a seventh for the affine local aligner and the affine exact semi-global aligner against theirs
+(local_affine_oracle.c, sgfull_affine_oracle.c): the grids and inputs of tests/affine_edges.py, random (open, extend) of
+every family (extend < open, open < extend, either or both 0)."""
 import argparse, ctypes, os, sys, time
 from concurrent.futures import ThreadPoolExecutor
 import numpy as np
@@ -24,6 +27,8 @@ ap.add_argument("--sg-seconds", type=float, default=60)
 ap.add_argument("--ba-seconds", type=float, default=30)
 ap.add_argument("--local-seconds", type=float, default=30)
 ap.add_argument("--sgfull-seconds", type=float, default=60)
+ap.add_argument("--local-affine-seconds", type=float, default=30)
+ap.add_argument("--sgfull-affine-seconds", type=float, default=60)
 args = ap.parse_args()
 swmi.init(0)
 vp = ctypes.c_void_p
@@ -153,10 +158,13 @@ print("banded affine fuzz vs oracle: %d alignments, %d mismatches (11 lengths 64
 # ---- the table aligners vs their C restatements: grid shapes, random shapes, the constructed edge inputs ---------------
 import tempfile
 import table_edges as te
+import affine_edges as ae
+from local_affine_support import AffineOracle
 from local_support import LocalOracle
+from sgfull_affine_support import SgAffineOracle
 from sgfull_support import SgFullOracle
 _tmp = tempfile.mkdtemp()
-lorc, sorc = LocalOracle(_tmp), SgFullOracle(_tmp)
+lorc, sorc, laorc, saorc = LocalOracle(_tmp), SgFullOracle(_tmp), AffineOracle(_tmp), SgAffineOracle(_tmp)
 
 
 def table_params():
@@ -170,22 +178,35 @@ def table_params():
     return swmi.match_matrix(int(rng.integers(1, 128)), -int(rng.integers(0, 129))), int(rng.integers(0, 128))
 
 
+def affine_params():
+    """a matrix of table_params and (open, extend) of one family: extend < open, open < extend, any, (g, 0), (0, g), (0, 0)"""
+    sm, g = table_params()
+    family = int(rng.integers(0, 6))
+    h = int(rng.integers(0, 128)) if g > 8 else int(rng.integers(0, 9))
+    return sm, ((max(g, h), min(g, h)), (min(g, h), max(g, h)), (g, h), (g, 0), (0, g), (0, 0))[family]
+
+
 def table_round(kind, cases, draw, count_offset):
     """one batch: a constructed case (its own parameters, or random ones) every third round, else a drawn shape; returns
-    (alignments, mismatching alignments)"""
+    (alignments, mismatching alignments).  gap: one penalty (the linear aligners) or (open, extend) (the affine ones)."""
     global table_iter
     table_iter += 1
+    affine = kind.endswith("_affine")
+    params = affine_params if affine else table_params
     if table_iter % 3 == 0:
         case = cases[int(rng.integers(0, len(cases)))]
         a, b = case.a, case.b
-        sm, gap = (case.sm, case.gap) if rng.random() < 0.5 else table_params()
+        sm, gap = (case.sm, case.gaps if affine else case.gap) if rng.random() < 0.5 else params()
     else:
-        (a, b), (sm, gap) = draw(), table_params()
+        (a, b), (sm, gap) = draw(), params()
     tb = bool(rng.random() < 0.75)
-    if kind == "local":
-        got, want = swmi.local_align(a, b, sm, gap, traceback=tb), lorc.align(a, b, sm, gap)
+    if kind.startswith("local"):
+        got, want = (swmi.local_align_affine(a, b, sm, *gap, traceback=tb), laorc.align(a, b, sm, *gap)) if affine else \
+            (swmi.local_align(a, b, sm, gap, traceback=tb), lorc.align(a, b, sm, gap))
         if not tb:
             got, want = (got[0], got[1][:, :2], None, None), (want[0], want[1][:, :2], None, None)
+    elif affine:
+        got, want = swmi.semiglobal_full_affine(a, b, sm, *gap, traceback=tb), saorc.align(a, b, sm, *gap, traceback=tb)
     else:
         got, want = swmi.semiglobal_full(a, b, sm, gap, traceback=tb), sorc.align(a, b, sm, gap, traceback=tb)
     bad = 0
@@ -195,7 +216,7 @@ def table_round(kind, cases, draw, count_offset):
             break
         field, k = diff
         if bad == 0:
-            print("MISMATCH %s %dx%d gap %d sm %s traceback %d: alignment %d %s" % (kind, a.shape[1], b.shape[1], gap, np.asarray(sm).tolist(),
+            print("MISMATCH %s %dx%d gap %s sm %s traceback %d: alignment %d %s" % (kind, a.shape[1], b.shape[1], gap, np.asarray(sm).tolist(),
                                                                                  tb, k, field), flush=True)
         bad += 1
         keep = np.arange(len(got[0])) != k
@@ -205,15 +226,15 @@ def table_round(kind, cases, draw, count_offset):
     return len(a) + bad, bad
 
 
-def draw_local():
-    len1 = int(rng.choice(te.LOC_LEN1)) if rng.random() < 0.6 else int(rng.integers(1, te.LOC_MAX_LEN + 1))
-    n = int(rng.choice(te.LOC_N)) if len1 > 4096 else int(rng.integers(1, 300))
+def draw_local(len1s=te.LOC_LEN1, ns=te.LOC_N):
+    len1 = int(rng.choice(len1s)) if rng.random() < 0.6 else int(rng.integers(1, te.LOC_MAX_LEN + 1))
+    n = int(rng.choice(ns)) if len1 > 4096 else int(rng.integers(1, 300))
     return te.local_mixed_pairs(n, len1, int(rng.integers(0, 2**62)))
 
 
-def draw_sgfull():
+def draw_sgfull(grid=te.sg_shape_grid()):
     if rng.random() < 0.5:
-        len1, len2, n = te.sg_shape_grid()[int(rng.integers(0, len(te.sg_shape_grid())))]
+        len1, len2, n = grid[int(rng.integers(0, len(grid)))]
     else:
         len1, len2 = int(rng.integers(1, te.SG_MAX_LEN + 1)), int(rng.integers(1, te.SG_MAX_LEN + 1))
         while len1 * len2 > 1 << 26:
@@ -226,7 +247,11 @@ table_iter = 0
 for kind, seconds, cases, draw, offset in (
         ("local", args.local_seconds, lambda: te.local_insertion_cases() + te.local_tie_cases() + te.local_extreme_cases(), draw_local, 0),
         ("sgfull", args.sgfull_seconds, lambda: (te.sg_gap_run_cases() + te.sg_staircase_cases() + te.sg_corner_cases()
-                                                 + te.sg_wave_edge_end_cases() + te.sg_tie_cases() + te.sg_pad_cases()), draw_sgfull, 1)):
+                                                 + te.sg_wave_edge_end_cases() + te.sg_tie_cases() + te.sg_pad_cases()), draw_sgfull, 1),
+        ("local_affine", args.local_affine_seconds, lambda: [c for make in ae.LOCAL_GROUPS.values() for c in make()] + ae.local_extreme_cases(),
+         lambda: draw_local(ae.LOCA_LEN1, ae.LOCA_N), 0),
+        ("sgfull_affine", args.sgfull_affine_seconds, lambda: [c for make in ae.SG_GROUPS.values() for c in make()],
+         lambda: draw_sgfull(ae.sg_shape_grid()), 1)):
     if seconds <= 0:
         continue
     built = cases()

@@ -29,7 +29,9 @@ def kernel_constants(source):
     env = {}
     with open(os.path.join(CSRC, source)) as fh:
         for name, expr in re.findall(r"constexpr int (k\w+) = ([^;]+);", fh.read()):
-            env[name] = int(eval(expr, {"__builtins__": {}}, dict(env)))
+            cast = expr.startswith("(int)")                 # a 32-bit pattern written in hex: wrap it as the compiler does
+            v = int(eval(expr[5:] if cast else expr, {"__builtins__": {}}, dict(env)))
+            env[name] = (v + (1 << 31)) % (1 << 32) - (1 << 31) if cast else v
     return env
 
 
@@ -56,28 +58,39 @@ def sg_waves(len2):
 # len1 at the edges of the trip (kUnroll steps), the chunk (kChunk steps: local_chunks = ceil((len1 + 63) / kChunk) steps
 # up at len1 = 32 m + 1), the 64-lane pipeline of a wave (lane 63 is 63 rows behind lane 0), the staging block
 # (kStageRows), the ring (kRing), 16 rings, and the longest sequence
-SG_LEN1 = sorted({1, 2, 3} | set(_around(SG["kUnroll"])) | set(range(SG["kChunk"] - 1, SG["kChunk"] + 3)) | set(_around(WAVE))
-                 | set(_around(SG_STAGE_ROWS)) | set(_around(SG["kRing"])) | set(_around(16 * SG["kRing"]))
-                 | {SG_MAX_LEN - 1, SG_MAX_LEN})
+def sg_len1_grid(sg):
+    return sorted({1, 2, 3} | set(_around(sg["kUnroll"])) | set(range(sg["kChunk"] - 1, sg["kChunk"] + 3)) | set(_around(WAVE))
+                  | set(_around(sg["kStageRows"])) | set(_around(sg["kRing"])) | set(_around(16 * sg["kRing"]))
+                  | {SG_MAX_LEN - 1, SG_MAX_LEN})
+
+
+SG_LEN1 = sg_len1_grid(SG)
 # W whose len2 take every edge of the wave: W * 1024 (no pad column in the last wave), W * 1024 - 1, (W - 1) * 1024 + 1
 # (one valid column in the last wave) and a value = 15 (mod 16) (every lane of the last one but the last column valid);
 # every other W takes one of them
 SG_FULL_W = (1, 2, 4, 6, 11, SG["kMaxWaves"])
 
 
-def _len2_edges(W):
-    return [SG_WAVE_COLS * W, SG_WAVE_COLS * W - 1, SG_WAVE_COLS * (W - 1) + 1,
-            SG_WAVE_COLS * (W - 1) + SG["kCols"] * ((37 * W) % WAVE) + SG["kCols"] - 1]
+def _len2_edges(W, sg=SG):
+    wave_cols = WAVE * sg["kCols"]
+    return [wave_cols * W, wave_cols * W - 1, wave_cols * (W - 1) + 1,
+            wave_cols * (W - 1) + sg["kCols"] * ((37 * W) % WAVE) + sg["kCols"] - 1]
 
 
-SG_LEN2 = sorted({v for W in range(1, SG["kMaxWaves"] + 1) for v in (_len2_edges(W) if W in SG_FULL_W else [_len2_edges(W)[W % 4]])})
+def sg_len2_grid(sg, full_w=SG_FULL_W):
+    return sorted({v for W in range(1, sg["kMaxWaves"] + 1)
+                   for v in (_len2_edges(W, sg) if W in full_w else [_len2_edges(W, sg)[W % 4]])})
 
 
-def sg_shape_grid():
-    """[(len1, len2, n)]: a covering of SG_LEN1 x SG_LEN2 (every value of both at least once), the longest len2 with the
+SG_LEN2 = sg_len2_grid(SG)
+
+
+def sg_shape_grid(len1s=None, len2s=None):
+    """[(len1, len2, n)]: a covering of SG_LEN1 x SG_LEN2 (or of the two lists given: the same grid derived from another
+    kernel's constants), every value of both at least once, the longest len2 with the
     shortest len1 and the other way round, then a second pass rotated by a third that keeps shapes under 2^25 cells; n so
     that a shape holds about 2^24 cells (one or two alignments at 16384 rows or columns)."""
-    l1, l2 = SG_LEN1, SG_LEN2[::-1]
+    l1, l2 = SG_LEN1 if len1s is None else len1s, (SG_LEN2 if len2s is None else len2s)[::-1]
     shapes = [(l1[k % len(l1)], l2[k % len(l2)]) for k in range(max(len(l1), len(l2)))]
     rot = len(l1) // 3
     shapes += [(l1[(k + rot) % len(l1)], l2[k]) for k in range(len(l2)) if l1[(k + rot) % len(l1)] * l2[k] <= 1 << 25]
@@ -92,14 +105,23 @@ SG_PARAMS = [("(1,-1,1)", K111, 1), ("(5,-4,0)", match_matrix(5, -4), 0), ("rand
 
 # len1 where n_steps = len1 + kLanes - 1 sits at the edges of a trip of kUnroll steps (and of a step pair of codes), and
 # around 128, 256, 1024 and the longest sequence; n at the edges of kAlnPerWave and kAlnPerBlock alignments
-_LOC_TRIP = [v for v in range(1, 3 * LOC["kUnroll"]) if (v + LOC["kLanes"] - 1) % LOC["kUnroll"] in (0, 1, LOC["kUnroll"] - 1)]
-LOC_LEN1 = sorted(set(_LOC_TRIP) | {v for x in (128, 256, 1024, LOC_MAX_LEN) for v in _around(x, hi=LOC_MAX_LEN)})
-LOC_N = sorted({1} | set(_around(LOC["kAlnPerWave"])) | set(_around(LOC["kAlnPerBlock"])) | set(_around(WAVE)) | {3})
+def local_len1_grid(loc):
+    trip = [v for v in range(1, 3 * loc["kUnroll"]) if (v + loc["kLanes"] - 1) % loc["kUnroll"] in (0, 1, loc["kUnroll"] - 1)]
+    return sorted(set(trip) | {v for x in (128, 256, 1024, LOC_MAX_LEN) for v in _around(x, hi=LOC_MAX_LEN)})
 
 
-def local_shape_grid():
-    """[(len1, n)]: every len1 with two n of LOC_N (every n at least once)."""
-    return [(len1, LOC_N[(2 * k + d) % len(LOC_N)]) for k, len1 in enumerate(LOC_LEN1) for d in (0, 1)]
+def local_n_grid(loc):
+    return sorted({1} | set(_around(loc["kAlnPerWave"])) | set(_around(loc["kAlnPerBlock"])) | set(_around(WAVE)) | {3})
+
+
+LOC_LEN1 = local_len1_grid(LOC)
+LOC_N = local_n_grid(LOC)
+
+
+def local_shape_grid(len1s=None, ns=None):
+    """[(len1, n)]: every len1 of LOC_LEN1 (or of the list given) with two n of LOC_N (every n at least once)."""
+    len1s, ns = LOC_LEN1 if len1s is None else len1s, LOC_N if ns is None else ns
+    return [(len1, ns[(2 * k + d) % len(ns)]) for k, len1 in enumerate(len1s) for d in (0, 1)]
 
 
 LOCAL_PARAMS = [("(10,-30,15)", match_matrix(10, -30), 15), ("(5,-4,0)", match_matrix(5, -4), 0), ("(1,-1,1)", match_matrix(1, -1), 1),
@@ -562,16 +584,17 @@ def gap_runs(c, i, j):
     return [(int(c[s]), int(e - s), int(i[s]), int(j[s])) for s, e in zip(starts, ends) if c[s] in (1, 2)]
 
 
-def staging_exits(i, j):
-    """How the sgfull walk leaves each staging block it loads (kStageRows rows x kStageLanes lanes ending at its cell):
-    [(exit, block spans two waves)], exit 'top', 'left' or 'corner' (both at one diagonal move), or 'border' (row or column
-    0 reached inside the block)."""
+def staging_exits(i, j, stage_rows=SG_STAGE_ROWS, stage_lanes=SG["kStageLanes"], steps=False):
+    """How the sgfull walk leaves each staging block it loads (stage_rows rows x stage_lanes lanes ending at its cell; the
+    linear kernel's by default): [(exit, block spans two waves)], exit 'top', 'left' or 'corner' (both at one diagonal
+    move), or 'border' (row or column 0 reached inside the block).  steps=True: [(exit, spans, t)], move t - 1 the one
+    that left the block and cell t the first outside it."""
     out = []
     t, n = 0, len(i) - 1
     while i[t] > 0 and j[t] > 0:
         g1 = (j[t] - 1) // SG["kCols"]
-        i_lo = max(i[t] - SG_STAGE_ROWS + 1, 1)
-        g_lo = max(g1 - SG["kStageLanes"] + 1, 0)
+        i_lo = max(i[t] - stage_rows + 1, 1)
+        g_lo = max(g1 - stage_lanes + 1, 0)
         rest_i, rest_j = i[t:], j[t:]
         top = rest_i < i_lo
         left = (rest_j - 1) // SG["kCols"] < g_lo
@@ -582,26 +605,32 @@ def staging_exits(i, j):
         s = int(out_at[0])
         kind = "border" if border[s] and not (top[s] and i_lo > 1) and not (left[s] and rest_j[s] > 0) else \
             "corner" if top[s] and left[s] else "top" if top[s] else "left"
-        out.append((kind, g_lo // WAVE != g1 // WAVE))
         t += s
+        out.append((kind, g_lo // WAVE != g1 // WAVE) + ((t,) if steps else ()))
         if t >= n:
             break
     return out
 
 
-def sg_path_facts(score, ends, moves, length):
-    """The walk-shape predicates of one sgfull alignment (oracle or GPU result)."""
-    end_i, end_j = int(ends[0]), int(ends[1])
-    c, i, j = walk_cells(moves, int(length) - 1, end_i, end_j)
+def sg_path_facts(score, ends, moves, length, stage_rows=SG_STAGE_ROWS, stage_lanes=SG["kStageLanes"]):
+    """The walk-shape predicates of one sgfull alignment (oracle or GPU result), for a staging block of stage_rows x
+    stage_lanes (the linear kernel's by default)."""
+    c, i, j = walk_cells(moves, int(length) - 1, int(ends[0]), int(ends[1]))
+    return sg_walk_facts(score, c, i, j, stage_rows, stage_lanes)
+
+
+def sg_walk_facts(score, c, i, j, stage_rows=SG_STAGE_ROWS, stage_lanes=SG["kStageLanes"]):
+    """sg_path_facts of a walk given as walk_cells returns it"""
+    end_j = int(j[0])
     runs = gap_runs(c, i, j)
     left = [(L, ri, rj) for code, L, ri, rj in runs if code == 1 and ri > 0]
     up = [(L, ri, rj) for code, L, ri, rj in runs if code == 2 and rj > 0]
-    exits = staging_exits(i, j)
+    exits = staging_exits(i, j, stage_rows, stage_lanes)
     crosses = lambda L, rj: (rj - 1) // SG_WAVE_COLS > (rj - L - 1) // SG_WAVE_COLS  # noqa: E731  (columns rj - L .. rj)
     return {
         "left_run_1100_across_waves": any(L >= 1100 and rj - L >= 1 and crosses(L, rj) for L, ri, rj in left),
-        "left_run_over_1024": any(L > SG_STAGE_COLS for L, _, _ in left),
-        "up_run_over_128": any(L > SG_STAGE_ROWS for L, _, _ in up),
+        "left_run_over_1024": any(L > stage_lanes * SG["kCols"] for L, _, _ in left),     # wider than a staging block
+        "up_run_over_128": any(L > stage_rows for L, _, _ in up),
         "staircase": sum(100 <= L <= 250 for L, _, _ in left) >= 2 and sum(100 <= L <= 250 for L, _, _ in up) >= 2,
         "block_exit_top": any(e == "top" for e, _ in exits),
         "block_exit_left": any(e == "left" for e, _ in exits),
