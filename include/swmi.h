@@ -221,8 +221,9 @@ SWMI_API int swmi_sharded_time(swmi_sharded_batch *b, const int8_t score_matrix[
  * parity is NOT pinned by the reference.  n pairs of `len`-mers (64 <= len <= 1792, pair k at byte offset
  * len*k), local alignment restricted to the 128 diagonals -64 <= j - i <= 63, a gap of length k costs
  * gap_open + (k-1)*gap_extend (both in [0,127]).  One wavefront per alignment -- or per TWO alignments that share every
- * register as 16-bit halves (sw_banded_affine_pk_kernel, round 4) where len * max(s) + 2 max(0, -min s) + gap_open +
- * gap_extend + 64 < 0x7C00; swmi_banded_affine_kernel_for() reports which -- see DESIGN.md section 9. */
+ * register as 16-bit halves (sw_banded_affine_pk_kernel, round 4) where len * max(s, 0) + 18 max(0, -min s) + gap_open +
+ * gap_extend + 64 < 0x7C00 (18 = the kernel's trip of 16 iterations + 2); swmi_banded_affine_kernel_for() reports which --
+ * see DESIGN.md section 9. */
 SWMI_API int swmi_score_banded_affine(const uint8_t *seq1s, const uint8_t *seq2s, size_t n, int len,
                                       const int8_t score_matrix[16], int gap_open, int gap_extend,
                                       int32_t *scores);

@@ -1019,7 +1019,8 @@ sw_banded_affine_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__rest
 //                     the floor max(B, open) >= B repairs M < B, and it is <= B + open, i.e. E' <= 0 in true terms)
 //   Per cell and PAIR of alignments: perm, 1/2 paired add, max3, 2 sat-sub, 2 max3, 2 sub, 1/2 max3 (running best) = 9
 //   instructions (10 for open < ext) = 4.5 per alignment-cell against the int32 kernel's 8.25.
-// Domain (decided on the host, launch_banded_affine): len * max(s, 0) + 2 B + open + ext + 64 < 0x7C00; else the int32 kernel.
+// Domain (decided on the host, banded_affine_kernel_choice): len * max(s, 0) + (kBandedTrip + 2) B + open + ext + 64 < 0x7C00
+// (the bias grows to kBandedTrip B inside a trip, see below); else the int32 kernel.
 __device__ __forceinline__ unsigned ba_pk_max3(unsigned a, unsigned b, unsigned c)
 {
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));

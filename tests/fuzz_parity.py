@@ -7,7 +7,8 @@ the reference's own TestSimdSmithWaterman idea (source.cpp:2943-2982: fresh rand
 Every round generates a fresh batch on the device (counter-based generator, new seed), scores it through the C ABI,
 copies the inputs back and scores them with oracle/liboracle.so on all host cores (OpenMP); any mismatch is dumped.
 A second phase does the same for the semi-global aligner against the reference's simd_mark4 (full tracebacks); a third
-one for the banded affine extension against the oracle's scalar Gotoh (random lengths, matrices, open / extend); a fourth
+one for the banded affine extension against the oracle's scalar Gotoh (random lengths, matrices, open / extend, and the
+shifted copies and gap runs of tests/banded_edges.py on the band's edge diagonals); a fourth
 and a fifth for the local aligner and the exact semi-global aligner against their C restatements (tests/native/
 local_oracle.c, sgfull_oracle.c): shapes from the grids of tests/table_edges.py and the inputs built there, every field;
 a sixth and a seventh for the affine local aligner and the affine exact semi-global aligner against theirs
@@ -127,9 +128,11 @@ swmi.semiglobal_set_exact(False)
 print("semi-global fuzz vs %s: %d alignments (score + full traceback; positions entry and moves entry + host expansion in turn), %d mismatches" % ("reference simd_mark4" if ref else "oracle", sg_total, sg_bad), flush=True)
 
 # ---- banded affine extension vs oracle/sw_oracle.c (no reference counterpart: parity unpinned by the reference) ----
+import banded_edges as be
 orc.sw_oracle_banded_affine.restype = ctypes.c_int
 ba_total = ba_bad = 0
 ba_kernels = {}
+ba_edges = {}
 t_end = time.time() + args.ba_seconds
 while time.time() < t_end:
     length = int(rng.choice([64, 65, 100, 128, 200, 333, 512, 1000, 1024, 1500, 1792]))
@@ -140,6 +143,16 @@ while time.time() < t_end:
     for k in range(0, m, 3):             # indels: offsets up to and beyond the band
         cut = int(rng.integers(1, length)); sh = int(rng.integers(1, 80))
         b[k, cut:] = np.roll(b[k], sh)[cut:]
+    if length >= 100:                    # the band's edges (banded_edges.py): a copy on, or one gap run onto, diagonal -66 .. -62 / 62 .. 65
+        for k in range(1, m, 3):
+            s = int(rng.choice(be.SHIFTS))
+            if length < 200 or rng.random() < 0.5:
+                a[k], b[k] = be.shifted_pair(rng, length, s)
+                edge = "shift %+d" % s
+            else:
+                a[k], b[k] = be.gap_run_pair(rng, length, abs(s), s > 0)
+                edge = "%s %d" % ("insert" if s > 0 else "delete", abs(s))
+            ba_edges[edge] = ba_edges.get(edge, 0) + 1
     kind = int(rng.integers(0, 4))       # any int8 matrix / match-mismatch with any gaps / the usual small gaps / small scores, any gaps
     if kind == 3:                        # scores small enough for the packed kernel at every length, either sign
         sm = rng.integers(-128 if rng.random() < 0.3 else -12, 15, 16).astype(np.int8)
@@ -154,6 +167,7 @@ while time.time() < t_end:
     ba_total += m; ba_bad += int((got != want).sum())
 print("banded affine fuzz vs oracle: %d alignments, %d mismatches (11 lengths 64..1792, random matrices, open/extend 0..127 either order); per kernel: %s" % (
     ba_total, ba_bad, ", ".join("%s %d" % kv for kv in sorted(ba_kernels.items()))), flush=True)
+print("... of which at the band's edges: %s" % ", ".join("%s: %d" % kv for kv in sorted(ba_edges.items())), flush=True)
 
 # ---- the table aligners vs their C restatements: grid shapes, random shapes, the constructed edge inputs ---------------
 import tempfile

@@ -7,27 +7,8 @@ leave the band, (3) the GPU kernel against the oracle, bit-exact."""
 import numpy as np
 import pytest
 
+from banded_edges import numpy_banded_gotoh            # the per-cell formulation, band bounds as parameters (default -64, 63)
 from conftest import match_matrix
-
-NEG = -(1 << 29)
-
-
-def numpy_banded_gotoh(a, b, sm, gap_open, gap_ext):
-    """Independent restatement: anti-diagonal-free, row by row with explicit band mask, int64 arrays."""
-    n = len(a)
-    sm = np.asarray(sm, np.int64).reshape(4, 4)
-    H = np.zeros((n + 1, n + 1), np.int64)
-    E = np.full((n + 1, n + 1), NEG, np.int64)
-    F = np.full((n + 1, n + 1), NEG, np.int64)
-    best = 0
-    for i in range(1, n + 1):
-        lo, hi = max(1, i - 64), min(n, i + 63)
-        for j in range(lo, hi + 1):
-            E[i, j] = max(E[i, j - 1] - gap_ext, H[i, j - 1] - gap_open)
-            F[i, j] = max(F[i - 1, j] - gap_ext, H[i - 1, j] - gap_open)
-            H[i, j] = max(0, H[i - 1, j - 1] + sm[a[i - 1] & 3, b[j - 1] & 3], E[i, j], F[i, j])
-            best = max(best, H[i, j])
-    return int(best)
 
 
 def _related(rng, n, length, sub=0.08, indel=0.02):
@@ -114,16 +95,17 @@ def test_gpu_banded_affine_batch_shapes_and_errors(gpu, oracle):
 
 def test_banded_affine_kernel_choice_needs_no_device(swmi_mod):
     """swmi_banded_affine_kernel_for: the packed kernel (two alignments per wavefront, 16-bit halves) where every value stays
-    a finite half-precision pattern -- len * max(s) + 2 max(0, -min s) + open + extend + 64 < 0x7C00 -- else the int32 cell."""
+    a finite half-precision pattern -- len * max(s) + 18 max(0, -min s) + open + extend + 64 < 0x7C00 (18 = kBandedTrip + 2: the bias grows
+    inside a trip) -- else the int32 cell."""
     k = swmi_mod.banded_affine_kernel_for
     assert k(1024, match_matrix(2, -3), 5, 1) == ("sw_banded_affine_pk_kernel<1>", 2)
     assert k(1024, match_matrix(2, -3), 1, 4) == ("sw_banded_affine_pk_kernel<0>", 2)
-    assert k(1792, match_matrix(10, -30), 15, 15) == ("sw_banded_affine_pk_kernel<1>", 2)      # 17920 + 60 + 30 + 64
-    assert k(1024, match_matrix(30, -30), 5, 1)[0] == "sw_banded_affine_pk_kernel<1>"          # 30720 + 60 + 6 + 64 = 30850 < 31744
+    assert k(1792, match_matrix(10, -30), 15, 15) == ("sw_banded_affine_pk_kernel<1>", 2)      # 17920 + 540 + 30 + 64
+    assert k(1024, match_matrix(30, -30), 5, 1)[0] == "sw_banded_affine_pk_kernel<1>"          # 30720 + 540 + 6 + 64 = 31330 < 31744
     assert k(1024, match_matrix(31, -30), 5, 1) == ("sw_banded_affine_kernel<1,1>", 1)         # 31744 + ...: too large, still < 2^15
     assert k(1024, match_matrix(32, -30), 5, 1) == ("sw_banded_affine_kernel<1,0>", 1)         # 32768: the plain int32 cell
-    assert k(64, match_matrix(127, -127), 127, 0) == ("sw_banded_affine_pk_kernel<1>", 2)      # 8128 + 254 + 127 + 64
-    assert k(256, match_matrix(127, -127), 0, 127)[0] == "sw_banded_affine_kernel<0,1>"       # 32512 + 254 + 127 + 64 > 0x7C00, < 2^15
+    assert k(64, match_matrix(127, -127), 127, 0) == ("sw_banded_affine_pk_kernel<1>", 2)      # 8128 + 2286 + 127 + 64
+    assert k(256, match_matrix(127, -127), 0, 127)[0] == "sw_banded_affine_kernel<0,1>"       # 32512 + 2286 + 127 + 64 > 0x7C00, 32512 < 2^15
 
 
 @pytest.mark.gpu
