@@ -514,6 +514,59 @@ SWMI_API int swmi_semiglobal_full_affine_time_device(const void *d_seq1s, size_t
                                                      void *d_scores, void *d_ends, void *d_moves, void *d_lengths, void *stream,
                                                      int iters, float *avg_ms);
 
+/* ---- local alignment of two sequences of ANY length, with end cell, start cell and traceback -----
+ * swmi_local_align (SmithWaterman_111_long, source.cpp:1526-1576) with a seq2 of len2 bases instead of 128.  n alignments of
+ * seq1 (len1 bytes, alignment k at seq1s + len1 * k) against seq2 (len2 bytes, at seq2s + len2 * k), one (len1, len2) per
+ * call, 1 <= len1, len2 <= 16384; any int8 matrix, gap in [0, 127]; bases are taken modulo 4.
+ *     H(i,0) = H(0,j) = 0
+ *     H(i,j) = max(0, H(i-1,j-1) + sm[seq1[i-1]*4 + seq2[j-1]], H(i-1,j) - gap, H(i,j-1) - gap),  i = 1..len1, j = 1..len2
+ * scores[k] = max H, at most 127 * min(len1, len2) < 2^21.  ends[k] = (end_i, end_j, start_i, start_j): the end cell is the
+ * first cell in row-major order that holds the score ((0, 0) when it is 0, source.cpp:1545).  The walk from it
+ * (source.cpp:1555-1570) stops at a cell holding 0, the start cell -- that test comes first, so a cell holding 0 ends the
+ * walk even when its diagonal candidate is also 0 -- else takes a diagonal step when H(i,j) = H(i-1,j-1) + s, else an up step
+ * (i - 1) when H(i,j) = H(i-1,j) - gap, else a left step (j - 1).  Border cells hold 0: there is no forced walk along a
+ * border.  moves + k * SWMI_LOCAL_FULL_MOVE_WORDS(len1, len2) receives the steps in WALKING order (step 0 leaves the end
+ * cell), step t at bits 2 (t % 32) of word t / 32: 3 = diagonal, 2 = up, 1 = left; steps[k] = their number, so
+ * swmi_local_full_expand_moves rebuilds the reference's list of steps[k] + 1 positions; words past the last step are
+ * unspecified.  moves and steps both NULL: ENDS-ONLY -- no codes are stored or walked, the start cell is reported as (-1, -1).
+ * With len2 == 128 every field equals swmi_local_align's -- and swmi_local_align is the FASTER entry for that shape (its
+ * kernel puts 16 lanes on the 128 columns; this one gives every alignment a workgroup of at least one wavefront of 1024
+ * columns, of which 128 columns keep 8 lanes busy).  Use this entry when len2 is not 128.
+ * Host buffers.  The batch runs in SLICES (swmi_local_full_slices_for) on two sets of device buffers, one slice's copies
+ * beside the other's kernel.  Errors: SWMI_ERR_INVALID_ARGUMENT for a length outside [1, 16384], a NULL buffer, or only one
+ * of moves / steps; SWMI_ERR_DOMAIN for gap_penalty < 0; n = 0 is a no-op that needs no device.  Every argument is checked
+ * before any device is touched. */
+#define SWMI_LOCAL_FULL_MAX_LEN 16384
+#define SWMI_LOCAL_FULL_MOVE_WORDS(len1, len2) ((((((size_t)(len1)) + ((size_t)(len2)) + 31) / 32) + 1) & ~(size_t)1)   /* 16-byte rows */
+SWMI_API int swmi_local_full(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t len2, size_t n,
+                             const int8_t score_matrix[16], int8_t gap_penalty, int32_t *scores, int32_t *ends, uint64_t *moves,
+                             uint32_t *steps);
+/* The slices a swmi_local_full call of n alignments cuts its batch into (traceback = 0: ends-only), in order; returns how
+ * many there are and writes the first `cap` sizes (NULL to count).  With a traceback a slice's device buffers stay within
+ * what 256 alignments of 16384 x 16384 take (about 16.1 GiB: 64.25 MiB of codes each), so that a full-size slice gives every
+ * CU of an MI355X a workgroup; ends-only slices stay within 256 MiB of inputs and results.  At most 2^20 alignments per
+ * slice.  Needs no device.  0 for a length outside [1, 16384]. */
+SWMI_API size_t swmi_local_full_slices_for(size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap);
+/* Same with every buffer in device memory (16-byte aligned), asynchronous on `stream`.  The traceback codes (2 bits per
+ * cell) go to a workspace of the library's per (GPU, stream), grown on demand up to one slice and kept until
+ * swmi_local_full_release_workspaces() / swmi_shutdown(): calls on one stream serialise by themselves, calls on different
+ * streams may be in flight together. */
+SWMI_API int swmi_local_full_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
+                                    const int8_t score_matrix[16], int8_t gap_penalty, void *d_scores, void *d_ends,
+                                    void *d_moves, void *d_steps, void *stream);
+/* Free the device buffers of both entries above on the current GPU (synchronises the device first). */
+SWMI_API int swmi_local_full_release_workspaces(void);
+/* Measurement helper: `iters` swmi_local_full_device calls back to back on `stream`, bracketed by HIP events; *avg_ms = the
+ * average time of one call.  Synchronous. */
+SWMI_API int swmi_local_full_time_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
+                                         const int8_t score_matrix[16], int8_t gap_penalty, void *d_scores, void *d_ends,
+                                         void *d_moves, void *d_steps, void *stream, int iters, float *avg_ms);
+/* One alignment's moves -> the reference's list of (i, j) positions from the start cell to the end cell (steps + 1 of them;
+ * at most `cap` are written), on the host: swmi_local_expand_moves with both axes up to 16384.  No device.
+ * SWMI_ERR_INVALID_ARGUMENT for an end cell outside the matrix, a move of 0, or moves that leave the matrix. */
+SWMI_API int swmi_local_full_expand_moves(const uint64_t *moves, uint32_t steps, int32_t end_i, int32_t end_j, int32_t *positions,
+                                          size_t cap);
+
 /* unpack() itself (source.cpp:1580-1583) for n packed sequences, on the GPU. Host buffers. */
 SWMI_API int swmi_unpack(const uint8_t *packed, size_t n_seqs, uint8_t *unpacked);
 

@@ -149,6 +149,13 @@ def load():
     lib.swmi_semiglobal_full_affine_slices_for.restype = sz
     lib.swmi_semiglobal_full_affine_time_device.argtypes = [vp, sz, vp, sz, sz, vp, ci, ci, vp, vp, vp, vp, vp, ci,
                                                             ctypes.POINTER(ctypes.c_float)]
+    lib.swmi_local_full.argtypes = [vp, sz, vp, sz, sz, vp, i8, vp, vp, vp, vp]
+    lib.swmi_local_full_device.argtypes = [vp, sz, vp, sz, sz, vp, i8, vp, vp, vp, vp, vp]
+    lib.swmi_local_full_slices_for.argtypes = [sz, sz, sz, ctypes.c_int, vp, sz]
+    lib.swmi_local_full_slices_for.restype = sz
+    lib.swmi_local_full_time_device.argtypes = [vp, sz, vp, sz, sz, vp, i8, vp, vp, vp, vp, vp, ctypes.c_int,
+                                                ctypes.POINTER(ctypes.c_float)]
+    lib.swmi_local_full_expand_moves.argtypes = [vp, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32, vp, sz]
     _lib = lib
     return lib
 
@@ -854,6 +861,82 @@ def semiglobal_full_affine_slices_for(n, len1, len2, traceback=True):
 def semiglobal_full_affine_release_workspaces():
     """Free the affine exact semi-global aligner's device buffers on the current GPU."""
     _check(load().swmi_semiglobal_full_affine_release_workspaces())
+
+
+LOCAL_FULL_MAX_LEN = 16384
+
+
+def local_full_move_words(len1, len2):
+    """64-bit words of moves per alignment of swmi_local_full (SWMI_LOCAL_FULL_MOVE_WORDS)."""
+    return (((int(len1) + int(len2) + 31) // 32) + 1) & ~1
+
+
+def local_full(seq1s, seq2s, score_matrix, gap_penalty, traceback=True):
+    """Local alignment of two sequences of any length with end cell, start cell and traceback (swmi_local_full): local_align
+    with a seq2 of any length in [1, 16384] (one (len1, len2) per call), any int8 matrix and gap.  seq1s: (n, len1) bases,
+    seq2s: (n, len2).  For len2 == 128 local_align gives the same results faster.
+
+    Returns (scores[n] int32, ends[n, 4] int32 = (end_i, end_j, start_i, start_j), moves[n, local_full_move_words(len1, len2)]
+    uint64, steps[n] uint32); move t of alignment k = (moves[k, t // 32] >> 2 * (t % 32)) & 3 in walking order from the end
+    cell (3 diagonal, 2 up, 1 left); local_full_expand_moves(moves[k], steps[k], end_i, end_j) gives the reference's list.
+    traceback=False: ends-only (moves and steps are None, the start cell is (-1, -1))."""
+    a = np.ascontiguousarray(seq1s, dtype=np.uint8)
+    b = np.ascontiguousarray(seq2s, dtype=np.uint8)
+    if a.ndim != 2 or b.ndim != 2:
+        raise ValueError("seq1s and seq2s must be (n, len1) and (n, len2)")
+    n, len1 = a.shape
+    len2 = b.shape[1]
+    if b.shape[0] != n:
+        raise ValueError("seq1s and seq2s hold different numbers of sequences")
+    sm, gap = _sm(score_matrix), _gap(gap_penalty)
+    scores = np.zeros(n, np.int32)
+    ends = np.zeros((n, 4), np.int32)
+    moves = np.zeros((n, local_full_move_words(len1, len2)), np.uint64) if traceback else None
+    steps = np.zeros(n, np.uint32) if traceback else None
+    _check(load().swmi_local_full(a.ctypes.data, len1, b.ctypes.data, len2, n, sm.ctypes.data, gap, scores.ctypes.data,
+                                  ends.ctypes.data, moves.ctypes.data if traceback else None,
+                                  steps.ctypes.data if traceback else None))
+    return scores, ends, moves, steps
+
+
+def local_full_device(d_seq1s, len1, d_seq2s, len2, n, score_matrix, gap_penalty, d_scores, d_ends, d_moves=None, d_steps=None,
+                      stream=0):
+    """swmi_local_full_device on device pointers (asynchronous on `stream`); d_moves = d_steps = None: ends-only."""
+    sm = _sm(score_matrix)
+    _check(load().swmi_local_full_device(d_seq1s, len1, d_seq2s, len2, n, sm.ctypes.data, _gap(gap_penalty), d_scores, d_ends,
+                                         d_moves, d_steps, stream))
+
+
+def local_full_time_device(d_seq1s, len1, d_seq2s, len2, n, score_matrix, gap_penalty, d_scores, d_ends, d_moves=None,
+                           d_steps=None, stream=0, iters=10):
+    """Average ms of one swmi_local_full_device call over `iters` back-to-back calls (HIP events on `stream`)."""
+    sm = _sm(score_matrix)
+    ms = ctypes.c_float()
+    _check(load().swmi_local_full_time_device(d_seq1s, len1, d_seq2s, len2, n, sm.ctypes.data, _gap(gap_penalty), d_scores,
+                                              d_ends, d_moves, d_steps, stream, int(iters), ctypes.byref(ms)))
+    return float(ms.value)
+
+
+def local_full_slices_for(n, len1, len2, traceback=True):
+    """The slices swmi_local_full cuts n alignments into (needs no device)."""
+    count = load().swmi_local_full_slices_for(n, len1, len2, 1 if traceback else 0, None, 0)
+    buf = (ctypes.c_size_t * max(count, 1))()
+    load().swmi_local_full_slices_for(n, len1, len2, 1 if traceback else 0, buf, count)
+    return [int(buf[k]) for k in range(count)]
+
+
+def local_full_expand_moves(moves_row, steps, end_i, end_j, cap=None):
+    """One alignment's moves -> the reference's (steps + 1, 2) int32 list of (i, j) from the start cell to the end cell."""
+    row = np.ascontiguousarray(moves_row, dtype=np.uint64)
+    count = int(steps) + 1 if cap is None else min(int(steps) + 1, int(cap))
+    pos = np.zeros((count, 2), np.int32)
+    _check(load().swmi_local_full_expand_moves(row.ctypes.data, int(steps), int(end_i), int(end_j), pos.ctypes.data, count))
+    return pos
+
+
+def local_full_release_workspaces():
+    """Free the any-length local aligner's device buffers on the current GPU."""
+    _check(load().swmi_local_full_release_workspaces())
 
 
 def unpack(packed):
