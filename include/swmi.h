@@ -567,6 +567,61 @@ SWMI_API int swmi_local_full_time_device(const void *d_seq1s, size_t len1, const
 SWMI_API int swmi_local_full_expand_moves(const uint64_t *moves, uint32_t steps, int32_t end_i, int32_t end_j, int32_t *positions,
                                           size_t cap);
 
+/* ---- local alignment of two sequences of ANY length with AFFINE gaps, end cell, start cell and traceback (DESIGN.md
+ * section 18) ------------------------------------------------------------------------------------------------------------
+ * No reference counterpart: swmi_local_full with Gotoh's gaps, a gap of length k costing gap_open + (k-1) gap_extend (the
+ * convention of swmi_score_banded_affine, swmi_local_align_affine and swmi_semiglobal_full_affine).  n alignments; seq1 k =
+ * the len1 bytes at seq1s + len1 * k, seq2 k = the len2 bytes at seq2s + len2 * k, one (len1, len2) per call,
+ * 1 <= len1, len2 <= 16384 (SWMI_LOCAL_FULL_MAX_LEN); any int8 matrix; gap_open and gap_extend each in [0, 127], in either
+ * order; bases are taken modulo 4.
+ *     H(i,0) = H(0,j) = 0;  E(0,j) = -inf;  F(i,0) = -inf
+ *     E(i,j) = max(H(i-1,j) - open, E(i-1,j) - extend)        vertical gap: consumes seq1, an up move
+ *     F(i,j) = max(H(i,j-1) - open, F(i,j-1) - extend)        horizontal gap: consumes seq2, a left move
+ *     H(i,j) = max(0, H(i-1,j-1) + sm[seq1[i-1]*4 + seq2[j-1]], E(i,j), F(i,j)),   i = 1..len1, j = 1..len2
+ * scores[k] = max H, at most 127 * min(len1, len2) < 2^21.  ends[k] = (end_i, end_j, start_i, start_j): the end cell is the
+ * first cell in row-major order that holds the score, (0, 0) when it is 0.  The walk is swmi_local_align_affine's on
+ * swmi_local_full's borders.  It starts at the end cell in state H.  State H at (i,j): stop if H = 0 (this test comes first:
+ * the floor wins every tie at 0), else a diagonal step if H = H(i-1,j-1) + s, else state E if H = E(i,j), else state F.
+ * State E: an up step to (i-1,j), after which the state is H if E(i,j) = H(i-1,j) - open (opening wins a tie) and stays E
+ * otherwise; state F likewise with left steps.  Border cells hold 0 and E(1,j), F(i,1) always open, so the walk arrives on
+ * a border in state H and stops there: there is no forced walk along a border.
+ * moves + k * SWMI_LOCAL_FULL_MOVE_WORDS(len1, len2) receives the steps in WALKING order, step t at bits 2 (t % 32) of word
+ * t / 32: 3 = diagonal, 2 = up, 1 = left; steps[k] = their number.  Every step decreases i or j, so
+ * swmi_local_full_expand_moves rebuilds the list of steps[k] + 1 positions from the start cell to the end cell; words past
+ * the last step are unspecified.  moves and steps both NULL: ENDS-ONLY -- no codes are stored or walked, the start cell is
+ * reported as (-1, -1).
+ * With gap_open == gap_extend == g, E(i,j) = H(i-1,j) - g exactly and opening wins the tie, so every field equals
+ * swmi_local_full's with gap g.  With len2 == 128 every field equals swmi_local_align_affine's -- and
+ * swmi_local_align_affine is the FASTER entry for that shape (its kernel puts 16 lanes on the 128 columns; this one gives
+ * every alignment a workgroup of at least one wavefront of 1024 columns).  Use this entry when len2 is not 128.
+ * Host buffers, in SLICES (swmi_local_full_affine_slices_for) on two sets of device buffers.  Errors:
+ * SWMI_ERR_INVALID_ARGUMENT for a length outside [1, 16384], a NULL buffer or matrix, or only one of moves / steps;
+ * SWMI_ERR_DOMAIN for gap_open or gap_extend outside [0, 127]; n = 0 is a no-op that needs no device.  Every argument is
+ * checked before any device is touched. */
+SWMI_API int swmi_local_full_affine(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t len2, size_t n,
+                                    const int8_t score_matrix[16], int gap_open, int gap_extend, int32_t *scores, int32_t *ends,
+                                    uint64_t *moves, uint32_t *steps);
+/* The slices a swmi_local_full_affine call of n alignments cuts its batch into (traceback = 0: ends-only), in order; returns
+ * how many there are and writes the first `cap` sizes (NULL to count).  With a traceback a slice's device buffers stay
+ * within what 256 alignments of 16384 x 16384 take (about 32.1 GiB: 128.5 MiB of codes each, 4 bits per cell), so that a
+ * full-size slice gives every CU of an MI355X a workgroup; ends-only slices stay within 256 MiB.  At most 2^20 alignments
+ * per slice.  Needs no device.  0 for a length outside [1, 16384]. */
+SWMI_API size_t swmi_local_full_affine_slices_for(size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap);
+/* Same with every buffer in device memory (16-byte aligned), asynchronous on `stream`.  The traceback codes go to a workspace
+ * of the library's per (GPU, stream), grown on demand up to one slice and kept until
+ * swmi_local_full_affine_release_workspaces() / swmi_shutdown(). */
+SWMI_API int swmi_local_full_affine_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
+                                           const int8_t score_matrix[16], int gap_open, int gap_extend, void *d_scores,
+                                           void *d_ends, void *d_moves, void *d_steps, void *stream);
+/* Free the device buffers of both entries above on the current GPU (synchronises the device first). */
+SWMI_API int swmi_local_full_affine_release_workspaces(void);
+/* Measurement helper: `iters` swmi_local_full_affine_device calls back to back on `stream`, bracketed by HIP events;
+ * *avg_ms = the average time of one call.  Synchronous. */
+SWMI_API int swmi_local_full_affine_time_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
+                                                const int8_t score_matrix[16], int gap_open, int gap_extend, void *d_scores,
+                                                void *d_ends, void *d_moves, void *d_steps, void *stream, int iters,
+                                                float *avg_ms);
+
 /* unpack() itself (source.cpp:1580-1583) for n packed sequences, on the GPU. Host buffers. */
 SWMI_API int swmi_unpack(const uint8_t *packed, size_t n_seqs, uint8_t *unpacked);
 

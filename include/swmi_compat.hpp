@@ -73,6 +73,14 @@ inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_long_mi355
                                                                                  const std::vector<uint8_t> &seq2,
                                                                                  const std::array<int8_t, 16> &score_matrix,
                                                                                  const int8_t gap_penalty);
+// The same any-length local alignment with affine gaps, a gap of length k costing gap_open + (k-1) gap_extend
+// (swmi_local_full_affine: no reference counterpart).  One synchronous call per alignment;
+// swmi::SmithWaterman_long_affine_mi355x_batch is the throughput form.  For a 128-base seq2 SmithWaterman_affine_mi355x gives
+// the same result faster.  SmithWaterman_long_affine_mi355x(a, b, 111-matrix, 1, 1) == SmithWaterman_long_mi355x(a, b, 111-matrix, 1).
+inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_long_affine_mi355x(const std::vector<uint8_t> &seq1,
+                                                                                        const std::vector<uint8_t> &seq2,
+                                                                                        const std::array<int8_t, 16> &score_matrix,
+                                                                                        int gap_open, int gap_extend);
 
 namespace swmi {
 
@@ -454,6 +462,52 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SmithWaterm
     });
 }
 
+// Any-length affine local alignment of seq1s[k] against seq2s[k], every seq1 of one length and every seq2 of one length:
+// result[k] == SmithWaterman_long_affine_mi355x(seq1s[k], seq2s[k], score_matrix, gap_open, gap_extend).  The batch goes to the
+// GPU in pieces of `piece` alignments, at most one traceback slice of swmi_local_full_affine (0 = one slice: 256 at
+// 16384 x 16384); only two pieces' moves are held at a time, and the paths of one piece are rebuilt on `threads` host
+// threads (0 = as many as the machine reports, at most 64) while the GPU aligns the next.
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SmithWaterman_long_affine_mi355x_batch(
+    const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::vector<uint8_t>> &seq2s,
+    const std::array<int8_t, 16> &score_matrix, int gap_open, int gap_extend, size_t piece = 0, unsigned threads = 0)
+{
+    if (seq1s.size() != seq2s.size())
+        throw std::invalid_argument("SmithWaterman_long_affine_mi355x_batch: seq1s and seq2s differ in length");
+    const size_t len1 = seq1s.empty() ? 0 : seq1s[0].size(), len2 = seq2s.empty() ? 0 : seq2s[0].size();
+    for (const auto &s : seq1s)
+        if (s.size() != len1) throw std::invalid_argument("SmithWaterman_long_affine_mi355x_batch: every seq1 must have the same length");
+    for (const auto &s : seq2s)
+        if (s.size() != len2) throw std::invalid_argument("SmithWaterman_long_affine_mi355x_batch: every seq2 must have the same length");
+    if (seq1s.empty()) return {};
+    size_t slice = 0;
+    if (swmi_local_full_affine_slices_for(seq1s.size(), len1, len2, 1, &slice, 1) == 0)
+        detail::check(swmi_local_full_affine(nullptr, len1, nullptr, len2, 1, score_matrix.data(), gap_open, gap_extend, nullptr,
+                                             nullptr, nullptr, nullptr),
+                      "swmi_local_full_affine");            // (a length out of range: throws the library's error)
+    if (piece == 0 || piece > slice) piece = slice;
+    if (threads == 0) threads = std::thread::hardware_concurrency();
+    threads = threads < 1 ? 1 : threads > 64 ? 64 : threads;
+    const size_t mw = SWMI_LOCAL_FULL_MOVE_WORDS(len1, len2);
+    auto align = [&](detail::PieceBuffers &p, size_t off, size_t m) {
+        p.seq1s.resize(m * (len1 + len2));
+        uint8_t *s2 = p.seq1s.data() + m * len1;
+        for (size_t k = 0; k < m; ++k) {
+            std::copy(seq1s[off + k].begin(), seq1s[off + k].end(), p.seq1s.begin() + k * len1);
+            std::copy(seq2s[off + k].begin(), seq2s[off + k].end(), s2 + k * len2);
+        }
+        p.scores.resize(m);
+        p.ends.resize(4 * m);
+        p.moves.resize(m * mw);
+        p.counts.resize(m);
+        detail::check(swmi_local_full_affine(p.seq1s.data(), len1, s2, len2, m, score_matrix.data(), gap_open, gap_extend,
+                                             p.scores.data(), p.ends.data(), p.moves.data(), p.counts.data()),
+                      "swmi_local_full_affine");
+    };
+    return detail::run_in_pieces(seq1s.size(), piece, threads, align, [&](const detail::PieceBuffers &p, size_t k) {
+        return detail::Result{p.scores[k], expand_local_full_moves(p.moves.data() + k * mw, p.counts[k], p.ends[4 * k], p.ends[4 * k + 1])};
+    });
+}
+
 // The reference's 1M-call loop (source.cpp:3074-3082) over arrays of pairs, on every GPU the library is bound to:
 // scores[k] == SmithWaterman(seq1s[k], seq2s[k], score_matrix, gap_penalty).  std::array<uint8_t,128> has no padding, so a
 // vector of them IS the concatenated layout the C ABI takes.  With swmi_init(device) it runs on that one GPU, with
@@ -561,6 +615,20 @@ inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_long_mi355
     swmi::detail::check(swmi_local_full(seq1.data(), seq1.size(), seq2.data(), seq2.size(), 1, score_matrix.data(), gap_penalty, &score,
                                         ends, moves.data(), &steps),
                         "swmi_local_full");
+    return {score, swmi::expand_local_full_moves(moves.data(), steps, ends[0], ends[1])};
+}
+
+inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_long_affine_mi355x(const std::vector<uint8_t> &seq1,
+                                                                                        const std::vector<uint8_t> &seq2,
+                                                                                        const std::array<int8_t, 16> &score_matrix,
+                                                                                        int gap_open, int gap_extend)
+{
+    int32_t score = 0, ends[4] = {0, 0, 0, 0};
+    uint32_t steps = 0;
+    std::vector<uint64_t> moves(SWMI_LOCAL_FULL_MOVE_WORDS(seq1.size(), seq2.size()));
+    swmi::detail::check(swmi_local_full_affine(seq1.data(), seq1.size(), seq2.data(), seq2.size(), 1, score_matrix.data(), gap_open,
+                                               gap_extend, &score, ends, moves.data(), &steps),
+                        "swmi_local_full_affine");
     return {score, swmi::expand_local_full_moves(moves.data(), steps, ends[0], ends[1])};
 }
 

@@ -174,6 +174,7 @@ struct Context {
     std::shared_ptr<void> local_affine_state;   // the affine local aligner's (local_affine_api.cpp through the same pipeline)
     std::shared_ptr<void> sgfull_affine_state;  // the affine exact semi-global aligner's (sgfull_affine_api.cpp, likewise)
     std::shared_ptr<void> local_full_state;     // the any-length local aligner's (local_full_api.cpp, likewise)
+    std::shared_ptr<void> local_full_affine_state;  // the any-length affine local aligner's (local_full_affine_api.cpp, likewise)
     std::mutex mu;                      // serialises use of the slots, the sg sets and the pinned buffer
 };
 

@@ -1,15 +1,15 @@
 // swmi_table.cpp -- host side of the aligners that fill the whole table, write codes and walk them (include/swmi.h): the local
 // aligner with end cell, start cell and traceback (swmi_local_*) and the exact semi-global aligner with
 // traceback (swmi_semiglobal_full*, section 13) here, and the one slice pipeline that they and the affine aligners
-// (local_affine_api.cpp, section 14; sgfull_affine_api.cpp, section 16) and the any-length local aligner (local_full_api.cpp,
-// section 17) run through.  What differs between them is data (struct Table, swmi_host.h).
+// (local_affine_api.cpp, section 14; sgfull_affine_api.cpp, section 16) and the any-length local aligners (local_full_api.cpp,
+// section 17; local_full_affine_api.cpp, section 18) run through.  What differs between them is data (struct Table, swmi_host.h).
 //
 // Their device buffers hang off Context::local_state, sgfull_state, local_affine_state, sgfull_affine_state and
-// local_full_state, which
+// local_full_state and local_full_affine_state, which
 // destroy_context (swmi_api.cpp) drops at swmi_shutdown: that file names no symbol of this one, so the host-only builds of swmi_api.cpp /
 // swmi_multi.cpp (tests/test_multi_fake.py, tests/test_sanitizers.py) link without these kernels -- and this file names no
 // launcher but launch_local and launch_sgfull, so that the fake-GPU build of every swmi_*.cpp (tests/test_table_host_fake.py)
-// links without the affine kernels and the any-length local one.
+// links without the affine kernels and the any-length local ones.
 #include "swmi_host.h"
 
 #include <algorithm>

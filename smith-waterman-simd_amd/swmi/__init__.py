@@ -156,6 +156,12 @@ def load():
     lib.swmi_local_full_time_device.argtypes = [vp, sz, vp, sz, sz, vp, i8, vp, vp, vp, vp, vp, ctypes.c_int,
                                                 ctypes.POINTER(ctypes.c_float)]
     lib.swmi_local_full_expand_moves.argtypes = [vp, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32, vp, sz]
+    lib.swmi_local_full_affine.argtypes = [vp, sz, vp, sz, sz, vp, ci, ci, vp, vp, vp, vp]
+    lib.swmi_local_full_affine_device.argtypes = [vp, sz, vp, sz, sz, vp, ci, ci, vp, vp, vp, vp, vp]
+    lib.swmi_local_full_affine_slices_for.argtypes = [sz, sz, sz, ci, vp, sz]
+    lib.swmi_local_full_affine_slices_for.restype = sz
+    lib.swmi_local_full_affine_time_device.argtypes = [vp, sz, vp, sz, sz, vp, ci, ci, vp, vp, vp, vp, vp, ci,
+                                                       ctypes.POINTER(ctypes.c_float)]
     _lib = lib
     return lib
 
@@ -937,6 +943,62 @@ def local_full_expand_moves(moves_row, steps, end_i, end_j, cap=None):
 def local_full_release_workspaces():
     """Free the any-length local aligner's device buffers on the current GPU."""
     _check(load().swmi_local_full_release_workspaces())
+
+
+def local_full_affine(seq1s, seq2s, score_matrix, gap_open, gap_extend, traceback=True):
+    """Local alignment of two sequences of any length with affine gaps, end cell, start cell and traceback
+    (swmi_local_full_affine): local_full with a gap of length k costing gap_open + (k-1) gap_extend.  Same arguments and return
+    value as local_full, with (gap_open, gap_extend) for the gap; local_full_move_words and local_full_expand_moves apply.
+    For len2 == 128 local_align_affine gives the same results faster."""
+    a = np.ascontiguousarray(seq1s, dtype=np.uint8)
+    b = np.ascontiguousarray(seq2s, dtype=np.uint8)
+    if a.ndim != 2 or b.ndim != 2:
+        raise ValueError("seq1s and seq2s must be (n, len1) and (n, len2)")
+    n, len1 = a.shape
+    len2 = b.shape[1]
+    if b.shape[0] != n:
+        raise ValueError("seq1s and seq2s hold different numbers of sequences")
+    sm = _sm(score_matrix)
+    scores = np.zeros(n, np.int32)
+    ends = np.zeros((n, 4), np.int32)
+    moves = np.zeros((n, local_full_move_words(len1, len2)), np.uint64) if traceback else None
+    steps = np.zeros(n, np.uint32) if traceback else None
+    _check(load().swmi_local_full_affine(a.ctypes.data, len1, b.ctypes.data, len2, n, sm.ctypes.data, int(gap_open),
+                                         int(gap_extend), scores.ctypes.data, ends.ctypes.data,
+                                         moves.ctypes.data if traceback else None, steps.ctypes.data if traceback else None))
+    return scores, ends, moves, steps
+
+
+def local_full_affine_device(d_seq1s, len1, d_seq2s, len2, n, score_matrix, gap_open, gap_extend, d_scores, d_ends,
+                             d_moves=None, d_steps=None, stream=0):
+    """swmi_local_full_affine_device on device pointers (asynchronous on `stream`); d_moves = d_steps = None: ends-only."""
+    sm = _sm(score_matrix)
+    _check(load().swmi_local_full_affine_device(d_seq1s, len1, d_seq2s, len2, n, sm.ctypes.data, int(gap_open), int(gap_extend),
+                                                d_scores, d_ends, d_moves, d_steps, stream))
+
+
+def local_full_affine_time_device(d_seq1s, len1, d_seq2s, len2, n, score_matrix, gap_open, gap_extend, d_scores, d_ends,
+                                  d_moves=None, d_steps=None, stream=0, iters=10):
+    """Average ms of one swmi_local_full_affine_device call over `iters` back-to-back calls (HIP events on `stream`)."""
+    sm = _sm(score_matrix)
+    ms = ctypes.c_float()
+    _check(load().swmi_local_full_affine_time_device(d_seq1s, len1, d_seq2s, len2, n, sm.ctypes.data, int(gap_open),
+                                                     int(gap_extend), d_scores, d_ends, d_moves, d_steps, stream, int(iters),
+                                                     ctypes.byref(ms)))
+    return float(ms.value)
+
+
+def local_full_affine_slices_for(n, len1, len2, traceback=True):
+    """The slices swmi_local_full_affine cuts n alignments into (needs no device)."""
+    count = load().swmi_local_full_affine_slices_for(n, len1, len2, 1 if traceback else 0, None, 0)
+    buf = (ctypes.c_size_t * max(count, 1))()
+    load().swmi_local_full_affine_slices_for(n, len1, len2, 1 if traceback else 0, buf, count)
+    return [int(buf[k]) for k in range(count)]
+
+
+def local_full_affine_release_workspaces():
+    """Free the any-length affine local aligner's device buffers on the current GPU."""
+    _check(load().swmi_local_full_affine_release_workspaces())
 
 
 def unpack(packed):
