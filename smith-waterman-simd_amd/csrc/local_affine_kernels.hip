@@ -24,7 +24,7 @@
 // E's open bit, bit 24 + c = F's open bit -- so the 16 lanes of an alignment store the 64 contiguous bytes of one step with
 // one instruction.  The cell (i, j) sits at step s = i + (j-1)/8 - 1, dword 16 s + (j-1)/8.  The walk (one lane per
 // alignment, a state of H / E / F) reads them back in the same launch after an s_waitcnt vmcnt(0), with non-temporal loads.
-#include "swmi_internal.h"
+#include "tile_sweep.h"   // imax, max3, SmCols, sm_cols
 
 namespace swmi {
 namespace {
@@ -46,10 +46,6 @@ __device__ __forceinline__ int from_left(int edge, int v)
     return __builtin_amdgcn_update_dpp(edge, v, 0x111 /* row_shr:1 */, 0xf, 0xf, false);
 }
 
-__device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
-
-__device__ __forceinline__ int max3(int a, int b, int c) { return imax(imax(a, b), c); }
-
 // 8 * (seq1[idx] & 3), or 0 outside the sequence (clamped load: it issues a whole trip ahead of its use)
 __device__ __forceinline__ int base_shift(const uint8_t *s1, int idx, int len1)
 {
@@ -65,11 +61,6 @@ __device__ __forceinline__ int base_shift_any(const uint8_t *s1, int idx, int le
     const int b = s1[c < 0 ? 0 : c];
     return (idx >= 0 && idx < len1) ? 8 * (b & 3) : 0;
 }
-
-// cols[b] = bytes a = 0..3: sm[a*4 + b] -- the column of the score matrix that a seq2 base b selects
-struct SmCols {
-    uint32_t c[4];
-};
 
 // RAGGED: slot k computes the alignment work[k] names, as in local_kernels.hip
 template <bool TB, bool RAGGED>
@@ -254,17 +245,6 @@ size_t local_affine_code_words(int len1)
     const int n_steps = len1 + kLanes - 1;
     const int trips = (n_steps + kUnroll - 1) / kUnroll;
     return (size_t)trips * kUnroll * kLanes;
-}
-
-static SmCols sm_cols(const int8_t *sm)
-{
-    SmCols cols;
-    for (int b = 0; b < 4; ++b) {
-        uint32_t c = 0;
-        for (int a = 0; a < 4; ++a) c |= uint32_t(uint8_t(sm[4 * a + b])) << (8 * a);
-        cols.c[b] = c;
-    }
-    return cols;
 }
 
 hipError_t launch_local_affine(const uint8_t *d_seq1s, const uint8_t *d_seq2s, int len1, size_t n, const int8_t *sm, int gap_open,

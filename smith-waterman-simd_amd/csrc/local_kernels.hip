@@ -32,7 +32,7 @@
 // (s/2)*16 + (j-1)/8, bits 16 (s%2) + 2 ((j-1)%8).  The walk (one lane per alignment) reads them back in the same launch:
 // the sweep's stores are drained by an explicit s_waitcnt vmcnt(0) and the walk's loads are non-temporal, which bypass the
 // CU's L1 and read the XCD's L2, where the stores landed.
-#include "swmi_internal.h"
+#include "tile_sweep.h"   // imax, max3, SmCols, sm_cols
 
 namespace swmi {
 namespace {
@@ -52,12 +52,6 @@ __device__ __forceinline__ int from_left(int v)
     return __builtin_amdgcn_update_dpp(kBoundary, v, 0x111 /* row_shr:1 */, 0xf, 0xf, false);
 }
 
-__device__ __forceinline__ int max3(int a, int b, int c)
-{
-    const int m = a > b ? a : b;
-    return m > c ? m : c;
-}
-
 // 8 * (seq1[idx] & 3), or 0 outside the sequence.  The load itself is clamped into the sequence instead of predicated, so
 // that it issues a whole trip ahead of its use (a predicated load is waited for on the spot).
 __device__ __forceinline__ int base_shift(const uint8_t *s1, int idx, int len1)
@@ -75,11 +69,6 @@ __device__ __forceinline__ int base_shift_any(const uint8_t *s1, int idx, int le
     const int b = s1[c < 0 ? 0 : c];
     return (idx >= 0 && idx < len1) ? 8 * (b & 3) : 0;
 }
-
-// cols[b] = bytes a = 0..3: sm[a*4 + b] -- the column of the score matrix that a seq2 base b selects
-struct SmCols {
-    uint32_t c[4];
-};
 
 // RAGGED: slot k of the launch computes the alignment work[k] names (its own length, seq1, codes and moves, results at
 // work[k].k); otherwise alignment k of len1 bytes at seq1s + len1 k, codes and moves at k code_words / k move_words.
@@ -240,17 +229,6 @@ size_t local_code_words(int len1)
     const int n_steps = len1 + kLanes - 1;
     const int trips = (n_steps + kUnroll - 1) / kUnroll;
     return (size_t)trips * (kUnroll / 2) * kLanes;
-}
-
-static SmCols sm_cols(const int8_t *sm)
-{
-    SmCols cols;
-    for (int b = 0; b < 4; ++b) {
-        uint32_t c = 0;
-        for (int a = 0; a < 4; ++a) c |= uint32_t(uint8_t(sm[4 * a + b])) << (8 * a);
-        cols.c[b] = c;
-    }
-    return cols;
 }
 
 hipError_t launch_local(const uint8_t *d_seq1s, const uint8_t *d_seq2s, int len1, size_t n, const int8_t *sm, int gap,

@@ -10,13 +10,12 @@
 // The best cell is that of sgfull_kernels.hip; the walk goes back from it in state H (diagonal, E, F) and through E / F runs
 // (opening wins a tie), forced along row 0 and column 0.
 //
-// Mapping: that of sgfull_kernels.hip: ONE workgroup per alignment, W = ceil(len2 / 1024) wavefronts,
-// lane l of wave w owns the 16 columns 16 G + 1 .. 16 G + 16 of G = 64 w + l and computes row s - l + 1 at the wave's local
-// step s; chunks of 32 steps between workgroup barriers, wave w 3 chunks behind wave w - 1.  E runs down a column and stays
-// in the lane's registers; F runs along the row, so a step passes lane l - 1's H(i, 16 G) AND its F(i, 16 G) to lane l: two
-// v_mov_b32_dpp wave_shr:1 per step.  Lane 63 of wave w - 1 hands both to lane 0 of wave w through an LDS ring of 256
-// (H, F) pairs per wave boundary, written and read at the rows and steps of sgfull_kernels.hip, so its timing argument holds
-// unchanged.
+// Mapping, ring timing, best-cell rule and code layout: tile_sweep.h, which also holds the constants, the helpers and the
+// launcher.  The sweep and the walk are written out here and not taken from tile_sweep_body.inc: with the (H, F) carry and
+// the two-dword code behind the body's types the compiler allocated other registers and other loops (DESIGN.md section
+// 13), so this kernel keeps the code it had.
+// E runs down a column and stays with the lane; F runs along the row, so the Carry from lane l - 1 (and through the ring) is
+// its H(i, 16 G) AND its F(i, 16 G): two v_mov_b32_dpp wave_shr:1 per step, (H, F) pairs in the ring.
 //
 // The cell as KEYS: key = value << 6 | tag << 4 | low, |value| < 2^23 (below).  A stored H key has tag 3 and low = 15 - jj
 // (jj = the column within the lane); E and F are kept as keys of tag 2 and 1 with a traceback (one v_and_or_b32 after their
@@ -42,70 +41,44 @@
 // gap cost is >= 0, so H(p) <= M(p): a padded cell never holds a value that an earlier valid cell lacks, and the best-cell
 // rule (strictly greater; row, then column ascending) never picks one.
 //
-// Best cell: as in sgfull_kernels.hip -- per row one v_max3 chain over the lane's 16 keys, kept when strictly greater;
-// lanes and waves reduced at the end (value desc, row asc, column asc).
+// Codes: 4 bits per cell, one qword per lane and row: the low dword holds H's field of the lane's 16 columns (2 bits each,
+// as sgfull_kernels.hip's codes), the high one E's open bit of column jj at bit jj and F's at bit 16 + jj.
 //
-// Codes: 4 bits per cell, two dwords per lane and row: the low one holds H's field of the lane's 16 columns (2 bits each,
-// as sgfull_kernels.hip's codes), the high one E's open bit of column jj at bit jj and F's at bit 16 + jj.  A lane keeps the
-// 8 dwords of a trip (4 steps) and stores them as two 16-byte stores, so a wave writes 2 KiB contiguous per trip: qword
-// (w * n_trips + s / 4) * 256 + l * 4 + s % 4 of the alignment's codes holds row s - l + 1 of lane l.
-//
-// Walk: as in sgfull_kernels.hip the whole workgroup loads a block of codes ending at the walk's cell into LDS -- here
-// 128 rows x 32 lanes (512 columns) of qwords -- and one lane walks inside it, carrying its state (H / E / F) from block to
-// block in a register.  Every block takes the walk at least 128 rows or 512 columns further.  E(1,j) and F(i,1) always open
-// (E(0,j) = F(i,0) = -inf), so the walk reaches row 0 or column 0 in state H and the border walk is forced.
-#include "swmi_internal.h"
+// Walk: a staging block is 128 rows x 32 lanes (512 columns) of qwords; the walking lane carries its state (H / E / F) from
+// block to block.  E(1,j) and F(i,1) always open (E(0,j) = F(i,0) = -inf), so the walk reaches row 0 or column 0 in state H
+// and the border walk is forced.
+#include "tile_sweep.h"
 
 namespace swmi {
 namespace {
 
-constexpr int kCols = 16;              // columns per lane
-constexpr int kMaxWaves = 16;          // 16 x 64 x 16 = 16384 columns
-constexpr int kUnroll = 4;             // steps per trip (two 16-byte code stores)
-constexpr int kChunk = 32;             // steps between two workgroup barriers
-constexpr int kDelay = 3;              // chunks between wave w - 1 and wave w
-constexpr int kRing = 256;             // (H, F) pairs of each wave boundary's LDS ring
-constexpr int kStageRows = 128;        // walk staging block: rows x lanes (x 16 columns) of qwords
+using namespace tile;
+
+// The geometry this file's proofs, bounds and code word were written against (tile_sweep.h owns it; a change there must
+// revisit them)
+namespace written_for {
+constexpr int kCols = 16;
+constexpr int kMaxWaves = 16;
+constexpr int kUnroll = 4;
+constexpr int kChunk = 32;
+constexpr int kDelay = 3;
+constexpr int kRing = 256;
+constexpr int kStageRows = 128;
+static_assert(kCols == tile::kCols && kMaxWaves == tile::kMaxWaves && kUnroll == tile::kUnroll && kChunk == tile::kChunk &&
+              kDelay == tile::kDelay && kRing == tile::kRing && kStageRows == tile::kStageRows);
+}  // namespace written_for
+
 constexpr int kStageLanes = 32;
 constexpr int kTagH = 3 << 4;
 constexpr int kTagE = 2 << 4;
 constexpr int kTagF = 1 << 4;
 constexpr int kMinusInf = -(1 << 30);  // E on row 0, F on column 0
 
-__device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
-
-__device__ __forceinline__ int max3(int a, int b, int c) { return imax(imax(a, b), c); }
-
-// the same register in lane l - 1 of the wave; lane 0 gets `edge`
-__device__ __forceinline__ int from_left(int edge, int v)
-{
-    return __builtin_amdgcn_update_dpp(edge, v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
-}
-
-// 8 * (seq1[idx] & 3), the load clamped into the sequence (so that it issues a trip ahead of its use)
-__device__ __forceinline__ int base_shift(const uint8_t *s1, int idx, int len1)
-{
-    const int c = idx < 0 ? 0 : idx >= len1 ? len1 - 1 : idx;
-    return 8 * (s1[c] & 3);
-}
-
 // H(0, j) = H(j, 0) for j >= 1 (and 0 at j = 0) as a stored key
 __device__ __forceinline__ int border_key(int j, int gap_open, int gap_extend)
 {
     const int h = j > 0 ? -(gap_open + (j - 1) * gap_extend) : 0;
     return (h << 6) | kTagH;
-}
-
-// cols[b] = bytes a = 0..3: sm[a*4 + b] -- the column of the score matrix that a seq2 base b selects
-struct SmCols {
-    uint32_t c[4];
-};
-
-// qword of the codes of row i, lane G (i >= 1)
-__device__ __forceinline__ size_t code_index(int i, int G, uint32_t n_trips)
-{
-    const int w = G >> 6, l = G & 63, s = i + l - 1;
-    return (((size_t)w * n_trips + (uint32_t)(s >> 2)) * 64 + l) * 4 + (s & 3);
 }
 
 template <bool TB>
@@ -330,28 +303,14 @@ __global__ __launch_bounds__(64 * kMaxWaves) void sg_full_affine_kernel(
 }  // namespace
 
 // qwords of codes per alignment: 4 bits per cell of every lane's 16 columns, for every step of the padded sweep
-size_t sgfull_affine_code_qwords(int len1, int len2) { return (size_t)sgfull_waves(len2) * sgfull_trips(len1) * 256; }
+size_t sgfull_affine_code_qwords(int len1, int len2) { return tile::code_words(len1, len2); }
 
 hipError_t launch_sgfull_affine(const uint8_t *d_seq1s, const uint8_t *d_seq2s, int len1, int len2, size_t n, const int8_t *sm,
                                 int gap_open, int gap_extend, int32_t *d_scores, int32_t *d_ends, unsigned long long *d_codes,
                                 unsigned long long *d_moves, uint32_t *d_lengths, size_t move_words, hipStream_t stream)
 {
-    if (n == 0) return hipSuccess;
-    SmCols cols;
-    for (int b = 0; b < 4; ++b) {
-        uint32_t c = 0;
-        for (int a = 0; a < 4; ++a) c |= uint32_t(uint8_t(sm[4 * a + b])) << (8 * a);
-        cols.c[b] = c;
-    }
-    const dim3 grid((unsigned)n), block(64 * sgfull_waves(len2));
-    const uint32_t trips = (uint32_t)sgfull_trips(len1);
-    if (d_moves)
-        hipLaunchKernelGGL(sg_full_affine_kernel<true>, grid, block, 0, stream, d_seq1s, d_seq2s, len1, len2, cols, gap_open,
-                           gap_extend, d_scores, d_ends, d_codes, d_moves, d_lengths, (uint32_t)move_words, trips);
-    else
-        hipLaunchKernelGGL(sg_full_affine_kernel<false>, grid, block, 0, stream, d_seq1s, d_seq2s, len1, len2, cols, gap_open,
-                           gap_extend, d_scores, d_ends, nullptr, nullptr, nullptr, 0u, trips);
-    return hipGetLastError();
+    return tile::launch<sg_full_affine_kernel<true>, sg_full_affine_kernel<false>>(d_seq1s, d_seq2s, len1, len2, n, sm, d_scores, d_ends, d_codes, d_moves, d_lengths,
+        move_words, stream, gap_open, gap_extend);
 }
 
 }  // namespace swmi

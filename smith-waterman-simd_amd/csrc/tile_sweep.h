@@ -1,0 +1,146 @@
+// tile_sweep.h -- what the four any-length aligners share (sgfull_kernels.hip, sgfull_affine_kernels.hip,
+// local_full_kernels.hip, local_full_affine_kernels.hip): the mapping and its constants, the helpers,
+// the geometry and the launcher; the few helpers that the 16-lane local aligners take from here as well.  The sweep and the
+// walk of the two linear-gap kernels are tile_sweep_body.inc; the two affine kernels keep theirs written out (below).
+//
+// Mapping: ONE workgroup per alignment, W = ceil(len2 / 1024) wavefronts; lane l of wave w owns the 16 columns
+// 16 G + 1 .. 16 G + 16 of G = 64 w + l.  Inside a wave, lane l computes row s - l + 1 at the wave's local step s; what
+// the lane needs of the column to its left (H's key; with affine gaps F too) comes from lane l - 1 one step earlier (one
+// v_mov_b32_dpp wave_shr:1 per dword and step).  Lane 0 of wave w > 0 takes it from lane 63 of wave w - 1 through an LDS
+// ring of 256 rows per wave boundary; lane 0 of wave 0 takes the border.
+//
+// Ring timing: the waves run in CHUNKS of 32 steps separated by a workgroup barrier, wave w delayed by 3 chunks behind
+// wave w - 1.  Lane 63 of wave w - 1 computes row r at its step r + 62, lane 0 of wave w needs it at its step r - 1, and
+// floor((r + 62) / 32) - floor((r - 1) / 32) <= 2 < 3, so every ring entry is written a chunk before it is read; at most
+// 64 rows separate the newest entry written from the oldest one still to read, so 256 entries never wrap onto one unread.
+// Neither the step at which a lane computes a row nor the ring's indexing depends on the recurrence or on what an entry
+// holds, so the argument holds for all four kernels.
+//
+// Columns past len2 (the last lanes of the last wave) are computed with every score -128 (the profile's padding); each
+// kernel's file proves that the best-cell rule never picks one and that the walk never enters one.
+//
+// Best cell: per row one max chain over the lane's 16 stored keys names the row's largest H and its FIRST column (the low
+// bits hold 15 - jj); it replaces the lane's best only when its H is strictly greater (compared against best | 63), so the
+// lane keeps the first row.  Lanes and waves are reduced at the end (value desc, row asc, column asc).
+//
+// Codes: one code word (a dword, with affine gaps a qword) per lane and row.  A lane keeps the words of a trip (4 steps)
+// and writes them with 16-byte stores, so a wave writes 1 or 2 KiB contiguous per trip: word
+// ((w * n_trips + s / 4) * 64 + l) * 4 + s % 4 of the alignment's codes holds row s - l + 1 of lane l (code_index).
+//
+// Walk: after the sweep every wave drains its stores (s_waitcnt vmcnt(0): a workgroup-scope fence lowers to nothing here,
+// DESIGN.md section 12) and the workgroup meets at a barrier; then the whole workgroup loads a block of 128 rows x
+// kStageLanes lanes (64 dwords or 32 qwords: 32 KiB of LDS) of code words ending at the walk's cell into LDS (non-temporal
+// loads: the stores went to L2), and one lane walks inside the block.  The walk only moves up and left, so every block
+// takes it at least 128 rows or 16 kStageLanes columns further.  Moves are packed 32 to a word, first move in the low bits.
+//
+// tile_sweep_body.inc is that sweep and walk for a linear-gap VARIANT, a type that is built from the kernel's gap argument
+// and supplies what depends on the recurrence:
+//     Gaps                          the kernel's gap arguments as an aggregate
+//     kStageLanes, kEnds            lanes of a staging block; int32 of `ends` per alignment (2: end cell; 4: start cell too)
+//     kRowMin, kZeroKey             below every stored key (where a row's max chain starts); the stored key of H = 0
+//     row0(jj, -j, gaps)            the stored key of row 0 in the lane's column jj (global column j)
+//     border(-j), left_border(-i)   the stored key of H(0, j) = H(j, 0), column bits aside; that of column 0 in row i
+//     cell<TB>(jj, sc, diag, left, key, code)
+//                                   one cell with substitution score sc: diag, left and key hold its neighbours before and
+//                                   ITS values after (diag the key above, for the next column); returns the stored key
+//                                   and, with TB, the cell's bits of the row's code word
+//     step(word, cc)                the walk's move (3 / 2 / 1 = diagonal / up / left, 0 = stop) at column cc of a word
+//     kWalkStops                    whether a code can stop the walk (else it goes on to (0, 0), forced on the border)
+// The borders take the NEGATED row or column so that the caller's sum folds into the negation as it did before the split.
+//
+// Why the body is an include and why the affine kernels are not on it: this compiler optimises a function on its own before
+// it inlines it.  A body behind a call -- even the unchanged kernel moved into a forceinline function -- is optimised twice
+// and came out with 12 fewer SGPRs and 30 more instructions per sweep loop in the linear traceback kernels; a variant that
+// held the key array or the column loop lost the array-to-vector promotion (68 VGPRs for 119).  As text inside the named
+// kernel the linear pair compiles to the loops it had, instruction for instruction.  The affine pair needs two values in
+// the carry and two dwords in the code word; behind the body's types they became other allocas, other registers and other
+// loops, so those two kernels keep their own sweep and walk and take the rest from here.
+#pragma once
+#include "swmi_internal.h"
+
+namespace swmi {
+
+__device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
+
+__device__ __forceinline__ int max3(int a, int b, int c) { return imax(imax(a, b), c); }
+
+// cols[b] = bytes a = 0..3: sm[a*4 + b] -- the column of the score matrix that a seq2 base b selects
+struct SmCols {
+    uint32_t c[4];
+};
+
+inline SmCols sm_cols(const int8_t *sm)
+{
+    SmCols cols;
+    for (int b = 0; b < 4; ++b) {
+        uint32_t c = 0;
+        for (int a = 0; a < 4; ++a) c |= uint32_t(uint8_t(sm[4 * a + b])) << (8 * a);
+        cols.c[b] = c;
+    }
+    return cols;
+}
+
+namespace tile {
+
+constexpr int kCols = 16;              // columns per lane
+constexpr int kMaxWaves = 16;          // 16 x 64 x 16 = 16384 columns
+constexpr int kUnroll = 4;             // steps per trip (one or two 16-byte code stores)
+constexpr int kChunk = 32;             // steps between two workgroup barriers
+constexpr int kDelay = 3;              // chunks between wave w - 1 and wave w
+constexpr int kRing = 256;             // rows of each wave boundary's LDS ring
+constexpr int kStageRows = 128;        // rows of a walk staging block
+
+inline int waves(int len2) { return (len2 + 64 * kCols - 1) / (64 * kCols); }
+
+inline size_t trips(int len1) { return (size_t)((len1 + 63 + kChunk - 1) / kChunk) * (kChunk / kUnroll); }
+
+// code words per alignment: one per lane for every step of the padded sweep
+inline size_t code_words(int len1, int len2) { return (size_t)waves(len2) * trips(len1) * 256; }
+
+// the code word of row i, lane G (i >= 1)
+__device__ __forceinline__ size_t code_index(int i, int G, uint32_t n_trips)
+{
+    const int w = G >> 6, l = G & 63, s = i + l - 1;
+    return (((size_t)w * n_trips + (uint32_t)(s >> 2)) * 64 + l) * 4 + (s & 3);
+}
+
+// the same register in lane l - 1 of the wave; lane 0 gets `edge`
+__device__ __forceinline__ int from_left(int edge, int v)
+{
+    return __builtin_amdgcn_update_dpp(edge, v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
+}
+
+// 8 * (seq1[idx] & 3), the load clamped into the sequence (so that it issues a trip ahead of its use)
+__device__ __forceinline__ int base_shift(const uint8_t *s1, int idx, int len1)
+{
+    const int c = idx < 0 ? 0 : idx >= len1 ? len1 - 1 : idx;
+    return 8 * (s1[c] & 3);
+}
+
+__device__ __forceinline__ uint4 code_quad(const unsigned long long *c)
+{
+    return make_uint4((uint32_t)c[0], (uint32_t)(c[0] >> 32), (uint32_t)c[1], (uint32_t)(c[1] >> 32));
+}
+
+// Launches KTb (codes, walk) or KEnds (d_moves NULL: no codes, no walk; d_codes and d_counts unused), one workgroup of
+// waves(len2) wavefronts per alignment; `gaps` are the kernels' gap arguments.
+template <auto KTb, auto KEnds, class Code, class... Gaps>
+hipError_t launch(const uint8_t *d_seq1s, const uint8_t *d_seq2s, int len1, int len2, size_t n, const int8_t *sm, int32_t *d_scores,
+                  int32_t *d_ends, Code *d_codes, unsigned long long *d_moves, uint32_t *d_counts, size_t move_words,
+                  hipStream_t stream, Gaps... gaps)
+{
+    if (n == 0) return hipSuccess;
+    const SmCols cols = sm_cols(sm);
+    const dim3 grid((unsigned)n), block(64 * waves(len2));
+    const uint32_t n_trips = (uint32_t)trips(len1);
+    if (d_moves)
+        hipLaunchKernelGGL(KTb, grid, block, 0, stream, d_seq1s, d_seq2s, len1, len2, cols, gaps..., d_scores, d_ends, d_codes, d_moves,
+                           d_counts, (uint32_t)move_words, n_trips);
+    else
+        hipLaunchKernelGGL(KEnds, grid, block, 0, stream, d_seq1s, d_seq2s, len1, len2, cols, gaps..., d_scores, d_ends,
+                           (Code *)nullptr, (unsigned long long *)nullptr, (uint32_t *)nullptr, 0u, n_trips);
+    return hipGetLastError();
+}
+
+}  // namespace tile
+}  // namespace swmi

@@ -1,0 +1,186 @@
+// tile_sweep_body.inc -- the sweep and the walk of a linear-gap tile aligner: the body of its kernel (tile_sweep.h tells
+// the mapping and what a variant V supplies).  Included INSIDE the kernel, after `using V = <variant>;` and
+// `const V::Gaps gaps{<gap argument>};`, where the kernel's parameters are named seq1s, seq2s, len1, len2, cols, scores,
+// ends, codes, moves, counts, move_words, n_trips and its template parameter TB.  Text and not a function on purpose:
+// tile_sweep.h says why.
+    __shared__ int ring[(kMaxWaves - 1) * kRing];
+    __shared__ unsigned long long red[kMaxWaves];
+    __shared__ int walk_at[V::kWalkStops ? 3 : 2];
+    __shared__ uint32_t stage[TB ? kStageRows * V::kStageLanes : 1];
+
+    const int W = blockDim.x >> 6;
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, G = tid;
+    const size_t k = blockIdx.x;
+    const uint8_t *s1 = seq1s + k * (size_t)len1;
+    const uint8_t *s2 = seq2s + k * (size_t)len2;
+    const int jbase = kCols * G;                        // the lane's columns are jbase + 1 .. jbase + 16
+
+    uint32_t prof[kCols];
+    int key[kCols];                                     // H's stored keys of the row the lane computed last
+#pragma unroll
+    for (int jj = 0; jj < kCols; ++jj) {
+        const int j = jbase + jj + 1;
+        const uint32_t b = s2[j <= len2 ? j - 1 : 0] & 3u;
+        prof[jj] = j > len2 ? 0x80808080u : b == 0 ? cols.c[0] : b == 1 ? cols.c[1] : b == 2 ? cols.c[2] : cols.c[3];
+        key[jj] = V::row0(jj, -j, gaps);
+    }
+    V lane(gaps);
+    int diag_in = lane.border(-jbase);                   // key(0, jbase)
+    int best = V::kZeroKey, best_row = 0;               // H = 0 at (0, 0)
+
+    const int local_chunks = (len1 + 63 + kChunk - 1) / kChunk;
+    const int total_chunks = local_chunks + kDelay * (W - 1);
+    const int *ring_in = ring + (w > 0 ? w - 1 : 0) * kRing;   // read by waves 1.. (wave 0's left column is the border)
+    int *ring_out = ring + (w < W - 1 ? w : 0) * kRing;        // written by waves ..W-2
+    uint32_t *cw_out = TB ? codes + k * ((size_t)W * n_trips * 256) + ((size_t)w * n_trips * 64 + l) * 4 : nullptr;
+
+    int sh_next[kUnroll];
+#pragma unroll
+    for (int t = 0; t < kUnroll; ++t) sh_next[t] = base_shift(s1, t - l, len1);
+
+    for (int c = 0; c < total_chunks; ++c) {
+        const int lc = c - kDelay * w;
+        if (lc >= 0 && lc < local_chunks) {
+            for (int q = 0; q < kChunk / kUnroll; ++q) {
+                const int s0 = lc * kChunk + q * kUnroll;
+                int sh[kUnroll];
+                int bound[kUnroll], edge[kUnroll];
+                uint32_t cw[kUnroll];
+#pragma unroll
+                for (int t = 0; t < kUnroll; ++t) {
+                    sh[t] = sh_next[t];
+                    sh_next[t] = base_shift(s1, s0 + kUnroll + t - l, len1);
+                    // lane 0's left column for row s0 + t + 1
+                    bound[t] = w > 0 ? ring_in[(s0 + t) & (kRing - 1)] : lane.left_border(-(s0 + t + 1));
+                    cw[t] = 0;
+                }
+#pragma unroll
+                for (int t = 0; t < kUnroll; ++t) {
+                    const int left_in = from_left(bound[t], key[kCols - 1]);   // lane l - 1's key(i, jbase), one step ago
+                    const int row = s0 + t - l + 1;
+                    if (row >= 1 && row <= len1) {
+                        int d = diag_in, lft = left_in, rk = V::kRowMin;
+#pragma unroll
+                        for (int jj = 0; jj < kCols; ++jj) {
+                            const int sc = __builtin_amdgcn_sbfe((int)prof[jj], sh[t], 8);
+                            uint32_t code;
+                            const int nk = lane.template cell<TB>(jj, sc, d, lft, key[jj], code);
+                            if constexpr (TB) cw[t] |= code;
+                            rk = rk > nk ? rk : nk;
+                        }
+                        if (rk > (best | 63)) {
+                            best = rk;
+                            best_row = row;
+                        }
+                    }
+                    edge[t] = key[kCols - 1];
+                    diag_in = left_in;
+                }
+                if (w < W - 1 && l == 63) {
+#pragma unroll
+                    for (int t = 0; t < kUnroll; ++t) {
+                        const int row = s0 + t - 62;
+                        if (row >= 1 && row <= len1) ring_out[(row - 1) & (kRing - 1)] = edge[t];
+                    }
+                }
+                if constexpr (TB) {
+                    *reinterpret_cast<uint4 *>(cw_out + (size_t)(s0 >> 2) * 256) = make_uint4(cw[0], cw[1], cw[2], cw[3]);
+                }
+            }
+        }
+        if (W > 1) __syncthreads();
+    }
+
+    // best cell: (H desc, row asc, column asc) over the lanes, then over the waves
+    const int h = best >> 6;
+    const int col = h > 0 ? jbase + (kCols - 1 - (best & 15)) + 1 : 0;
+    unsigned long long r = ((unsigned long long)(uint32_t)h << 34) | ((unsigned long long)(0x1FFFF - best_row) << 17) |
+                           (unsigned long long)(0x1FFFF - col);
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long v = __shfl_xor(r, o, 64);
+        r = v > r ? v : r;
+    }
+    if (l == 0) red[w] = r;
+    if constexpr (TB) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's code stores have reached L2
+    __syncthreads();
+    r = red[0];
+    for (int x = 1; x < W; ++x) r = red[x] > r ? red[x] : r;
+    const int score = (int)(r >> 34);
+    const int end_i = score > 0 ? 0x1FFFF - (int)((r >> 17) & 0x1FFFF) : 0;
+    const int end_j = score > 0 ? 0x1FFFF - (int)(r & 0x1FFFF) : 0;
+    if (tid == 0) {
+        scores[k] = score;
+        ends[V::kEnds * k + 0] = end_i;
+        ends[V::kEnds * k + 1] = end_j;
+        if constexpr (!TB)                              // what only a walk finds
+            for (int x = 2; x < V::kEnds; ++x) ends[V::kEnds * k + x] = -1;
+    }
+    if constexpr (TB) {
+        const uint32_t *cd = codes + k * ((size_t)W * n_trips * 256);
+        unsigned long long *mv = moves + k * (size_t)move_words;
+        int i = end_i, j = end_j, stopped = 0;
+        uint32_t t = 0;
+        unsigned long long acc = 0;
+        while ((!V::kWalkStops || !stopped) && i > 0 && j > 0) {            // uniform: every thread holds the same (i, j, stopped)
+            const int g1 = (j - 1) >> 4;
+            const int i_lo = i - kStageRows + 1 > 1 ? i - kStageRows + 1 : 1;
+            const int g_lo = g1 - V::kStageLanes + 1 > 0 ? g1 - V::kStageLanes + 1 : 0;
+            const int rows = i - i_lo + 1, lanes = g1 - g_lo + 1;
+            for (int e = tid; e < rows * lanes; e += blockDim.x) {
+                const int rr = e / lanes, gg = e - rr * lanes;
+                stage[rr * V::kStageLanes + gg] = __builtin_nontemporal_load(cd + code_index(i_lo + rr, g_lo + gg, n_trips));
+            }
+            __syncthreads();
+            if (tid == 0) {
+                int st = 0;
+                while (i > 0 && j > 0 && i >= i_lo && ((j - 1) >> 4) >= g_lo) {
+                    const uint32_t wd = stage[(i - i_lo) * V::kStageLanes + ((j - 1) >> 4) - g_lo];
+                    const uint32_t m = V::step(wd, (j - 1) & 15);
+                    if (V::kWalkStops && m == 0) {
+                        st = 1;
+                        break;
+                    }
+                    acc |= (unsigned long long)m << (2 * (t & 31));   // 32 moves to a word
+                    i -= m != 1u;
+                    j -= m != 2u;
+                    ++t;
+                    if ((t & 31) == 0) {
+                        mv[(t >> 5) - 1] = acc;
+                        acc = 0;
+                    }
+                }
+                walk_at[0] = i;
+                walk_at[1] = j;
+                if constexpr (V::kWalkStops) walk_at[2] = st;
+            }
+            __syncthreads();
+            i = walk_at[0];
+            j = walk_at[1];
+            if constexpr (V::kWalkStops) stopped = walk_at[2];
+        }
+        if (tid == 0) {
+            if constexpr (V::kWalkStops) {
+                // the walk ended on its start cell: the count is the moves
+                if (t & 31) mv[t >> 5] = acc;
+                counts[k] = t;
+                ends[V::kEnds * k + 2] = i;
+                ends[V::kEnds * k + 3] = j;
+            } else {
+                // the walk goes on to (0, 0), forced on the border: up along column 0, left along row 0 (the reference's
+                // source.cpp:1821-1826); the count is the path's cells, moves + 1
+                for (; i > 0 || j > 0; ++t) {
+                    const uint32_t m = i > 0 ? 2u : 1u;
+                    acc |= (unsigned long long)m << (2 * (t & 31));
+                    i -= m == 2u;
+                    j -= m == 1u;
+                    if (((t + 1) & 31) == 0) {
+                        mv[t >> 5] = acc;
+                        acc = 0;
+                    }
+                }
+                if (t & 31) mv[t >> 5] = acc;
+                counts[k] = t + 1;
+            }
+        }
+    }

@@ -24,11 +24,16 @@ CSRC = os.path.join(ROOT, "smith-waterman-simd_amd", "csrc")
 WAVE = 64                                    # lanes of a gfx950 wavefront
 
 
-def kernel_constants(source):
-    """{name: value} of the `constexpr int kName = ...;` lines of a kernel source (integer expressions of earlier ones)."""
-    env = {}
+def kernel_constants(source, env=None):
+    """{name: value} of the `constexpr int kName = ...;` lines of a kernel source (integer expressions of earlier ones), those of
+    the csrc headers it includes first, as the compiler reads them (a name the source defines again takes its value)."""
+    env = {} if env is None else env
     with open(os.path.join(CSRC, source)) as fh:
-        for name, expr in re.findall(r"constexpr int (k\w+) = ([^;]+);", fh.read()):
+        for include, name, expr in re.findall(r'#include "([^"]+)"|constexpr int (k\w+) = ([^;]+);', fh.read()):
+            if include:
+                if os.path.basename(include) == include and os.path.exists(os.path.join(CSRC, include)):
+                    kernel_constants(include, env)
+                continue
             cast = expr.startswith("(int)")                 # a 32-bit pattern written in hex: wrap it as the compiler does
             v = int(eval(expr[5:] if cast else expr, {"__builtins__": {}}, dict(env)))
             env[name] = (v + (1 << 31)) % (1 << 32) - (1 << 31) if cast else v
