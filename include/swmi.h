@@ -622,6 +622,51 @@ SWMI_API int swmi_local_full_affine_time_device(const void *d_seq1s, size_t len1
                                                 void *d_ends, void *d_moves, void *d_steps, void *stream, int iters,
                                                 float *avg_ms);
 
+/* ---- the any-length local aligners on a batch of MIXED (len1, len2) ----------------------------------
+ * swmi_local_full and swmi_local_full_affine with one (len1, len2) per alignment.  Alignment k is seq1 = bytes
+ * [seq1_offsets[k], seq1_offsets[k+1]) of seq1s against seq2 = bytes [seq2_offsets[k], seq2_offsets[k+1]) of seq2s; both
+ * offset arrays hold n + 1 non-decreasing entries, and every length is in [0, 16384].  If either length is 0 the alignment
+ * gives score 0, ends (0, 0, 0, 0) and 0 steps (ends-only: (0, 0, -1, -1)), and reads no byte of either sequence.  scores,
+ * ends and steps are those of the fixed-length entries, in caller order, with the same semantics, tie rules and move
+ * encoding.  Alignment k's moves start at word move_offsets[k] = the sum over m < k of
+ * SWMI_LOCAL_FULL_MOVE_WORDS(len1 of m, len2 of m) (swmi_local_full_ragged_move_offsets), so
+ * swmi_local_full_expand_moves(moves + move_offsets[k], ...) rebuilds its path.  moves and steps both NULL: ends-only.
+ * Host buffers.  The batch runs in slices (swmi_local_full_ragged_slices_for) on two sets of device buffers.  One workgroup
+ * of ceil(len2 / 1024) wavefronts computes an alignment, so a slice runs as one launch per wave count present in it, the
+ * widest first, and inside a launch the longest seq1 first; results go to caller positions.
+ * Errors: SWMI_ERR_INVALID_ARGUMENT for decreasing offsets, a length above 16384, a NULL buffer, or only one of moves /
+ * steps; SWMI_ERR_DOMAIN for parameters out of range (those of the fixed-length entries).  n = 0 is a no-op that needs no
+ * device.  Every argument is checked before any device is touched. */
+SWMI_API int swmi_local_full_ragged(const uint8_t *seq1s, const uint64_t *seq1_offsets, const uint8_t *seq2s,
+                                    const uint64_t *seq2_offsets, size_t n, const int8_t score_matrix[16], int8_t gap_penalty,
+                                    int32_t *scores, int32_t *ends, uint64_t *moves, uint32_t *steps);
+SWMI_API int swmi_local_full_affine_ragged(const uint8_t *seq1s, const uint64_t *seq1_offsets, const uint8_t *seq2s,
+                                           const uint64_t *seq2_offsets, size_t n, const int8_t score_matrix[16], int gap_open,
+                                           int gap_extend, int32_t *scores, int32_t *ends, uint64_t *moves, uint32_t *steps);
+/* move_offsets[0 .. n] of a ragged batch (the layout of its moves).  Needs no device.  SWMI_ERR_INVALID_ARGUMENT as above. */
+SWMI_API int swmi_local_full_ragged_move_offsets(const uint64_t *seq1_offsets, const uint64_t *seq2_offsets, size_t n,
+                                                 uint64_t *move_offsets);
+/* The slices a ragged call of n alignments cuts its batch into (affine = 0: swmi_local_full_ragged, else the affine one;
+ * traceback = 0: ends-only), in order; returns how many there are and writes the first `cap` sizes (NULL to count).  Each is
+ * the longest run of the alignments left, in caller order, whose device bytes -- inputs, slots and results, plus codes, moves
+ * and steps with a traceback -- fit the fixed-length aligner's budget for one slice (swmi_local_full_slices_for's or
+ * swmi_local_full_affine_slices_for's with a traceback; 256 MiB ends-only), at most 2^20 alignments and at least one.  Needs
+ * no device.  0 for invalid offsets. */
+SWMI_API size_t swmi_local_full_ragged_slices_for(const uint64_t *seq1_offsets, const uint64_t *seq2_offsets, size_t n, int affine,
+                                                  int traceback, size_t *sizes, size_t cap);
+/* Same with every data buffer in device memory (16-byte aligned at its base; an alignment's offsets need no alignment),
+ * asynchronous on `stream`; d_moves uses the move_offsets layout.  Both offset arrays stay HOST arrays, read during the call
+ * only (they size the workspace and order the work).  The codes and slots go to the workspace of the fixed-length entry per
+ * (GPU, stream). */
+SWMI_API int swmi_local_full_ragged_device(const void *d_seq1s, const uint64_t *seq1_offsets, const void *d_seq2s,
+                                           const uint64_t *seq2_offsets, size_t n, const int8_t score_matrix[16],
+                                           int8_t gap_penalty, void *d_scores, void *d_ends, void *d_moves, void *d_steps,
+                                           void *stream);
+SWMI_API int swmi_local_full_affine_ragged_device(const void *d_seq1s, const uint64_t *seq1_offsets, const void *d_seq2s,
+                                                  const uint64_t *seq2_offsets, size_t n, const int8_t score_matrix[16],
+                                                  int gap_open, int gap_extend, void *d_scores, void *d_ends, void *d_moves,
+                                                  void *d_steps, void *stream);
+
 /* unpack() itself (source.cpp:1580-1583) for n packed sequences, on the GPU. Host buffers. */
 SWMI_API int swmi_unpack(const uint8_t *packed, size_t n_seqs, uint8_t *unpacked);
 

@@ -105,6 +105,8 @@ inline void check(int rc, const char *what)
 struct PieceBuffers {
     std::vector<uint8_t> seq1s;                        // seq1s staged back to back
     std::vector<uint64_t> seq1_offsets, move_offsets;  // a ragged piece's layouts
+    std::vector<uint8_t> seq2s;                        // seq2s staged back to back (a piece ragged on both sides)
+    std::vector<uint64_t> seq2_offsets;
     std::vector<int32_t> scores, ends;
     std::vector<uint64_t> moves;
     std::vector<uint32_t> counts;                      // steps or lengths
@@ -506,6 +508,77 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SmithWaterm
     return detail::run_in_pieces(seq1s.size(), piece, threads, align, [&](const detail::PieceBuffers &p, size_t k) {
         return detail::Result{p.scores[k], expand_local_full_moves(p.moves.data() + k * mw, p.counts[k], p.ends[4 * k], p.ends[4 * k + 1])};
     });
+}
+
+// Any-length local alignments of mixed shapes (swmi_local_full_ragged and its affine twin): seq1s[k] and seq2s[k] each of any
+// length in [0, 16384], in pieces of at most `piece` alignments (0 counts as 4096), each one ragged call, so only two pieces'
+// inputs and moves are held at a time; the paths of one piece are rebuilt on `threads` host threads (0 = as many as the
+// machine reports, at most 64) while the GPU aligns the next.  call(seq1 bytes, offsets, seq2 bytes, offsets, m, scores,
+// ends, moves, steps) is the C entry with its parameters bound.
+template <class Call>
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> local_full_ragged_batch(
+    const char *name, const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::vector<uint8_t>> &seq2s, size_t piece,
+    unsigned threads, Call call)
+{
+    if (seq1s.size() != seq2s.size()) throw std::invalid_argument(std::string(name) + ": seq1s and seq2s differ in length");
+    if (piece == 0) piece = 4096;
+    if (threads == 0) threads = std::thread::hardware_concurrency();
+    threads = threads < 1 ? 1 : threads > 64 ? 64 : threads;
+    auto stage = [](const std::vector<std::vector<uint8_t>> &seqs, size_t off, size_t m, std::vector<uint8_t> &bytes,
+                    std::vector<uint64_t> &offsets) {
+        bytes.clear();
+        offsets.assign(1, 0);
+        for (size_t k = 0; k < m; ++k) {
+            bytes.insert(bytes.end(), seqs[off + k].begin(), seqs[off + k].end());
+            offsets.push_back(bytes.size());
+        }
+        if (bytes.empty()) bytes.push_back(0);          // (every sequence of the piece is empty: a pointer that is never read)
+    };
+    auto align = [&](detail::PieceBuffers &p, size_t off, size_t m) {
+        stage(seq1s, off, m, p.seq1s, p.seq1_offsets);
+        stage(seq2s, off, m, p.seq2s, p.seq2_offsets);
+        p.move_offsets.resize(m + 1);
+        if (swmi_local_full_ragged_move_offsets(p.seq1_offsets.data(), p.seq2_offsets.data(), m, p.move_offsets.data()) != SWMI_OK)
+            throw std::invalid_argument(std::string(name) + ": " + swmi_last_error());
+        p.scores.resize(m);
+        p.ends.resize(4 * m);
+        p.moves.resize(p.move_offsets[m] ? p.move_offsets[m] : 1);
+        p.counts.resize(m);
+        detail::check(call(p.seq1s.data(), p.seq1_offsets.data(), p.seq2s.data(), p.seq2_offsets.data(), m, p.scores.data(),
+                           p.ends.data(), p.moves.data(), p.counts.data()),
+                      name);
+    };
+    return detail::run_in_pieces(seq1s.size(), piece, threads, align, [](const detail::PieceBuffers &p, size_t k) {
+        return detail::Result{p.scores[k],
+                              expand_local_full_moves(p.moves.data() + p.move_offsets[k], p.counts[k], p.ends[4 * k], p.ends[4 * k + 1])};
+    });
+}
+
+// Any-length local alignment of seq1s[k] against seq2s[k], every sequence of a length of its own in [0, 16384]: result[k] ==
+// SmithWaterman_long_mi355x(seq1s[k], seq2s[k], score_matrix, gap_penalty), and (0, {(0, 0)}) when either is empty.
+// SmithWaterman_long_mi355x_batch keeps requiring one shape and throws on differing lengths.
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SmithWaterman_long_mi355x_ragged_batch(
+    const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::vector<uint8_t>> &seq2s,
+    const std::array<int8_t, 16> &score_matrix, const int8_t gap_penalty, size_t piece = 0, unsigned threads = 0)
+{
+    return local_full_ragged_batch("SmithWaterman_long_mi355x_ragged_batch", seq1s, seq2s, piece, threads,
+                                   [&](const uint8_t *a, const uint64_t *oa, const uint8_t *b, const uint64_t *ob, size_t m, int32_t *sc,
+                                       int32_t *e, uint64_t *mv, uint32_t *st) {
+                                       return swmi_local_full_ragged(a, oa, b, ob, m, score_matrix.data(), gap_penalty, sc, e, mv, st);
+                                   });
+}
+
+// The same with affine gaps: result[k] == SmithWaterman_long_affine_mi355x(seq1s[k], seq2s[k], score_matrix, gap_open, gap_extend).
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SmithWaterman_long_affine_mi355x_ragged_batch(
+    const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::vector<uint8_t>> &seq2s,
+    const std::array<int8_t, 16> &score_matrix, int gap_open, int gap_extend, size_t piece = 0, unsigned threads = 0)
+{
+    return local_full_ragged_batch("SmithWaterman_long_affine_mi355x_ragged_batch", seq1s, seq2s, piece, threads,
+                                   [&](const uint8_t *a, const uint64_t *oa, const uint8_t *b, const uint64_t *ob, size_t m, int32_t *sc,
+                                       int32_t *e, uint64_t *mv, uint32_t *st) {
+                                       return swmi_local_full_affine_ragged(a, oa, b, ob, m, score_matrix.data(), gap_open, gap_extend,
+                                                                            sc, e, mv, st);
+                                   });
 }
 
 // The reference's 1M-call loop (source.cpp:3074-3082) over arrays of pairs, on every GPU the library is bound to:

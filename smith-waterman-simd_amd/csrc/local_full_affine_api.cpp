@@ -36,6 +36,8 @@ int check_local_full_affine(size_t len1, size_t len2, const int8_t *sm, int gap_
 // codes in the Table's unit (dwords): two per qword
 size_t code_dwords(size_t len1, size_t len2) { return 2 * swmi::local_full_affine_code_qwords((int)len1, (int)len2); }
 
+}  // namespace
+
 Table local_full_affine_table(size_t len1, size_t len2, const int8_t *sm, int gap_open, int gap_extend)
 {
     Table t{launch_local_full_affine_slice, &Context::local_full_affine_state, 0, "steps", len1, len2, 4, code_dwords(len1, len2),
@@ -48,7 +50,6 @@ Table local_full_affine_table(size_t len1, size_t len2, const int8_t *sm, int ga
     return t;
 }
 
-}  // namespace
 }  // namespace host
 }  // namespace swmi
 

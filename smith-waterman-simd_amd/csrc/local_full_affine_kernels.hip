@@ -88,12 +88,18 @@ constexpr int kOpenBit = 5;            // of E's and of F's winner: set when the
 constexpr uint32_t kStop = 3;          // code of a cell whose floor won
 constexpr int kMinusInf = -(1 << 30);  // E on row 0, F on column 0
 
-template <bool TB>
+// RAGGED: one TileWork per workgroup (work[blockIdx.x]) names the alignment, and the launch's own shape (fixed_*, move_words)
+// is unused; else `work` is NULL and unread (tile_sweep.h).
+template <bool TB, bool RAGGED = false>
 __global__ __launch_bounds__(64 * kMaxWaves) void local_full_affine_kernel(
-    const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ seq2s, int len1, int len2, SmCols cols, int gap_open,
+    const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ seq2s, int fixed_len1, int fixed_len2, SmCols cols, int gap_open,
     int gap_extend, int32_t *__restrict__ scores, int32_t *__restrict__ ends, unsigned long long *__restrict__ codes,
-    unsigned long long *__restrict__ moves, uint32_t *__restrict__ steps, uint32_t move_words, uint32_t n_trips)
+    unsigned long long *__restrict__ moves, uint32_t *__restrict__ steps, uint32_t move_words, uint32_t fixed_trips,
+    const TileWork *__restrict__ work)
 {
+    const TileWork slot = load_slot<RAGGED>(work);
+    const int len1 = RAGGED ? (int)slot.len1 : fixed_len1, len2 = RAGGED ? (int)slot.len2 : fixed_len2;
+    const uint32_t n_trips = RAGGED ? (uint32_t)trips(len1) : fixed_trips;
     __shared__ int2 ring[(kMaxWaves - 1) * kRing];
     __shared__ unsigned long long red[kMaxWaves];
     __shared__ int walk_at[3];
@@ -101,9 +107,23 @@ __global__ __launch_bounds__(64 * kMaxWaves) void local_full_affine_kernel(
 
     const int W = blockDim.x >> 6;
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, G = tid;
-    const size_t k = blockIdx.x;
-    const uint8_t *s1 = seq1s + k * (size_t)len1;
-    const uint8_t *s2 = seq2s + k * (size_t)len2;
+    const size_t k = RAGGED ? (size_t)slot.k : (size_t)blockIdx.x;
+    const uint8_t *s1 = seq1s + (RAGGED ? (size_t)slot.s1_off : k * (size_t)len1);
+    const uint8_t *s2 = seq2s + (RAGGED ? (size_t)slot.s2_off : k * (size_t)len2);
+    if constexpr (RAGGED) {
+        // a slot with a zero length: the whole workgroup (one wavefront) leaves here, before any barrier and any sequence load
+        if (len1 == 0 || len2 == 0) {
+            if (tid == 0) {
+                scores[k] = 0;
+                ends[4 * k + 0] = 0;
+                ends[4 * k + 1] = 0;
+                ends[4 * k + 2] = TB ? 0 : -1;
+                ends[4 * k + 3] = TB ? 0 : -1;
+                if constexpr (TB) steps[k] = 0;
+            }
+            return;
+        }
+    }
     const int jbase = kCols * G;                        // the lane's columns are jbase + 1 .. jbase + 16
 
     uint32_t prof[kCols];
@@ -126,7 +146,9 @@ __global__ __launch_bounds__(64 * kMaxWaves) void local_full_affine_kernel(
     const int total_chunks = local_chunks + kDelay * (W - 1);
     const int2 *ring_in = ring + (w > 0 ? w - 1 : 0) * kRing;  // read by waves 1.. (wave 0's left column is the border)
     int2 *ring_out = ring + (w < W - 1 ? w : 0) * kRing;       // written by waves ..W-2
-    unsigned long long *cw_out = TB ? codes + k * ((size_t)W * n_trips * 256) + ((size_t)w * n_trips * 64 + l) * 4 : nullptr;
+    unsigned long long *cw_out = TB ? codes + (RAGGED ? (size_t)slot.code_base : k * ((size_t)W * n_trips * 256)) +
+                                          ((size_t)w * n_trips * 64 + l) * 4
+                                    : nullptr;
 
     int sh_next[kUnroll];
 #pragma unroll
@@ -241,8 +263,8 @@ __global__ __launch_bounds__(64 * kMaxWaves) void local_full_affine_kernel(
         }
     }
     if constexpr (TB) {
-        const unsigned long long *cd = codes + k * ((size_t)W * n_trips * 256);
-        unsigned long long *mv = moves + k * (size_t)move_words;
+        const unsigned long long *cd = codes + (RAGGED ? (size_t)slot.code_base : k * ((size_t)W * n_trips * 256));
+        unsigned long long *mv = moves + (RAGGED ? (size_t)slot.move_base : k * (size_t)move_words);
         int i = end_i, j = end_j, stopped = 0;
         int state = 0;                                  // 0 = H, 1 = E, 2 = F (thread 0's only)
         uint32_t t = 0;
@@ -320,6 +342,15 @@ hipError_t launch_local_full_affine(const uint8_t *d_seq1s, const uint8_t *d_seq
 {
     return tile::launch<local_full_affine_kernel<true>, local_full_affine_kernel<false>>(d_seq1s, d_seq2s, len1, len2, n, sm, d_scores, d_ends, d_codes, d_moves, d_steps,
         move_words, stream, gap_open, gap_extend);
+}
+
+hipError_t launch_local_full_affine_ragged(const uint8_t *d_seq1s, const uint8_t *d_seq2s, const TileWork *d_work, size_t n,
+                                           int waves, const int8_t *sm, int gap_open, int gap_extend, int32_t *d_scores,
+                                           int32_t *d_ends, unsigned long long *d_codes, unsigned long long *d_moves,
+                                           uint32_t *d_steps, hipStream_t stream)
+{
+    return tile::launch_ragged<local_full_affine_kernel<true, true>, local_full_affine_kernel<false, true>>(
+        d_seq1s, d_seq2s, d_work, n, waves, sm, d_scores, d_ends, d_codes, d_moves, d_steps, stream, gap_open, gap_extend);
 }
 
 }  // namespace swmi

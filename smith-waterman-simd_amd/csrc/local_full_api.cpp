@@ -28,6 +28,8 @@ int check_local_full(size_t len1, size_t len2, const int8_t *sm, int gap)
     return check_params(sm, gap);
 }
 
+}  // namespace
+
 Table local_full_table(size_t len1, size_t len2, const int8_t *sm, int gap)
 {
     Table t{launch_local_full_slice, &Context::local_full_state, 0, "steps", len1, len2, 4,
@@ -40,7 +42,6 @@ Table local_full_table(size_t len1, size_t len2, const int8_t *sm, int gap)
     return t;
 }
 
-}  // namespace
 }  // namespace host
 }  // namespace swmi
 

@@ -99,15 +99,21 @@ struct LocalLinear {
     }
 };
 
-template <bool TB>
+// RAGGED: one TileWork per workgroup (work[blockIdx.x]) names the alignment, and the launch's own shape (fixed_*, move_words)
+// is unused; else `work` is NULL and unread (tile_sweep.h).
+template <bool TB, bool RAGGED = false>
 __global__ __launch_bounds__(64 * kMaxWaves) void local_full_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ seq2s,
-                                                                     int len1, int len2, SmCols cols, int gap, int32_t *__restrict__ scores,
-                                                                     int32_t *__restrict__ ends, uint32_t *__restrict__ codes,
-                                                                     unsigned long long *__restrict__ moves, uint32_t *__restrict__ counts,
-                                                                     uint32_t move_words, uint32_t n_trips)
+                                                                     int fixed_len1, int fixed_len2, SmCols cols, int gap,
+                                                                     int32_t *__restrict__ scores, int32_t *__restrict__ ends,
+                                                                     uint32_t *__restrict__ codes, unsigned long long *__restrict__ moves,
+                                                                     uint32_t *__restrict__ counts, uint32_t move_words,
+                                                                     uint32_t fixed_trips, const TileWork *__restrict__ work)
 {
     using V = LocalLinear;
     const V::Gaps gaps{gap};
+    const TileWork slot = load_slot<RAGGED>(work);
+    const int len1 = RAGGED ? (int)slot.len1 : fixed_len1, len2 = RAGGED ? (int)slot.len2 : fixed_len2;
+    const uint32_t n_trips = RAGGED ? (uint32_t)trips(len1) : fixed_trips;
 #include "tile_sweep_body.inc"
 }
 
@@ -121,6 +127,16 @@ hipError_t launch_local_full(const uint8_t *d_seq1s, const uint8_t *d_seq2s, int
 {
     return tile::launch<local_full_kernel<true>, local_full_kernel<false>>(d_seq1s, d_seq2s, len1, len2, n, sm, d_scores, d_ends, d_codes,
                                                                            d_moves, d_steps, move_words, stream, gap);
+}
+
+int local_full_ragged_waves(int len1, int len2) { return len1 > 0 && len2 > 0 ? tile::waves(len2) : 1; }
+
+hipError_t launch_local_full_ragged(const uint8_t *d_seq1s, const uint8_t *d_seq2s, const TileWork *d_work, size_t n, int waves,
+                                    const int8_t *sm, int gap, int32_t *d_scores, int32_t *d_ends, uint32_t *d_codes,
+                                    unsigned long long *d_moves, uint32_t *d_steps, hipStream_t stream)
+{
+    return tile::launch_ragged<local_full_kernel<true, true>, local_full_kernel<false, true>>(d_seq1s, d_seq2s, d_work, n, waves, sm, d_scores,
+                                                                                             d_ends, d_codes, d_moves, d_steps, stream, gap);
 }
 
 }  // namespace swmi

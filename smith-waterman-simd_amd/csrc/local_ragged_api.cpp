@@ -12,16 +12,18 @@ namespace swmi {
 namespace host {
 namespace {
 
-hipError_t launch_linear_ragged(const Table &t, const uint8_t *s1, const uint8_t *s2, const LocalWork *work, size_t n, int32_t *scores,
-                                int32_t *ends, uint32_t *codes, unsigned long long *moves, uint32_t *counts, hipStream_t st)
+hipError_t launch_linear_ragged(const Table &t, size_t, const uint8_t *s1, const uint8_t *s2, const void *work, size_t n,
+                                int32_t *scores, int32_t *ends, uint32_t *codes, unsigned long long *moves, uint32_t *counts,
+                                hipStream_t st)
 {
-    return swmi::launch_local_ragged(s1, s2, work, n, t.sm, t.gap, scores, ends, codes, moves, counts, st);
+    return swmi::launch_local_ragged(s1, s2, static_cast<const LocalWork *>(work), n, t.sm, t.gap, scores, ends, codes, moves, counts, st);
 }
 
-hipError_t launch_affine_ragged(const Table &t, const uint8_t *s1, const uint8_t *s2, const LocalWork *work, size_t n, int32_t *scores,
-                                int32_t *ends, uint32_t *codes, unsigned long long *moves, uint32_t *counts, hipStream_t st)
+hipError_t launch_affine_ragged(const Table &t, size_t, const uint8_t *s1, const uint8_t *s2, const void *work, size_t n,
+                                int32_t *scores, int32_t *ends, uint32_t *codes, unsigned long long *moves, uint32_t *counts,
+                                hipStream_t st)
 {
-    return swmi::launch_local_affine_ragged(s1, s2, work, n, t.sm, t.gap, t.gap_extend, scores, ends, codes, moves, counts, st);
+    return swmi::launch_local_affine_ragged(s1, s2, static_cast<const LocalWork *>(work), n, t.sm, t.gap, t.gap_extend, scores, ends, codes, moves, counts, st);
 }
 
 size_t code_words(bool affine, size_t len1)
@@ -100,6 +102,8 @@ void make_plan(RaggedPlan &p, const uint64_t *off, size_t n, bool affine, bool t
     fill_move_offsets(off, n, p.move_offsets.data());
     p.first = cut(off, n, affine, tb);
     p.work.resize(n);
+    p.slots = p.work.data();
+    p.slot_bytes = sizeof(LocalWork);
     p.code_words.assign(p.first.size() - 1, 0);
     std::vector<uint32_t> at(SWMI_LOCAL_MAX_LEN + 1);       // per length: the next slot of that length
     for (size_t s = 0; s + 1 < p.first.size(); ++s) {

@@ -206,19 +206,26 @@ int score_host_batch(Context &ctx, const uint8_t *s1, const uint8_t *s2, size_t 
 struct Table;
 using TableLaunch = hipError_t (*)(const Table &t, const uint8_t *s1, const uint8_t *s2, size_t n, int32_t *scores, int32_t *ends,
                                    uint32_t *codes, unsigned long long *moves, uint32_t *counts, hipStream_t st);
-using RaggedLaunch = hipError_t (*)(const Table &t, const uint8_t *s1, const uint8_t *s2, const LocalWork *work, size_t n,
+// launches slice `slice` of t.plan: its n slots lie at `work` (device memory; the plan's slot type), everything slice-relative
+using RaggedLaunch = hipError_t (*)(const Table &t, size_t slice, const uint8_t *s1, const uint8_t *s2, const void *work, size_t n,
                                     int32_t *scores, int32_t *ends, uint32_t *codes, unsigned long long *moves, uint32_t *counts,
                                     hipStream_t st);
-// A batch of the local aligners with a seq1 length of its own per alignment (local_ragged_api.cpp): its slices, contiguous in
-// caller order, and one LocalWork per alignment, slice-relative, the slots of each slice ordered longest first.
+// A batch with lengths of its own per alignment: the local aligners' with a seq1 length each (local_ragged_api.cpp), the
+// any-length local aligners' with a seq1 and a seq2 length each (local_full_ragged_api.cpp).  Its slices, contiguous in caller
+// order, and one slot per alignment (LocalWork or TileWork: the pipeline copies slots as bytes and hands them to `launch`),
+// slice-relative, in the order the plan's owner gave the slots of each slice.
 struct RaggedPlan {
     RaggedLaunch launch;
     const uint64_t *seq1_offsets;               // the caller's n + 1
-    std::vector<uint64_t> move_offsets;         // n + 1: moves of alignment k at word move_offsets[k] (SWMI_LOCAL_MOVE_WORDS)
+    const uint64_t *seq2_offsets = nullptr;     // likewise; NULL: seq2 k is the Table's len2 bytes at len2 * k
+    std::vector<uint64_t> move_offsets;         // n + 1: moves of alignment k at word move_offsets[k]
     std::vector<size_t> first;                  // slice s = alignments [first[s], first[s + 1]); first.back() = n
     std::vector<size_t> code_words;             // per slice: dwords of codes (0 ends-only)
-    std::vector<LocalWork> work;                // [n]: slice s's slots at [first[s], first[s + 1])
-    size_t max_m = 0, max_seq1 = 0, max_codes = 0, max_moves = 0;  // the largest slice's alignments, seq1 bytes, codes, moves
+    std::vector<LocalWork> work;                // the local aligners' slots [n]: slice s's at [first[s], first[s + 1])
+    const void *slots = nullptr;                // [n] slots of slot_bytes each, slice s's at [first[s], first[s + 1])
+    size_t slot_bytes = 0;
+    size_t max_m = 0, max_seq1 = 0, max_seq2 = 0, max_codes = 0, max_moves = 0;  // the largest slice's alignments, seq1 bytes,
+                                                                                 //   seq2 bytes (with seq2_offsets), codes, moves
 };
 struct Table {
     TableLaunch launch;
@@ -246,6 +253,12 @@ int table_time_device(const Table &t, const char *entry, const void *d_seq1s, co
 int table_check_timer(size_t n, int iters, const float *avg_ms);   // what the timers check before their first call
 Table local_table(size_t len1, const int8_t *sm, int gap);                               // swmi_table.cpp
 Table affine_table(size_t len1, const int8_t *sm, int gap_open, int gap_extend);         // local_affine_api.cpp
+Table local_full_table(size_t len1, size_t len2, const int8_t *sm, int gap);             // local_full_api.cpp
+Table local_full_affine_table(size_t len1, size_t len2, const int8_t *sm, int gap_open, int gap_extend);   // local_full_affine_api.cpp
+// local_full_ragged_api.cpp: the plan of a ragged any-length batch alone (no device), for tests of its arithmetic -- per slice
+// its alignments and device bytes; true when every code base equals the 64-bit running sum of the code words before it
+bool local_full_ragged_plan_check(const uint64_t *seq1_offsets, const uint64_t *seq2_offsets, size_t n, bool affine, bool tb,
+                                  std::vector<size_t> *slice_sizes, std::vector<size_t> *slice_bytes);
 // Free one aligner's device buffers on the current GPU (synchronises the device first): the body of the *_release_workspaces entries
 int table_release_workspaces(std::shared_ptr<void> Context::*member);
 

@@ -152,3 +152,35 @@ hipError_t launch_local_full_affine(const uint8_t *d_seq1s, const uint8_t *d_seq
                                     int gap_open, int gap_extend, int32_t *d_scores, int32_t *d_ends, unsigned long long *d_codes,
                                     unsigned long long *d_moves, uint32_t *d_steps, size_t move_words, hipStream_t stream);
 }  // namespace swmi
+
+namespace swmi {
+// One slot of a ragged launch of the any-length local aligners (launch_local_full_ragged, launch_local_full_affine_ragged):
+// the alignment its workgroup computes, every field relative to the launch's buffers.  Every field is uniform across the
+// workgroup, which reads its slot through blockIdx.x, so the values live in SGPRs.
+// Widths: a slice holds at most 2^20 alignments (k), and a length is at most 16384.  The offsets and bases are 64-bit,
+// because 32 bits are not enough: a traceback slice of the affine aligner holds up to about 32 GiB of codes (2^35 bytes, 2^33
+// dwords), and a slice of 2^20 alignments whose other sequence is empty holds up to 2^34 sequence bytes and no codes at all.
+// The planner's budget for a slice is below 2^36 bytes, and a 64-bit field counts that in any unit, so no field can wrap.
+struct TileWork {
+    uint64_t s1_off;        // seq1 = the len1 bytes at d_seq1s + s1_off (not read when either length is 0)
+    uint64_t s2_off;        // seq2 = the len2 bytes at d_seq2s + s2_off (likewise)
+    uint64_t code_base;     // codes at d_codes + code_base, in the kernel's code words (dwords; affine: qwords)
+    uint64_t move_base;     // moves at d_moves + move_base: SWMI_LOCAL_FULL_MOVE_WORDS(len1, len2) words
+    uint32_t k;             // results at index k
+    uint32_t len1, len2;    // 0 .. 16384 each
+    uint32_t pad;
+};
+
+// The wave count of a slot's workgroup, 1 .. 16: one wavefront per 1024 columns; a slot with a zero length runs (and returns
+// at once) in a workgroup of one wavefront.
+int local_full_ragged_waves(int len1, int len2);
+// n slots of d_work (device memory), ALL of wave count `waves`, one workgroup of that many wavefronts each: results at
+// d_scores[work.k] etc.  The slice launcher calls it once per wave count present (local_full_ragged_api.cpp).
+hipError_t launch_local_full_ragged(const uint8_t *d_seq1s, const uint8_t *d_seq2s, const TileWork *d_work, size_t n, int waves,
+                                    const int8_t *sm, int gap, int32_t *d_scores, int32_t *d_ends, uint32_t *d_codes,
+                                    unsigned long long *d_moves, uint32_t *d_steps, hipStream_t stream);
+hipError_t launch_local_full_affine_ragged(const uint8_t *d_seq1s, const uint8_t *d_seq2s, const TileWork *d_work, size_t n,
+                                           int waves, const int8_t *sm, int gap_open, int gap_extend, int32_t *d_scores,
+                                           int32_t *d_ends, unsigned long long *d_codes, unsigned long long *d_moves,
+                                           uint32_t *d_steps, hipStream_t stream);
+}  // namespace swmi

@@ -1,8 +1,9 @@
 // swmi_table.cpp -- host side of the aligners that fill the whole table, write codes and walk them (include/swmi.h): the local
 // aligner with end cell, start cell and traceback (swmi_local_*) and the exact semi-global aligner with
 // traceback (swmi_semiglobal_full*, section 13) here, and the one slice pipeline that they and the affine aligners
-// (local_affine_api.cpp, section 14; sgfull_affine_api.cpp, section 16) and the any-length local aligners (local_full_api.cpp,
-// section 17; local_full_affine_api.cpp, section 18) run through.  What differs between them is data (struct Table, swmi_host.h).
+// (local_affine_api.cpp, section 14; sgfull_affine_api.cpp, section 16), the any-length local aligners (local_full_api.cpp,
+// section 17; local_full_affine_api.cpp, section 18) and the ragged batches (local_ragged_api.cpp, section 15;
+// local_full_ragged_api.cpp, section 19) run through.  What differs between them is data (struct Table, swmi_host.h).
 //
 // Their device buffers hang off Context::local_state, sgfull_state, local_affine_state, sgfull_affine_state and
 // local_full_state and local_full_affine_state, which
@@ -71,7 +72,7 @@ struct HostSet {
     int32_t *d_scores = nullptr, *d_ends = nullptr;
     uint32_t *d_codes = nullptr, *d_counts = nullptr;
     unsigned long long *d_moves = nullptr;
-    LocalWork *d_work = nullptr;                                             // a ragged batch's slots
+    unsigned char *d_work = nullptr;                                         // a ragged batch's slots, as bytes
     struct { size_t d1, d2, scores, ends, codes, counts, moves, work; } have{};   // capacity in elements
     size_t off = 0, m = 0;                                                   // slice in flight
     void release()
@@ -84,8 +85,8 @@ struct HostSet {
 
 // pinned copy of a ragged device call's slots, read by that call's upload; `done` is recorded behind the upload
 struct Staging {
-    LocalWork *host = nullptr;
-    size_t cap = 0;
+    unsigned char *host = nullptr;
+    size_t cap = 0;                                  // bytes
     hipEvent_t done = nullptr;
 };
 
@@ -121,7 +122,7 @@ TableState &state(Context &ctx, std::shared_ptr<void> Context::*member)
 bool len_ok(size_t len, size_t max) { return len >= 1 && len <= max; }
 
 // Where slice by slice a batch's data lie: evenly cut for one length, as the plan says for a ragged batch.  Offsets count
-// alignments (first), seq1 bytes (seq1) and move words (moves) from the start of the caller's arrays.
+// alignments (first), seq1 and seq2 bytes (seq1, seq2) and move words (moves) from the start of the caller's arrays.
 struct Slices {
     const Table &t;
     size_t n, slice;            // slice: alignments per slice of a fixed-length batch
@@ -129,19 +130,21 @@ struct Slices {
     size_t first(size_t s) const { return t.plan ? t.plan->first[s] : s * slice; }
     size_t size(size_t s) const { return t.plan ? t.plan->first[s + 1] - t.plan->first[s] : n - s * slice < slice ? n - s * slice : slice; }
     size_t seq1(size_t k) const { return t.plan ? size_t(t.plan->seq1_offsets[k]) : k * t.len1; }
+    size_t seq2(size_t k) const { return t.plan && t.plan->seq2_offsets ? size_t(t.plan->seq2_offsets[k]) : k * t.len2; }
     size_t moves(size_t k) const { return t.plan ? size_t(t.plan->move_offsets[k]) : k * t.move_words; }
     size_t codes(size_t s) const { return t.plan ? t.plan->code_words[s] : size(s) * t.code_words; }
-    // capacity one set of buffers needs: alignments, seq1 bytes, code dwords, move words
+    // capacity one set of buffers needs: alignments, seq1 bytes, seq2 bytes, code dwords, move words
     size_t max_m() const { return t.plan ? t.plan->max_m : slice; }
     size_t max_seq1() const { return t.plan ? t.plan->max_seq1 : slice * t.len1; }
+    size_t max_seq2() const { return t.plan && t.plan->seq2_offsets ? t.plan->max_seq2 : max_m() * t.len2; }
     size_t max_codes() const { return t.plan ? t.plan->max_codes : slice * t.code_words; }
     size_t max_moves() const { return t.plan ? t.plan->max_moves : slice * t.move_words; }
 };
 
-hipError_t launch_table(const Table &t, const uint8_t *s1, const uint8_t *s2, const LocalWork *work, size_t m,
+hipError_t launch_table(const Table &t, size_t slice, const uint8_t *s1, const uint8_t *s2, const void *work, size_t m,
                         int32_t *scores, int32_t *ends, uint32_t *codes, unsigned long long *moves, uint32_t *counts, hipStream_t st)
 {
-    if (t.plan) return t.plan->launch(t, s1, s2, work, m, scores, ends, codes, moves, counts, st);
+    if (t.plan) return t.plan->launch(t, slice, s1, s2, work, m, scores, ends, codes, moves, counts, st);
     return t.launch(t, s1, s2, m, scores, ends, codes, moves, counts, st);
 }
 
@@ -210,9 +213,10 @@ int table_device(const Table &t, const void *d_seq1s, const void *d_seq2s, size_
     // this stream only: earlier launches on it may still use the old one).  A ragged batch's slots follow the codes.
     std::lock_guard<std::mutex> lock(ts.mu);
     uint32_t *codes = nullptr;
-    LocalWork *work = nullptr;
+    unsigned char *work = nullptr;
     const size_t code_bytes = ((tb ? sl.max_codes() * sizeof(uint32_t) : 0) + 15) & ~size_t(15);
-    const size_t need = code_bytes + (t.plan ? n * sizeof(LocalWork) : 0);
+    const size_t slot_bytes = t.plan ? t.plan->slot_bytes : 0;
+    const size_t need = code_bytes + n * slot_bytes;
     if (need) {
         Workspace &ws = ts.workspaces[st];
         if (need > ws.bytes) {
@@ -226,26 +230,26 @@ int table_device(const Table &t, const void *d_seq1s, const void *d_seq2s, size_
         codes = tb ? static_cast<uint32_t *>(ws.ptr) : nullptr;
         if (t.plan) {
             // the slots go up from pinned memory that the stream's last ragged upload has finished reading
-            work = reinterpret_cast<LocalWork *>(static_cast<char *>(ws.ptr) + code_bytes);
+            work = static_cast<unsigned char *>(ws.ptr) + code_bytes;
             Staging &g = ts.staging[st];
             if (g.done) SWMI_HIP_TRY(hipEventSynchronize(g.done));
             else SWMI_HIP_TRY(hipEventCreateWithFlags(&g.done, hipEventDisableTiming));
-            if (g.cap < n) {
+            if (g.cap < n * slot_bytes) {
                 if (g.host) (void)hipHostFree(g.host);
                 g.host = nullptr;
                 g.cap = 0;
-                SWMI_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&g.host), n * sizeof(LocalWork), 0));
-                g.cap = n;
+                SWMI_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&g.host), n * slot_bytes, 0));
+                g.cap = n * slot_bytes;
             }
-            std::copy(t.plan->work.begin(), t.plan->work.end(), g.host);
-            SWMI_HIP_TRY(hipMemcpyAsync(work, g.host, n * sizeof(LocalWork), hipMemcpyHostToDevice, st));
+            std::copy_n(static_cast<const unsigned char *>(t.plan->slots), n * slot_bytes, g.host);
+            SWMI_HIP_TRY(hipMemcpyAsync(work, g.host, n * slot_bytes, hipMemcpyHostToDevice, st));
             SWMI_HIP_TRY(hipEventRecord(g.done, st));
         }
     }
     const uint8_t *s1 = static_cast<const uint8_t *>(d_seq1s), *s2 = static_cast<const uint8_t *>(d_seq2s);
     for (size_t s = 0; s < sl.count(); ++s) {
         const size_t off = sl.first(s);
-        SWMI_HIP_TRY(launch_table(t, s1 + sl.seq1(off), s2 + off * t.len2, work ? work + off : nullptr, sl.size(s),
+        SWMI_HIP_TRY(launch_table(t, s, s1 + sl.seq1(off), s2 + sl.seq2(off), work ? work + off * slot_bytes : nullptr, sl.size(s),
                                   static_cast<int32_t *>(d_scores) + off, static_cast<int32_t *>(d_ends) + t.ends * off, codes,
                                   tb ? static_cast<unsigned long long *>(d_moves) + sl.moves(off) : nullptr,
                                   tb ? static_cast<uint32_t *>(d_counts) + off : nullptr, st));
@@ -264,7 +268,8 @@ int table_host(const Table &t, const char *entry, const uint8_t *seq1s, const ui
     if (!ctx) return last_status();
     const bool tb = moves != nullptr;
     const Slices sl{t, n, t.plan ? 0 : slice_size(t, n, tb)};
-    const size_t mw = t.move_words, len2 = t.len2;
+    const size_t mw = t.move_words;
+    const size_t slot_bytes = t.plan ? t.plan->slot_bytes : 0;
     TableState &ts = state(*ctx, t.state);
     std::lock_guard<std::mutex> lock(ctx->mu);
     HostSet *sets = ts.sets;
@@ -275,13 +280,13 @@ int table_host(const Table &t, const char *entry, const uint8_t *seq1s, const ui
         s.off = s.m = 0;
         const size_t slice = sl.max_m();
         int rc = grow(s.d1, s.have.d1, sl.max_seq1());
-        if (rc == SWMI_OK) rc = grow(s.d2, s.have.d2, slice * len2);
+        if (rc == SWMI_OK) rc = grow(s.d2, s.have.d2, sl.max_seq2());
         if (rc == SWMI_OK) rc = grow(s.d_scores, s.have.scores, slice);
         if (rc == SWMI_OK) rc = grow(s.d_ends, s.have.ends, slice * t.ends);
         if (rc == SWMI_OK) rc = grow(s.d_counts, s.have.counts, slice);
         if (rc == SWMI_OK && tb) rc = grow(s.d_codes, s.have.codes, sl.max_codes());
         if (rc == SWMI_OK && tb) rc = grow(s.d_moves, s.have.moves, sl.max_moves());
-        if (rc == SWMI_OK && t.plan) rc = grow(s.d_work, s.have.work, slice);
+        if (rc == SWMI_OK && t.plan) rc = grow(s.d_work, s.have.work, slice * slot_bytes);
         if (rc != SWMI_OK) return rc;
     }
     // results of the slice a set holds -> host; only as many move words per alignment as the slice's longest walk needs (a
@@ -324,11 +329,13 @@ int table_host(const Table &t, const char *entry, const uint8_t *seq1s, const ui
         const size_t seq1_bytes = sl.seq1(off + s.m) - sl.seq1(off);     // (0 for a ragged slice of empty seq1s only)
         if (seq1_bytes)
             e = hipMemcpyAsync(s.d1, seq1s + sl.seq1(off), seq1_bytes, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(s.d2, seq2s + off * len2, s.m * len2, hipMemcpyHostToDevice, st);
+        const size_t seq2_bytes = sl.seq2(off + s.m) - sl.seq2(off);     // (0 for a ragged slice of empty seq2s only)
+        if (e == hipSuccess && seq2_bytes) e = hipMemcpyAsync(s.d2, seq2s + sl.seq2(off), seq2_bytes, hipMemcpyHostToDevice, st);
         if (e == hipSuccess && t.plan)
-            e = hipMemcpyAsync(s.d_work, t.plan->work.data() + off, s.m * sizeof(LocalWork), hipMemcpyHostToDevice, st);
+            e = hipMemcpyAsync(s.d_work, static_cast<const unsigned char *>(t.plan->slots) + off * slot_bytes, s.m * slot_bytes,
+                               hipMemcpyHostToDevice, st);
         if (e == hipSuccess)
-            e = launch_table(t, s.d1, s.d2, s.d_work, s.m, s.d_scores, s.d_ends, tb ? s.d_codes : nullptr, tb ? s.d_moves : nullptr,
+            e = launch_table(t, sc, s.d1, s.d2, s.d_work, s.m, s.d_scores, s.d_ends, tb ? s.d_codes : nullptr, tb ? s.d_moves : nullptr,
                              tb ? s.d_counts : nullptr, st);
         if (e == hipSuccess && n_sets == 2) e = drain(turn ^ 1);         // the previous slice, while this one computes
     }

@@ -48,6 +48,16 @@
 //     kWalkStops                    whether a code can stop the walk (else it goes on to (0, 0), forced on the border)
 // The borders take the NEGATED row or column so that the caller's sum folds into the negation as it did before the split.
 //
+// Ragged launches (the two local kernels): a kernel with a template parameter RAGGED has a last
+// parameter `work` (NULL and unread in a fixed launch; last, so that every other argument lies where it did), and with RAGGED
+// takes its alignment from one TileWork per workgroup, `slot` = work[blockIdx.x], instead of from k = blockIdx.x and the
+// launch's one (len1, len2): its sequences, lengths, trips, code block, move row and result index.  The slot is loaded through an address
+// that is uniform by construction, so all of it stays in SGPRs.  The body reads the names RAGGED and slot; a kernel without
+// a ragged form (sgfull) finds tile::RAGGED = false and an empty tile::slot below, and a kernel with one shadows both.  One
+// launch serves one wave count: every slot of a launch has W = blockDim.x >> 6, so no wave ever leaves before the
+// workgroup's last barrier -- except that a slot with a zero length, which runs in a W = 1 launch, returns as a whole
+// workgroup, on a uniform test, before the first barrier and before any load from either sequence.
+//
 // Why the body is an include and why the affine kernels are not on it: this compiler optimises a function on its own before
 // it inlines it.  A body behind a call -- even the unchanged kernel moved into a forceinline function -- is optimised twice
 // and came out with 12 fewer SGPRs and 30 more instructions per sweep loop in the linear traceback kernels; a variant that
@@ -90,12 +100,15 @@ constexpr int kDelay = 3;              // chunks between wave w - 1 and wave w
 constexpr int kRing = 256;             // rows of each wave boundary's LDS ring
 constexpr int kStageRows = 128;        // rows of a walk staging block
 
-inline int waves(int len2) { return (len2 + 64 * kCols - 1) / (64 * kCols); }
+constexpr bool RAGGED = false;         // what a kernel without a ragged form sees (above)
+constexpr TileWork slot{};
 
-inline size_t trips(int len1) { return (size_t)((len1 + 63 + kChunk - 1) / kChunk) * (kChunk / kUnroll); }
+__host__ __device__ inline int waves(int len2) { return (len2 + 64 * kCols - 1) / (64 * kCols); }
+
+__host__ __device__ inline size_t trips(int len1) { return (size_t)((len1 + 63 + kChunk - 1) / kChunk) * (kChunk / kUnroll); }
 
 // code words per alignment: one per lane for every step of the padded sweep
-inline size_t code_words(int len1, int len2) { return (size_t)waves(len2) * trips(len1) * 256; }
+__host__ __device__ inline size_t code_words(int len1, int len2) { return (size_t)waves(len2) * trips(len1) * 256; }
 
 // the code word of row i, lane G (i >= 1)
 __device__ __forceinline__ size_t code_index(int i, int G, uint32_t n_trips)
@@ -122,6 +135,22 @@ __device__ __forceinline__ uint4 code_quad(const unsigned long long *c)
     return make_uint4((uint32_t)c[0], (uint32_t)(c[0] >> 32), (uint32_t)c[1], (uint32_t)(c[1] >> 32));
 }
 
+// the slot of a ragged launch's workgroup; nothing is loaded for a fixed launch
+template <bool RAGGED>
+__device__ __forceinline__ TileWork load_slot(const TileWork *work)
+{
+    if constexpr (RAGGED) return work[blockIdx.x];
+    else return TileWork{};
+}
+
+// launches k with `args`, and with a last argument of nullptr when k takes one more (the `work` of a kernel with a ragged form)
+template <class... P, class... A>
+void fire(void (*k)(P...), dim3 grid, dim3 block, hipStream_t stream, A... args)
+{
+    if constexpr (sizeof...(P) == sizeof...(A) + 1) hipLaunchKernelGGL(k, grid, block, 0, stream, args..., nullptr);
+    else hipLaunchKernelGGL(k, grid, block, 0, stream, args...);
+}
+
 // Launches KTb (codes, walk) or KEnds (d_moves NULL: no codes, no walk; d_codes and d_counts unused), one workgroup of
 // waves(len2) wavefronts per alignment; `gaps` are the kernels' gap arguments.
 template <auto KTb, auto KEnds, class Code, class... Gaps>
@@ -134,11 +163,31 @@ hipError_t launch(const uint8_t *d_seq1s, const uint8_t *d_seq2s, int len1, int 
     const dim3 grid((unsigned)n), block(64 * waves(len2));
     const uint32_t n_trips = (uint32_t)trips(len1);
     if (d_moves)
-        hipLaunchKernelGGL(KTb, grid, block, 0, stream, d_seq1s, d_seq2s, len1, len2, cols, gaps..., d_scores, d_ends, d_codes, d_moves,
-                           d_counts, (uint32_t)move_words, n_trips);
+        fire(KTb, grid, block, stream, d_seq1s, d_seq2s, len1, len2, cols, gaps..., d_scores, d_ends, d_codes, d_moves, d_counts,
+             (uint32_t)move_words, n_trips);
     else
-        hipLaunchKernelGGL(KEnds, grid, block, 0, stream, d_seq1s, d_seq2s, len1, len2, cols, gaps..., d_scores, d_ends,
-                           (Code *)nullptr, (unsigned long long *)nullptr, (uint32_t *)nullptr, 0u, n_trips);
+        fire(KEnds, grid, block, stream, d_seq1s, d_seq2s, len1, len2, cols, gaps..., d_scores, d_ends, (Code *)nullptr,
+             (unsigned long long *)nullptr, (uint32_t *)nullptr, 0u, n_trips);
+    return hipGetLastError();
+}
+
+// The ragged sibling: n slots of d_work, all of wave count `waves`, one workgroup of that many wavefronts each (KTb, KEnds: the
+// RAGGED instantiations).  The launch's own lengths, move_words and n_trips are unused (0): the slot holds them.
+template <auto KTb, auto KEnds, class Code, class... Gaps>
+hipError_t launch_ragged(const uint8_t *d_seq1s, const uint8_t *d_seq2s, const TileWork *d_work, size_t n, int waves, const int8_t *sm,
+                         int32_t *d_scores, int32_t *d_ends, Code *d_codes, unsigned long long *d_moves, uint32_t *d_counts,
+                         hipStream_t stream, Gaps... gaps)
+{
+    if (n == 0) return hipSuccess;
+    if (waves < 1 || waves > kMaxWaves || n > (size_t(1) << 20)) return hipErrorInvalidValue;
+    const SmCols cols = sm_cols(sm);
+    const dim3 grid((unsigned)n), block(64 * waves);
+    if (d_moves)
+        hipLaunchKernelGGL(KTb, grid, block, 0, stream, d_seq1s, d_seq2s, 0, 0, cols, gaps..., d_scores, d_ends, d_codes, d_moves,
+                           d_counts, 0u, 0u, d_work);
+    else
+        hipLaunchKernelGGL(KEnds, grid, block, 0, stream, d_seq1s, d_seq2s, 0, 0, cols, gaps..., d_scores, d_ends, (Code *)nullptr,
+                           (unsigned long long *)nullptr, (uint32_t *)nullptr, 0u, 0u, d_work);
     return hipGetLastError();
 }
 

@@ -1,7 +1,8 @@
 // tile_sweep_body.inc -- the sweep and the walk of a linear-gap tile aligner: the body of its kernel (tile_sweep.h tells
 // the mapping and what a variant V supplies).  Included INSIDE the kernel, after `using V = <variant>;` and
 // `const V::Gaps gaps{<gap argument>};`, where the kernel's parameters are named seq1s, seq2s, len1, len2, cols, scores,
-// ends, codes, moves, counts, move_words, n_trips and its template parameter TB.  Text and not a function on purpose:
+// ends, codes, moves, counts, move_words, n_trips and its template parameter TB.  A kernel with a ragged form also names
+// RAGGED and slot, and then len1, len2 and n_trips are the slot's (tile_sweep.h).  Text and not a function on purpose:
 // tile_sweep.h says why.
     __shared__ int ring[(kMaxWaves - 1) * kRing];
     __shared__ unsigned long long red[kMaxWaves];
@@ -10,9 +11,22 @@
 
     const int W = blockDim.x >> 6;
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, G = tid;
-    const size_t k = blockIdx.x;
-    const uint8_t *s1 = seq1s + k * (size_t)len1;
-    const uint8_t *s2 = seq2s + k * (size_t)len2;
+    const size_t k = RAGGED ? (size_t)slot.k : (size_t)blockIdx.x;
+    const uint8_t *s1 = seq1s + (RAGGED ? (size_t)slot.s1_off : k * (size_t)len1);
+    const uint8_t *s2 = seq2s + (RAGGED ? (size_t)slot.s2_off : k * (size_t)len2);
+    if constexpr (RAGGED) {
+        // a slot with a zero length: the whole workgroup (one wavefront) leaves here, before any barrier and any sequence load
+        if (len1 == 0 || len2 == 0) {
+            if (tid == 0) {
+                scores[k] = 0;
+                ends[V::kEnds * k + 0] = 0;
+                ends[V::kEnds * k + 1] = 0;
+                for (int x = 2; x < V::kEnds; ++x) ends[V::kEnds * k + x] = TB ? 0 : -1;
+                if constexpr (TB) counts[k] = 0;
+            }
+            return;
+        }
+    }
     const int jbase = kCols * G;                        // the lane's columns are jbase + 1 .. jbase + 16
 
     uint32_t prof[kCols];
@@ -32,7 +46,9 @@
     const int total_chunks = local_chunks + kDelay * (W - 1);
     const int *ring_in = ring + (w > 0 ? w - 1 : 0) * kRing;   // read by waves 1.. (wave 0's left column is the border)
     int *ring_out = ring + (w < W - 1 ? w : 0) * kRing;        // written by waves ..W-2
-    uint32_t *cw_out = TB ? codes + k * ((size_t)W * n_trips * 256) + ((size_t)w * n_trips * 64 + l) * 4 : nullptr;
+    uint32_t *cw_out = TB ? codes + (RAGGED ? (size_t)slot.code_base : k * ((size_t)W * n_trips * 256)) +
+                                ((size_t)w * n_trips * 64 + l) * 4
+                          : nullptr;
 
     int sh_next[kUnroll];
 #pragma unroll
@@ -117,8 +133,8 @@
             for (int x = 2; x < V::kEnds; ++x) ends[V::kEnds * k + x] = -1;
     }
     if constexpr (TB) {
-        const uint32_t *cd = codes + k * ((size_t)W * n_trips * 256);
-        unsigned long long *mv = moves + k * (size_t)move_words;
+        const uint32_t *cd = codes + (RAGGED ? (size_t)slot.code_base : k * ((size_t)W * n_trips * 256));
+        unsigned long long *mv = moves + (RAGGED ? (size_t)slot.move_base : k * (size_t)move_words);
         int i = end_i, j = end_j, stopped = 0;
         uint32_t t = 0;
         unsigned long long acc = 0;

@@ -162,6 +162,13 @@ def load():
     lib.swmi_local_full_affine_slices_for.restype = sz
     lib.swmi_local_full_affine_time_device.argtypes = [vp, sz, vp, sz, sz, vp, ci, ci, vp, vp, vp, vp, vp, ci,
                                                        ctypes.POINTER(ctypes.c_float)]
+    lib.swmi_local_full_ragged.argtypes = [vp, vp, vp, vp, sz, vp, i8, vp, vp, vp, vp]
+    lib.swmi_local_full_affine_ragged.argtypes = [vp, vp, vp, vp, sz, vp, ci, ci, vp, vp, vp, vp]
+    lib.swmi_local_full_ragged_device.argtypes = [vp, vp, vp, vp, sz, vp, i8, vp, vp, vp, vp, vp]
+    lib.swmi_local_full_affine_ragged_device.argtypes = [vp, vp, vp, vp, sz, vp, ci, ci, vp, vp, vp, vp, vp]
+    lib.swmi_local_full_ragged_move_offsets.argtypes = [vp, vp, sz, vp]
+    lib.swmi_local_full_ragged_slices_for.argtypes = [vp, vp, sz, ci, ci, vp, sz]
+    lib.swmi_local_full_ragged_slices_for.restype = sz
     _lib = lib
     return lib
 
@@ -999,6 +1006,105 @@ def local_full_affine_slices_for(n, len1, len2, traceback=True):
 def local_full_affine_release_workspaces():
     """Free the any-length affine local aligner's device buffers on the current GPU."""
     _check(load().swmi_local_full_affine_release_workspaces())
+
+
+def _affine_gap(name, value):
+    """ctypes converts to int without an overflow check (2**32 + 1 would align as gap 1): check the range here, so that the
+    C side's domain check sees what the caller meant."""
+    g = int(value)
+    if g < -2**31 or g > 2**31 - 1:
+        raise SwmiError(ERR_DOMAIN, "%s %d is outside the supported domain [0,127]" % (name, g))
+    return g
+
+
+def _ragged_pair(seq1s, seq2s):
+    """Both sides of a ragged any-length batch as (concatenated, offsets): each a list of 1-D arrays or such a pair."""
+    cat1, off1 = _ragged_seq1s(seq1s)
+    cat2, off2 = _ragged_seq1s(seq2s)
+    if len(off1) != len(off2):
+        raise ValueError("seq1s and seq2s hold different numbers of sequences")
+    return cat1, off1, cat2, off2
+
+
+def _offsets_pair(seq1_offsets, seq2_offsets):
+    off1 = np.ascontiguousarray(seq1_offsets, dtype=np.uint64).reshape(-1)
+    off2 = np.ascontiguousarray(seq2_offsets, dtype=np.uint64).reshape(-1)
+    if len(off1) < 1 or len(off1) != len(off2):
+        raise ValueError("seq1_offsets and seq2_offsets must both hold n + 1 entries")
+    return off1, off2
+
+
+def local_full_ragged_move_offsets(seq1_offsets, seq2_offsets):
+    """move_offsets[n + 1] of a ragged any-length batch (swmi_local_full_ragged_move_offsets; needs no device)."""
+    off1, off2 = _offsets_pair(seq1_offsets, seq2_offsets)
+    out = np.zeros(len(off1), np.uint64)
+    _check(load().swmi_local_full_ragged_move_offsets(off1.ctypes.data, off2.ctypes.data, len(off1) - 1, out.ctypes.data))
+    return out
+
+
+def local_full_ragged_slices_for(seq1_offsets, seq2_offsets, affine=False, traceback=True):
+    """The slices a ragged any-length call cuts its batch into (swmi_local_full_ragged_slices_for; needs no device)."""
+    off1, off2 = _offsets_pair(seq1_offsets, seq2_offsets)
+    lib = load()
+    args = (off1.ctypes.data, off2.ctypes.data, len(off1) - 1, 1 if affine else 0, 1 if traceback else 0)
+    count = lib.swmi_local_full_ragged_slices_for(*args, None, 0)
+    buf = (ctypes.c_size_t * max(count, 1))()
+    lib.swmi_local_full_ragged_slices_for(*args, buf, count)
+    return [int(buf[k]) for k in range(count)]
+
+
+def _full_ragged_call(entry, seq1s, seq2s, params, traceback):
+    cat1, off1, cat2, off2 = _ragged_pair(seq1s, seq2s)
+    n = len(off1) - 1
+    mo = local_full_ragged_move_offsets(off1, off2) if traceback else None
+    scores = np.zeros(n, np.int32)
+    ends = np.zeros((n, 4), np.int32)
+    moves = np.zeros(int(mo[-1]), np.uint64) if traceback else None
+    steps = np.zeros(n, np.uint32) if traceback else None
+    if len(cat1) == 0:
+        cat1 = np.zeros(16, np.uint8)       # every seq1 is empty: a valid pointer the library never reads
+    if len(cat2) == 0:
+        cat2 = np.zeros(16, np.uint8)
+    _check(entry(cat1.ctypes.data, off1.ctypes.data, cat2.ctypes.data, off2.ctypes.data, n, *params, scores.ctypes.data,
+                 ends.ctypes.data, moves.ctypes.data if traceback else None, steps.ctypes.data if traceback else None))
+    return scores, ends, moves, mo, steps
+
+
+def local_full_ragged(seq1s, seq2s, score_matrix, gap_penalty, traceback=True):
+    """swmi_local_full_ragged: local_full with a (len1, len2) of its own (0 .. 16384 each) per alignment.  seq1s and seq2s:
+    each a list of 1-D uint8 arrays, or a (concatenated, offsets[n + 1]) pair.
+
+    Returns (scores[n] int32, ends[n, 4] int32, moves uint64 (flat: alignment k's at move_offsets[k] ..), move_offsets[n + 1],
+    steps[n] uint32); traceback=False: moves, move_offsets and steps are None."""
+    sm = _sm(score_matrix)
+    return _full_ragged_call(load().swmi_local_full_ragged, seq1s, seq2s, (sm.ctypes.data, _gap(gap_penalty)), traceback)
+
+
+def local_full_affine_ragged(seq1s, seq2s, score_matrix, gap_open, gap_extend, traceback=True):
+    """swmi_local_full_affine_ragged: local_full_affine on a ragged batch; arguments and result as local_full_ragged."""
+    sm = _sm(score_matrix)
+    return _full_ragged_call(load().swmi_local_full_affine_ragged, seq1s, seq2s,
+                             (sm.ctypes.data, _affine_gap("gap_open", gap_open), _affine_gap("gap_extend", gap_extend)), traceback)
+
+
+def local_full_ragged_device(d_seq1s, seq1_offsets, d_seq2s, seq2_offsets, score_matrix, gap_penalty, d_scores, d_ends,
+                             d_moves=None, d_steps=None, stream=0):
+    """swmi_local_full_ragged_device: device pointers, both offset arrays host arrays of n + 1 (asynchronous on `stream`)."""
+    sm = _sm(score_matrix)
+    off1, off2 = _offsets_pair(seq1_offsets, seq2_offsets)
+    _check(load().swmi_local_full_ragged_device(d_seq1s, off1.ctypes.data, d_seq2s, off2.ctypes.data, len(off1) - 1, sm.ctypes.data,
+                                                _gap(gap_penalty), d_scores, d_ends, d_moves, d_steps, stream))
+
+
+def local_full_affine_ragged_device(d_seq1s, seq1_offsets, d_seq2s, seq2_offsets, score_matrix, gap_open, gap_extend, d_scores,
+                                    d_ends, d_moves=None, d_steps=None, stream=0):
+    """swmi_local_full_affine_ragged_device: as local_full_ragged_device with (gap_open, gap_extend)."""
+    sm = _sm(score_matrix)
+    off1, off2 = _offsets_pair(seq1_offsets, seq2_offsets)
+    _check(load().swmi_local_full_affine_ragged_device(d_seq1s, off1.ctypes.data, d_seq2s, off2.ctypes.data, len(off1) - 1,
+                                                       sm.ctypes.data, _affine_gap("gap_open", gap_open),
+                                                       _affine_gap("gap_extend", gap_extend), d_scores, d_ends, d_moves, d_steps,
+                                                       stream))
 
 
 def unpack(packed):
