@@ -11,11 +11,8 @@
 // (opening wins a tie), forced along row 0 and column 0.
 //
 // Mapping, ring timing, best-cell rule and code layout: tile_sweep.h, which also holds the constants, the helpers and the
-// launcher.  The sweep and the walk are written out here and not taken from tile_sweep_body.inc: with the (H, F) carry and
-// the two-dword code behind the body's types the compiler allocated other registers and other loops (DESIGN.md section
-// 13), so this kernel keeps the code it had.
-// E runs down a column and stays with the lane; F runs along the row, so the Carry from lane l - 1 (and through the ring) is
-// its H(i, 16 G) AND its F(i, 16 G): two v_mov_b32_dpp wave_shr:1 per step, (H, F) pairs in the ring.
+// launcher.  The sweep and the walk (the (H, F) hand-over, the code word, the walk's states) are
+// tile_sweep_affine_body.inc, shared with local_full_affine_kernels.hip; this file holds what depends on the recurrence.
 //
 // The cell as KEYS: key = value << 6 | tag << 4 | low, |value| < 2^23 (below).  A stored H key has tag 3 and low = 15 - jj
 // (jj = the column within the lane); E and F are kept as keys of tag 2 and 1 with a traceback (one v_and_or_b32 after their
@@ -41,12 +38,9 @@
 // gap cost is >= 0, so H(p) <= M(p): a padded cell never holds a value that an earlier valid cell lacks, and the best-cell
 // rule (strictly greater; row, then column ascending) never picks one.
 //
-// Codes: 4 bits per cell, one qword per lane and row: the low dword holds H's field of the lane's 16 columns (2 bits each,
-// as sgfull_kernels.hip's codes), the high one E's open bit of column jj at bit jj and F's at bit 16 + jj.
+// Codes: H's field of the low dword is the winner's tag (3 / 2 / 1 = diagonal / E / F), as sgfull_kernels.hip's codes.
 //
-// Walk: a staging block is 128 rows x 32 lanes (512 columns) of qwords; the walking lane carries its state (H / E / F) from
-// block to block.  E(1,j) and F(i,1) always open (E(0,j) = F(i,0) = -inf), so the walk reaches row 0 or column 0 in state H
-// and the border walk is forced.
+// Walk: no code stops it; it reaches row 0 or column 0 in state H, and from there it is forced to (0, 0).
 #include "tile_sweep.h"
 
 namespace swmi {
@@ -68,236 +62,34 @@ static_assert(kCols == tile::kCols && kMaxWaves == tile::kMaxWaves && kUnroll ==
               kDelay == tile::kDelay && kRing == tile::kRing && kStageRows == tile::kStageRows);
 }  // namespace written_for
 
-constexpr int kStageLanes = 32;
-constexpr int kTagH = 3 << 4;
-constexpr int kTagE = 2 << 4;
-constexpr int kTagF = 1 << 4;
-constexpr int kMinusInf = -(1 << 30);  // E on row 0, F on column 0
+struct SgAffine {
+    static constexpr bool kWalkStops = false;
+    static constexpr int kEnds = 2;
+    static constexpr int kRowMin = (int)0x80000000;
+    static constexpr int kTagH = 3 << 4;
+    static constexpr int kTagE = 2 << 4;
+    static constexpr int kTagF = 1 << 4;
+    static constexpr int kOpenBitE = 4;            // kTagH has it, kTagE has not
+    static constexpr int kOpenBitF = 5;            // kTagH has it, kTagF has not
 
-// H(0, j) = H(j, 0) for j >= 1 (and 0 at j = 0) as a stored key
-__device__ __forceinline__ int border_key(int j, int gap_open, int gap_extend)
-{
-    const int h = j > 0 ? -(gap_open + (j - 1) * gap_extend) : 0;
-    return (h << 6) | kTagH;
-}
+    // H(0, j) = H(j, 0) for j >= 1 (and 0 at j = 0) as a stored key
+    static __device__ __forceinline__ int border(int j, int gap_open, int gap_extend)
+    {
+        const int h = j > 0 ? -(gap_open + (j - 1) * gap_extend) : 0;
+        return (h << 6) | kTagH;
+    }
+    static __device__ __forceinline__ int row0(int, int j, int gap_open, int gap_extend) { return border(j, gap_open, gap_extend); }
+    static __device__ __forceinline__ int floor(int m) { return m; }
+};
 
 template <bool TB>
 __global__ __launch_bounds__(64 * kMaxWaves) void sg_full_affine_kernel(
     const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ seq2s, int len1, int len2, SmCols cols, int gap_open,
     int gap_extend, int32_t *__restrict__ scores, int32_t *__restrict__ ends, unsigned long long *__restrict__ codes,
-    unsigned long long *__restrict__ moves, uint32_t *__restrict__ lengths, uint32_t move_words, uint32_t n_trips)
+    unsigned long long *__restrict__ moves, uint32_t *__restrict__ counts, uint32_t move_words, uint32_t n_trips)
 {
-    __shared__ int2 ring[(kMaxWaves - 1) * kRing];
-    __shared__ unsigned long long red[kMaxWaves];
-    __shared__ int walk_at[2];
-    __shared__ unsigned long long stage[TB ? kStageRows * kStageLanes : 1];
-
-    const int W = blockDim.x >> 6;
-    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, G = tid;
-    const size_t k = blockIdx.x;
-    const uint8_t *s1 = seq1s + k * (size_t)len1;
-    const uint8_t *s2 = seq2s + k * (size_t)len2;
-    const int jbase = kCols * G;                        // the lane's columns are jbase + 1 .. jbase + 16
-
-    uint32_t prof[kCols];
-    int key[kCols], e[kCols];
-#pragma unroll
-    for (int jj = 0; jj < kCols; ++jj) {
-        const int j = jbase + jj + 1;
-        const uint32_t b = s2[j <= len2 ? j - 1 : 0] & 3u;
-        prof[jj] = j > len2 ? 0x80808080u : b == 0 ? cols.c[0] : b == 1 ? cols.c[1] : b == 2 ? cols.c[2] : cols.c[3];
-        key[jj] = border_key(j, gap_open, gap_extend);  // row 0
-        e[jj] = kMinusInf;
-    }
-    const int g_open = -(gap_open << 6);
-    const int g_ext = -(gap_extend << 6);
-    int diag_in = border_key(jbase, gap_open, gap_extend);   // key(0, jbase)
-    int f_last = kMinusInf;                             // F(i, jbase + 16) of the lane's last row, for lane l + 1
-    int best = kTagH, best_row = 0;                     // H = 0 at (0, 0)
-
-    const int local_chunks = (len1 + 63 + kChunk - 1) / kChunk;
-    const int total_chunks = local_chunks + kDelay * (W - 1);
-    const int2 *ring_in = ring + (w > 0 ? w - 1 : 0) * kRing;  // read by waves 1.. (wave 0's left column is the border)
-    int2 *ring_out = ring + (w < W - 1 ? w : 0) * kRing;       // written by waves ..W-2
-    unsigned long long *cw_out = TB ? codes + k * ((size_t)W * n_trips * 256) + ((size_t)w * n_trips * 64 + l) * 4 : nullptr;
-
-    int sh_next[kUnroll];
-#pragma unroll
-    for (int t = 0; t < kUnroll; ++t) sh_next[t] = base_shift(s1, t - l, len1);
-
-    for (int c = 0; c < total_chunks; ++c) {
-        const int lc = c - kDelay * w;
-        if (lc >= 0 && lc < local_chunks) {
-            for (int q = 0; q < kChunk / kUnroll; ++q) {
-                const int s0 = lc * kChunk + q * kUnroll;
-                int sh[kUnroll], bound_h[kUnroll], bound_f[kUnroll], edge_h[kUnroll], edge_f[kUnroll];
-                uint32_t cw[kUnroll], co[kUnroll];
-#pragma unroll
-                for (int t = 0; t < kUnroll; ++t) {
-                    sh[t] = sh_next[t];
-                    sh_next[t] = base_shift(s1, s0 + kUnroll + t - l, len1);
-                    // lane 0's left column for row s0 + t + 1
-                    if (w > 0) {
-                        const int2 v = ring_in[(s0 + t) & (kRing - 1)];
-                        bound_h[t] = v.x;
-                        bound_f[t] = v.y;
-                    } else {
-                        bound_h[t] = border_key(s0 + t + 1, gap_open, gap_extend);
-                        bound_f[t] = kMinusInf;
-                    }
-                    cw[t] = 0;
-                    co[t] = 0;
-                }
-#pragma unroll
-                for (int t = 0; t < kUnroll; ++t) {
-                    const int left_in = from_left(bound_h[t], key[kCols - 1]);   // lane l-1's key(i, jbase), one step ago
-                    const int f_in = from_left(bound_f[t], f_last);              // ... and its F(i, jbase)
-                    const int row = s0 + t - l + 1;
-                    if (row >= 1 && row <= len1) {
-                        int d = diag_in, lft = left_in, f = f_in, rk = (int)0x80000000;
-#pragma unroll
-                        for (int jj = 0; jj < kCols; ++jj) {
-                            const int sc = __builtin_amdgcn_sbfe((int)prof[jj], sh[t], 8);
-                            const int ev = imax(key[jj] + g_open, e[jj] + g_ext);
-                            const int fv = imax(lft + g_open, f + g_ext);
-                            int ec = ev, fc = fv;
-                            if constexpr (TB) {
-                                ec = (ev & ~63) | kTagE;
-                                fc = (fv & ~63) | kTagF;
-                            }
-                            const int m = max3(d + (sc << 6), ec, fc);
-                            const int nk = (m & ~63) | (kTagH | (kCols - 1 - jj));
-                            if constexpr (TB) {
-                                cw[t] |= ((uint32_t)(m >> 4) & 3u) << (2 * jj);
-                                co[t] |= (((uint32_t)ev >> 4) & 1u) << jj;
-                                co[t] |= (((uint32_t)fv >> 5) & 1u) << (16 + jj);
-                            }
-                            d = key[jj];
-                            key[jj] = nk;
-                            e[jj] = ec;
-                            f = fc;
-                            lft = nk;
-                            rk = rk > nk ? rk : nk;
-                        }
-                        f_last = f;
-                        if (rk > (best | 63)) {
-                            best = rk;
-                            best_row = row;
-                        }
-                    }
-                    edge_h[t] = key[kCols - 1];
-                    edge_f[t] = f_last;
-                    diag_in = left_in;
-                }
-                if (w < W - 1 && l == 63) {
-#pragma unroll
-                    for (int t = 0; t < kUnroll; ++t) {
-                        const int row = s0 + t - 62;
-                        if (row >= 1 && row <= len1) ring_out[(row - 1) & (kRing - 1)] = make_int2(edge_h[t], edge_f[t]);
-                    }
-                }
-                if constexpr (TB) {
-                    uint4 *o = reinterpret_cast<uint4 *>(cw_out + (size_t)(s0 >> 2) * 256);
-                    o[0] = make_uint4(cw[0], co[0], cw[1], co[1]);
-                    o[1] = make_uint4(cw[2], co[2], cw[3], co[3]);
-                }
-            }
-        }
-        if (W > 1) __syncthreads();
-    }
-
-    // best cell: (H desc, row asc, column asc) over the lanes, then over the waves
-    const int h = best >> 6;
-    const int col = h > 0 ? jbase + (kCols - 1 - (best & 15)) + 1 : 0;
-    unsigned long long r = ((unsigned long long)(uint32_t)h << 34) | ((unsigned long long)(0x1FFFF - best_row) << 17) |
-                           (unsigned long long)(0x1FFFF - col);
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long v = __shfl_xor(r, o, 64);
-        r = v > r ? v : r;
-    }
-    if (l == 0) red[w] = r;
-    if constexpr (TB) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's code stores have reached L2
-    __syncthreads();
-    r = red[0];
-    for (int x = 1; x < W; ++x) r = red[x] > r ? red[x] : r;
-    const int score = (int)(r >> 34);
-    const int end_i = score > 0 ? 0x1FFFF - (int)((r >> 17) & 0x1FFFF) : 0;
-    const int end_j = score > 0 ? 0x1FFFF - (int)(r & 0x1FFFF) : 0;
-    if (tid == 0) {
-        scores[k] = score;
-        ends[2 * k + 0] = end_i;
-        ends[2 * k + 1] = end_j;
-    }
-    if constexpr (TB) {
-        const unsigned long long *cd = codes + k * ((size_t)W * n_trips * 256);
-        unsigned long long *mv = moves + k * (size_t)move_words;
-        int i = end_i, j = end_j;
-        int state = 0;                                  // 0 = H, 1 = E, 2 = F (thread 0's only)
-        uint32_t t = 0;
-        unsigned long long acc = 0;
-        while (i > 0 && j > 0) {                        // uniform: every thread holds the same (i, j)
-            const int g1 = (j - 1) >> 4;
-            const int i_lo = i - kStageRows + 1 > 1 ? i - kStageRows + 1 : 1;
-            const int g_lo = g1 - kStageLanes + 1 > 0 ? g1 - kStageLanes + 1 : 0;
-            const int rows = i - i_lo + 1, lanes = g1 - g_lo + 1;
-            for (int x = tid; x < rows * lanes; x += blockDim.x) {
-                const int rr = x / lanes, gg = x - rr * lanes;
-                stage[rr * kStageLanes + gg] = __builtin_nontemporal_load(cd + code_index(i_lo + rr, g_lo + gg, n_trips));
-            }
-            __syncthreads();
-            if (tid == 0) {
-                while (i > 0 && j > 0 && i >= i_lo && ((j - 1) >> 4) >= g_lo) {
-                    const unsigned long long wd = stage[(i - i_lo) * kStageLanes + ((j - 1) >> 4) - g_lo];
-                    const int cc = (j - 1) & 15;
-                    if (state == 0) {
-                        const uint32_t hf = (uint32_t)(wd >> (2 * cc)) & 3u;
-                        state = hf == 3u ? 0 : hf == 2u ? 1 : 2;
-                    }
-                    uint32_t mvc;
-                    if (state == 0) {
-                        mvc = 3;                        // diagonal
-                        --i;
-                        --j;
-                    } else if (state == 1) {
-                        mvc = 2;                        // up, inside E; back to H where E opened
-                        state = (wd >> (32 + cc)) & 1u ? 0 : 1;
-                        --i;
-                    } else {
-                        mvc = 1;                        // left, inside F; back to H where F opened
-                        state = (wd >> (48 + cc)) & 1u ? 0 : 2;
-                        --j;
-                    }
-                    acc |= (unsigned long long)mvc << (2 * (t & 31));
-                    ++t;
-                    if ((t & 31) == 0) {
-                        mv[(t >> 5) - 1] = acc;
-                        acc = 0;
-                    }
-                }
-                walk_at[0] = i;
-                walk_at[1] = j;
-            }
-            __syncthreads();
-            i = walk_at[0];
-            j = walk_at[1];
-        }
-        if (tid == 0) {
-            // on the border the walk is forced: up along column 0, left along row 0
-            for (; i > 0 || j > 0; ++t) {
-                const uint32_t mvc = i > 0 ? 2u : 1u;
-                acc |= (unsigned long long)mvc << (2 * (t & 31));
-                i -= mvc == 2u;
-                j -= mvc == 1u;
-                if (((t + 1) & 31) == 0) {
-                    mv[t >> 5] = acc;
-                    acc = 0;
-                }
-            }
-            if (t & 31) mv[t >> 5] = acc;
-            lengths[k] = t + 1;
-        }
-    }
+    using V = SgAffine;
+#include "tile_sweep_affine_body.inc"
 }
 
 }  // namespace

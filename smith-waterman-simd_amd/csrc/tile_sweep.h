@@ -1,7 +1,7 @@
 // tile_sweep.h -- what the four any-length aligners share (sgfull_kernels.hip, sgfull_affine_kernels.hip,
 // local_full_kernels.hip, local_full_affine_kernels.hip): the mapping and its constants, the helpers,
 // the geometry and the launcher; the few helpers that the 16-lane local aligners take from here as well.  The sweep and the
-// walk of the two linear-gap kernels are tile_sweep_body.inc; the two affine kernels keep theirs written out (below).
+// walk of the two linear-gap kernels are tile_sweep_body.inc, those of the two affine kernels tile_sweep_affine_body.inc.
 //
 // Mapping: ONE workgroup per alignment, W = ceil(len2 / 1024) wavefronts; lane l of wave w owns the 16 columns
 // 16 G + 1 .. 16 G + 16 of G = 64 w + l.  Inside a wave, lane l computes row s - l + 1 at the wave's local step s; what
@@ -48,23 +48,35 @@
 //     kWalkStops                    whether a code can stop the walk (else it goes on to (0, 0), forced on the border)
 // The borders take the NEGATED row or column so that the caller's sum folds into the negation as it did before the split.
 //
+// tile_sweep_affine_body.inc is the sweep and walk for an affine-gap variant, a type of static members only (the body reads
+// the kernel's gap_open and gap_extend itself).  The key array, E's array, the column loop and the E / F recurrences stay in
+// the body; the variant supplies
+//     kEnds, kWalkStops, kRowMin    as above; where kWalkStops, the code that stops the walk is kTagH's + 1 (the floor's)
+//     kTagH, kTagE, kTagF           tag << 4 of a stored H key (also the key of H = 0 and, >> 4, the walk's diagonal code), of
+//                                   E and of F as kept with a traceback
+//     kOpenBitE, kOpenBitF          the bit of E's / F's winner that is set when the gap opens (kTagH has it, the gap's tag not)
+//     row0(jj, j, open, extend)     the stored key of row 0 in the lane's column jj (global column j)
+//     border(j, open, extend)       the stored key of H(0, j) = H(j, 0), column bits aside
+//     floor(m)                      H's largest candidate m with the zero floor joined, or m itself
+//
 // Ragged launches (the two local kernels): a kernel with a template parameter RAGGED has a last
 // parameter `work` (NULL and unread in a fixed launch; last, so that every other argument lies where it did), and with RAGGED
 // takes its alignment from one TileWork per workgroup, `slot` = work[blockIdx.x], instead of from k = blockIdx.x and the
 // launch's one (len1, len2): its sequences, lengths, trips, code block, move row and result index.  The slot is loaded through an address
-// that is uniform by construction, so all of it stays in SGPRs.  The body reads the names RAGGED and slot; a kernel without
-// a ragged form (sgfull) finds tile::RAGGED = false and an empty tile::slot below, and a kernel with one shadows both.  One
+// that is uniform by construction, so all of it stays in SGPRs.  Both bodies read the names RAGGED and slot; a kernel without
+// a ragged form (the semi-global pair) finds tile::RAGGED = false and an empty tile::slot below, and a kernel with one shadows both.  One
 // launch serves one wave count: every slot of a launch has W = blockDim.x >> 6, so no wave ever leaves before the
 // workgroup's last barrier -- except that a slot with a zero length, which runs in a W = 1 launch, returns as a whole
 // workgroup, on a uniform test, before the first barrier and before any load from either sequence.
 //
-// Why the body is an include and why the affine kernels are not on it: this compiler optimises a function on its own before
-// it inlines it.  A body behind a call -- even the unchanged kernel moved into a forceinline function -- is optimised twice
-// and came out with 12 fewer SGPRs and 30 more instructions per sweep loop in the linear traceback kernels; a variant that
-// held the key array or the column loop lost the array-to-vector promotion (68 VGPRs for 119).  As text inside the named
-// kernel the linear pair compiles to the loops it had, instruction for instruction.  The affine pair needs two values in
-// the carry and two dwords in the code word; behind the body's types they became other allocas, other registers and other
-// loops, so those two kernels keep their own sweep and walk and take the rest from here.
+// Why the bodies are includes, and why there are two: this compiler optimises a function on its own before it inlines it.
+// A body behind a call -- even the unchanged kernel moved into a forceinline function -- is optimised twice and came out
+// with 12 fewer SGPRs and 30 more instructions per sweep loop in the linear traceback kernels; a variant that held the key
+// array or the column loop lost the array-to-vector promotion (68 VGPRs for 119).  As text inside the named kernel each pair
+// compiles to the code it had.  The affine pair needs two values in the carry and two dwords in the code word; behind
+// generic carry and code types of the linear body they became other allocas, other registers and other loops (DESIGN.md
+// section 13), so it has a body of its own, written with the concrete types both affine kernels had (an int2 ring, separate
+// H and F arrays, two code dwords): from it both compile to the parent's instructions, one for one.
 #pragma once
 #include "swmi_internal.h"
 

@@ -1,0 +1,265 @@
+// tile_sweep_affine_body.inc -- the sweep and the walk of an AFFINE-gap tile aligner: the body of its kernel (tile_sweep.h
+// tells the mapping and what an affine variant V supplies).  Included INSIDE the kernel, after `using V = <variant>;`,
+// where the kernel's parameters are named seq1s, seq2s, len1, len2, cols, gap_open, gap_extend, scores, ends, codes, moves,
+// counts, move_words, n_trips and its template parameter TB.  A kernel with a ragged form also names RAGGED and slot, and
+// then len1, len2 and n_trips are the slot's (tile_sweep.h).  Text and not a function on purpose: tile_sweep.h says why.
+//
+// E runs down a column and stays with the lane; F runs along the row, so what lane l - 1 hands over (and lane 63 through
+// the ring) is its H(i, 16 G) AND its F(i, 16 G): two v_mov_b32_dpp wave_shr:1 per step, (H, F) pairs in the ring.  With a
+// traceback E and F are kept masked to V's tags (one v_and_or_b32 after their max); ends-only they are not.
+//
+// Code word: 4 bits per cell, one qword per lane and row.  The low dword holds the tag of H's winner in the lane's 16
+// columns (2 bits each, column jj at bits 2 jj); the high dword E's open bit of column jj at bit jj and F's at bit
+// 16 + jj.  A staging block of the walk is 128 rows x 32 lanes (512 columns) of qwords.
+//
+// Walk: one lane, in state H / E / F, carried from block to block.  In H it reads the cell's H code -- the floor's (V::kTagH's
+// code + 1, where V::kWalkStops) ends the walk on that cell -- and goes on in the state the code names; a cell's H code is not
+// consulted inside E or F.  H takes a diagonal; E an up and F a left step, back to H where that cell's open bit is set.  E(1,j)
+// and F(i,1) always open (E(0,j) = F(i,0) = -inf), so the walk reaches row 0 or column 0 in state H.
+    constexpr int kStageLanes = 32;
+    constexpr int kMinusInf = -(1 << 30);               // E on row 0, F on column 0
+    __shared__ int2 ring[(kMaxWaves - 1) * kRing];
+    __shared__ unsigned long long red[kMaxWaves];
+    __shared__ int walk_at[V::kWalkStops ? 3 : 2];
+    __shared__ unsigned long long stage[TB ? kStageRows * kStageLanes : 1];
+
+    const int W = blockDim.x >> 6;
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, G = tid;
+    const size_t k = RAGGED ? (size_t)slot.k : (size_t)blockIdx.x;
+    const uint8_t *s1 = seq1s + (RAGGED ? (size_t)slot.s1_off : k * (size_t)len1);
+    const uint8_t *s2 = seq2s + (RAGGED ? (size_t)slot.s2_off : k * (size_t)len2);
+    if constexpr (RAGGED) {
+        // a slot with a zero length: the whole workgroup (one wavefront) leaves here, before any barrier and any sequence load
+        if (len1 == 0 || len2 == 0) {
+            if (tid == 0) {
+                scores[k] = 0;
+                ends[V::kEnds * k + 0] = 0;
+                ends[V::kEnds * k + 1] = 0;
+                for (int x = 2; x < V::kEnds; ++x) ends[V::kEnds * k + x] = TB ? 0 : -1;
+                if constexpr (TB) counts[k] = 0;
+            }
+            return;
+        }
+    }
+    const int jbase = kCols * G;                        // the lane's columns are jbase + 1 .. jbase + 16
+
+    uint32_t prof[kCols];
+    int key[kCols], e[kCols];                           // H's stored keys and E of the row the lane computed last
+#pragma unroll
+    for (int jj = 0; jj < kCols; ++jj) {
+        const int j = jbase + jj + 1;
+        const uint32_t b = s2[j <= len2 ? j - 1 : 0] & 3u;
+        prof[jj] = j > len2 ? 0x80808080u : b == 0 ? cols.c[0] : b == 1 ? cols.c[1] : b == 2 ? cols.c[2] : cols.c[3];
+        key[jj] = V::row0(jj, j, gap_open, gap_extend);
+        e[jj] = kMinusInf;
+    }
+    const int g_open = -(gap_open << 6);
+    const int g_ext = -(gap_extend << 6);
+    int diag_in = V::border(jbase, gap_open, gap_extend);   // key(0, jbase)
+    int f_last = kMinusInf;                             // F(i, jbase + 16) of the lane's last row, for lane l + 1
+    int best = V::kTagH, best_row = 0;                  // H = 0 at (0, 0)
+
+    const int local_chunks = (len1 + 63 + kChunk - 1) / kChunk;
+    const int total_chunks = local_chunks + kDelay * (W - 1);
+    const int2 *ring_in = ring + (w > 0 ? w - 1 : 0) * kRing;  // read by waves 1.. (wave 0's left column is the border)
+    int2 *ring_out = ring + (w < W - 1 ? w : 0) * kRing;       // written by waves ..W-2
+    unsigned long long *cw_out = TB ? codes + (RAGGED ? (size_t)slot.code_base : k * ((size_t)W * n_trips * 256)) +
+                                          ((size_t)w * n_trips * 64 + l) * 4
+                                    : nullptr;
+
+    int sh_next[kUnroll];
+#pragma unroll
+    for (int t = 0; t < kUnroll; ++t) sh_next[t] = base_shift(s1, t - l, len1);
+
+    for (int c = 0; c < total_chunks; ++c) {
+        const int lc = c - kDelay * w;
+        if (lc >= 0 && lc < local_chunks) {
+            for (int q = 0; q < kChunk / kUnroll; ++q) {
+                const int s0 = lc * kChunk + q * kUnroll;
+                int sh[kUnroll], bound_h[kUnroll], bound_f[kUnroll], edge_h[kUnroll], edge_f[kUnroll];
+                uint32_t cw[kUnroll], co[kUnroll];
+#pragma unroll
+                for (int t = 0; t < kUnroll; ++t) {
+                    sh[t] = sh_next[t];
+                    sh_next[t] = base_shift(s1, s0 + kUnroll + t - l, len1);
+                    // lane 0's left column for row s0 + t + 1: the ring, or the border's H and F = -inf
+                    if (w > 0) {
+                        const int2 v = ring_in[(s0 + t) & (kRing - 1)];
+                        bound_h[t] = v.x;
+                        bound_f[t] = v.y;
+                    } else {
+                        bound_h[t] = V::border(s0 + t + 1, gap_open, gap_extend);
+                        bound_f[t] = kMinusInf;
+                    }
+                    cw[t] = 0;
+                    co[t] = 0;
+                }
+#pragma unroll
+                for (int t = 0; t < kUnroll; ++t) {
+                    const int left_in = from_left(bound_h[t], key[kCols - 1]);   // lane l-1's key(i, jbase), one step ago
+                    const int f_in = from_left(bound_f[t], f_last);              // ... and its F(i, jbase)
+                    const int row = s0 + t - l + 1;
+                    if (row >= 1 && row <= len1) {
+                        int d = diag_in, lft = left_in, f = f_in, rk = V::kRowMin;
+#pragma unroll
+                        for (int jj = 0; jj < kCols; ++jj) {
+                            const int sc = __builtin_amdgcn_sbfe((int)prof[jj], sh[t], 8);
+                            const int ev = imax(key[jj] + g_open, e[jj] + g_ext);
+                            const int fv = imax(lft + g_open, f + g_ext);
+                            int ec = ev, fc = fv;
+                            if constexpr (TB) {
+                                ec = (ev & ~63) | V::kTagE;
+                                fc = (fv & ~63) | V::kTagF;
+                            }
+                            const int m = V::floor(max3(d + (sc << 6), ec, fc));
+                            const int nk = (m & ~63) | (V::kTagH | (kCols - 1 - jj));
+                            if constexpr (TB) {
+                                cw[t] |= ((uint32_t)(m >> 4) & 3u) << (2 * jj);
+                                co[t] |= (((uint32_t)ev >> V::kOpenBitE) & 1u) << jj;
+                                co[t] |= (((uint32_t)fv >> V::kOpenBitF) & 1u) << (16 + jj);
+                            }
+                            d = key[jj];
+                            key[jj] = nk;
+                            e[jj] = ec;
+                            f = fc;
+                            lft = nk;
+                            rk = rk > nk ? rk : nk;
+                        }
+                        f_last = f;
+                        if (rk > (best | 63)) {
+                            best = rk;
+                            best_row = row;
+                        }
+                    }
+                    edge_h[t] = key[kCols - 1];
+                    edge_f[t] = f_last;
+                    diag_in = left_in;
+                }
+                if (w < W - 1 && l == 63) {
+#pragma unroll
+                    for (int t = 0; t < kUnroll; ++t) {
+                        const int row = s0 + t - 62;
+                        if (row >= 1 && row <= len1) ring_out[(row - 1) & (kRing - 1)] = make_int2(edge_h[t], edge_f[t]);
+                    }
+                }
+                if constexpr (TB) {
+                    uint4 *o = reinterpret_cast<uint4 *>(cw_out + (size_t)(s0 >> 2) * 256);
+                    o[0] = make_uint4(cw[0], co[0], cw[1], co[1]);
+                    o[1] = make_uint4(cw[2], co[2], cw[3], co[3]);
+                }
+            }
+        }
+        if (W > 1) __syncthreads();
+    }
+
+    // best cell: (H desc, row asc, column asc) over the lanes, then over the waves
+    const int h = best >> 6;
+    const int col = h > 0 ? jbase + (kCols - 1 - (best & 15)) + 1 : 0;
+    unsigned long long r = ((unsigned long long)(uint32_t)h << 34) | ((unsigned long long)(0x1FFFF - best_row) << 17) |
+                           (unsigned long long)(0x1FFFF - col);
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long v = __shfl_xor(r, o, 64);
+        r = v > r ? v : r;
+    }
+    if (l == 0) red[w] = r;
+    if constexpr (TB) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's code stores have reached L2
+    __syncthreads();
+    r = red[0];
+    for (int x = 1; x < W; ++x) r = red[x] > r ? red[x] : r;
+    const int score = (int)(r >> 34);
+    const int end_i = score > 0 ? 0x1FFFF - (int)((r >> 17) & 0x1FFFF) : 0;
+    const int end_j = score > 0 ? 0x1FFFF - (int)(r & 0x1FFFF) : 0;
+    if (tid == 0) {
+        scores[k] = score;
+        ends[V::kEnds * k + 0] = end_i;
+        ends[V::kEnds * k + 1] = end_j;
+        if constexpr (!TB)                              // what only a walk finds
+            for (int x = 2; x < V::kEnds; ++x) ends[V::kEnds * k + x] = -1;
+    }
+    if constexpr (TB) {
+        constexpr uint32_t kCodeH = V::kTagH >> 4, kCodeE = V::kTagE >> 4;
+        const unsigned long long *cd = codes + (RAGGED ? (size_t)slot.code_base : k * ((size_t)W * n_trips * 256));
+        unsigned long long *mv = moves + (RAGGED ? (size_t)slot.move_base : k * (size_t)move_words);
+        int i = end_i, j = end_j, stopped = 0;
+        int state = 0;                                  // 0 = H, 1 = E, 2 = F (thread 0's only)
+        uint32_t t = 0;
+        unsigned long long acc = 0;
+        while ((!V::kWalkStops || !stopped) && i > 0 && j > 0) {   // uniform: every thread holds the same (i, j, stopped)
+            const int g1 = (j - 1) >> 4;
+            const int i_lo = i - kStageRows + 1 > 1 ? i - kStageRows + 1 : 1;
+            const int g_lo = g1 - kStageLanes + 1 > 0 ? g1 - kStageLanes + 1 : 0;
+            const int rows = i - i_lo + 1, lanes = g1 - g_lo + 1;
+            for (int x = tid; x < rows * lanes; x += blockDim.x) {
+                const int rr = x / lanes, gg = x - rr * lanes;
+                stage[rr * kStageLanes + gg] = __builtin_nontemporal_load(cd + code_index(i_lo + rr, g_lo + gg, n_trips));
+            }
+            __syncthreads();
+            if (tid == 0) {
+                int st = 0;
+                while (i > 0 && j > 0 && i >= i_lo && ((j - 1) >> 4) >= g_lo) {
+                    const unsigned long long wd = stage[(i - i_lo) * kStageLanes + ((j - 1) >> 4) - g_lo];
+                    const int cc = (j - 1) & 15;
+                    if (state == 0) {
+                        const uint32_t hc = (uint32_t)(wd >> (2 * cc)) & 3u;
+                        if (V::kWalkStops && hc == kCodeH + 1) {   // the floor won: the cell holds 0, the start cell
+                            st = 1;
+                            break;
+                        }
+                        state = hc == kCodeH ? 0 : hc == kCodeE ? 1 : 2;
+                    }
+                    uint32_t mvc;
+                    if (state == 0) {
+                        mvc = 3;                        // diagonal
+                        --i;
+                        --j;
+                    } else if (state == 1) {
+                        mvc = 2;                        // up, inside E; back to H where E opened
+                        state = (wd >> (32 + cc)) & 1u ? 0 : 1;
+                        --i;
+                    } else {
+                        mvc = 1;                        // left, inside F; back to H where F opened
+                        state = (wd >> (48 + cc)) & 1u ? 0 : 2;
+                        --j;
+                    }
+                    acc |= (unsigned long long)mvc << (2 * (t & 31));
+                    ++t;
+                    if ((t & 31) == 0) {
+                        mv[(t >> 5) - 1] = acc;
+                        acc = 0;
+                    }
+                }
+                walk_at[0] = i;
+                walk_at[1] = j;
+                if constexpr (V::kWalkStops) walk_at[2] = st;
+            }
+            __syncthreads();
+            i = walk_at[0];
+            j = walk_at[1];
+            if constexpr (V::kWalkStops) stopped = walk_at[2];
+        }
+        if (tid == 0) {
+            if constexpr (V::kWalkStops) {
+                // the walk ended on its start cell: the count is the moves
+                if (t & 31) mv[t >> 5] = acc;
+                counts[k] = t;
+                ends[V::kEnds * k + 2] = i;
+                ends[V::kEnds * k + 3] = j;
+            } else {
+                // the walk goes on to (0, 0), forced on the border: up along column 0, left along row 0; the count is the
+                // path's cells, moves + 1
+                for (; i > 0 || j > 0; ++t) {
+                    const uint32_t mvc = i > 0 ? 2u : 1u;
+                    acc |= (unsigned long long)mvc << (2 * (t & 31));
+                    i -= mvc == 2u;
+                    j -= mvc == 1u;
+                    if (((t + 1) & 31) == 0) {
+                        mv[t >> 5] = acc;
+                        acc = 0;
+                    }
+                }
+                if (t & 31) mv[t >> 5] = acc;
+                counts[k] = t + 1;
+            }
+        }
+    }
