@@ -670,6 +670,68 @@ SWMI_API int swmi_local_full_affine_ragged_device(const void *d_seq1s, const uin
 /* unpack() itself (source.cpp:1580-1583) for n packed sequences, on the GPU. Host buffers. */
 SWMI_API int swmi_unpack(const uint8_t *packed, size_t n_seqs, uint8_t *unpacked);
 
+/* ---- global and free-end-gap alignment of two sequences of ANY length, with end cell, start cell and traceback (DESIGN.md
+ * section 20) ------------------------------------------------------------------------------------------------------------
+ * No reference counterpart: Needleman-Wunsch and its end-gap-free relatives, with linear gaps.  n alignments; seq1 k = the
+ * len1 bytes at seq1s + len1 * k, seq2 k = the len2 bytes at seq2s + len2 * k, one (len1, len2) per call,
+ * 1 <= len1, len2 <= 16384 (SWMI_GLOBAL_FULL_MAX_LEN); any int8 matrix, gap in [0, 127]; bases are taken modulo 4.
+ * free_ends is a mask of SWMI_FREE_* that says which end gaps cost nothing; all 16 masks are valid:
+ *     SWMI_FREE_BEGIN1  leading bases of seq1 may stay unaligned: H(i,0) = 0, else H(i,0) = -i gap
+ *     SWMI_FREE_BEGIN2  H(0,j) = 0, else H(0,j) = -j gap
+ *     SWMI_FREE_END1    trailing bases of seq1 are free: the end cell may be any (i, len2), i = 0..len1
+ *     SWMI_FREE_END2    the end cell may be any (len1, j), j = 0..len2
+ * SWMI_ENDS_GLOBAL (0) aligns both sequences end to end, SWMI_ENDS_FIT all of seq1 against a stretch of seq2,
+ * SWMI_ENDS_OVERLAP a suffix of one sequence against a prefix of the other.
+ *     H(0,0) = 0
+ *     H(i,j) = max(H(i-1,j-1) + sm[seq1[i-1]*4 + seq2[j-1]], H(i-1,j) - gap, H(i,j-1) - gap),  i = 1..len1, j = 1..len2
+ * with no zero floor.  The end cell is (len1, len2), or with SWMI_FREE_END1 / SWMI_FREE_END2 the cell of the last column /
+ * last row (border cells (0, len2) and (len1, 0) included) that holds the largest H; among equal ones the first in row-major
+ * order (smallest i, then smallest j).  scores[k] = that H, which may be NEGATIVE; |score| < 2^22.
+ * ends[k] = (end_i, end_j, start_i, start_j).  The walk goes back from the end cell: a diagonal step when
+ * H(i,j) = H(i-1,j-1) + s, else an up step (i - 1) when H(i,j) = H(i-1,j) - gap, else a left step (j - 1).  At (0, 0) it
+ * ends.  On row 0 with j > 0 it ends if SWMI_FREE_BEGIN2 is set, else goes left to (0, 0) by forced steps; on column 0 with
+ * i > 0 it ends if SWMI_FREE_BEGIN1 is set, else goes up to (0, 0) by forced steps.  The start cell is where it ended.
+ * moves + k * SWMI_GLOBAL_FULL_MOVE_WORDS(len1, len2) receives the steps in WALKING order (step 0 leaves the end cell), step t
+ * at bits 2 (t % 32) of word t / 32: 3 = diagonal, 2 = up, 1 = left; steps[k] = their number, forced steps included, so
+ * swmi_local_full_expand_moves rebuilds the list of steps[k] + 1 positions from the start cell to the end cell; words past
+ * the last step are unspecified.  moves and steps both NULL: ENDS-ONLY -- no codes are stored or walked, the start cell is
+ * reported as (-1, -1).
+ * Host buffers.  The batch runs in SLICES (swmi_global_full_slices_for) on two sets of device buffers, one slice's copies
+ * beside the other's kernel.  Errors: SWMI_ERR_INVALID_ARGUMENT for a length outside [1, 16384], free_ends above 15, a NULL
+ * buffer, or only one of moves / steps; SWMI_ERR_DOMAIN for gap_penalty < 0; n = 0 is a no-op that needs no device.  Every
+ * argument is checked before any device is touched. */
+#define SWMI_FREE_BEGIN1 1u
+#define SWMI_FREE_BEGIN2 2u
+#define SWMI_FREE_END1 4u
+#define SWMI_FREE_END2 8u
+#define SWMI_ENDS_GLOBAL 0u
+#define SWMI_ENDS_FIT (SWMI_FREE_BEGIN2 | SWMI_FREE_END2)
+#define SWMI_ENDS_OVERLAP (SWMI_FREE_BEGIN1 | SWMI_FREE_BEGIN2 | SWMI_FREE_END1 | SWMI_FREE_END2)
+#define SWMI_GLOBAL_FULL_MAX_LEN 16384
+#define SWMI_GLOBAL_FULL_MOVE_WORDS(len1, len2) ((((((size_t)(len1)) + ((size_t)(len2)) + 31) / 32) + 1) & ~(size_t)1)   /* 16-byte rows */
+SWMI_API int swmi_global_full(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t len2, size_t n,
+                              const int8_t score_matrix[16], int8_t gap_penalty, unsigned free_ends, int32_t *scores,
+                              int32_t *ends, uint64_t *moves, uint32_t *steps);
+/* The slices a swmi_global_full call of n alignments cuts its batch into (traceback = 0: ends-only), in order; returns how
+ * many there are and writes the first `cap` sizes (NULL to count).  The budgets are swmi_local_full_slices_for's: with a
+ * traceback what 256 alignments of 16384 x 16384 take (about 16.1 GiB), ends-only 256 MiB; at most 2^20 alignments per
+ * slice.  Needs no device.  0 for a length outside [1, 16384]. */
+SWMI_API size_t swmi_global_full_slices_for(size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap);
+/* Same with every buffer in device memory (16-byte aligned), asynchronous on `stream`.  The traceback codes (2 bits per
+ * cell) go to a workspace of the library's per (GPU, stream), grown on demand up to one slice and kept until
+ * swmi_global_full_release_workspaces() / swmi_shutdown(): calls on one stream serialise by themselves, calls on different
+ * streams may be in flight together. */
+SWMI_API int swmi_global_full_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
+                                     const int8_t score_matrix[16], int8_t gap_penalty, unsigned free_ends, void *d_scores,
+                                     void *d_ends, void *d_moves, void *d_steps, void *stream);
+/* Free the device buffers of both entries above on the current GPU (synchronises the device first). */
+SWMI_API int swmi_global_full_release_workspaces(void);
+/* Measurement helper: `iters` swmi_global_full_device calls back to back on `stream`, bracketed by HIP events; *avg_ms = the
+ * average time of one call.  Synchronous. */
+SWMI_API int swmi_global_full_time_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
+                                          const int8_t score_matrix[16], int8_t gap_penalty, unsigned free_ends, void *d_scores,
+                                          void *d_ends, void *d_moves, void *d_steps, void *stream, int iters, float *avg_ms);
+
 /* ---- deferred queue behind the per-pair signature -------------------------------------
  * Lets a per-pair caller (the reference's timing loop) keep its call shape while the
  * library batches: submit() copies the pair into pinned staging memory and returns its

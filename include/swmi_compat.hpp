@@ -82,6 +82,17 @@ inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_long_affin
                                                                                         const std::array<int8_t, 16> &score_matrix,
                                                                                         int gap_open, int gap_extend);
 
+// Global (Needleman-Wunsch) and free-end-gap alignment of two sequences of any lengths in [1, 16384], any score matrix and
+// gap (swmi_global_full: no reference counterpart): (score, path of (i, j) from the start cell to the end cell), forced steps
+// along a border that is not free included.  free_ends is a mask of SWMI_FREE_*: SWMI_ENDS_GLOBAL (end to end, from (0, 0) to
+// (len1, len2)), SWMI_ENDS_FIT (all of seq1 against a stretch of seq2), SWMI_ENDS_OVERLAP, or any other of the 16.  The score
+// may be negative.  One synchronous call per alignment; swmi::NeedlemanWunsch_mi355x_batch is the throughput form.
+inline std::pair<int, std::vector<std::pair<int, int>>> NeedlemanWunsch_mi355x(const std::vector<uint8_t> &seq1,
+                                                                              const std::vector<uint8_t> &seq2,
+                                                                              const std::array<int8_t, 16> &score_matrix,
+                                                                              const int8_t gap_penalty,
+                                                                              unsigned free_ends = SWMI_ENDS_GLOBAL);
+
 namespace swmi {
 
 // match 1, mismatch -1 (source.cpp:1786)
@@ -464,6 +475,52 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SmithWaterm
     });
 }
 
+// Global / free-end-gap alignment of seq1s[k] against seq2s[k], every seq1 of one length and every seq2 of one length:
+// result[k] == NeedlemanWunsch_mi355x(seq1s[k], seq2s[k], score_matrix, gap_penalty, free_ends).  The batch goes to the GPU in
+// pieces of `piece` alignments, at most one traceback slice of swmi_global_full (0 = one slice: 256 at 16384 x 16384); only
+// two pieces' moves are held at a time, and the paths of one piece are rebuilt on `threads` host threads (0 = as many as the
+// machine reports, at most 64) while the GPU aligns the next.
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> NeedlemanWunsch_mi355x_batch(
+    const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::vector<uint8_t>> &seq2s,
+    const std::array<int8_t, 16> &score_matrix, const int8_t gap_penalty, unsigned free_ends = SWMI_ENDS_GLOBAL, size_t piece = 0,
+    unsigned threads = 0)
+{
+    if (seq1s.size() != seq2s.size()) throw std::invalid_argument("NeedlemanWunsch_mi355x_batch: seq1s and seq2s differ in length");
+    const size_t len1 = seq1s.empty() ? 0 : seq1s[0].size(), len2 = seq2s.empty() ? 0 : seq2s[0].size();
+    for (const auto &s : seq1s)
+        if (s.size() != len1) throw std::invalid_argument("NeedlemanWunsch_mi355x_batch: every seq1 must have the same length");
+    for (const auto &s : seq2s)
+        if (s.size() != len2) throw std::invalid_argument("NeedlemanWunsch_mi355x_batch: every seq2 must have the same length");
+    if (seq1s.empty()) return {};
+    size_t slice = 0;
+    if (swmi_global_full_slices_for(seq1s.size(), len1, len2, 1, &slice, 1) == 0)
+        detail::check(swmi_global_full(nullptr, len1, nullptr, len2, 1, score_matrix.data(), gap_penalty, free_ends, nullptr, nullptr,
+                                       nullptr, nullptr),
+                      "swmi_global_full");                  // (a length out of range: throws the library's error)
+    if (piece == 0 || piece > slice) piece = slice;
+    if (threads == 0) threads = std::thread::hardware_concurrency();
+    threads = threads < 1 ? 1 : threads > 64 ? 64 : threads;
+    const size_t mw = SWMI_GLOBAL_FULL_MOVE_WORDS(len1, len2);
+    auto align = [&](detail::PieceBuffers &p, size_t off, size_t m) {
+        p.seq1s.resize(m * (len1 + len2));
+        uint8_t *s2 = p.seq1s.data() + m * len1;
+        for (size_t k = 0; k < m; ++k) {
+            std::copy(seq1s[off + k].begin(), seq1s[off + k].end(), p.seq1s.begin() + k * len1);
+            std::copy(seq2s[off + k].begin(), seq2s[off + k].end(), s2 + k * len2);
+        }
+        p.scores.resize(m);
+        p.ends.resize(4 * m);
+        p.moves.resize(m * mw);
+        p.counts.resize(m);
+        detail::check(swmi_global_full(p.seq1s.data(), len1, s2, len2, m, score_matrix.data(), gap_penalty, free_ends, p.scores.data(),
+                                       p.ends.data(), p.moves.data(), p.counts.data()),
+                      "swmi_global_full");
+    };
+    return detail::run_in_pieces(seq1s.size(), piece, threads, align, [&](const detail::PieceBuffers &p, size_t k) {
+        return detail::Result{p.scores[k], expand_local_full_moves(p.moves.data() + k * mw, p.counts[k], p.ends[4 * k], p.ends[4 * k + 1])};
+    });
+}
+
 // Any-length affine local alignment of seq1s[k] against seq2s[k], every seq1 of one length and every seq2 of one length:
 // result[k] == SmithWaterman_long_affine_mi355x(seq1s[k], seq2s[k], score_matrix, gap_open, gap_extend).  The batch goes to the
 // GPU in pieces of `piece` alignments, at most one traceback slice of swmi_local_full_affine (0 = one slice: 256 at
@@ -702,6 +759,20 @@ inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_long_affin
     swmi::detail::check(swmi_local_full_affine(seq1.data(), seq1.size(), seq2.data(), seq2.size(), 1, score_matrix.data(), gap_open,
                                                gap_extend, &score, ends, moves.data(), &steps),
                         "swmi_local_full_affine");
+    return {score, swmi::expand_local_full_moves(moves.data(), steps, ends[0], ends[1])};
+}
+
+inline std::pair<int, std::vector<std::pair<int, int>>> NeedlemanWunsch_mi355x(const std::vector<uint8_t> &seq1,
+                                                                              const std::vector<uint8_t> &seq2,
+                                                                              const std::array<int8_t, 16> &score_matrix,
+                                                                              const int8_t gap_penalty, unsigned free_ends)
+{
+    int32_t score = 0, ends[4] = {0, 0, 0, 0};
+    uint32_t steps = 0;
+    std::vector<uint64_t> moves(SWMI_GLOBAL_FULL_MOVE_WORDS(seq1.size(), seq2.size()));
+    swmi::detail::check(swmi_global_full(seq1.data(), seq1.size(), seq2.data(), seq2.size(), 1, score_matrix.data(), gap_penalty,
+                                         free_ends, &score, ends, moves.data(), &steps),
+                        "swmi_global_full");
     return {score, swmi::expand_local_full_moves(moves.data(), steps, ends[0], ends[1])};
 }
 

@@ -184,3 +184,13 @@ hipError_t launch_local_full_affine_ragged(const uint8_t *d_seq1s, const uint8_t
                                            int32_t *d_ends, unsigned long long *d_codes, unsigned long long *d_moves,
                                            uint32_t *d_steps, hipStream_t stream);
 }  // namespace swmi
+
+namespace swmi {
+// Global and free-end-gap aligner for two sequences of any length (global_full_kernels.hip): launch_local_full's shapes,
+// workgroups, codes and d_ends, with free_ends a mask of SWMI_FREE_* (include/swmi.h; above 15: hipErrorInvalidValue).
+// d_moves NULL: the ends-only kernel (no codes, no walk; d_codes and d_steps unused).
+size_t global_full_code_words(int len1, int len2);
+hipError_t launch_global_full(const uint8_t *d_seq1s, const uint8_t *d_seq2s, int len1, int len2, size_t n, const int8_t *sm, int gap,
+                              unsigned free_ends, int32_t *d_scores, int32_t *d_ends, uint32_t *d_codes, unsigned long long *d_moves,
+                              uint32_t *d_steps, size_t move_words, hipStream_t stream);
+}  // namespace swmi

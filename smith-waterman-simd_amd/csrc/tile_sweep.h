@@ -1,5 +1,5 @@
-// tile_sweep.h -- what the four any-length aligners share (sgfull_kernels.hip, sgfull_affine_kernels.hip,
-// local_full_kernels.hip, local_full_affine_kernels.hip): the mapping and its constants, the helpers,
+// tile_sweep.h -- what the any-length aligners share (sgfull_kernels.hip, sgfull_affine_kernels.hip,
+// local_full_kernels.hip, local_full_affine_kernels.hip, global_full_kernels.hip): the mapping and its constants, the helpers,
 // the geometry and the launcher; the few helpers that the 16-lane local aligners take from here as well.  The sweep and the
 // walk of the two linear-gap kernels are tile_sweep_body.inc, those of the two affine kernels tile_sweep_affine_body.inc.
 //
@@ -48,6 +48,22 @@
 //     kWalkStops                    whether a code can stop the walk (else it goes on to (0, 0), forced on the border)
 // The borders take the NEGATED row or column so that the caller's sum folds into the negation as it did before the split.
 //
+// The END RULE (global_full_kernels.hip): a variant with a static member kFreeEnds = true -- the other
+// variants have no such member, and kEndRule<V> is then false -- asks the body for another best cell and another end of the
+// walk.  Its kernel has an argument `free_ends` (uniform, so in SGPRs; a kernel without one finds tile::free_ends = 0 below),
+// a mask of kFreeBegin1 / kFreeBegin2 (column 0 / row 0 hold 0: the variant's left_border / row0 and border follow them) and
+// kFreeEnd1 / kFreeEnd2 (the end cell may lie anywhere in column len2 / row len1).  Such a variant has kWalkStops = false,
+// kEnds = 4 and kRowMin below every key.  With it
+//     the sweep keeps no row maximum: the one lane that owns column len2 reads that column's key from the finished row (only
+//     with kFreeEnd1), so the loop has no max chain over the cells;
+//     after the sweep key[] holds row len1: each lane takes the largest key of its columns <= len2 (kFreeEnd2; the key's low
+//     bits name the first such column), the owner of column len2 the corner, thread 0 the border cells (0, len2) and
+//     (len1, 0) in closed form; columns past len2 are masked out, so no proof about them is needed;
+//     the reduction packs H + kEndBias above the row and column fields (end_pack), so that a negative H orders as it should:
+//     H descending, row ascending, column ascending, as for the other variants;
+//     the walk runs as staged while i > 0 and j > 0; on a border it ends if that border is free, else goes on to (0, 0) by
+//     forced moves; the count is the moves, ends[2..3] the cell where it ended.
+//
 // tile_sweep_affine_body.inc is the sweep and walk for an affine-gap variant, a type of static members only (the body reads
 // the kernel's gap_open and gap_extend itself).  The key array, E's array, the column loop and the E / F recurrences stay in
 // the body; the variant supplies
@@ -79,6 +95,8 @@
 // H and F arrays, two code dwords): from it both compile to the parent's instructions, one for one.
 #pragma once
 #include "swmi_internal.h"
+
+#include <type_traits>
 
 namespace swmi {
 
@@ -114,6 +132,25 @@ constexpr int kStageRows = 128;        // rows of a walk staging block
 
 constexpr bool RAGGED = false;         // what a kernel without a ragged form sees (above)
 constexpr TileWork slot{};
+
+// The end rule (above).  The flags are SWMI_FREE_* of include/swmi.h, which no kernel file includes.
+constexpr unsigned kFreeBegin1 = 1, kFreeBegin2 = 2, kFreeEnd1 = 4, kFreeEnd2 = 8;
+constexpr unsigned free_ends = 0;      // what a kernel without the argument sees
+constexpr int kEndBias = 1 << 22;      // |H| <= 128 * 32768 = 2^22, and the bound is never met: H + kEndBias > 0
+
+template <class V, class = void>
+constexpr bool kEndRule = false;
+template <class V>
+constexpr bool kEndRule<V, std::void_t<decltype(V::kFreeEnds)>> = V::kFreeEnds;
+
+// a candidate end cell for the reduction's maximum: H descending, row ascending, column ascending; above 0, which no cell packs to
+__device__ __forceinline__ unsigned long long end_pack(int h, int row, int col)
+{
+    return ((unsigned long long)(uint32_t)(h + kEndBias) << 34) | ((unsigned long long)(0x1FFFF - row) << 17) |
+           (unsigned long long)(0x1FFFF - col);
+}
+
+__device__ __forceinline__ unsigned long long umax64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
 
 __host__ __device__ inline int waves(int len2) { return (len2 + 64 * kCols - 1) / (64 * kCols); }
 

@@ -2,8 +2,8 @@
 // the mapping and what a variant V supplies).  Included INSIDE the kernel, after `using V = <variant>;` and
 // `const V::Gaps gaps{<gap argument>};`, where the kernel's parameters are named seq1s, seq2s, len1, len2, cols, scores,
 // ends, codes, moves, counts, move_words, n_trips and its template parameter TB.  A kernel with a ragged form also names
-// RAGGED and slot, and then len1, len2 and n_trips are the slot's (tile_sweep.h).  Text and not a function on purpose:
-// tile_sweep.h says why.
+// RAGGED and slot, and then len1, len2 and n_trips are the slot's (tile_sweep.h).  A kernel whose variant has the end rule
+// (kEndRule<V>, tile_sweep.h) also names free_ends.  Text and not a function on purpose: tile_sweep.h says why.
     __shared__ int ring[(kMaxWaves - 1) * kRing];
     __shared__ unsigned long long red[kMaxWaves];
     __shared__ int walk_at[V::kWalkStops ? 3 : 2];
@@ -40,7 +40,11 @@
     }
     V lane(gaps);
     int diag_in = lane.border(-jbase);                   // key(0, jbase)
-    int best = V::kZeroKey, best_row = 0;               // H = 0 at (0, 0)
+    int best = kEndRule<V> ? V::kRowMin : V::kZeroKey, best_row = 0;   // H = 0 at (0, 0); end rule: no last-column cell yet
+    // end rule: the lane that owns column len2 keeps the best cell of that column, if seq1's end is free
+    const int end_jj = (len2 - 1) & (kCols - 1);
+    const bool end_col_wave = kEndRule<V> && (free_ends & kFreeEnd1) && w == W - 1;
+    const bool end_col_lane = end_col_wave && G == (len2 - 1) >> 4;
 
     const int local_chunks = (len1 + 63 + kChunk - 1) / kChunk;
     const int total_chunks = local_chunks + kDelay * (W - 1);
@@ -82,9 +86,37 @@
                             uint32_t code;
                             const int nk = lane.template cell<TB>(jj, sc, d, lft, key[jj], code);
                             if constexpr (TB) cw[t] |= code;
-                            rk = rk > nk ? rk : nk;
+                            if constexpr (!kEndRule<V>) rk = rk > nk ? rk : nk;
                         }
-                        if (rk > (best | 63)) {
+                        if constexpr (kEndRule<V>) {
+                            // H(row, len2), read from the finished row: one register of one lane, no chain over the cells
+                            // (a uniform switch: an index into key[] would become sixteen selects, more than the chain it replaces)
+                            if (end_col_wave) {
+                                int end_key;
+                                switch (end_jj) {
+                                case 0: end_key = key[0]; break;
+                                case 1: end_key = key[1]; break;
+                                case 2: end_key = key[2]; break;
+                                case 3: end_key = key[3]; break;
+                                case 4: end_key = key[4]; break;
+                                case 5: end_key = key[5]; break;
+                                case 6: end_key = key[6]; break;
+                                case 7: end_key = key[7]; break;
+                                case 8: end_key = key[8]; break;
+                                case 9: end_key = key[9]; break;
+                                case 10: end_key = key[10]; break;
+                                case 11: end_key = key[11]; break;
+                                case 12: end_key = key[12]; break;
+                                case 13: end_key = key[13]; break;
+                                case 14: end_key = key[14]; break;
+                                default: end_key = key[15]; break;
+                                }
+                                if (end_col_lane && end_key > best) {
+                                    best = end_key;
+                                    best_row = row;
+                                }
+                            }
+                        } else if (rk > (best | 63)) {
                             best = rk;
                             best_row = row;
                         }
@@ -108,10 +140,33 @@
     }
 
     // best cell: (H desc, row asc, column asc) over the lanes, then over the waves
-    const int h = best >> 6;
-    const int col = h > 0 ? jbase + (kCols - 1 - (best & 15)) + 1 : 0;
-    unsigned long long r = ((unsigned long long)(uint32_t)h << 34) | ((unsigned long long)(0x1FFFF - best_row) << 17) |
-                           (unsigned long long)(0x1FFFF - col);
+    unsigned long long r;
+    if constexpr (kEndRule<V>) {
+        // the lane's candidates (tile_sweep.h): key[] holds row len1 now.  Last row, columns past len2 masked out; the
+        // corner; the last column's best; thread 0 adds the two border cells, which are closed forms
+        r = 0;
+        int last = V::kRowMin, corner = V::kRowMin;
+#pragma unroll
+        for (int jj = 0; jj < kCols; ++jj) {
+            const int j = jbase + jj + 1;
+            if (j <= len2 && key[jj] > last) last = key[jj];
+            if (j == len2) corner = key[jj];
+        }
+        if ((free_ends & kFreeEnd2) && jbase < len2) r = end_pack(last >> 6, len1, jbase + (kCols - 1 - (last & 15)) + 1);
+        if (G == (len2 - 1) >> 4) {
+            r = umax64(r, end_pack(corner >> 6, len1, len2));
+            if (end_col_lane) r = umax64(r, end_pack(best >> 6, best_row, len2));
+        }
+        if (tid == 0) {
+            if (free_ends & kFreeEnd1) r = umax64(r, end_pack(lane.border(-len2) >> 6, 0, len2));
+            if (free_ends & kFreeEnd2) r = umax64(r, end_pack(lane.left_border(-len1) >> 6, len1, 0));
+        }
+    } else {
+        const int h = best >> 6;
+        const int col = h > 0 ? jbase + (kCols - 1 - (best & 15)) + 1 : 0;
+        r = ((unsigned long long)(uint32_t)h << 34) | ((unsigned long long)(0x1FFFF - best_row) << 17) |
+            (unsigned long long)(0x1FFFF - col);
+    }
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
         const unsigned long long v = __shfl_xor(r, o, 64);
@@ -122,9 +177,9 @@
     __syncthreads();
     r = red[0];
     for (int x = 1; x < W; ++x) r = red[x] > r ? red[x] : r;
-    const int score = (int)(r >> 34);
-    const int end_i = score > 0 ? 0x1FFFF - (int)((r >> 17) & 0x1FFFF) : 0;
-    const int end_j = score > 0 ? 0x1FFFF - (int)(r & 0x1FFFF) : 0;
+    const int score = kEndRule<V> ? (int)(r >> 34) - kEndBias : (int)(r >> 34);
+    const int end_i = kEndRule<V> || score > 0 ? 0x1FFFF - (int)((r >> 17) & 0x1FFFF) : 0;
+    const int end_j = kEndRule<V> || score > 0 ? 0x1FFFF - (int)(r & 0x1FFFF) : 0;
     if (tid == 0) {
         scores[k] = score;
         ends[V::kEnds * k + 0] = end_i;
@@ -178,6 +233,25 @@
         if (tid == 0) {
             if constexpr (V::kWalkStops) {
                 // the walk ended on its start cell: the count is the moves
+                if (t & 31) mv[t >> 5] = acc;
+                counts[k] = t;
+                ends[V::kEnds * k + 2] = i;
+                ends[V::kEnds * k + 3] = j;
+            } else if constexpr (kEndRule<V>) {
+                // the walk reached a border: it ends there if that border is free, else it goes on to (0, 0) by forced
+                // moves (up along column 0, left along row 0); the count is the moves, the start cell where it ended
+                const uint32_t m = i > 0 ? 2u : 1u;
+                if (!(free_ends & (i > 0 ? kFreeBegin1 : kFreeBegin2))) {
+                    for (; i > 0 || j > 0; ++t) {
+                        acc |= (unsigned long long)m << (2 * (t & 31));
+                        i -= m == 2u;
+                        j -= m == 1u;
+                        if (((t + 1) & 31) == 0) {
+                            mv[t >> 5] = acc;
+                            acc = 0;
+                        }
+                    }
+                }
                 if (t & 31) mv[t >> 5] = acc;
                 counts[k] = t;
                 ends[V::kEnds * k + 2] = i;

@@ -169,6 +169,13 @@ def load():
     lib.swmi_local_full_ragged_move_offsets.argtypes = [vp, vp, sz, vp]
     lib.swmi_local_full_ragged_slices_for.argtypes = [vp, vp, sz, ci, ci, vp, sz]
     lib.swmi_local_full_ragged_slices_for.restype = sz
+    cu = ctypes.c_uint
+    lib.swmi_global_full.argtypes = [vp, sz, vp, sz, sz, vp, i8, cu, vp, vp, vp, vp]
+    lib.swmi_global_full_device.argtypes = [vp, sz, vp, sz, sz, vp, i8, cu, vp, vp, vp, vp, vp]
+    lib.swmi_global_full_slices_for.argtypes = [sz, sz, sz, ci, vp, sz]
+    lib.swmi_global_full_slices_for.restype = sz
+    lib.swmi_global_full_time_device.argtypes = [vp, sz, vp, sz, sz, vp, i8, cu, vp, vp, vp, vp, vp, ci,
+                                                 ctypes.POINTER(ctypes.c_float)]
     _lib = lib
     return lib
 
@@ -950,6 +957,86 @@ def local_full_expand_moves(moves_row, steps, end_i, end_j, cap=None):
 def local_full_release_workspaces():
     """Free the any-length local aligner's device buffers on the current GPU."""
     _check(load().swmi_local_full_release_workspaces())
+
+
+GLOBAL_FULL_MAX_LEN = 16384
+FREE_BEGIN1, FREE_BEGIN2, FREE_END1, FREE_END2 = 1, 2, 4, 8     # SWMI_FREE_*: which end gaps cost nothing
+ENDS_GLOBAL = 0                                                 # Needleman-Wunsch, end to end
+ENDS_FIT = FREE_BEGIN2 | FREE_END2                              # all of seq1 against a stretch of seq2
+ENDS_OVERLAP = FREE_BEGIN1 | FREE_BEGIN2 | FREE_END1 | FREE_END2
+
+
+def _free_ends(free_ends):
+    """The mask as the C side takes it (an unsigned int; a value outside 0 .. 15, a negative one included, is refused there)."""
+    return int(free_ends) & 0xFFFFFFFF
+
+
+def global_full_move_words(len1, len2):
+    """64-bit words of moves per alignment of swmi_global_full (SWMI_GLOBAL_FULL_MOVE_WORDS)."""
+    return (((int(len1) + int(len2) + 31) // 32) + 1) & ~1
+
+
+def global_full(seq1s, seq2s, score_matrix, gap_penalty, free_ends=ENDS_GLOBAL, traceback=True):
+    """Global (Needleman-Wunsch) and free-end-gap alignment of two sequences of any length in [1, 16384] with end cell, start
+    cell and traceback (swmi_global_full), one (len1, len2) per call, any int8 matrix and gap, no zero floor.  free_ends is a
+    mask: FREE_BEGIN1 / FREE_BEGIN2 make column 0 / row 0 hold 0, FREE_END1 / FREE_END2 let the end cell be the best of the
+    last column / last row (first in row-major order among equals); ENDS_GLOBAL, ENDS_FIT and ENDS_OVERLAP name the usual
+    ones.  seq1s: (n, len1) bases, seq2s: (n, len2).
+
+    Returns (scores[n] int32, which may be negative, ends[n, 4] int32 = (end_i, end_j, start_i, start_j),
+    moves[n, global_full_move_words(len1, len2)] uint64, steps[n] uint32); move t of alignment k =
+    (moves[k, t // 32] >> 2 * (t % 32)) & 3 in walking order from the end cell (3 diagonal, 2 up, 1 left), forced moves along
+    a border that is not free included; local_full_expand_moves(moves[k], steps[k], end_i, end_j) gives the positions from
+    the start cell to the end cell.  traceback=False: ends-only (moves and steps are None, the start cell is (-1, -1))."""
+    a = np.ascontiguousarray(seq1s, dtype=np.uint8)
+    b = np.ascontiguousarray(seq2s, dtype=np.uint8)
+    if a.ndim != 2 or b.ndim != 2:
+        raise ValueError("seq1s and seq2s must be (n, len1) and (n, len2)")
+    n, len1 = a.shape
+    len2 = b.shape[1]
+    if b.shape[0] != n:
+        raise ValueError("seq1s and seq2s hold different numbers of sequences")
+    sm, gap, mask = _sm(score_matrix), _gap(gap_penalty), _free_ends(free_ends)
+    scores = np.zeros(n, np.int32)
+    ends = np.zeros((n, 4), np.int32)
+    moves = np.zeros((n, global_full_move_words(len1, len2)), np.uint64) if traceback else None
+    steps = np.zeros(n, np.uint32) if traceback else None
+    _check(load().swmi_global_full(a.ctypes.data, len1, b.ctypes.data, len2, n, sm.ctypes.data, gap, mask, scores.ctypes.data,
+                                   ends.ctypes.data, moves.ctypes.data if traceback else None,
+                                   steps.ctypes.data if traceback else None))
+    return scores, ends, moves, steps
+
+
+def global_full_device(d_seq1s, len1, d_seq2s, len2, n, score_matrix, gap_penalty, free_ends, d_scores, d_ends, d_moves=None,
+                       d_steps=None, stream=0):
+    """swmi_global_full_device on device pointers (asynchronous on `stream`); d_moves = d_steps = None: ends-only."""
+    sm = _sm(score_matrix)
+    _check(load().swmi_global_full_device(d_seq1s, len1, d_seq2s, len2, n, sm.ctypes.data, _gap(gap_penalty), _free_ends(free_ends),
+                                          d_scores, d_ends, d_moves, d_steps, stream))
+
+
+def global_full_time_device(d_seq1s, len1, d_seq2s, len2, n, score_matrix, gap_penalty, free_ends, d_scores, d_ends, d_moves=None,
+                            d_steps=None, stream=0, iters=10):
+    """Average ms of one swmi_global_full_device call over `iters` back-to-back calls (HIP events on `stream`)."""
+    sm = _sm(score_matrix)
+    ms = ctypes.c_float()
+    _check(load().swmi_global_full_time_device(d_seq1s, len1, d_seq2s, len2, n, sm.ctypes.data, _gap(gap_penalty),
+                                               _free_ends(free_ends), d_scores, d_ends, d_moves, d_steps, stream, int(iters),
+                                               ctypes.byref(ms)))
+    return float(ms.value)
+
+
+def global_full_slices_for(n, len1, len2, traceback=True):
+    """The slices swmi_global_full cuts n alignments into (needs no device)."""
+    count = load().swmi_global_full_slices_for(n, len1, len2, 1 if traceback else 0, None, 0)
+    buf = (ctypes.c_size_t * max(count, 1))()
+    load().swmi_global_full_slices_for(n, len1, len2, 1 if traceback else 0, buf, count)
+    return [int(buf[k]) for k in range(count)]
+
+
+def global_full_release_workspaces():
+    """Free the global aligner's device buffers on the current GPU."""
+    _check(load().swmi_global_full_release_workspaces())
 
 
 def local_full_affine(seq1s, seq2s, score_matrix, gap_open, gap_extend, traceback=True):
