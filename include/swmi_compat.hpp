@@ -179,6 +179,98 @@ std::vector<Result> run_in_pieces(size_t n, size_t piece, unsigned threads, Alig
     return out;
 }
 
+// The host threads a batch overload expands paths on: 0 = as many as the machine reports, at most 64.
+inline unsigned expander_threads(unsigned threads)
+{
+    if (threads == 0) threads = std::thread::hardware_concurrency();
+    return threads < 1 ? 1 : threads > 64 ? 64 : threads;
+}
+
+using Sequences = std::vector<std::vector<uint8_t>>;
+
+// The length every sequence of a batch overload with one shape must have.
+inline size_t common_length(const Sequences &seqs) { return seqs.empty() ? 0 : seqs[0].size(); }
+
+// Throws std::invalid_argument unless every sequence has the length `len`; `which` is "seq1" or "seq2".
+inline void check_lengths(const char *name, const Sequences &seqs, size_t len, const char *which)
+{
+    for (const auto &s : seqs)
+        if (s.size() != len) throw std::invalid_argument(std::string(name) + ": every " + which + " must have the same length");
+}
+
+// The batch overloads of the (len1, 128) aligners (swmi_local_align and its affine twin), every seq1 of one length, named
+// `name`: in pieces of at most `piece` alignments, each expanded on the calling thread.  call(seq1s, len1, seq2s, m, scores,
+// ends, moves, steps) is the C entry `entry` with its parameters bound.
+template <class Call, class Expand>
+std::vector<Result> local_batch(const char *name, const char *entry, const Sequences &seq1s,
+                                const std::vector<std::array<uint8_t, 128>> &seq2s, size_t piece, Call call, Expand expand)
+{
+    if (seq1s.size() != seq2s.size()) throw std::invalid_argument(std::string(name) + ": seq1s and seq2s differ in length");
+    const size_t len1 = common_length(seq1s), mw = SWMI_LOCAL_MOVE_WORDS(len1);
+    check_lengths(name, seq1s, len1, "seq1");
+    auto align = [&](PieceBuffers &p, size_t off, size_t m) {
+        p.seq1s.resize(m * len1);
+        for (size_t k = 0; k < m; ++k) std::copy(seq1s[off + k].begin(), seq1s[off + k].end(), p.seq1s.begin() + k * len1);
+        p.scores.resize(m);
+        p.ends.resize(4 * m);
+        p.moves.resize(m * mw);
+        p.counts.resize(m);
+        check(call(p.seq1s.data(), len1, seq2s[off].data(), m, p.scores.data(), p.ends.data(), p.moves.data(), p.counts.data()),
+              entry);
+    };
+    return run_in_pieces(seq1s.size(), piece, 0, align, [&](const PieceBuffers &p, size_t k) {
+        return Result{p.scores[k], expand(p.moves.data() + k * mw, p.counts[k], p.ends.data() + 4 * k)};
+    });
+}
+
+// The batch overloads of the aligners with one (len1, len2) per call, every seq1 of one length and every seq2 of one length,
+// named `name`: in pieces of `piece` alignments, at most one traceback slice of the aligner (0 = one slice), both sides of a
+// piece staged in one buffer, piece p expanded on `threads` host threads (expander_threads) while piece p + 1 is aligned.
+// slices_for is the aligner's *_slices_for; call(seq1s, len1, seq2s, len2, m, scores, ends, moves, counts) is the C entry
+// `entry` with its parameters bound; its rows hold `move_words` words and `ends_width` ends.
+template <class SlicesFor, class Call, class Expand>
+std::vector<Result> shaped_batch(const char *name, const char *entry, const Sequences &seq1s, const Sequences &seq2s, size_t piece,
+                                 unsigned threads, size_t ends_width, size_t move_words, SlicesFor slices_for, Call call, Expand expand)
+{
+    if (seq1s.size() != seq2s.size()) throw std::invalid_argument(std::string(name) + ": seq1s and seq2s differ in length");
+    const size_t len1 = common_length(seq1s), len2 = common_length(seq2s);
+    check_lengths(name, seq1s, len1, "seq1");
+    check_lengths(name, seq2s, len2, "seq2");
+    if (seq1s.empty()) return {};
+    size_t slice = 0;
+    if (slices_for(seq1s.size(), len1, len2, 1, &slice, 1) == 0)               // (a length out of range: throws the library's error)
+        check(call(nullptr, len1, nullptr, len2, 1, nullptr, nullptr, nullptr, nullptr), entry);
+    if (piece == 0 || piece > slice) piece = slice;
+    auto align = [&](PieceBuffers &p, size_t off, size_t m) {
+        p.seq1s.resize(m * (len1 + len2));
+        uint8_t *s2 = p.seq1s.data() + m * len1;
+        for (size_t k = 0; k < m; ++k) {
+            std::copy(seq1s[off + k].begin(), seq1s[off + k].end(), p.seq1s.begin() + k * len1);
+            std::copy(seq2s[off + k].begin(), seq2s[off + k].end(), s2 + k * len2);
+        }
+        p.scores.resize(m);
+        p.ends.resize(ends_width * m);
+        p.moves.resize(m * move_words);
+        p.counts.resize(m);
+        check(call(p.seq1s.data(), len1, s2, len2, m, p.scores.data(), p.ends.data(), p.moves.data(), p.counts.data()), entry);
+    };
+    return run_in_pieces(seq1s.size(), piece, expander_threads(threads), align, [&](const PieceBuffers &p, size_t k) {
+        return Result{p.scores[k], expand(p.moves.data() + k * move_words, p.counts[k], p.ends.data() + k * ends_width)};
+    });
+}
+
+// One alignment through a C entry: call(score, ends, moves, count) is the entry `entry` with its sequences and parameters
+// bound (the semi-global entries fill two of the four ends, the X-drop entry none).
+template <class Call, class Expand>
+Result one_alignment(const char *entry, size_t move_words, Call call, Expand expand)
+{
+    int32_t score = 0, ends[4] = {0, 0, 0, 0};
+    uint32_t count = 0;
+    std::vector<uint64_t> moves(move_words);
+    check(call(&score, ends, moves.data(), &count), entry);
+    return {score, expand(moves.data(), count, ends)};
+}
+
 }  // namespace detail
 
 // One local alignment's moves (swmi_local_align) -> the reference's path vector (source.cpp:1571-1575).
@@ -191,6 +283,43 @@ inline std::vector<std::pair<int, int>> expand_local_moves(const uint64_t *moves
     return path;
 }
 
+// One alignment's moves (swmi_semiglobal_xdrop_moves) -> the reference's traceback vector (source.cpp:1962-1975).
+inline std::vector<std::pair<int, int>> expand_moves(const uint64_t *moves, uint32_t length)
+{
+    static_assert(sizeof(std::pair<int, int>) == 2 * sizeof(int32_t), "std::pair<int,int> must be two packed ints");
+    std::vector<std::pair<int, int>> tb(length);
+    detail::check(swmi_semiglobal_expand_moves(moves, length, reinterpret_cast<int32_t *>(tb.data()), length), "swmi_semiglobal_expand_moves");
+    return tb;
+}
+
+// One any-length local alignment's moves (swmi_local_full) -> the reference's path vector (source.cpp:1571-1575).
+inline std::vector<std::pair<int, int>> expand_local_full_moves(const uint64_t *moves, uint32_t steps, int32_t end_i, int32_t end_j)
+{
+    static_assert(sizeof(std::pair<int, int>) == 2 * sizeof(int32_t), "std::pair<int,int> must be two packed ints");
+    std::vector<std::pair<int, int>> path(size_t(steps) + 1);
+    detail::check(swmi_local_full_expand_moves(moves, steps, end_i, end_j, reinterpret_cast<int32_t *>(path.data()), path.size()),
+                  "swmi_local_full_expand_moves");
+    return path;
+}
+
+namespace detail {
+
+// The three expanders as detail::local_batch, shaped_batch and one_alignment call them: (moves row, count, the alignment's ends).
+inline std::vector<std::pair<int, int>> local_path(const uint64_t *moves, uint32_t steps, const int32_t *ends)
+{
+    return expand_local_moves(moves, steps, ends[0], ends[1]);
+}
+inline std::vector<std::pair<int, int>> semiglobal_path(const uint64_t *moves, uint32_t length, const int32_t *)
+{
+    return expand_moves(moves, length);
+}
+inline std::vector<std::pair<int, int>> local_full_path(const uint64_t *moves, uint32_t steps, const int32_t *ends)
+{
+    return expand_local_full_moves(moves, steps, ends[0], ends[1]);
+}
+
+}  // namespace detail
+
 // Local alignment of seq1s[k] (every one of the same length) against seq2s[k]: result[k] == SmithWaterman_local_mi355x(seq1s[k],
 // seq2s[k], score_matrix, gap_penalty).  The batch goes to the GPU in pieces of at most `piece` alignments, so only one piece's
 // inputs and moves are staged at a time (not n rows of moves up front); each piece's paths are built on the host.
@@ -198,24 +327,12 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SmithWaterm
     const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::array<uint8_t, 128>> &seq2s,
     const std::array<int8_t, 16> &score_matrix, const int8_t gap_penalty, size_t piece = 65536)
 {
-    if (seq1s.size() != seq2s.size()) throw std::invalid_argument("SmithWaterman_local_mi355x_batch: seq1s and seq2s differ in length");
-    const size_t len1 = seq1s.empty() ? 0 : seq1s[0].size(), mw = SWMI_LOCAL_MOVE_WORDS(len1);
-    for (const auto &s : seq1s)
-        if (s.size() != len1) throw std::invalid_argument("SmithWaterman_local_mi355x_batch: every seq1 must have the same length");
-    auto align = [&](detail::PieceBuffers &p, size_t off, size_t m) {
-        p.seq1s.resize(m * len1);
-        for (size_t k = 0; k < m; ++k) std::copy(seq1s[off + k].begin(), seq1s[off + k].end(), p.seq1s.begin() + k * len1);
-        p.scores.resize(m);
-        p.ends.resize(4 * m);
-        p.moves.resize(m * mw);
-        p.counts.resize(m);
-        detail::check(swmi_local_align(p.seq1s.data(), len1, seq2s[off].data(), m, score_matrix.data(), gap_penalty, p.scores.data(),
-                                       p.ends.data(), p.moves.data(), p.counts.data()),
-                      "swmi_local_align");
-    };
-    return detail::run_in_pieces(seq1s.size(), piece, 0, align, [&](const detail::PieceBuffers &p, size_t k) {
-        return detail::Result{p.scores[k], expand_local_moves(p.moves.data() + k * mw, p.counts[k], p.ends[4 * k], p.ends[4 * k + 1])};
-    });
+    return detail::local_batch(
+        "SmithWaterman_local_mi355x_batch", "swmi_local_align", seq1s, seq2s, piece,
+        [&](const uint8_t *a, size_t len1, const uint8_t *b, size_t m, auto... out) {
+            return swmi_local_align(a, len1, b, m, score_matrix.data(), gap_penalty, out...);
+        },
+        detail::local_path);
 }
 
 // Affine local alignment of seq1s[k] (every one of the same length) against seq2s[k]: result[k] ==
@@ -225,24 +342,12 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SmithWaterm
     const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::array<uint8_t, 128>> &seq2s,
     const std::array<int8_t, 16> &score_matrix, int gap_open, int gap_extend, size_t piece = 65536)
 {
-    if (seq1s.size() != seq2s.size()) throw std::invalid_argument("SmithWaterman_affine_mi355x_batch: seq1s and seq2s differ in length");
-    const size_t len1 = seq1s.empty() ? 0 : seq1s[0].size(), mw = SWMI_LOCAL_MOVE_WORDS(len1);
-    for (const auto &s : seq1s)
-        if (s.size() != len1) throw std::invalid_argument("SmithWaterman_affine_mi355x_batch: every seq1 must have the same length");
-    auto align = [&](detail::PieceBuffers &p, size_t off, size_t m) {
-        p.seq1s.resize(m * len1);
-        for (size_t k = 0; k < m; ++k) std::copy(seq1s[off + k].begin(), seq1s[off + k].end(), p.seq1s.begin() + k * len1);
-        p.scores.resize(m);
-        p.ends.resize(4 * m);
-        p.moves.resize(m * mw);
-        p.counts.resize(m);
-        detail::check(swmi_local_align_affine(p.seq1s.data(), len1, seq2s[off].data(), m, score_matrix.data(), gap_open, gap_extend,
-                                              p.scores.data(), p.ends.data(), p.moves.data(), p.counts.data()),
-                      "swmi_local_align_affine");
-    };
-    return detail::run_in_pieces(seq1s.size(), piece, 0, align, [&](const detail::PieceBuffers &p, size_t k) {
-        return detail::Result{p.scores[k], expand_local_moves(p.moves.data() + k * mw, p.counts[k], p.ends[4 * k], p.ends[4 * k + 1])};
-    });
+    return detail::local_batch(
+        "SmithWaterman_affine_mi355x_batch", "swmi_local_align_affine", seq1s, seq2s, piece,
+        [&](const uint8_t *a, size_t len1, const uint8_t *b, size_t m, auto... out) {
+            return swmi_local_align_affine(a, len1, b, m, score_matrix.data(), gap_open, gap_extend, out...);
+        },
+        detail::local_path);
 }
 
 // Ragged local alignments (swmi_local_align_ragged and its affine twin): seq1s[k] of any length in [0, 16384] against
@@ -310,15 +415,6 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SmithWaterm
     return SmithWaterman_local_mi355x_ragged_batch(seq1s, seq2s, semiglobal_111_matrix(), 1, piece);
 }
 
-// One alignment's moves (swmi_semiglobal_xdrop_moves) -> the reference's traceback vector (source.cpp:1962-1975).
-inline std::vector<std::pair<int, int>> expand_moves(const uint64_t *moves, uint32_t length)
-{
-    static_assert(sizeof(std::pair<int, int>) == 2 * sizeof(int32_t), "std::pair<int,int> must be two packed ints");
-    std::vector<std::pair<int, int>> tb(length);
-    detail::check(swmi_semiglobal_expand_moves(moves, length, reinterpret_cast<int32_t *>(tb.data()), length), "swmi_semiglobal_expand_moves");
-    return tb;
-}
-
 // The reference's SpeedtestSemiGlobal loop (source.cpp:2818-2856) over arrays of pairs: result[k] ==
 // SemiGlobal_AdaptiveBanded_XDrop_111_32_70(seq1s[k], seq2s[k]).  The GPU returns 2 bits per traceback step (8 KB per
 // alignment over PCIe instead of the 262 KB its positions take).  The batch goes to the GPU in pieces of `piece` alignments
@@ -332,8 +428,7 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SemiGlobal_
 {
     static_assert(sizeof(std::array<uint8_t, 16384>) == 16384, "std::array<uint8_t,16384> must be 16384 contiguous bytes");
     if (seq1s.size() != seq2s.size()) throw std::invalid_argument("SemiGlobal_mi355x_batch: seq1s and seq2s differ in length");
-    if (threads == 0) threads = std::thread::hardware_concurrency();
-    threads = threads < 1 ? 1 : threads > 64 ? 64 : threads;
+    threads = detail::expander_threads(threads);
     const size_t mw = SWMI_SG_MOVE_WORDS;
     auto align = [&](detail::PieceBuffers &p, size_t off, size_t m) {
         p.scores.resize(m);
@@ -358,8 +453,7 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SemiGlobal_
 {
     static_assert(sizeof(std::array<uint8_t, 16384>) == 16384, "std::array<uint8_t,16384> must be 16384 contiguous bytes");
     if (seq1s.size() != seq2s.size()) throw std::invalid_argument("SemiGlobal_111_mi355x_batch: seq1s and seq2s differ in length");
-    if (threads == 0) threads = std::thread::hardware_concurrency();
-    threads = threads < 1 ? 1 : threads > 64 ? 64 : threads;
+    threads = detail::expander_threads(threads);
     const size_t mw = SWMI_SGFULL_MOVE_WORDS(16384, 16384);
     auto align = [&](detail::PieceBuffers &p, size_t off, size_t m) {
         p.scores.resize(m);
@@ -384,50 +478,13 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SemiGlobal_
     const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::vector<uint8_t>> &seq2s,
     const std::array<int8_t, 16> &score_matrix, int gap_open, int gap_extend, unsigned threads = 0, size_t piece = 0)
 {
-    if (seq1s.size() != seq2s.size()) throw std::invalid_argument("SemiGlobal_affine_mi355x_batch: seq1s and seq2s differ in length");
-    const size_t len1 = seq1s.empty() ? 0 : seq1s[0].size(), len2 = seq2s.empty() ? 0 : seq2s[0].size();
-    for (const auto &s : seq1s)
-        if (s.size() != len1) throw std::invalid_argument("SemiGlobal_affine_mi355x_batch: every seq1 must have the same length");
-    for (const auto &s : seq2s)
-        if (s.size() != len2) throw std::invalid_argument("SemiGlobal_affine_mi355x_batch: every seq2 must have the same length");
-    if (seq1s.empty()) return {};
-    size_t slice = 0;
-    if (swmi_semiglobal_full_affine_slices_for(seq1s.size(), len1, len2, 1, &slice, 1) == 0)
-        detail::check(swmi_semiglobal_full_affine(nullptr, len1, nullptr, len2, 1, score_matrix.data(), gap_open, gap_extend, nullptr,
-                                                  nullptr, nullptr, nullptr),
-                      "swmi_semiglobal_full_affine");       // (a length out of range: throws the library's error)
-    if (piece == 0 || piece > slice) piece = slice;
-    if (threads == 0) threads = std::thread::hardware_concurrency();
-    threads = threads < 1 ? 1 : threads > 64 ? 64 : threads;
-    const size_t mw = SWMI_SGFULL_MOVE_WORDS(len1, len2);
-    auto align = [&](detail::PieceBuffers &p, size_t off, size_t m) {
-        p.seq1s.resize(m * (len1 + len2));
-        uint8_t *s2 = p.seq1s.data() + m * len1;
-        for (size_t k = 0; k < m; ++k) {
-            std::copy(seq1s[off + k].begin(), seq1s[off + k].end(), p.seq1s.begin() + k * len1);
-            std::copy(seq2s[off + k].begin(), seq2s[off + k].end(), s2 + k * len2);
-        }
-        p.scores.resize(m);
-        p.ends.resize(2 * m);
-        p.moves.resize(m * mw);
-        p.counts.resize(m);
-        detail::check(swmi_semiglobal_full_affine(p.seq1s.data(), len1, s2, len2, m, score_matrix.data(), gap_open, gap_extend,
-                                                  p.scores.data(), p.ends.data(), p.moves.data(), p.counts.data()),
-                      "swmi_semiglobal_full_affine");
-    };
-    return detail::run_in_pieces(seq1s.size(), piece, threads, align, [&](const detail::PieceBuffers &p, size_t k) {
-        return detail::Result{p.scores[k], expand_moves(p.moves.data() + k * mw, p.counts[k])};
-    });
-}
-
-// One any-length local alignment's moves (swmi_local_full) -> the reference's path vector (source.cpp:1571-1575).
-inline std::vector<std::pair<int, int>> expand_local_full_moves(const uint64_t *moves, uint32_t steps, int32_t end_i, int32_t end_j)
-{
-    static_assert(sizeof(std::pair<int, int>) == 2 * sizeof(int32_t), "std::pair<int,int> must be two packed ints");
-    std::vector<std::pair<int, int>> path(size_t(steps) + 1);
-    detail::check(swmi_local_full_expand_moves(moves, steps, end_i, end_j, reinterpret_cast<int32_t *>(path.data()), path.size()),
-                  "swmi_local_full_expand_moves");
-    return path;
+    return detail::shaped_batch(
+        "SemiGlobal_affine_mi355x_batch", "swmi_semiglobal_full_affine", seq1s, seq2s, piece, threads, 2,
+        SWMI_SGFULL_MOVE_WORDS(detail::common_length(seq1s), detail::common_length(seq2s)), swmi_semiglobal_full_affine_slices_for,
+        [&](const uint8_t *a, size_t len1, const uint8_t *b, size_t len2, size_t m, auto... out) {
+            return swmi_semiglobal_full_affine(a, len1, b, len2, m, score_matrix.data(), gap_open, gap_extend, out...);
+        },
+        detail::semiglobal_path);
 }
 
 // Any-length local alignment of seq1s[k] against seq2s[k], every seq1 of one length and every seq2 of one length:
@@ -439,40 +496,13 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SmithWaterm
     const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::vector<uint8_t>> &seq2s,
     const std::array<int8_t, 16> &score_matrix, const int8_t gap_penalty, size_t piece = 0, unsigned threads = 0)
 {
-    if (seq1s.size() != seq2s.size()) throw std::invalid_argument("SmithWaterman_long_mi355x_batch: seq1s and seq2s differ in length");
-    const size_t len1 = seq1s.empty() ? 0 : seq1s[0].size(), len2 = seq2s.empty() ? 0 : seq2s[0].size();
-    for (const auto &s : seq1s)
-        if (s.size() != len1) throw std::invalid_argument("SmithWaterman_long_mi355x_batch: every seq1 must have the same length");
-    for (const auto &s : seq2s)
-        if (s.size() != len2) throw std::invalid_argument("SmithWaterman_long_mi355x_batch: every seq2 must have the same length");
-    if (seq1s.empty()) return {};
-    size_t slice = 0;
-    if (swmi_local_full_slices_for(seq1s.size(), len1, len2, 1, &slice, 1) == 0)
-        detail::check(swmi_local_full(nullptr, len1, nullptr, len2, 1, score_matrix.data(), gap_penalty, nullptr, nullptr, nullptr,
-                                      nullptr),
-                      "swmi_local_full");                   // (a length out of range: throws the library's error)
-    if (piece == 0 || piece > slice) piece = slice;
-    if (threads == 0) threads = std::thread::hardware_concurrency();
-    threads = threads < 1 ? 1 : threads > 64 ? 64 : threads;
-    const size_t mw = SWMI_LOCAL_FULL_MOVE_WORDS(len1, len2);
-    auto align = [&](detail::PieceBuffers &p, size_t off, size_t m) {
-        p.seq1s.resize(m * (len1 + len2));
-        uint8_t *s2 = p.seq1s.data() + m * len1;
-        for (size_t k = 0; k < m; ++k) {
-            std::copy(seq1s[off + k].begin(), seq1s[off + k].end(), p.seq1s.begin() + k * len1);
-            std::copy(seq2s[off + k].begin(), seq2s[off + k].end(), s2 + k * len2);
-        }
-        p.scores.resize(m);
-        p.ends.resize(4 * m);
-        p.moves.resize(m * mw);
-        p.counts.resize(m);
-        detail::check(swmi_local_full(p.seq1s.data(), len1, s2, len2, m, score_matrix.data(), gap_penalty, p.scores.data(),
-                                      p.ends.data(), p.moves.data(), p.counts.data()),
-                      "swmi_local_full");
-    };
-    return detail::run_in_pieces(seq1s.size(), piece, threads, align, [&](const detail::PieceBuffers &p, size_t k) {
-        return detail::Result{p.scores[k], expand_local_full_moves(p.moves.data() + k * mw, p.counts[k], p.ends[4 * k], p.ends[4 * k + 1])};
-    });
+    return detail::shaped_batch(
+        "SmithWaterman_long_mi355x_batch", "swmi_local_full", seq1s, seq2s, piece, threads, 4,
+        SWMI_LOCAL_FULL_MOVE_WORDS(detail::common_length(seq1s), detail::common_length(seq2s)), swmi_local_full_slices_for,
+        [&](const uint8_t *a, size_t len1, const uint8_t *b, size_t len2, size_t m, auto... out) {
+            return swmi_local_full(a, len1, b, len2, m, score_matrix.data(), gap_penalty, out...);
+        },
+        detail::local_full_path);
 }
 
 // Global / free-end-gap alignment of seq1s[k] against seq2s[k], every seq1 of one length and every seq2 of one length:
@@ -485,40 +515,13 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> NeedlemanWu
     const std::array<int8_t, 16> &score_matrix, const int8_t gap_penalty, unsigned free_ends = SWMI_ENDS_GLOBAL, size_t piece = 0,
     unsigned threads = 0)
 {
-    if (seq1s.size() != seq2s.size()) throw std::invalid_argument("NeedlemanWunsch_mi355x_batch: seq1s and seq2s differ in length");
-    const size_t len1 = seq1s.empty() ? 0 : seq1s[0].size(), len2 = seq2s.empty() ? 0 : seq2s[0].size();
-    for (const auto &s : seq1s)
-        if (s.size() != len1) throw std::invalid_argument("NeedlemanWunsch_mi355x_batch: every seq1 must have the same length");
-    for (const auto &s : seq2s)
-        if (s.size() != len2) throw std::invalid_argument("NeedlemanWunsch_mi355x_batch: every seq2 must have the same length");
-    if (seq1s.empty()) return {};
-    size_t slice = 0;
-    if (swmi_global_full_slices_for(seq1s.size(), len1, len2, 1, &slice, 1) == 0)
-        detail::check(swmi_global_full(nullptr, len1, nullptr, len2, 1, score_matrix.data(), gap_penalty, free_ends, nullptr, nullptr,
-                                       nullptr, nullptr),
-                      "swmi_global_full");                  // (a length out of range: throws the library's error)
-    if (piece == 0 || piece > slice) piece = slice;
-    if (threads == 0) threads = std::thread::hardware_concurrency();
-    threads = threads < 1 ? 1 : threads > 64 ? 64 : threads;
-    const size_t mw = SWMI_GLOBAL_FULL_MOVE_WORDS(len1, len2);
-    auto align = [&](detail::PieceBuffers &p, size_t off, size_t m) {
-        p.seq1s.resize(m * (len1 + len2));
-        uint8_t *s2 = p.seq1s.data() + m * len1;
-        for (size_t k = 0; k < m; ++k) {
-            std::copy(seq1s[off + k].begin(), seq1s[off + k].end(), p.seq1s.begin() + k * len1);
-            std::copy(seq2s[off + k].begin(), seq2s[off + k].end(), s2 + k * len2);
-        }
-        p.scores.resize(m);
-        p.ends.resize(4 * m);
-        p.moves.resize(m * mw);
-        p.counts.resize(m);
-        detail::check(swmi_global_full(p.seq1s.data(), len1, s2, len2, m, score_matrix.data(), gap_penalty, free_ends, p.scores.data(),
-                                       p.ends.data(), p.moves.data(), p.counts.data()),
-                      "swmi_global_full");
-    };
-    return detail::run_in_pieces(seq1s.size(), piece, threads, align, [&](const detail::PieceBuffers &p, size_t k) {
-        return detail::Result{p.scores[k], expand_local_full_moves(p.moves.data() + k * mw, p.counts[k], p.ends[4 * k], p.ends[4 * k + 1])};
-    });
+    return detail::shaped_batch(
+        "NeedlemanWunsch_mi355x_batch", "swmi_global_full", seq1s, seq2s, piece, threads, 4,
+        SWMI_GLOBAL_FULL_MOVE_WORDS(detail::common_length(seq1s), detail::common_length(seq2s)), swmi_global_full_slices_for,
+        [&](const uint8_t *a, size_t len1, const uint8_t *b, size_t len2, size_t m, auto... out) {
+            return swmi_global_full(a, len1, b, len2, m, score_matrix.data(), gap_penalty, free_ends, out...);
+        },
+        detail::local_full_path);
 }
 
 // Any-length affine local alignment of seq1s[k] against seq2s[k], every seq1 of one length and every seq2 of one length:
@@ -530,41 +533,13 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SmithWaterm
     const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::vector<uint8_t>> &seq2s,
     const std::array<int8_t, 16> &score_matrix, int gap_open, int gap_extend, size_t piece = 0, unsigned threads = 0)
 {
-    if (seq1s.size() != seq2s.size())
-        throw std::invalid_argument("SmithWaterman_long_affine_mi355x_batch: seq1s and seq2s differ in length");
-    const size_t len1 = seq1s.empty() ? 0 : seq1s[0].size(), len2 = seq2s.empty() ? 0 : seq2s[0].size();
-    for (const auto &s : seq1s)
-        if (s.size() != len1) throw std::invalid_argument("SmithWaterman_long_affine_mi355x_batch: every seq1 must have the same length");
-    for (const auto &s : seq2s)
-        if (s.size() != len2) throw std::invalid_argument("SmithWaterman_long_affine_mi355x_batch: every seq2 must have the same length");
-    if (seq1s.empty()) return {};
-    size_t slice = 0;
-    if (swmi_local_full_affine_slices_for(seq1s.size(), len1, len2, 1, &slice, 1) == 0)
-        detail::check(swmi_local_full_affine(nullptr, len1, nullptr, len2, 1, score_matrix.data(), gap_open, gap_extend, nullptr,
-                                             nullptr, nullptr, nullptr),
-                      "swmi_local_full_affine");            // (a length out of range: throws the library's error)
-    if (piece == 0 || piece > slice) piece = slice;
-    if (threads == 0) threads = std::thread::hardware_concurrency();
-    threads = threads < 1 ? 1 : threads > 64 ? 64 : threads;
-    const size_t mw = SWMI_LOCAL_FULL_MOVE_WORDS(len1, len2);
-    auto align = [&](detail::PieceBuffers &p, size_t off, size_t m) {
-        p.seq1s.resize(m * (len1 + len2));
-        uint8_t *s2 = p.seq1s.data() + m * len1;
-        for (size_t k = 0; k < m; ++k) {
-            std::copy(seq1s[off + k].begin(), seq1s[off + k].end(), p.seq1s.begin() + k * len1);
-            std::copy(seq2s[off + k].begin(), seq2s[off + k].end(), s2 + k * len2);
-        }
-        p.scores.resize(m);
-        p.ends.resize(4 * m);
-        p.moves.resize(m * mw);
-        p.counts.resize(m);
-        detail::check(swmi_local_full_affine(p.seq1s.data(), len1, s2, len2, m, score_matrix.data(), gap_open, gap_extend,
-                                             p.scores.data(), p.ends.data(), p.moves.data(), p.counts.data()),
-                      "swmi_local_full_affine");
-    };
-    return detail::run_in_pieces(seq1s.size(), piece, threads, align, [&](const detail::PieceBuffers &p, size_t k) {
-        return detail::Result{p.scores[k], expand_local_full_moves(p.moves.data() + k * mw, p.counts[k], p.ends[4 * k], p.ends[4 * k + 1])};
-    });
+    return detail::shaped_batch(
+        "SmithWaterman_long_affine_mi355x_batch", "swmi_local_full_affine", seq1s, seq2s, piece, threads, 4,
+        SWMI_LOCAL_FULL_MOVE_WORDS(detail::common_length(seq1s), detail::common_length(seq2s)), swmi_local_full_affine_slices_for,
+        [&](const uint8_t *a, size_t len1, const uint8_t *b, size_t len2, size_t m, auto... out) {
+            return swmi_local_full_affine(a, len1, b, len2, m, score_matrix.data(), gap_open, gap_extend, out...);
+        },
+        detail::local_full_path);
 }
 
 // Any-length local alignments of mixed shapes (swmi_local_full_ragged and its affine twin): seq1s[k] and seq2s[k] each of any
@@ -579,8 +554,7 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> local_full_
 {
     if (seq1s.size() != seq2s.size()) throw std::invalid_argument(std::string(name) + ": seq1s and seq2s differ in length");
     if (piece == 0) piece = 4096;
-    if (threads == 0) threads = std::thread::hardware_concurrency();
-    threads = threads < 1 ? 1 : threads > 64 ? 64 : threads;
+    threads = detail::expander_threads(threads);
     auto stage = [](const std::vector<std::vector<uint8_t>> &seqs, size_t off, size_t m, std::vector<uint8_t> &bytes,
                     std::vector<uint64_t> &offsets) {
         bytes.clear();
@@ -693,11 +667,12 @@ private:
 inline std::pair<int, std::vector<std::pair<int, int>>> SemiGlobal_AdaptiveBanded_XDrop_mi355x(const std::array<uint8_t, 16384> &seq1,
                                                                                               const std::array<uint8_t, 16384> &seq2)
 {
-    int32_t score = 0;
-    uint32_t length = 0;
-    std::vector<uint64_t> moves(SWMI_SG_MOVE_WORDS);
-    swmi::detail::check(swmi_semiglobal_xdrop_moves(seq1.data(), seq2.data(), 1, &score, moves.data(), &length), "swmi_semiglobal_xdrop_moves");
-    return {score, swmi::expand_moves(moves.data(), length)};
+    return swmi::detail::one_alignment(
+        "swmi_semiglobal_xdrop_moves", SWMI_SG_MOVE_WORDS,
+        [&](int32_t *sc, int32_t *, uint64_t *mv, uint32_t *ln) {
+            return swmi_semiglobal_xdrop_moves(seq1.data(), seq2.data(), 1, sc, mv, ln);
+        },
+        swmi::detail::semiglobal_path);
 }
 
 inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_local_mi355x(const std::vector<uint8_t> &seq1,
@@ -705,13 +680,12 @@ inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_local_mi35
                                                                                   const std::array<int8_t, 16> &score_matrix,
                                                                                   const int8_t gap_penalty)
 {
-    int32_t score = 0, ends[4] = {0, 0, 0, 0};
-    uint32_t steps = 0;
-    std::vector<uint64_t> moves(SWMI_LOCAL_MOVE_WORDS(seq1.size()));
-    swmi::detail::check(swmi_local_align(seq1.data(), seq1.size(), seq2.data(), 1, score_matrix.data(), gap_penalty, &score, ends,
-                                         moves.data(), &steps),
-                        "swmi_local_align");
-    return {score, swmi::expand_local_moves(moves.data(), steps, ends[0], ends[1])};
+    return swmi::detail::one_alignment(
+        "swmi_local_align", SWMI_LOCAL_MOVE_WORDS(seq1.size()),
+        [&](auto... out) {
+            return swmi_local_align(seq1.data(), seq1.size(), seq2.data(), 1, score_matrix.data(), gap_penalty, out...);
+        },
+        swmi::detail::local_path);
 }
 
 inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_affine_mi355x(const std::vector<uint8_t> &seq1,
@@ -719,13 +693,12 @@ inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_affine_mi3
                                                                                    const std::array<int8_t, 16> &score_matrix,
                                                                                    int gap_open, int gap_extend)
 {
-    int32_t score = 0, ends[4] = {0, 0, 0, 0};
-    uint32_t steps = 0;
-    std::vector<uint64_t> moves(SWMI_LOCAL_MOVE_WORDS(seq1.size()));
-    swmi::detail::check(swmi_local_align_affine(seq1.data(), seq1.size(), seq2.data(), 1, score_matrix.data(), gap_open, gap_extend, &score,
-                                                ends, moves.data(), &steps),
-                        "swmi_local_align_affine");
-    return {score, swmi::expand_local_moves(moves.data(), steps, ends[0], ends[1])};
+    return swmi::detail::one_alignment(
+        "swmi_local_align_affine", SWMI_LOCAL_MOVE_WORDS(seq1.size()),
+        [&](auto... out) {
+            return swmi_local_align_affine(seq1.data(), seq1.size(), seq2.data(), 1, score_matrix.data(), gap_open, gap_extend, out...);
+        },
+        swmi::detail::local_path);
 }
 
 inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_111_long_mi355x(const std::vector<uint8_t> &seq1,
@@ -739,13 +712,12 @@ inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_long_mi355
                                                                                  const std::array<int8_t, 16> &score_matrix,
                                                                                  const int8_t gap_penalty)
 {
-    int32_t score = 0, ends[4] = {0, 0, 0, 0};
-    uint32_t steps = 0;
-    std::vector<uint64_t> moves(SWMI_LOCAL_FULL_MOVE_WORDS(seq1.size(), seq2.size()));
-    swmi::detail::check(swmi_local_full(seq1.data(), seq1.size(), seq2.data(), seq2.size(), 1, score_matrix.data(), gap_penalty, &score,
-                                        ends, moves.data(), &steps),
-                        "swmi_local_full");
-    return {score, swmi::expand_local_full_moves(moves.data(), steps, ends[0], ends[1])};
+    return swmi::detail::one_alignment(
+        "swmi_local_full", SWMI_LOCAL_FULL_MOVE_WORDS(seq1.size(), seq2.size()),
+        [&](auto... out) {
+            return swmi_local_full(seq1.data(), seq1.size(), seq2.data(), seq2.size(), 1, score_matrix.data(), gap_penalty, out...);
+        },
+        swmi::detail::local_full_path);
 }
 
 inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_long_affine_mi355x(const std::vector<uint8_t> &seq1,
@@ -753,13 +725,13 @@ inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_long_affin
                                                                                         const std::array<int8_t, 16> &score_matrix,
                                                                                         int gap_open, int gap_extend)
 {
-    int32_t score = 0, ends[4] = {0, 0, 0, 0};
-    uint32_t steps = 0;
-    std::vector<uint64_t> moves(SWMI_LOCAL_FULL_MOVE_WORDS(seq1.size(), seq2.size()));
-    swmi::detail::check(swmi_local_full_affine(seq1.data(), seq1.size(), seq2.data(), seq2.size(), 1, score_matrix.data(), gap_open,
-                                               gap_extend, &score, ends, moves.data(), &steps),
-                        "swmi_local_full_affine");
-    return {score, swmi::expand_local_full_moves(moves.data(), steps, ends[0], ends[1])};
+    return swmi::detail::one_alignment(
+        "swmi_local_full_affine", SWMI_LOCAL_FULL_MOVE_WORDS(seq1.size(), seq2.size()),
+        [&](auto... out) {
+            return swmi_local_full_affine(seq1.data(), seq1.size(), seq2.data(), seq2.size(), 1, score_matrix.data(), gap_open, gap_extend,
+                                          out...);
+        },
+        swmi::detail::local_full_path);
 }
 
 inline std::pair<int, std::vector<std::pair<int, int>>> NeedlemanWunsch_mi355x(const std::vector<uint8_t> &seq1,
@@ -767,25 +739,24 @@ inline std::pair<int, std::vector<std::pair<int, int>>> NeedlemanWunsch_mi355x(c
                                                                               const std::array<int8_t, 16> &score_matrix,
                                                                               const int8_t gap_penalty, unsigned free_ends)
 {
-    int32_t score = 0, ends[4] = {0, 0, 0, 0};
-    uint32_t steps = 0;
-    std::vector<uint64_t> moves(SWMI_GLOBAL_FULL_MOVE_WORDS(seq1.size(), seq2.size()));
-    swmi::detail::check(swmi_global_full(seq1.data(), seq1.size(), seq2.data(), seq2.size(), 1, score_matrix.data(), gap_penalty,
-                                         free_ends, &score, ends, moves.data(), &steps),
-                        "swmi_global_full");
-    return {score, swmi::expand_local_full_moves(moves.data(), steps, ends[0], ends[1])};
+    return swmi::detail::one_alignment(
+        "swmi_global_full", SWMI_GLOBAL_FULL_MOVE_WORDS(seq1.size(), seq2.size()),
+        [&](auto... out) {
+            return swmi_global_full(seq1.data(), seq1.size(), seq2.data(), seq2.size(), 1, score_matrix.data(), gap_penalty, free_ends,
+                                    out...);
+        },
+        swmi::detail::local_full_path);
 }
 
 inline std::pair<int, std::vector<std::pair<int, int>>> SemiGlobal_111_mi355x(const std::array<uint8_t, 16384> &seq1,
                                                                              const std::array<uint8_t, 16384> &seq2)
 {
-    int32_t score = 0, ends[2] = {0, 0};
-    uint32_t length = 0;
-    std::vector<uint64_t> moves(SWMI_SGFULL_MOVE_WORDS(16384, 16384));
-    swmi::detail::check(swmi_semiglobal_full(seq1.data(), 16384, seq2.data(), 16384, 1, swmi::semiglobal_111_matrix().data(), 1, &score, ends,
-                                             moves.data(), &length),
-                        "swmi_semiglobal_full");
-    return {score, swmi::expand_moves(moves.data(), length)};
+    return swmi::detail::one_alignment(
+        "swmi_semiglobal_full", SWMI_SGFULL_MOVE_WORDS(16384, 16384),
+        [&](auto... out) {
+            return swmi_semiglobal_full(seq1.data(), 16384, seq2.data(), 16384, 1, swmi::semiglobal_111_matrix().data(), 1, out...);
+        },
+        swmi::detail::semiglobal_path);
 }
 
 inline std::pair<int, std::vector<std::pair<int, int>>> SemiGlobal_affine_mi355x(const std::vector<uint8_t> &seq1,
@@ -793,11 +764,11 @@ inline std::pair<int, std::vector<std::pair<int, int>>> SemiGlobal_affine_mi355x
                                                                                 const std::array<int8_t, 16> &score_matrix,
                                                                                 int gap_open, int gap_extend)
 {
-    int32_t score = 0, ends[2] = {0, 0};
-    uint32_t length = 0;
-    std::vector<uint64_t> moves(SWMI_SGFULL_MOVE_WORDS(seq1.size(), seq2.size()));
-    swmi::detail::check(swmi_semiglobal_full_affine(seq1.data(), seq1.size(), seq2.data(), seq2.size(), 1, score_matrix.data(), gap_open,
-                                                    gap_extend, &score, ends, moves.data(), &length),
-                        "swmi_semiglobal_full_affine");
-    return {score, swmi::expand_moves(moves.data(), length)};
+    return swmi::detail::one_alignment(
+        "swmi_semiglobal_full_affine", SWMI_SGFULL_MOVE_WORDS(seq1.size(), seq2.size()),
+        [&](auto... out) {
+            return swmi_semiglobal_full_affine(seq1.data(), seq1.size(), seq2.data(), seq2.size(), 1, score_matrix.data(), gap_open,
+                                               gap_extend, out...);
+        },
+        swmi::detail::semiglobal_path);
 }

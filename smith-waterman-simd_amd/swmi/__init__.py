@@ -118,64 +118,40 @@ def load():
     lib.swmi_generate_pairs_host.argtypes = [vp, vp, sz, u64, u64]
     lib.swmi_time_batch_device.argtypes = [vp, vp, sz, vp, i8, vp, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
     lib.swmi_get_device_info.argtypes = [ctypes.POINTER(DeviceInfo)]
-    lib.swmi_local_align.argtypes = [vp, sz, vp, sz, vp, i8, vp, vp, vp, vp]
-    lib.swmi_local_align_device.argtypes = [vp, sz, vp, sz, vp, i8, vp, vp, vp, vp, vp]
-    lib.swmi_local_slices_for.argtypes = [sz, sz, ctypes.c_int, vp, sz]
-    lib.swmi_local_slices_for.restype = sz
+    # The table aligners, one row per family: (host entry, its timer, its *_slices_for, <shape>, <gap>).  Every entry takes
+    # <shape>, the matrix, <gap>, then scores, ends, moves and counts; <host entry>_device adds the stream, the timer the
+    # stream, iters and the result; *_slices_for takes the shape's sizes, traceback, a buffer and its capacity.
+    ci, cu, ms = ctypes.c_int, ctypes.c_uint, ctypes.POINTER(ctypes.c_float)
+    one_len, two_lens = [vp, sz, vp, sz], [vp, sz, vp, sz, sz]              # seq1s len1 seq2s n | seq1s len1 seq2s len2 n
+    ragged1, ragged2 = [vp, vp, vp, sz], [vp, vp, vp, vp, sz]               # seq1s offsets seq2s n | ... seq2s offsets n
+    for host, timer, slices, shape, gap in (
+            ("swmi_local_align", "swmi_local_time_device", "swmi_local_slices_for", one_len, [i8]),
+            ("swmi_local_align_affine", "swmi_local_affine_time_device", "swmi_local_affine_slices_for", one_len, [ci, ci]),
+            ("swmi_local_align_ragged", None, None, ragged1, [i8]),
+            ("swmi_local_align_affine_ragged", None, None, ragged1, [ci, ci]),
+            ("swmi_semiglobal_full", "swmi_semiglobal_full_time_device", "swmi_semiglobal_full_slices_for", two_lens, [i8]),
+            ("swmi_semiglobal_full_affine", "swmi_semiglobal_full_affine_time_device", "swmi_semiglobal_full_affine_slices_for",
+             two_lens, [ci, ci]),
+            ("swmi_local_full", "swmi_local_full_time_device", "swmi_local_full_slices_for", two_lens, [i8]),
+            ("swmi_local_full_affine", "swmi_local_full_affine_time_device", "swmi_local_full_affine_slices_for", two_lens, [ci, ci]),
+            ("swmi_local_full_ragged", None, None, ragged2, [i8]),
+            ("swmi_local_full_affine_ragged", None, None, ragged2, [ci, ci]),
+            ("swmi_global_full", "swmi_global_full_time_device", "swmi_global_full_slices_for", two_lens, [i8, cu])):
+        args = shape + [vp] + gap + [vp, vp, vp, vp]
+        getattr(lib, host).argtypes = args
+        getattr(lib, host + "_device").argtypes = args + [vp]
+        if timer:
+            getattr(lib, timer).argtypes = args + [vp, ci, ms]
+            getattr(lib, slices).argtypes = [sz] * shape.count(sz) + [ci, vp, sz]
+            getattr(lib, slices).restype = sz
     lib.swmi_local_expand_moves.argtypes = [vp, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32, vp, sz]
-    lib.swmi_local_time_device.argtypes = [vp, sz, vp, sz, vp, i8, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
-    ci = ctypes.c_int
-    lib.swmi_local_align_affine.argtypes = [vp, sz, vp, sz, vp, ci, ci, vp, vp, vp, vp]
-    lib.swmi_local_align_affine_device.argtypes = [vp, sz, vp, sz, vp, ci, ci, vp, vp, vp, vp, vp]
-    lib.swmi_local_affine_slices_for.argtypes = [sz, sz, ci, vp, sz]
-    lib.swmi_local_affine_slices_for.restype = sz
-    lib.swmi_local_affine_time_device.argtypes = [vp, sz, vp, sz, vp, ci, ci, vp, vp, vp, vp, vp, ci, ctypes.POINTER(ctypes.c_float)]
-    lib.swmi_local_align_ragged.argtypes = [vp, vp, vp, sz, vp, i8, vp, vp, vp, vp]
-    lib.swmi_local_align_affine_ragged.argtypes = [vp, vp, vp, sz, vp, ci, ci, vp, vp, vp, vp]
-    lib.swmi_local_align_ragged_device.argtypes = [vp, vp, vp, sz, vp, i8, vp, vp, vp, vp, vp]
-    lib.swmi_local_align_affine_ragged_device.argtypes = [vp, vp, vp, sz, vp, ci, ci, vp, vp, vp, vp, vp]
+    lib.swmi_local_full_expand_moves.argtypes = [vp, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32, vp, sz]
     lib.swmi_local_ragged_move_offsets.argtypes = [vp, sz, vp]
     lib.swmi_local_ragged_slices_for.argtypes = [vp, sz, ci, ci, vp, sz]
     lib.swmi_local_ragged_slices_for.restype = sz
-    lib.swmi_semiglobal_full.argtypes = [vp, sz, vp, sz, sz, vp, i8, vp, vp, vp, vp]
-    lib.swmi_semiglobal_full_device.argtypes = [vp, sz, vp, sz, sz, vp, i8, vp, vp, vp, vp, vp]
-    lib.swmi_semiglobal_full_slices_for.argtypes = [sz, sz, sz, ctypes.c_int, vp, sz]
-    lib.swmi_semiglobal_full_slices_for.restype = sz
-    lib.swmi_semiglobal_full_time_device.argtypes = [vp, sz, vp, sz, sz, vp, i8, vp, vp, vp, vp, vp, ctypes.c_int,
-                                                     ctypes.POINTER(ctypes.c_float)]
-    lib.swmi_semiglobal_full_affine.argtypes = [vp, sz, vp, sz, sz, vp, ci, ci, vp, vp, vp, vp]
-    lib.swmi_semiglobal_full_affine_device.argtypes = [vp, sz, vp, sz, sz, vp, ci, ci, vp, vp, vp, vp, vp]
-    lib.swmi_semiglobal_full_affine_slices_for.argtypes = [sz, sz, sz, ci, vp, sz]
-    lib.swmi_semiglobal_full_affine_slices_for.restype = sz
-    lib.swmi_semiglobal_full_affine_time_device.argtypes = [vp, sz, vp, sz, sz, vp, ci, ci, vp, vp, vp, vp, vp, ci,
-                                                            ctypes.POINTER(ctypes.c_float)]
-    lib.swmi_local_full.argtypes = [vp, sz, vp, sz, sz, vp, i8, vp, vp, vp, vp]
-    lib.swmi_local_full_device.argtypes = [vp, sz, vp, sz, sz, vp, i8, vp, vp, vp, vp, vp]
-    lib.swmi_local_full_slices_for.argtypes = [sz, sz, sz, ctypes.c_int, vp, sz]
-    lib.swmi_local_full_slices_for.restype = sz
-    lib.swmi_local_full_time_device.argtypes = [vp, sz, vp, sz, sz, vp, i8, vp, vp, vp, vp, vp, ctypes.c_int,
-                                                ctypes.POINTER(ctypes.c_float)]
-    lib.swmi_local_full_expand_moves.argtypes = [vp, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32, vp, sz]
-    lib.swmi_local_full_affine.argtypes = [vp, sz, vp, sz, sz, vp, ci, ci, vp, vp, vp, vp]
-    lib.swmi_local_full_affine_device.argtypes = [vp, sz, vp, sz, sz, vp, ci, ci, vp, vp, vp, vp, vp]
-    lib.swmi_local_full_affine_slices_for.argtypes = [sz, sz, sz, ci, vp, sz]
-    lib.swmi_local_full_affine_slices_for.restype = sz
-    lib.swmi_local_full_affine_time_device.argtypes = [vp, sz, vp, sz, sz, vp, ci, ci, vp, vp, vp, vp, vp, ci,
-                                                       ctypes.POINTER(ctypes.c_float)]
-    lib.swmi_local_full_ragged.argtypes = [vp, vp, vp, vp, sz, vp, i8, vp, vp, vp, vp]
-    lib.swmi_local_full_affine_ragged.argtypes = [vp, vp, vp, vp, sz, vp, ci, ci, vp, vp, vp, vp]
-    lib.swmi_local_full_ragged_device.argtypes = [vp, vp, vp, vp, sz, vp, i8, vp, vp, vp, vp, vp]
-    lib.swmi_local_full_affine_ragged_device.argtypes = [vp, vp, vp, vp, sz, vp, ci, ci, vp, vp, vp, vp, vp]
     lib.swmi_local_full_ragged_move_offsets.argtypes = [vp, vp, sz, vp]
     lib.swmi_local_full_ragged_slices_for.argtypes = [vp, vp, sz, ci, ci, vp, sz]
     lib.swmi_local_full_ragged_slices_for.restype = sz
-    cu = ctypes.c_uint
-    lib.swmi_global_full.argtypes = [vp, sz, vp, sz, sz, vp, i8, cu, vp, vp, vp, vp]
-    lib.swmi_global_full_device.argtypes = [vp, sz, vp, sz, sz, vp, i8, cu, vp, vp, vp, vp, vp]
-    lib.swmi_global_full_slices_for.argtypes = [sz, sz, sz, ci, vp, sz]
-    lib.swmi_global_full_slices_for.restype = sz
-    lib.swmi_global_full_time_device.argtypes = [vp, sz, vp, sz, sz, vp, i8, cu, vp, vp, vp, vp, vp, ci,
-                                                 ctypes.POINTER(ctypes.c_float)]
     _lib = lib
     return lib
 
@@ -211,6 +187,15 @@ def _gap(gap_penalty):
     return g
 
 
+def _affine_gap(name, value):
+    """ctypes converts to int without an overflow check (2**32 + 1 would align as gap 1): check the range here, so that the
+    C side's domain check sees what the caller meant."""
+    g = int(value)
+    if g < -2**31 or g > 2**31 - 1:
+        raise SwmiError(ERR_DOMAIN, "%s %d is outside the supported domain [0,127]" % (name, g))
+    return g
+
+
 def match_matrix(match, mismatch):
     """4x4 matrix with `match` on the diagonal and `mismatch` elsewhere (source.cpp:3041-3045)."""
     sm = np.full((4, 4), mismatch, np.int8)
@@ -219,6 +204,7 @@ def match_matrix(match, mismatch):
 
 
 def init(device=-1):
+    """Bind the process to one GPU (swmi_init): a HIP device ordinal, or -1 for the LOCAL_RANK environment variable if set, else 0."""
     _check(load().swmi_init(device))
 
 
@@ -234,6 +220,7 @@ def init_devices(devices):
 
 
 def num_gpus():
+    """The number of bound GPU contexts (0 before init)."""
     return int(load().swmi_num_gpus())
 
 
@@ -243,6 +230,7 @@ def use_gpu(index):
 
 
 def shutdown():
+    """Release every bound GPU context (swmi_shutdown)."""
     _check(load().swmi_shutdown())
 
 
@@ -254,14 +242,17 @@ def shard_bounds(n, shard, n_shards):
 
 
 def last_error():
+    """Text of the last error on the calling thread ("" if none)."""
     return load().swmi_last_error().decode()
 
 
 def set_schedule(lanes_per_alignment=0, flags=0):
+    """Lanes per alignment (0 = automatic) and the kernel flags NO_GAP_FOLD, USE_I16, USE_LUT, NO_PACKED (swmi_set_schedule)."""
     _check(load().swmi_set_schedule(lanes_per_alignment, flags))
 
 
 def get_schedule():
+    """(lanes per alignment, flags) as set_schedule left them."""
     lanes, flags = ctypes.c_int(), ctypes.c_uint()
     _check(load().swmi_get_schedule(ctypes.byref(lanes), ctypes.byref(flags)))
     return lanes.value, flags.value
@@ -307,6 +298,7 @@ def rccl_probe():
 
 
 def device_info():
+    """The current GPU's swmi_device_info as a dict."""
     info = DeviceInfo()
     _check(load().swmi_get_device_info(ctypes.byref(info)))
     return {"device": info.device, "compute_units": info.compute_units, "clock_khz": info.clock_khz,
@@ -331,6 +323,7 @@ def _scores_out(out, n):
 
 
 def score_batch(seq1s, seq2s, score_matrix, gap_penalty, out=None):
+    """scores[k] of n pairs of 128-mers, seq1s and seq2s both (n, 128), from host memory (swmi_score_batch)."""
     a, b, sm = _u8(seq1s, SEQ_LEN), _u8(seq2s, SEQ_LEN), _sm(score_matrix)
     if a.shape != b.shape:
         raise ValueError("seq1s and seq2s must have the same shape")
@@ -425,6 +418,7 @@ class ShardedBatch:
 
 
 def score_one_vs_many(seq1s, seq2, score_matrix, gap_penalty, out=None):
+    """scores[k] of seq1s[k] against the one seq2, all 128-mers, from host memory (swmi_score_one_vs_many)."""
     a, b, sm = _u8(seq1s, SEQ_LEN), _u8(seq2, SEQ_LEN), _sm(score_matrix)
     n = a.size // SEQ_LEN
     out = _scores_out(out, n)
@@ -433,6 +427,7 @@ def score_one_vs_many(seq1s, seq2, score_matrix, gap_penalty, out=None):
 
 
 def score_batch_packed(seq1s_packed, seq2s_packed, score_matrix, gap_penalty, out=None):
+    """score_batch on 2-bit packed 128-mers, 32 bytes each, as pack() writes them (swmi_score_batch_packed)."""
     a, b, sm = _u8(seq1s_packed, PACKED_LEN), _u8(seq2s_packed, PACKED_LEN), _sm(score_matrix)
     n = a.size // PACKED_LEN
     out = _scores_out(out, n)
@@ -465,6 +460,7 @@ def banded_affine_kernel_for(length, score_matrix, gap_open, gap_extend):
 
 
 def score_banded_affine_device(d_seq1s, d_seq2s, n, length, score_matrix, gap_open, gap_extend, d_scores, stream=0):
+    """swmi_score_banded_affine_device on device pointers (asynchronous on `stream`)."""
     sm = _sm(score_matrix)
     _check(load().swmi_score_banded_affine_device(d_seq1s, d_seq2s, n, length, sm.ctypes.data, int(gap_open),
                                                   int(gap_extend), d_scores, stream))
@@ -516,10 +512,12 @@ def semiglobal_expand_moves(moves_row, length, cap=None):
 
 
 def semiglobal_xdrop_moves_device(d_seq1s, d_seq2s, n, d_scores, d_moves, d_lengths, stream=0):
+    """swmi_semiglobal_xdrop_moves_device on device pointers (asynchronous on `stream`)."""
     _check(load().swmi_semiglobal_xdrop_moves_device(d_seq1s, d_seq2s, n, d_scores, d_moves, d_lengths, stream))
 
 
 def semiglobal_xdrop_device(d_seq1s, d_seq2s, n, d_scores, d_tracebacks, cap, d_lengths, stream=0):
+    """swmi_semiglobal_xdrop_device on device pointers (asynchronous on `stream`)."""
     _check(load().swmi_semiglobal_xdrop_device(d_seq1s, d_seq2s, n, d_scores, d_tracebacks, cap, d_lengths, stream))
 
 
@@ -559,9 +557,95 @@ LOCAL_SEQ2_LEN = 128
 LOCAL_MAX_LEN = 16384
 
 
+# The table aligners (local, exact semi-global, any-length local and global; linear and affine gaps; one shape or ragged) share
+# one argument order in include/swmi.h:
+#     entry(<shape>, matrix, <gap>, scores, ends, moves, counts[, stream[, iters, &ms]])
+# A public wrapper below names its C entry, builds <shape> and hands (matrix, <gap>) over as `params`; these helpers do the rest.
+
+def _linear(score_matrix, gap_penalty, *mask):
+    """`params` of a linear-gap aligner, checked: (matrix, gap) and, for the global aligner, the free-ends mask."""
+    return (_sm(score_matrix), _gap(gap_penalty)) + mask
+
+
+def _affine(score_matrix, gap_open, gap_extend):
+    """`params` of an affine aligner, checked: (matrix, gap_open, gap_extend)."""
+    return _sm(score_matrix), _affine_gap("gap_open", gap_open), _affine_gap("gap_extend", gap_extend)
+
+
+def _call(entry, shape, params, *tail):
+    """entry(*shape, matrix address, *gap, *tail), checked.  `params` carries the matrix itself, so that it outlives the call."""
+    return _check(entry(*shape, params[0].ctypes.data, *params[1:], *tail))
+
+
+def _ptr(array):
+    return None if array is None else array.ctypes.data
+
+
+def _table_align(entry, shape, params, n, ends_width, moves_shape, traceback):
+    """A host entry on fresh result arrays: (scores[n] int32, ends[n, ends_width] int32, moves[moves_shape] uint64, counts[n]
+    uint32 = steps or lengths); traceback=False: ends-only (moves and counts are None, in the call and in the result)."""
+    scores = np.zeros(n, np.int32)
+    ends = np.zeros((n, ends_width), np.int32)
+    moves = np.zeros(moves_shape, np.uint64) if traceback else None
+    counts = np.zeros(n, np.uint32) if traceback else None
+    _call(entry, shape, params, scores.ctypes.data, ends.ctypes.data, _ptr(moves), _ptr(counts))
+    return scores, ends, moves, counts
+
+
+def _table_time(entry, shape, params, *tail, iters):
+    """Average ms of a *_time_device entry; tail = (d_scores, d_ends, d_moves, d_counts, stream)."""
+    ms = ctypes.c_float()
+    _call(entry, shape, params, *tail, int(iters), ctypes.byref(ms))
+    return float(ms.value)
+
+
+def _slices(entry, *args):
+    """A *_slices_for entry's list: one call for the count, one to fill a buffer of that many."""
+    count = entry(*args, None, 0)
+    buf = (ctypes.c_size_t * max(count, 1))()
+    entry(*args, buf, count)
+    return [int(buf[k]) for k in range(count)]
+
+
+def _expand(entry, moves_row, steps, end_i, end_j, cap):
+    row = np.ascontiguousarray(moves_row, dtype=np.uint64)
+    count = int(steps) + 1 if cap is None else min(int(steps) + 1, int(cap))
+    pos = np.zeros((count, 2), np.int32)
+    _check(entry(row.ctypes.data, int(steps), int(end_i), int(end_j), pos.ctypes.data, count))
+    return pos
+
+
+def _move_words(len1, len2):
+    return (((int(len1) + int(len2) + 31) // 32) + 1) & ~1
+
+
+def _pair_batch_128(seq1s, seq2s):
+    """(a, b, n, len1) of a batch of one seq1 length against 128-mers."""
+    a = np.ascontiguousarray(seq1s, dtype=np.uint8)
+    if a.ndim != 2:
+        raise ValueError("seq1s must be (n, len1)")
+    b = _u8(seq2s, LOCAL_SEQ2_LEN).reshape(-1, LOCAL_SEQ2_LEN)
+    n, len1 = a.shape
+    if b.shape[0] != n:
+        raise ValueError("seq1s and seq2s hold different numbers of sequences")
+    return a, b, n, len1
+
+
+def _pair_batch(seq1s, seq2s):
+    """(a, b, n, len1, len2) of a batch of one (len1, len2)."""
+    a = np.ascontiguousarray(seq1s, dtype=np.uint8)
+    b = np.ascontiguousarray(seq2s, dtype=np.uint8)
+    if a.ndim != 2 or b.ndim != 2:
+        raise ValueError("seq1s and seq2s must be (n, len1) and (n, len2)")
+    n, len1 = a.shape
+    if b.shape[0] != n:
+        raise ValueError("seq1s and seq2s hold different numbers of sequences")
+    return a, b, n, len1, b.shape[1]
+
+
 def local_move_words(len1):
     """64-bit words of moves per alignment of swmi_local_align (SWMI_LOCAL_MOVE_WORDS)."""
-    return (((int(len1) + 128 + 31) // 32) + 1) & ~1
+    return _move_words(len1, LOCAL_SEQ2_LEN)
 
 
 def local_align(seq1s, seq2s, score_matrix, gap_penalty, traceback=True):
@@ -571,104 +655,60 @@ def local_align(seq1s, seq2s, score_matrix, gap_penalty, traceback=True):
     Returns (scores[n] int32, ends[n, 4] int32 = (end_i, end_j, start_i, start_j), moves[n, local_move_words(len1)] uint64,
     steps[n] uint32); move t of alignment k = (moves[k, t // 32] >> 2 * (t % 32)) & 3 in walking order from the end cell
     (3 diagonal, 2 up, 1 left).  traceback=False: ends-only (moves and steps are None, the start cell is (-1, -1))."""
-    a = np.ascontiguousarray(seq1s, dtype=np.uint8)
-    if a.ndim != 2:
-        raise ValueError("seq1s must be (n, len1)")
-    b = _u8(seq2s, LOCAL_SEQ2_LEN).reshape(-1, LOCAL_SEQ2_LEN)
-    n, len1 = a.shape
-    if b.shape[0] != n:
-        raise ValueError("seq1s and seq2s hold different numbers of sequences")
-    sm, gap = _sm(score_matrix), _gap(gap_penalty)
-    scores = np.zeros(n, np.int32)
-    ends = np.zeros((n, 4), np.int32)
-    moves = np.zeros((n, local_move_words(max(len1, 1))), np.uint64) if traceback else None
-    steps = np.zeros(n, np.uint32) if traceback else None
-    _check(load().swmi_local_align(a.ctypes.data, len1, b.ctypes.data, n, sm.ctypes.data, gap, scores.ctypes.data,
-                                   ends.ctypes.data, moves.ctypes.data if traceback else None,
-                                   steps.ctypes.data if traceback else None))
-    return scores, ends, moves, steps
+    a, b, n, len1 = _pair_batch_128(seq1s, seq2s)
+    return _table_align(load().swmi_local_align, (a.ctypes.data, len1, b.ctypes.data, n), _linear(score_matrix, gap_penalty), n, 4,
+                        (n, local_move_words(max(len1, 1))), traceback)
 
 
 def local_align_device(d_seq1s, len1, d_seq2s, n, score_matrix, gap_penalty, d_scores, d_ends, d_moves=None, d_steps=None,
                        stream=0):
     """swmi_local_align_device on device pointers (asynchronous on `stream`); d_moves = d_steps = None: ends-only."""
-    sm = _sm(score_matrix)
-    _check(load().swmi_local_align_device(d_seq1s, len1, d_seq2s, n, sm.ctypes.data, _gap(gap_penalty), d_scores, d_ends,
-                                          d_moves, d_steps, stream))
+    _call(load().swmi_local_align_device, (d_seq1s, len1, d_seq2s, n), _linear(score_matrix, gap_penalty), d_scores, d_ends,
+          d_moves, d_steps, stream)
 
 
 def local_time_device(d_seq1s, len1, d_seq2s, n, score_matrix, gap_penalty, d_scores, d_ends, d_moves=None, d_steps=None,
                       stream=0, iters=10):
     """Average ms of one swmi_local_align_device call over `iters` back-to-back calls (HIP events on `stream`)."""
-    sm = _sm(score_matrix)
-    ms = ctypes.c_float()
-    _check(load().swmi_local_time_device(d_seq1s, len1, d_seq2s, n, sm.ctypes.data, _gap(gap_penalty), d_scores, d_ends,
-                                         d_moves, d_steps, stream, int(iters), ctypes.byref(ms)))
-    return float(ms.value)
+    return _table_time(load().swmi_local_time_device, (d_seq1s, len1, d_seq2s, n), _linear(score_matrix, gap_penalty), d_scores,
+                       d_ends, d_moves, d_steps, stream, iters=iters)
 
 
 def local_expand_moves(moves_row, steps, end_i, end_j, cap=None):
     """One alignment's moves -> the reference's (steps + 1, 2) int32 list of (i, j) from the start cell to the end cell."""
-    row = np.ascontiguousarray(moves_row, dtype=np.uint64)
-    count = int(steps) + 1 if cap is None else min(int(steps) + 1, int(cap))
-    pos = np.zeros((count, 2), np.int32)
-    _check(load().swmi_local_expand_moves(row.ctypes.data, int(steps), int(end_i), int(end_j), pos.ctypes.data, count))
-    return pos
+    return _expand(load().swmi_local_expand_moves, moves_row, steps, end_i, end_j, cap)
 
 
 def local_slices_for(n, len1, traceback=True):
     """The slices swmi_local_align cuts n alignments into (needs no device)."""
-    count = load().swmi_local_slices_for(n, len1, 1 if traceback else 0, None, 0)
-    buf = (ctypes.c_size_t * max(count, 1))()
-    load().swmi_local_slices_for(n, len1, 1 if traceback else 0, buf, count)
-    return [int(buf[k]) for k in range(count)]
+    return _slices(load().swmi_local_slices_for, n, len1, 1 if traceback else 0)
 
 
 def local_align_affine(seq1s, seq2s, score_matrix, gap_open, gap_extend, traceback=True):
     """Local alignment with affine gaps, end cell, start cell and traceback (swmi_local_align_affine): a gap of length k costs
     gap_open + (k-1) gap_extend.  Same arguments and return value as local_align, with (gap_open, gap_extend) for the gap."""
-    a = np.ascontiguousarray(seq1s, dtype=np.uint8)
-    if a.ndim != 2:
-        raise ValueError("seq1s must be (n, len1)")
-    b = _u8(seq2s, LOCAL_SEQ2_LEN).reshape(-1, LOCAL_SEQ2_LEN)
-    n, len1 = a.shape
-    if b.shape[0] != n:
-        raise ValueError("seq1s and seq2s hold different numbers of sequences")
-    sm = _sm(score_matrix)
-    scores = np.zeros(n, np.int32)
-    ends = np.zeros((n, 4), np.int32)
-    moves = np.zeros((n, local_move_words(max(len1, 1))), np.uint64) if traceback else None
-    steps = np.zeros(n, np.uint32) if traceback else None
-    _check(load().swmi_local_align_affine(a.ctypes.data, len1, b.ctypes.data, n, sm.ctypes.data, int(gap_open), int(gap_extend),
-                                          scores.ctypes.data, ends.ctypes.data, moves.ctypes.data if traceback else None,
-                                          steps.ctypes.data if traceback else None))
-    return scores, ends, moves, steps
+    a, b, n, len1 = _pair_batch_128(seq1s, seq2s)
+    return _table_align(load().swmi_local_align_affine, (a.ctypes.data, len1, b.ctypes.data, n),
+                        _affine(score_matrix, gap_open, gap_extend), n, 4, (n, local_move_words(max(len1, 1))), traceback)
 
 
 def local_align_affine_device(d_seq1s, len1, d_seq2s, n, score_matrix, gap_open, gap_extend, d_scores, d_ends, d_moves=None,
                               d_steps=None, stream=0):
     """swmi_local_align_affine_device on device pointers (asynchronous on `stream`); d_moves = d_steps = None: ends-only."""
-    sm = _sm(score_matrix)
-    _check(load().swmi_local_align_affine_device(d_seq1s, len1, d_seq2s, n, sm.ctypes.data, int(gap_open), int(gap_extend), d_scores,
-                                                 d_ends, d_moves, d_steps, stream))
+    _call(load().swmi_local_align_affine_device, (d_seq1s, len1, d_seq2s, n), _affine(score_matrix, gap_open, gap_extend), d_scores,
+          d_ends, d_moves, d_steps, stream)
 
 
 def local_affine_time_device(d_seq1s, len1, d_seq2s, n, score_matrix, gap_open, gap_extend, d_scores, d_ends, d_moves=None,
                              d_steps=None, stream=0, iters=10):
     """Average ms of one swmi_local_align_affine_device call over `iters` back-to-back calls (HIP events on `stream`)."""
-    sm = _sm(score_matrix)
-    ms = ctypes.c_float()
-    _check(load().swmi_local_affine_time_device(d_seq1s, len1, d_seq2s, n, sm.ctypes.data, int(gap_open), int(gap_extend), d_scores,
-                                                d_ends, d_moves, d_steps, stream, int(iters), ctypes.byref(ms)))
-    return float(ms.value)
+    return _table_time(load().swmi_local_affine_time_device, (d_seq1s, len1, d_seq2s, n), _affine(score_matrix, gap_open, gap_extend),
+                       d_scores, d_ends, d_moves, d_steps, stream, iters=iters)
 
 
 def local_affine_slices_for(n, len1, traceback=True):
     """The slices swmi_local_align_affine cuts n alignments into (needs no device)."""
-    count = load().swmi_local_affine_slices_for(n, len1, 1 if traceback else 0, None, 0)
-    buf = (ctypes.c_size_t * max(count, 1))()
-    load().swmi_local_affine_slices_for(n, len1, 1 if traceback else 0, buf, count)
-    return [int(buf[k]) for k in range(count)]
+    return _slices(load().swmi_local_affine_slices_for, n, len1, 1 if traceback else 0)
 
 
 def _ragged_seq1s(seq1s):
@@ -701,11 +741,13 @@ def local_ragged_move_offsets(seq1_offsets):
 def local_ragged_slices_for(seq1_offsets, affine=False, traceback=True):
     """The slices a ragged call cuts its batch into (swmi_local_ragged_slices_for; needs no device)."""
     off = np.ascontiguousarray(seq1_offsets, dtype=np.uint64).reshape(-1)
-    lib = load()
-    count = lib.swmi_local_ragged_slices_for(off.ctypes.data, len(off) - 1, 1 if affine else 0, 1 if traceback else 0, None, 0)
-    buf = (ctypes.c_size_t * max(count, 1))()
-    lib.swmi_local_ragged_slices_for(off.ctypes.data, len(off) - 1, 1 if affine else 0, 1 if traceback else 0, buf, count)
-    return [int(buf[k]) for k in range(count)]
+    return _slices(load().swmi_local_ragged_slices_for, off.ctypes.data, len(off) - 1, 1 if affine else 0, 1 if traceback else 0)
+
+
+def _ragged_align(entry, shape, params, n, move_offsets, traceback):
+    """_table_align with the moves flat, alignment k's at move_offsets[k]: (scores, ends, moves, move_offsets, steps)."""
+    scores, ends, moves, steps = _table_align(entry, shape, params, n, 4, int(move_offsets[-1]) if traceback else 0, traceback)
+    return scores, ends, moves, move_offsets, steps
 
 
 def _ragged_call(entry, seq1s, seq2s, params, traceback):
@@ -715,15 +757,9 @@ def _ragged_call(entry, seq1s, seq2s, params, traceback):
     if b.shape[0] != n:
         raise ValueError("seq1s and seq2s hold different numbers of sequences")
     mo = local_ragged_move_offsets(off) if traceback else None
-    scores = np.zeros(n, np.int32)
-    ends = np.zeros((n, 4), np.int32)
-    moves = np.zeros(int(mo[-1]), np.uint64) if traceback else None
-    steps = np.zeros(n, np.uint32) if traceback else None
     if len(cat) == 0:
         cat = np.zeros(16, np.uint8)        # every seq1 is empty: a valid pointer the library never reads
-    _check(entry(cat.ctypes.data, off.ctypes.data, b.ctypes.data, n, *params, scores.ctypes.data, ends.ctypes.data,
-                 moves.ctypes.data if traceback else None, steps.ctypes.data if traceback else None))
-    return scores, ends, moves, mo, steps
+    return _ragged_align(entry, (cat.ctypes.data, off.ctypes.data, b.ctypes.data, n), params, n, mo, traceback)
 
 
 def local_align_ragged(seq1s, seq2s, score_matrix, gap_penalty, traceback=True):
@@ -732,33 +768,31 @@ def local_align_ragged(seq1s, seq2s, score_matrix, gap_penalty, traceback=True):
 
     Returns (scores[n] int32, ends[n, 4] int32, moves uint64 (flat: alignment k's at move_offsets[k] ..), move_offsets[n + 1],
     steps[n] uint32); traceback=False: moves, move_offsets and steps are None."""
-    sm = _sm(score_matrix)
-    return _ragged_call(load().swmi_local_align_ragged, seq1s, seq2s, (sm.ctypes.data, _gap(gap_penalty)), traceback)
+    return _ragged_call(load().swmi_local_align_ragged, seq1s, seq2s, _linear(score_matrix, gap_penalty), traceback)
 
 
 def local_align_affine_ragged(seq1s, seq2s, score_matrix, gap_open, gap_extend, traceback=True):
     """swmi_local_align_affine_ragged: local_align_affine on a ragged batch; arguments and result as local_align_ragged."""
-    sm = _sm(score_matrix)
-    return _ragged_call(load().swmi_local_align_affine_ragged, seq1s, seq2s, (sm.ctypes.data, int(gap_open), int(gap_extend)),
-                        traceback)
+    return _ragged_call(load().swmi_local_align_affine_ragged, seq1s, seq2s, _affine(score_matrix, gap_open, gap_extend), traceback)
+
+
+def _ragged_device(entry, d_seq1s, seq1_offsets, d_seq2s, params, *tail):
+    off = np.ascontiguousarray(seq1_offsets, dtype=np.uint64).reshape(-1)
+    _call(entry, (d_seq1s, off.ctypes.data, d_seq2s, len(off) - 1), params, *tail)
 
 
 def local_align_ragged_device(d_seq1s, seq1_offsets, d_seq2s, score_matrix, gap_penalty, d_scores, d_ends, d_moves=None,
                               d_steps=None, stream=0):
     """swmi_local_align_ragged_device: device pointers, seq1_offsets a host array of n + 1 (asynchronous on `stream`)."""
-    sm = _sm(score_matrix)
-    off = np.ascontiguousarray(seq1_offsets, dtype=np.uint64).reshape(-1)
-    _check(load().swmi_local_align_ragged_device(d_seq1s, off.ctypes.data, d_seq2s, len(off) - 1, sm.ctypes.data, _gap(gap_penalty),
-                                                 d_scores, d_ends, d_moves, d_steps, stream))
+    _ragged_device(load().swmi_local_align_ragged_device, d_seq1s, seq1_offsets, d_seq2s, _linear(score_matrix, gap_penalty),
+                   d_scores, d_ends, d_moves, d_steps, stream)
 
 
 def local_align_affine_ragged_device(d_seq1s, seq1_offsets, d_seq2s, score_matrix, gap_open, gap_extend, d_scores, d_ends,
                                      d_moves=None, d_steps=None, stream=0):
     """swmi_local_align_affine_ragged_device: as local_align_ragged_device with (gap_open, gap_extend)."""
-    sm = _sm(score_matrix)
-    off = np.ascontiguousarray(seq1_offsets, dtype=np.uint64).reshape(-1)
-    _check(load().swmi_local_align_affine_ragged_device(d_seq1s, off.ctypes.data, d_seq2s, len(off) - 1, sm.ctypes.data, int(gap_open),
-                                                        int(gap_extend), d_scores, d_ends, d_moves, d_steps, stream))
+    _ragged_device(load().swmi_local_align_affine_ragged_device, d_seq1s, seq1_offsets, d_seq2s,
+                   _affine(score_matrix, gap_open, gap_extend), d_scores, d_ends, d_moves, d_steps, stream)
 
 
 SGFULL_MAX_LEN = 16384
@@ -766,7 +800,7 @@ SGFULL_MAX_LEN = 16384
 
 def semiglobal_full_move_words(len1, len2):
     """64-bit words of moves per alignment of swmi_semiglobal_full (SWMI_SGFULL_MOVE_WORDS)."""
-    return (((int(len1) + int(len2) + 31) // 32) + 1) & ~1
+    return _move_words(len1, len2)
 
 
 def semiglobal_full(seq1s, seq2s, score_matrix, gap_penalty, traceback=True):
@@ -778,49 +812,28 @@ def semiglobal_full(seq1s, seq2s, score_matrix, gap_penalty, traceback=True):
     lengths[n] uint32); move t of alignment k = (moves[k, t // 32] >> 2 * (t % 32)) & 3 in walking order from the best
     cell to (0,0) (3 diagonal, 2 up, 1 left), lengths = steps + 1; semiglobal_expand_moves(moves[k], lengths[k]) gives the
     reference's list.  traceback=False: ends-only (moves and lengths are None)."""
-    a = np.ascontiguousarray(seq1s, dtype=np.uint8)
-    b = np.ascontiguousarray(seq2s, dtype=np.uint8)
-    if a.ndim != 2 or b.ndim != 2:
-        raise ValueError("seq1s and seq2s must be (n, len1) and (n, len2)")
-    n, len1 = a.shape
-    len2 = b.shape[1]
-    if b.shape[0] != n:
-        raise ValueError("seq1s and seq2s hold different numbers of sequences")
-    sm, gap = _sm(score_matrix), _gap(gap_penalty)
-    scores = np.zeros(n, np.int32)
-    ends = np.zeros((n, 2), np.int32)
-    moves = np.zeros((n, semiglobal_full_move_words(len1, len2)), np.uint64) if traceback else None
-    lengths = np.zeros(n, np.uint32) if traceback else None
-    _check(load().swmi_semiglobal_full(a.ctypes.data, len1, b.ctypes.data, len2, n, sm.ctypes.data, gap, scores.ctypes.data,
-                                       ends.ctypes.data, moves.ctypes.data if traceback else None,
-                                       lengths.ctypes.data if traceback else None))
-    return scores, ends, moves, lengths
+    a, b, n, len1, len2 = _pair_batch(seq1s, seq2s)
+    return _table_align(load().swmi_semiglobal_full, (a.ctypes.data, len1, b.ctypes.data, len2, n), _linear(score_matrix, gap_penalty),
+                        n, 2, (n, _move_words(len1, len2)), traceback)
 
 
 def semiglobal_full_device(d_seq1s, len1, d_seq2s, len2, n, score_matrix, gap_penalty, d_scores, d_ends, d_moves=None,
                            d_lengths=None, stream=0):
     """swmi_semiglobal_full_device on device pointers (asynchronous on `stream`); d_moves = d_lengths = None: ends-only."""
-    sm = _sm(score_matrix)
-    _check(load().swmi_semiglobal_full_device(d_seq1s, len1, d_seq2s, len2, n, sm.ctypes.data, _gap(gap_penalty), d_scores,
-                                              d_ends, d_moves, d_lengths, stream))
+    _call(load().swmi_semiglobal_full_device, (d_seq1s, len1, d_seq2s, len2, n), _linear(score_matrix, gap_penalty), d_scores,
+          d_ends, d_moves, d_lengths, stream)
 
 
 def semiglobal_full_time_device(d_seq1s, len1, d_seq2s, len2, n, score_matrix, gap_penalty, d_scores, d_ends, d_moves=None,
                                 d_lengths=None, stream=0, iters=10):
     """Average ms of one swmi_semiglobal_full_device call over `iters` back-to-back calls (HIP events on `stream`)."""
-    sm = _sm(score_matrix)
-    ms = ctypes.c_float()
-    _check(load().swmi_semiglobal_full_time_device(d_seq1s, len1, d_seq2s, len2, n, sm.ctypes.data, _gap(gap_penalty), d_scores,
-                                                   d_ends, d_moves, d_lengths, stream, int(iters), ctypes.byref(ms)))
-    return float(ms.value)
+    return _table_time(load().swmi_semiglobal_full_time_device, (d_seq1s, len1, d_seq2s, len2, n), _linear(score_matrix, gap_penalty),
+                       d_scores, d_ends, d_moves, d_lengths, stream, iters=iters)
 
 
 def semiglobal_full_slices_for(n, len1, len2, traceback=True):
     """The slices swmi_semiglobal_full cuts n alignments into (needs no device)."""
-    count = load().swmi_semiglobal_full_slices_for(n, len1, len2, 1 if traceback else 0, None, 0)
-    buf = (ctypes.c_size_t * max(count, 1))()
-    load().swmi_semiglobal_full_slices_for(n, len1, len2, 1 if traceback else 0, buf, count)
-    return [int(buf[k]) for k in range(count)]
+    return _slices(load().swmi_semiglobal_full_slices_for, n, len1, len2, 1 if traceback else 0)
 
 
 def semiglobal_full_release_workspaces():
@@ -832,50 +845,28 @@ def semiglobal_full_affine(seq1s, seq2s, score_matrix, gap_open, gap_extend, tra
     """Exact semi-global alignment with affine gaps and traceback (swmi_semiglobal_full_affine): semiglobal_full with a gap of
     length k costing gap_open + (k-1) gap_extend.  Same arguments and return value as semiglobal_full, with (gap_open,
     gap_extend) for the gap."""
-    a = np.ascontiguousarray(seq1s, dtype=np.uint8)
-    b = np.ascontiguousarray(seq2s, dtype=np.uint8)
-    if a.ndim != 2 or b.ndim != 2:
-        raise ValueError("seq1s and seq2s must be (n, len1) and (n, len2)")
-    n, len1 = a.shape
-    len2 = b.shape[1]
-    if b.shape[0] != n:
-        raise ValueError("seq1s and seq2s hold different numbers of sequences")
-    sm = _sm(score_matrix)
-    scores = np.zeros(n, np.int32)
-    ends = np.zeros((n, 2), np.int32)
-    moves = np.zeros((n, semiglobal_full_move_words(len1, len2)), np.uint64) if traceback else None
-    lengths = np.zeros(n, np.uint32) if traceback else None
-    _check(load().swmi_semiglobal_full_affine(a.ctypes.data, len1, b.ctypes.data, len2, n, sm.ctypes.data, int(gap_open),
-                                              int(gap_extend), scores.ctypes.data, ends.ctypes.data,
-                                              moves.ctypes.data if traceback else None, lengths.ctypes.data if traceback else None))
-    return scores, ends, moves, lengths
+    a, b, n, len1, len2 = _pair_batch(seq1s, seq2s)
+    return _table_align(load().swmi_semiglobal_full_affine, (a.ctypes.data, len1, b.ctypes.data, len2, n),
+                        _affine(score_matrix, gap_open, gap_extend), n, 2, (n, _move_words(len1, len2)), traceback)
 
 
 def semiglobal_full_affine_device(d_seq1s, len1, d_seq2s, len2, n, score_matrix, gap_open, gap_extend, d_scores, d_ends,
                                   d_moves=None, d_lengths=None, stream=0):
     """swmi_semiglobal_full_affine_device on device pointers (asynchronous on `stream`); d_moves = d_lengths = None: ends-only."""
-    sm = _sm(score_matrix)
-    _check(load().swmi_semiglobal_full_affine_device(d_seq1s, len1, d_seq2s, len2, n, sm.ctypes.data, int(gap_open), int(gap_extend),
-                                                     d_scores, d_ends, d_moves, d_lengths, stream))
+    _call(load().swmi_semiglobal_full_affine_device, (d_seq1s, len1, d_seq2s, len2, n), _affine(score_matrix, gap_open, gap_extend),
+          d_scores, d_ends, d_moves, d_lengths, stream)
 
 
 def semiglobal_full_affine_time_device(d_seq1s, len1, d_seq2s, len2, n, score_matrix, gap_open, gap_extend, d_scores, d_ends,
                                        d_moves=None, d_lengths=None, stream=0, iters=10):
     """Average ms of one swmi_semiglobal_full_affine_device call over `iters` back-to-back calls (HIP events on `stream`)."""
-    sm = _sm(score_matrix)
-    ms = ctypes.c_float()
-    _check(load().swmi_semiglobal_full_affine_time_device(d_seq1s, len1, d_seq2s, len2, n, sm.ctypes.data, int(gap_open),
-                                                          int(gap_extend), d_scores, d_ends, d_moves, d_lengths, stream, int(iters),
-                                                          ctypes.byref(ms)))
-    return float(ms.value)
+    return _table_time(load().swmi_semiglobal_full_affine_time_device, (d_seq1s, len1, d_seq2s, len2, n),
+                       _affine(score_matrix, gap_open, gap_extend), d_scores, d_ends, d_moves, d_lengths, stream, iters=iters)
 
 
 def semiglobal_full_affine_slices_for(n, len1, len2, traceback=True):
     """The slices swmi_semiglobal_full_affine cuts n alignments into (needs no device)."""
-    count = load().swmi_semiglobal_full_affine_slices_for(n, len1, len2, 1 if traceback else 0, None, 0)
-    buf = (ctypes.c_size_t * max(count, 1))()
-    load().swmi_semiglobal_full_affine_slices_for(n, len1, len2, 1 if traceback else 0, buf, count)
-    return [int(buf[k]) for k in range(count)]
+    return _slices(load().swmi_semiglobal_full_affine_slices_for, n, len1, len2, 1 if traceback else 0)
 
 
 def semiglobal_full_affine_release_workspaces():
@@ -888,7 +879,7 @@ LOCAL_FULL_MAX_LEN = 16384
 
 def local_full_move_words(len1, len2):
     """64-bit words of moves per alignment of swmi_local_full (SWMI_LOCAL_FULL_MOVE_WORDS)."""
-    return (((int(len1) + int(len2) + 31) // 32) + 1) & ~1
+    return _move_words(len1, len2)
 
 
 def local_full(seq1s, seq2s, score_matrix, gap_penalty, traceback=True):
@@ -900,58 +891,33 @@ def local_full(seq1s, seq2s, score_matrix, gap_penalty, traceback=True):
     uint64, steps[n] uint32); move t of alignment k = (moves[k, t // 32] >> 2 * (t % 32)) & 3 in walking order from the end
     cell (3 diagonal, 2 up, 1 left); local_full_expand_moves(moves[k], steps[k], end_i, end_j) gives the reference's list.
     traceback=False: ends-only (moves and steps are None, the start cell is (-1, -1))."""
-    a = np.ascontiguousarray(seq1s, dtype=np.uint8)
-    b = np.ascontiguousarray(seq2s, dtype=np.uint8)
-    if a.ndim != 2 or b.ndim != 2:
-        raise ValueError("seq1s and seq2s must be (n, len1) and (n, len2)")
-    n, len1 = a.shape
-    len2 = b.shape[1]
-    if b.shape[0] != n:
-        raise ValueError("seq1s and seq2s hold different numbers of sequences")
-    sm, gap = _sm(score_matrix), _gap(gap_penalty)
-    scores = np.zeros(n, np.int32)
-    ends = np.zeros((n, 4), np.int32)
-    moves = np.zeros((n, local_full_move_words(len1, len2)), np.uint64) if traceback else None
-    steps = np.zeros(n, np.uint32) if traceback else None
-    _check(load().swmi_local_full(a.ctypes.data, len1, b.ctypes.data, len2, n, sm.ctypes.data, gap, scores.ctypes.data,
-                                  ends.ctypes.data, moves.ctypes.data if traceback else None,
-                                  steps.ctypes.data if traceback else None))
-    return scores, ends, moves, steps
+    a, b, n, len1, len2 = _pair_batch(seq1s, seq2s)
+    return _table_align(load().swmi_local_full, (a.ctypes.data, len1, b.ctypes.data, len2, n), _linear(score_matrix, gap_penalty),
+                        n, 4, (n, _move_words(len1, len2)), traceback)
 
 
 def local_full_device(d_seq1s, len1, d_seq2s, len2, n, score_matrix, gap_penalty, d_scores, d_ends, d_moves=None, d_steps=None,
                       stream=0):
     """swmi_local_full_device on device pointers (asynchronous on `stream`); d_moves = d_steps = None: ends-only."""
-    sm = _sm(score_matrix)
-    _check(load().swmi_local_full_device(d_seq1s, len1, d_seq2s, len2, n, sm.ctypes.data, _gap(gap_penalty), d_scores, d_ends,
-                                         d_moves, d_steps, stream))
+    _call(load().swmi_local_full_device, (d_seq1s, len1, d_seq2s, len2, n), _linear(score_matrix, gap_penalty), d_scores, d_ends,
+          d_moves, d_steps, stream)
 
 
 def local_full_time_device(d_seq1s, len1, d_seq2s, len2, n, score_matrix, gap_penalty, d_scores, d_ends, d_moves=None,
                            d_steps=None, stream=0, iters=10):
     """Average ms of one swmi_local_full_device call over `iters` back-to-back calls (HIP events on `stream`)."""
-    sm = _sm(score_matrix)
-    ms = ctypes.c_float()
-    _check(load().swmi_local_full_time_device(d_seq1s, len1, d_seq2s, len2, n, sm.ctypes.data, _gap(gap_penalty), d_scores,
-                                              d_ends, d_moves, d_steps, stream, int(iters), ctypes.byref(ms)))
-    return float(ms.value)
+    return _table_time(load().swmi_local_full_time_device, (d_seq1s, len1, d_seq2s, len2, n), _linear(score_matrix, gap_penalty),
+                       d_scores, d_ends, d_moves, d_steps, stream, iters=iters)
 
 
 def local_full_slices_for(n, len1, len2, traceback=True):
     """The slices swmi_local_full cuts n alignments into (needs no device)."""
-    count = load().swmi_local_full_slices_for(n, len1, len2, 1 if traceback else 0, None, 0)
-    buf = (ctypes.c_size_t * max(count, 1))()
-    load().swmi_local_full_slices_for(n, len1, len2, 1 if traceback else 0, buf, count)
-    return [int(buf[k]) for k in range(count)]
+    return _slices(load().swmi_local_full_slices_for, n, len1, len2, 1 if traceback else 0)
 
 
 def local_full_expand_moves(moves_row, steps, end_i, end_j, cap=None):
     """One alignment's moves -> the reference's (steps + 1, 2) int32 list of (i, j) from the start cell to the end cell."""
-    row = np.ascontiguousarray(moves_row, dtype=np.uint64)
-    count = int(steps) + 1 if cap is None else min(int(steps) + 1, int(cap))
-    pos = np.zeros((count, 2), np.int32)
-    _check(load().swmi_local_full_expand_moves(row.ctypes.data, int(steps), int(end_i), int(end_j), pos.ctypes.data, count))
-    return pos
+    return _expand(load().swmi_local_full_expand_moves, moves_row, steps, end_i, end_j, cap)
 
 
 def local_full_release_workspaces():
@@ -973,7 +939,7 @@ def _free_ends(free_ends):
 
 def global_full_move_words(len1, len2):
     """64-bit words of moves per alignment of swmi_global_full (SWMI_GLOBAL_FULL_MOVE_WORDS)."""
-    return (((int(len1) + int(len2) + 31) // 32) + 1) & ~1
+    return _move_words(len1, len2)
 
 
 def global_full(seq1s, seq2s, score_matrix, gap_penalty, free_ends=ENDS_GLOBAL, traceback=True):
@@ -988,50 +954,28 @@ def global_full(seq1s, seq2s, score_matrix, gap_penalty, free_ends=ENDS_GLOBAL, 
     (moves[k, t // 32] >> 2 * (t % 32)) & 3 in walking order from the end cell (3 diagonal, 2 up, 1 left), forced moves along
     a border that is not free included; local_full_expand_moves(moves[k], steps[k], end_i, end_j) gives the positions from
     the start cell to the end cell.  traceback=False: ends-only (moves and steps are None, the start cell is (-1, -1))."""
-    a = np.ascontiguousarray(seq1s, dtype=np.uint8)
-    b = np.ascontiguousarray(seq2s, dtype=np.uint8)
-    if a.ndim != 2 or b.ndim != 2:
-        raise ValueError("seq1s and seq2s must be (n, len1) and (n, len2)")
-    n, len1 = a.shape
-    len2 = b.shape[1]
-    if b.shape[0] != n:
-        raise ValueError("seq1s and seq2s hold different numbers of sequences")
-    sm, gap, mask = _sm(score_matrix), _gap(gap_penalty), _free_ends(free_ends)
-    scores = np.zeros(n, np.int32)
-    ends = np.zeros((n, 4), np.int32)
-    moves = np.zeros((n, global_full_move_words(len1, len2)), np.uint64) if traceback else None
-    steps = np.zeros(n, np.uint32) if traceback else None
-    _check(load().swmi_global_full(a.ctypes.data, len1, b.ctypes.data, len2, n, sm.ctypes.data, gap, mask, scores.ctypes.data,
-                                   ends.ctypes.data, moves.ctypes.data if traceback else None,
-                                   steps.ctypes.data if traceback else None))
-    return scores, ends, moves, steps
+    a, b, n, len1, len2 = _pair_batch(seq1s, seq2s)
+    return _table_align(load().swmi_global_full, (a.ctypes.data, len1, b.ctypes.data, len2, n),
+                        _linear(score_matrix, gap_penalty, _free_ends(free_ends)), n, 4, (n, _move_words(len1, len2)), traceback)
 
 
 def global_full_device(d_seq1s, len1, d_seq2s, len2, n, score_matrix, gap_penalty, free_ends, d_scores, d_ends, d_moves=None,
                        d_steps=None, stream=0):
     """swmi_global_full_device on device pointers (asynchronous on `stream`); d_moves = d_steps = None: ends-only."""
-    sm = _sm(score_matrix)
-    _check(load().swmi_global_full_device(d_seq1s, len1, d_seq2s, len2, n, sm.ctypes.data, _gap(gap_penalty), _free_ends(free_ends),
-                                          d_scores, d_ends, d_moves, d_steps, stream))
+    _call(load().swmi_global_full_device, (d_seq1s, len1, d_seq2s, len2, n), _linear(score_matrix, gap_penalty, _free_ends(free_ends)),
+          d_scores, d_ends, d_moves, d_steps, stream)
 
 
 def global_full_time_device(d_seq1s, len1, d_seq2s, len2, n, score_matrix, gap_penalty, free_ends, d_scores, d_ends, d_moves=None,
                             d_steps=None, stream=0, iters=10):
     """Average ms of one swmi_global_full_device call over `iters` back-to-back calls (HIP events on `stream`)."""
-    sm = _sm(score_matrix)
-    ms = ctypes.c_float()
-    _check(load().swmi_global_full_time_device(d_seq1s, len1, d_seq2s, len2, n, sm.ctypes.data, _gap(gap_penalty),
-                                               _free_ends(free_ends), d_scores, d_ends, d_moves, d_steps, stream, int(iters),
-                                               ctypes.byref(ms)))
-    return float(ms.value)
+    return _table_time(load().swmi_global_full_time_device, (d_seq1s, len1, d_seq2s, len2, n),
+                       _linear(score_matrix, gap_penalty, _free_ends(free_ends)), d_scores, d_ends, d_moves, d_steps, stream, iters=iters)
 
 
 def global_full_slices_for(n, len1, len2, traceback=True):
     """The slices swmi_global_full cuts n alignments into (needs no device)."""
-    count = load().swmi_global_full_slices_for(n, len1, len2, 1 if traceback else 0, None, 0)
-    buf = (ctypes.c_size_t * max(count, 1))()
-    load().swmi_global_full_slices_for(n, len1, len2, 1 if traceback else 0, buf, count)
-    return [int(buf[k]) for k in range(count)]
+    return _slices(load().swmi_global_full_slices_for, n, len1, len2, 1 if traceback else 0)
 
 
 def global_full_release_workspaces():
@@ -1044,64 +988,33 @@ def local_full_affine(seq1s, seq2s, score_matrix, gap_open, gap_extend, tracebac
     (swmi_local_full_affine): local_full with a gap of length k costing gap_open + (k-1) gap_extend.  Same arguments and return
     value as local_full, with (gap_open, gap_extend) for the gap; local_full_move_words and local_full_expand_moves apply.
     For len2 == 128 local_align_affine gives the same results faster."""
-    a = np.ascontiguousarray(seq1s, dtype=np.uint8)
-    b = np.ascontiguousarray(seq2s, dtype=np.uint8)
-    if a.ndim != 2 or b.ndim != 2:
-        raise ValueError("seq1s and seq2s must be (n, len1) and (n, len2)")
-    n, len1 = a.shape
-    len2 = b.shape[1]
-    if b.shape[0] != n:
-        raise ValueError("seq1s and seq2s hold different numbers of sequences")
-    sm = _sm(score_matrix)
-    scores = np.zeros(n, np.int32)
-    ends = np.zeros((n, 4), np.int32)
-    moves = np.zeros((n, local_full_move_words(len1, len2)), np.uint64) if traceback else None
-    steps = np.zeros(n, np.uint32) if traceback else None
-    _check(load().swmi_local_full_affine(a.ctypes.data, len1, b.ctypes.data, len2, n, sm.ctypes.data, int(gap_open),
-                                         int(gap_extend), scores.ctypes.data, ends.ctypes.data,
-                                         moves.ctypes.data if traceback else None, steps.ctypes.data if traceback else None))
-    return scores, ends, moves, steps
+    a, b, n, len1, len2 = _pair_batch(seq1s, seq2s)
+    return _table_align(load().swmi_local_full_affine, (a.ctypes.data, len1, b.ctypes.data, len2, n),
+                        _affine(score_matrix, gap_open, gap_extend), n, 4, (n, _move_words(len1, len2)), traceback)
 
 
 def local_full_affine_device(d_seq1s, len1, d_seq2s, len2, n, score_matrix, gap_open, gap_extend, d_scores, d_ends,
                              d_moves=None, d_steps=None, stream=0):
     """swmi_local_full_affine_device on device pointers (asynchronous on `stream`); d_moves = d_steps = None: ends-only."""
-    sm = _sm(score_matrix)
-    _check(load().swmi_local_full_affine_device(d_seq1s, len1, d_seq2s, len2, n, sm.ctypes.data, int(gap_open), int(gap_extend),
-                                                d_scores, d_ends, d_moves, d_steps, stream))
+    _call(load().swmi_local_full_affine_device, (d_seq1s, len1, d_seq2s, len2, n), _affine(score_matrix, gap_open, gap_extend),
+          d_scores, d_ends, d_moves, d_steps, stream)
 
 
 def local_full_affine_time_device(d_seq1s, len1, d_seq2s, len2, n, score_matrix, gap_open, gap_extend, d_scores, d_ends,
                                   d_moves=None, d_steps=None, stream=0, iters=10):
     """Average ms of one swmi_local_full_affine_device call over `iters` back-to-back calls (HIP events on `stream`)."""
-    sm = _sm(score_matrix)
-    ms = ctypes.c_float()
-    _check(load().swmi_local_full_affine_time_device(d_seq1s, len1, d_seq2s, len2, n, sm.ctypes.data, int(gap_open),
-                                                     int(gap_extend), d_scores, d_ends, d_moves, d_steps, stream, int(iters),
-                                                     ctypes.byref(ms)))
-    return float(ms.value)
+    return _table_time(load().swmi_local_full_affine_time_device, (d_seq1s, len1, d_seq2s, len2, n),
+                       _affine(score_matrix, gap_open, gap_extend), d_scores, d_ends, d_moves, d_steps, stream, iters=iters)
 
 
 def local_full_affine_slices_for(n, len1, len2, traceback=True):
     """The slices swmi_local_full_affine cuts n alignments into (needs no device)."""
-    count = load().swmi_local_full_affine_slices_for(n, len1, len2, 1 if traceback else 0, None, 0)
-    buf = (ctypes.c_size_t * max(count, 1))()
-    load().swmi_local_full_affine_slices_for(n, len1, len2, 1 if traceback else 0, buf, count)
-    return [int(buf[k]) for k in range(count)]
+    return _slices(load().swmi_local_full_affine_slices_for, n, len1, len2, 1 if traceback else 0)
 
 
 def local_full_affine_release_workspaces():
     """Free the any-length affine local aligner's device buffers on the current GPU."""
     _check(load().swmi_local_full_affine_release_workspaces())
-
-
-def _affine_gap(name, value):
-    """ctypes converts to int without an overflow check (2**32 + 1 would align as gap 1): check the range here, so that the
-    C side's domain check sees what the caller meant."""
-    g = int(value)
-    if g < -2**31 or g > 2**31 - 1:
-        raise SwmiError(ERR_DOMAIN, "%s %d is outside the supported domain [0,127]" % (name, g))
-    return g
 
 
 def _ragged_pair(seq1s, seq2s):
@@ -1132,29 +1045,19 @@ def local_full_ragged_move_offsets(seq1_offsets, seq2_offsets):
 def local_full_ragged_slices_for(seq1_offsets, seq2_offsets, affine=False, traceback=True):
     """The slices a ragged any-length call cuts its batch into (swmi_local_full_ragged_slices_for; needs no device)."""
     off1, off2 = _offsets_pair(seq1_offsets, seq2_offsets)
-    lib = load()
-    args = (off1.ctypes.data, off2.ctypes.data, len(off1) - 1, 1 if affine else 0, 1 if traceback else 0)
-    count = lib.swmi_local_full_ragged_slices_for(*args, None, 0)
-    buf = (ctypes.c_size_t * max(count, 1))()
-    lib.swmi_local_full_ragged_slices_for(*args, buf, count)
-    return [int(buf[k]) for k in range(count)]
+    return _slices(load().swmi_local_full_ragged_slices_for, off1.ctypes.data, off2.ctypes.data, len(off1) - 1, 1 if affine else 0,
+                   1 if traceback else 0)
 
 
 def _full_ragged_call(entry, seq1s, seq2s, params, traceback):
     cat1, off1, cat2, off2 = _ragged_pair(seq1s, seq2s)
     n = len(off1) - 1
     mo = local_full_ragged_move_offsets(off1, off2) if traceback else None
-    scores = np.zeros(n, np.int32)
-    ends = np.zeros((n, 4), np.int32)
-    moves = np.zeros(int(mo[-1]), np.uint64) if traceback else None
-    steps = np.zeros(n, np.uint32) if traceback else None
     if len(cat1) == 0:
         cat1 = np.zeros(16, np.uint8)       # every seq1 is empty: a valid pointer the library never reads
     if len(cat2) == 0:
         cat2 = np.zeros(16, np.uint8)
-    _check(entry(cat1.ctypes.data, off1.ctypes.data, cat2.ctypes.data, off2.ctypes.data, n, *params, scores.ctypes.data,
-                 ends.ctypes.data, moves.ctypes.data if traceback else None, steps.ctypes.data if traceback else None))
-    return scores, ends, moves, mo, steps
+    return _ragged_align(entry, (cat1.ctypes.data, off1.ctypes.data, cat2.ctypes.data, off2.ctypes.data, n), params, n, mo, traceback)
 
 
 def local_full_ragged(seq1s, seq2s, score_matrix, gap_penalty, traceback=True):
@@ -1163,38 +1066,35 @@ def local_full_ragged(seq1s, seq2s, score_matrix, gap_penalty, traceback=True):
 
     Returns (scores[n] int32, ends[n, 4] int32, moves uint64 (flat: alignment k's at move_offsets[k] ..), move_offsets[n + 1],
     steps[n] uint32); traceback=False: moves, move_offsets and steps are None."""
-    sm = _sm(score_matrix)
-    return _full_ragged_call(load().swmi_local_full_ragged, seq1s, seq2s, (sm.ctypes.data, _gap(gap_penalty)), traceback)
+    return _full_ragged_call(load().swmi_local_full_ragged, seq1s, seq2s, _linear(score_matrix, gap_penalty), traceback)
 
 
 def local_full_affine_ragged(seq1s, seq2s, score_matrix, gap_open, gap_extend, traceback=True):
     """swmi_local_full_affine_ragged: local_full_affine on a ragged batch; arguments and result as local_full_ragged."""
-    sm = _sm(score_matrix)
-    return _full_ragged_call(load().swmi_local_full_affine_ragged, seq1s, seq2s,
-                             (sm.ctypes.data, _affine_gap("gap_open", gap_open), _affine_gap("gap_extend", gap_extend)), traceback)
+    return _full_ragged_call(load().swmi_local_full_affine_ragged, seq1s, seq2s, _affine(score_matrix, gap_open, gap_extend), traceback)
+
+
+def _full_ragged_device(entry, d_seq1s, seq1_offsets, d_seq2s, seq2_offsets, params, *tail):
+    off1, off2 = _offsets_pair(seq1_offsets, seq2_offsets)
+    _call(entry, (d_seq1s, off1.ctypes.data, d_seq2s, off2.ctypes.data, len(off1) - 1), params, *tail)
 
 
 def local_full_ragged_device(d_seq1s, seq1_offsets, d_seq2s, seq2_offsets, score_matrix, gap_penalty, d_scores, d_ends,
                              d_moves=None, d_steps=None, stream=0):
     """swmi_local_full_ragged_device: device pointers, both offset arrays host arrays of n + 1 (asynchronous on `stream`)."""
-    sm = _sm(score_matrix)
-    off1, off2 = _offsets_pair(seq1_offsets, seq2_offsets)
-    _check(load().swmi_local_full_ragged_device(d_seq1s, off1.ctypes.data, d_seq2s, off2.ctypes.data, len(off1) - 1, sm.ctypes.data,
-                                                _gap(gap_penalty), d_scores, d_ends, d_moves, d_steps, stream))
+    _full_ragged_device(load().swmi_local_full_ragged_device, d_seq1s, seq1_offsets, d_seq2s, seq2_offsets,
+                        _linear(score_matrix, gap_penalty), d_scores, d_ends, d_moves, d_steps, stream)
 
 
 def local_full_affine_ragged_device(d_seq1s, seq1_offsets, d_seq2s, seq2_offsets, score_matrix, gap_open, gap_extend, d_scores,
                                     d_ends, d_moves=None, d_steps=None, stream=0):
     """swmi_local_full_affine_ragged_device: as local_full_ragged_device with (gap_open, gap_extend)."""
-    sm = _sm(score_matrix)
-    off1, off2 = _offsets_pair(seq1_offsets, seq2_offsets)
-    _check(load().swmi_local_full_affine_ragged_device(d_seq1s, off1.ctypes.data, d_seq2s, off2.ctypes.data, len(off1) - 1,
-                                                       sm.ctypes.data, _affine_gap("gap_open", gap_open),
-                                                       _affine_gap("gap_extend", gap_extend), d_scores, d_ends, d_moves, d_steps,
-                                                       stream))
+    _full_ragged_device(load().swmi_local_full_affine_ragged_device, d_seq1s, seq1_offsets, d_seq2s, seq2_offsets,
+                        _affine(score_matrix, gap_open, gap_extend), d_scores, d_ends, d_moves, d_steps, stream)
 
 
 def unpack(packed):
+    """2-bit packed sequences (.., 32) -> bases (.., 128), on the GPU (swmi_unpack; source.cpp:1580-1583)."""
     p = _u8(packed, PACKED_LEN)
     n = p.size // PACKED_LEN
     out = np.zeros((n, SEQ_LEN), np.uint8)
@@ -1216,15 +1116,18 @@ def score_batch_device(d_seq1s, d_seq2s, n, score_matrix, gap_penalty, d_scores,
 
 
 def score_one_vs_many_device(d_seq1s, n, d_seq2, score_matrix, gap_penalty, d_scores, stream=0):
+    """swmi_score_one_vs_many_device on device pointers (asynchronous on `stream`)."""
     sm = _sm(score_matrix)
     _check(load().swmi_score_one_vs_many_device(d_seq1s, n, d_seq2, sm.ctypes.data, _gap(gap_penalty), d_scores, stream))
 
 
 def generate_pairs_device(d_seq1s, d_seq2s, n, seed, first_pair=0, stream=0):
+    """Fill device buffers with pairs first_pair .. first_pair + n of the counter-based generator (asynchronous on `stream`)."""
     _check(load().swmi_generate_pairs_device(d_seq1s, d_seq2s, n, seed, first_pair, stream))
 
 
 def generate_pairs_host(n, seed, first_pair=0):
+    """(seq1s, seq2s), each (n, 128): pairs first_pair .. first_pair + n of the counter-based generator, on the host."""
     a = np.zeros((n, SEQ_LEN), np.uint8)
     b = np.zeros((n, SEQ_LEN), np.uint8)
     _check(load().swmi_generate_pairs_host(a.ctypes.data, b.ctypes.data, n, seed, first_pair))
@@ -1232,6 +1135,7 @@ def generate_pairs_host(n, seed, first_pair=0):
 
 
 def time_batch_device(d_seq1s, d_seq2s, n, score_matrix, gap_penalty, d_scores, stream=0, iters=10):
+    """Average ms of one batch kernel launch over `iters` back-to-back launches (HIP events on `stream`)."""
     sm = _sm(score_matrix)
     ms = ctypes.c_float()
     _check(load().swmi_time_batch_device(d_seq1s, d_seq2s, n, sm.ctypes.data, _gap(gap_penalty), d_scores, stream, iters,

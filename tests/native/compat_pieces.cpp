@@ -4,14 +4,19 @@
 // from k.  One aligner call can be made to fail, and one alignment can be given a count its expander rejects.
 // Built and run by tests/test_compat_pieces.py (g++, ASan + UBSan).
 //
-//   compat_pieces <overload>     local | affine | ragged | affine_ragged | long_ragged | xdrop | sgfull
+//   compat_pieces <overload>     local | affine | ragged | affine_ragged | long_ragged | xdrop | sgfull |
+//                                long | long_affine | nw | sg_affine
 //
 // With several pieces and a short last one: every result; the pieces the aligner sees (order, sizes, the entry's arguments);
 // the moves buffers it is given (one for the overloads that expand on the calling thread, two in turn for the semi-global
 // ones, whose expanders overlap the next call); piece 0 counting as 1; a failing aligner call (std::runtime_error with the
 // stub's message, no call after it); a failing expansion in the first piece (std::runtime_error with the stub's message, no
 // piece after the one being aligned, on 3 threads for the semi-global overloads); unequal seq1s and seq2s, and for the ragged
-// overloads a seq1 the move layout rejects (std::invalid_argument).
+// overloads a seq1 the move layout rejects (std::invalid_argument).  The overloads with one (len1, len2) per batch (long,
+// long_affine, nw, sg_affine) expand on 3 threads too; their stub *_slices_for report slices of 4, so instead of piece 0
+// counting as 1, piece 0 and piece 9 both count as 4; nw's mask reaches every piece; sg_affine's ends are 2 wide, the others' 4;
+// a seq1 or seq2 of another length is std::invalid_argument, an empty batch makes no call, and a length the stub refuses
+// surfaces as std::runtime_error with its message before any piece is aligned.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -31,7 +36,9 @@
 using Results = std::vector<std::pair<int, std::vector<std::pair<int, int>>>>;
 
 constexpr uint32_t kRejected = 1000;           // a count the stub expanders reject
-constexpr size_t kLen1 = 40;                   // the fixed-length local overloads' seq1 length
+constexpr size_t kLen1 = 40;                   // the fixed-length overloads' seq1 length
+constexpr size_t kLen2 = 88;                   // the seq2 length of the overloads with one (len1, len2)
+constexpr size_t kSlice = 4;                   // the slice their stub *_slices_for report
 
 struct Call {                                  // one stub aligner call
     size_t first, n;                           // the index of the piece's first alignment, its alignments
@@ -39,6 +46,7 @@ struct Call {                                  // one stub aligner call
     size_t len1, len2;                         // (ragged: 0, 128)
     std::array<int8_t, 16> sm;
     int gap_open, gap_extend;                  // (a linear gap: the gap twice; X-drop: 0, 0)
+    unsigned free_ends;                        // (swmi_global_full only)
 };
 static std::vector<Call> g_calls;              // aligners run on the calling thread only
 static int g_fail_call = -1;                   // the aligner call that fails
@@ -146,6 +154,47 @@ static void semiglobal_results(const uint8_t *seq1s, const uint8_t *seq2s, size_
     }
 }
 
+static bool shaped_in_range(size_t len1, size_t len2) { return len1 >= 1 && len1 <= 16384 && len2 >= 4 && len2 <= 16384; }
+
+// The entries with one (len1, len2) per call; ends_width 2: the semi-global layout, 4: the local one.
+static int shaped_stub(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t len2, size_t n, const int8_t *sm, int gap_open,
+                       int gap_extend, unsigned free_ends, size_t ends_width, int32_t *scores, int32_t *ends, uint64_t *moves,
+                       uint32_t *counts)
+{
+    if (!shaped_in_range(len1, len2)) {
+        g_error = "stub: (" + std::to_string(len1) + ", " + std::to_string(len2) + ") is out of range";
+        return SWMI_ERR_INVALID_ARGUMENT;
+    }
+    Call c{index_of(seq2s), n, moves, len1, len2, {}, gap_open, gap_extend, free_ends};
+    memcpy(c.sm.data(), sm, 16);
+    if (!begin_call(c)) return SWMI_ERR_HIP;
+    const size_t mw = SWMI_LOCAL_FULL_MOVE_WORDS(len1, len2);
+    for (size_t r = 0; r < n; ++r) {
+        const size_t k = index_of(seq2s + len2 * r);
+        for (size_t i = 0; i < len1; ++i) CHECK(seq1s[len1 * r + i] == seq1_byte(k, i));
+        for (size_t i = 4; i < len2; ++i) CHECK(seq2s[len2 * r + i] == uint8_t(k));
+        if (ends_width == 4) {
+            local_results(r, k, scores, ends, counts);
+        } else {
+            scores[r] = score_of(k);
+            ends[2 * r] = end_of(k, 0);
+            ends[2 * r + 1] = end_of(k, 1);
+            counts[r] = count_of(k);
+        }
+        write_row(moves + mw * r, mw, k);
+    }
+    return SWMI_OK;
+}
+
+// Their *_slices_for as the overloads call it: the first slice only.
+static size_t shaped_slices(size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap)
+{
+    CHECK(traceback == 1 && sizes && cap == 1);
+    if (!shaped_in_range(len1, len2)) return 0;
+    sizes[0] = std::min(n, kSlice);
+    return (n + kSlice - 1) / kSlice;
+}
+
 extern "C" {
 
 int swmi_local_align(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t n, const int8_t score_matrix[16], int8_t gap_penalty,
@@ -221,6 +270,56 @@ int swmi_semiglobal_expand_moves(const uint64_t *moves, uint32_t length, int32_t
     return SWMI_OK;
 }
 
+int swmi_local_full(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t len2, size_t n, const int8_t score_matrix[16],
+                    int8_t gap_penalty, int32_t *scores, int32_t *ends, uint64_t *moves, uint32_t *steps)
+{
+    return shaped_stub(seq1s, len1, seq2s, len2, n, score_matrix, gap_penalty, gap_penalty, 0, 4, scores, ends, moves, steps);
+}
+
+int swmi_local_full_affine(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t len2, size_t n, const int8_t score_matrix[16],
+                           int gap_open, int gap_extend, int32_t *scores, int32_t *ends, uint64_t *moves, uint32_t *steps)
+{
+    return shaped_stub(seq1s, len1, seq2s, len2, n, score_matrix, gap_open, gap_extend, 0, 4, scores, ends, moves, steps);
+}
+
+int swmi_global_full(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t len2, size_t n, const int8_t score_matrix[16],
+                     int8_t gap_penalty, unsigned free_ends, int32_t *scores, int32_t *ends, uint64_t *moves, uint32_t *steps)
+{
+    return shaped_stub(seq1s, len1, seq2s, len2, n, score_matrix, gap_penalty, gap_penalty, free_ends, 4, scores, ends, moves, steps);
+}
+
+int swmi_semiglobal_full_affine(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t len2, size_t n,
+                                const int8_t score_matrix[16], int gap_open, int gap_extend, int32_t *scores, int32_t *ends,
+                                uint64_t *moves, uint32_t *lengths)
+{
+    return shaped_stub(seq1s, len1, seq2s, len2, n, score_matrix, gap_open, gap_extend, 0, 2, scores, ends, moves, lengths);
+}
+
+size_t swmi_local_full_slices_for(size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap)
+{
+    return shaped_slices(n, len1, len2, traceback, sizes, cap);
+}
+
+size_t swmi_local_full_affine_slices_for(size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap)
+{
+    return shaped_slices(n, len1, len2, traceback, sizes, cap);
+}
+
+size_t swmi_global_full_slices_for(size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap)
+{
+    return shaped_slices(n, len1, len2, traceback, sizes, cap);
+}
+
+size_t swmi_semiglobal_full_affine_slices_for(size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap)
+{
+    return shaped_slices(n, len1, len2, traceback, sizes, cap);
+}
+
+int swmi_local_full_expand_moves(const uint64_t *moves, uint32_t steps, int32_t end_i, int32_t end_j, int32_t *positions, size_t cap)
+{
+    return swmi_local_expand_moves(moves, steps, end_i, end_j, positions, cap);
+}
+
 const char *swmi_last_error(void) { return g_error.c_str(); }
 
 }  // extern "C"
@@ -231,6 +330,7 @@ struct Inputs {
     std::vector<std::vector<uint8_t>> seq1s;   // the local overloads
     std::vector<std::array<uint8_t, 128>> seq2s;
     std::vector<std::array<uint8_t, 16384>> sg1, sg2;   // the semi-global overloads
+    std::vector<std::vector<uint8_t>> long2s;  // the seq2s of the overloads with one (len1, len2); their seq1s are seq1s
 };
 
 struct Overload {
@@ -244,6 +344,8 @@ struct Overload {
     std::array<int8_t, 16> sm;
     int gap_open, gap_extend;
     Results (*run)(const Inputs &, size_t piece);
+    size_t slice = 0;                          // one (len1, len2) per batch: the slice that caps a piece (else 0)
+    unsigned free_ends = 0;
 };
 
 static const Overload kOverloads[] = {
@@ -265,15 +367,34 @@ static const Overload kOverloads[] = {
      0, 0, [](const Inputs &in, size_t piece) { return swmi::SemiGlobal_mi355x_batch(in.sg1, in.sg2, 3, piece); }},
     {"sgfull", "SemiGlobal_111_mi355x_batch", "swmi_semiglobal_full", "swmi_semiglobal_expand_moves", false, false, 3, 16384, 16384,
      swmi::semiglobal_111_matrix(), 1, 1, [](const Inputs &in, size_t piece) { return swmi::SemiGlobal_111_mi355x_batch(in.sg1, in.sg2, 3, piece); }},
+    {"long", "SmithWaterman_long_mi355x_batch", "swmi_local_full", "swmi_local_full_expand_moves", true, false, 3, kLen1, kLen2, kMatrix, 3,
+     3, [](const Inputs &in, size_t piece) { return swmi::SmithWaterman_long_mi355x_batch(in.seq1s, in.long2s, kMatrix, 3, piece, 3); },
+     kSlice},
+    {"long_affine", "SmithWaterman_long_affine_mi355x_batch", "swmi_local_full_affine", "swmi_local_full_expand_moves", true, false, 3,
+     kLen1, kLen2, kMatrix, 11, 2,
+     [](const Inputs &in, size_t piece) { return swmi::SmithWaterman_long_affine_mi355x_batch(in.seq1s, in.long2s, kMatrix, 11, 2, piece, 3); },
+     kSlice},
+    {"nw", "NeedlemanWunsch_mi355x_batch", "swmi_global_full", "swmi_local_full_expand_moves", true, false, 3, kLen1, kLen2, kMatrix, 3, 3,
+     [](const Inputs &in, size_t piece) { return swmi::NeedlemanWunsch_mi355x_batch(in.seq1s, in.long2s, kMatrix, 3, SWMI_ENDS_FIT, piece, 3); },
+     kSlice, SWMI_ENDS_FIT},
+    {"sg_affine", "SemiGlobal_affine_mi355x_batch", "swmi_semiglobal_full_affine", "swmi_semiglobal_expand_moves", false, false, 3, kLen1,
+     kLen2, kMatrix, 11, 2,
+     [](const Inputs &in, size_t piece) { return swmi::SemiGlobal_affine_mi355x_batch(in.seq1s, in.long2s, kMatrix, 11, 2, 3, piece); },
+     kSlice},
 };
 
 static Inputs inputs(const Overload &o, size_t n)
 {
     Inputs in;
     for (uint32_t k = 0; k < n; ++k) {
-        if (o.local) {
+        if (o.local || o.slice) {
             in.seq1s.emplace_back(o.ragged ? ragged_len(k) : kLen1);
             for (size_t i = 0; i < in.seq1s[k].size(); ++i) in.seq1s[k][i] = seq1_byte(k, i);
+        }
+        if (o.slice) {
+            in.long2s.emplace_back(kLen2, uint8_t(k));
+            memcpy(in.long2s[k].data(), &k, 4);
+        } else if (o.local) {
             in.seq2s.emplace_back();
             in.seq2s[k].fill(uint8_t(k));
             memcpy(in.seq2s[k].data(), &k, 4);
@@ -332,15 +453,25 @@ static void run(const Overload &o)
         const Call &call = g_calls[c];
         CHECK(call.first == 4 * c && call.n == (c < 2 ? 4u : 3u));
         CHECK(call.len1 == o.len1 && call.len2 == o.len2 && call.sm == o.sm && call.gap_open == o.gap_open && call.gap_extend == o.gap_extend);
+        CHECK(call.free_ends == o.free_ends);
         CHECK(o.threads == 0 || c == 0 || call.moves != g_calls[c - 1].moves);
         buffers.insert(call.moves);
     }
     CHECK(o.ragged || buffers.size() <= (o.threads ? 2u : 1u));
     printf("%s pieces: ok\n", o.name);
 
-    reset();
-    CHECK(o.run(inputs(o, 3), 0) == expected(o, 3));
-    CHECK(g_calls.size() == 3 && g_calls[0].n == 1 && g_calls[1].n == 1 && g_calls[2].n == 1);
+    if (o.slice) {                             // piece 0 and a piece above the slice both count as one slice
+        for (size_t piece : {size_t(0), size_t(9)}) {
+            reset();
+            CHECK(o.run(inputs(o, 11), piece) == expected(o, 11));
+            CHECK(g_calls.size() == 3 && g_calls[0].n == o.slice && g_calls[1].n == o.slice && g_calls[2].n == 11 - 2 * o.slice);
+            CHECK(g_calls[0].free_ends == o.free_ends && g_calls[2].free_ends == o.free_ends);
+        }
+    } else {
+        reset();
+        CHECK(o.run(inputs(o, 3), 0) == expected(o, 3));
+        CHECK(g_calls.size() == 3 && g_calls[0].n == 1 && g_calls[1].n == 1 && g_calls[2].n == 1);
+    }
     printf("%s piece 0: ok\n", o.name);
 
     reset();
@@ -358,7 +489,9 @@ static void run(const Overload &o)
 
     reset();
     Inputs in = inputs(o, 5);
-    if (o.local)
+    if (o.slice)
+        in.long2s.pop_back();
+    else if (o.local)
         in.seq2s.pop_back();
     else
         in.sg2.pop_back();
@@ -369,6 +502,19 @@ static void run(const Overload &o)
         in.seq1s[5].resize(SWMI_LOCAL_MAX_LEN + 1);
         expect_throw<std::invalid_argument>([&] { o.run(in, 4); }, std::string(o.batch) + ": stub: seq1 1 of the piece is out of range");
         CHECK(g_calls.size() == 1);
+    }
+    if (o.slice) {
+        in = inputs(o, 5);
+        in.seq1s[2].push_back(0);
+        expect_throw<std::invalid_argument>([&] { o.run(in, 4); }, std::string(o.batch) + ": every seq1 must have the same length");
+        in = inputs(o, 5);
+        in.long2s[4].pop_back();
+        expect_throw<std::invalid_argument>([&] { o.run(in, 4); }, std::string(o.batch) + ": every seq2 must have the same length");
+        CHECK(o.run(Inputs(), 4).empty());
+        in = inputs(o, 5);
+        for (auto &seq1 : in.seq1s) seq1.resize(16385);
+        expect_throw<std::runtime_error>([&] { o.run(in, 4); }, std::string(o.entry) + ": stub: (16385, 88) is out of range");
+        CHECK(g_calls.empty());
     }
     printf("%s argument errors: ok\n", o.name);
 }

@@ -38,6 +38,34 @@ def test_library_exports_every_declared_symbol():
     assert lib.swmi_version() == 300
 
 
+def _prototypes():
+    """(return type, name, parameter count) of every SWMI_API prototype of include/swmi.h; (void) counts as 0."""
+    text = open(os.path.join(ROOT, "include", "swmi.h")).read()
+    text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+    found = re.findall(r"SWMI_API\s+([^;(]*?)\b(swmi_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S)
+    return [(ret.strip(), name, 0 if params.strip() in ("", "void") else params.count(",") + 1) for ret, name, params in found]
+
+
+def test_python_argtypes_match_the_header(swmi_mod):
+    """swmi.load() against include/swmi.h: an entry whose argtypes are set has as many as its prototype has parameters, and a
+    size_t result is declared as one (ctypes' default int would cut it).  Only swmi_semiglobal_set_mapping(int) has parameters
+    and no argtypes, which an int converts for correctly."""
+    protos = _prototypes()
+    assert sorted(name for _, name, _ in protos) == _declared_symbols()
+    lib = swmi_mod.load()
+    unset = []
+    for ret, name, count in protos:
+        fn = getattr(lib, name)
+        if "size_t" in ret:
+            assert fn.restype is ctypes.c_size_t, name
+        if fn.argtypes is None:
+            if count:
+                unset.append(name)
+        else:
+            assert len(fn.argtypes) == count, "%s takes %d parameters, argtypes has %d" % (name, count, len(fn.argtypes))
+    assert unset == ["swmi_semiglobal_set_mapping"]
+
+
 def test_product_library_does_not_link_the_oracle():
     import subprocess
     out = subprocess.run(["ldd", os.path.join(PKG, "lib", "libswmi.so")], stdout=subprocess.PIPE, text=True).stdout

@@ -2,7 +2,9 @@
 compiled with g++ and ASan + UBSan, defines the aligners, expanders and swmi_last_error the overloads call, with results
 derived from an index in each seq2.  For each overload it checks every result over several pieces, the pieces and moves
 buffers the aligner sees, and that a failing aligner call or expansion (on 3 host threads for the semi-global overloads)
-surfaces as std::runtime_error with the stub's message while the program goes on."""
+surfaces as std::runtime_error with the stub's message while the program goes on.  For the overloads with one (len1, len2)
+per batch (long, long_affine, nw, sg_affine) also that a piece is capped at the slice their *_slices_for reports, that nw's
+mask reaches every piece, and that a length the library refuses surfaces with its message before any piece is aligned."""
 import os
 import shutil
 import subprocess
@@ -11,7 +13,7 @@ import pytest
 
 from conftest import ROOT
 
-OVERLOADS = ["local", "affine", "ragged", "affine_ragged", "long_ragged", "xdrop", "sgfull"]
+OVERLOADS = ["local", "affine", "ragged", "affine_ragged", "long_ragged", "xdrop", "sgfull", "long", "long_affine", "nw", "sg_affine"]
 
 
 @pytest.fixture(scope="module")
