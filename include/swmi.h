@@ -732,6 +732,67 @@ SWMI_API int swmi_global_full_time_device(const void *d_seq1s, size_t len1, cons
                                           const int8_t score_matrix[16], int8_t gap_penalty, unsigned free_ends, void *d_scores,
                                           void *d_ends, void *d_moves, void *d_steps, void *stream, int iters, float *avg_ms);
 
+/* ---- global and free-end-gap alignment with AFFINE gaps of two sequences of ANY length, with end cell, start cell and
+ * traceback ------------------------------------------------------------------------------------------
+ * No reference counterpart: swmi_global_full with Gotoh's gaps, a gap of length k costing gap_open + (k-1) gap_extend (the
+ * convention of swmi_semiglobal_full_affine and swmi_local_full_affine).  n alignments; seq1 k = the len1 bytes at
+ * seq1s + len1 * k, seq2 k = the len2 bytes at seq2s + len2 * k, one (len1, len2) per call, 1 <= len1, len2 <= 16384
+ * (SWMI_GLOBAL_FULL_MAX_LEN); any int8 matrix; gap_open and gap_extend each in [0, 127], in either order; bases are taken
+ * modulo 4.  free_ends is swmi_global_full's mask of SWMI_FREE_*; all 16 masks are valid.
+ *     H(0,0) = 0
+ *     H(i,0) = SWMI_FREE_BEGIN1 ? 0 : -(open + (i-1) extend)  (i >= 1)
+ *     H(0,j) = SWMI_FREE_BEGIN2 ? 0 : -(open + (j-1) extend)  (j >= 1)
+ *     E(0,j) = -inf;  F(i,0) = -inf
+ *     E(i,j) = max(H(i-1,j) - open, E(i-1,j) - extend)        vertical gap: consumes seq1, an up move
+ *     F(i,j) = max(H(i,j-1) - open, F(i,j-1) - extend)        horizontal gap: consumes seq2, a left move
+ *     H(i,j) = max(H(i-1,j-1) + sm[seq1[i-1]*4 + seq2[j-1]], E(i,j), F(i,j))          (no zero floor)
+ * The END CELL is swmi_global_full's rule on H: (len1, len2), or with SWMI_FREE_END1 / SWMI_FREE_END2 the cell of the last
+ * column / last row (border cells (0, len2) and (len1, 0) included, with the values above) that holds the largest H; among
+ * equal ones the first in row-major order.  scores[k] = that H, which may be NEGATIVE; every H, E and F that can be reached
+ * lies in [-127 (len1 + len2), 127 min(len1, len2)], so |score| < 2^22.  ends[k] = (end_i, end_j, start_i, start_j).
+ * The walk is swmi_semiglobal_full_affine's: it starts at the end cell in state H.  State H at (i,j), i > 0 and j > 0: a
+ * diagonal step if H = H(i-1,j-1) + s, else state E if H = E(i,j), else state F.  State E: an up step, after which the state
+ * is H if E(i,j) = H(i-1,j) - open (opening wins a tie) and stays E otherwise; state F likewise with left steps.  E(1,j) and
+ * F(i,1) always open, so the walk reaches row 0 or column 0 in state H, and there swmi_global_full's border rule holds: at
+ * (0, 0) it ends; on row 0 with j > 0 it ends if SWMI_FREE_BEGIN2 is set, else goes left to (0, 0) by forced steps; on column
+ * 0 with i > 0 it ends if SWMI_FREE_BEGIN1 is set, else goes up to (0, 0) by forced steps.  The start cell is where it ended.
+ * moves + k * SWMI_GLOBAL_FULL_MOVE_WORDS(len1, len2) receives the steps in WALKING order, 3 = diagonal, 2 = up, 1 = left;
+ * steps[k] = their number, forced steps included, so swmi_local_full_expand_moves rebuilds the list of steps[k] + 1 positions
+ * from the start cell to the end cell; words past the last step are unspecified.  moves and steps both NULL: ENDS-ONLY -- no
+ * codes are stored or walked, the start cell is reported as (-1, -1).
+ * Two identities follow from the definition:
+ *     gap_open == gap_extend == g: E(i,j) = H(i-1,j) - g and F(i,j) = H(i,j-1) - g exactly, opening wins the tie and the
+ *     borders are -i g / -j g or 0, so every field equals swmi_global_full's with gap g, under every mask;
+ *     mask 0: the table is swmi_semiglobal_full_affine's table.  For a pair whose best cell (ei, ej) there has ei, ej >= 1,
+ *     the mask-0 alignment of seq1[:ei] against seq2[:ej] has that score, steps == lengths - 1 and the same moves.
+ * Host buffers, in SLICES (swmi_global_full_affine_slices_for) on two sets of device buffers.  Errors:
+ * SWMI_ERR_INVALID_ARGUMENT for a length outside [1, 16384], free_ends above 15, a NULL buffer, or only one of moves / steps;
+ * SWMI_ERR_DOMAIN for gap_open or gap_extend outside [0, 127]; n = 0 is a no-op that needs no device.  Every argument is
+ * checked before any device is touched. */
+SWMI_API int swmi_global_full_affine(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t len2, size_t n,
+                                     const int8_t score_matrix[16], int gap_open, int gap_extend, unsigned free_ends,
+                                     int32_t *scores, int32_t *ends, uint64_t *moves, uint32_t *steps);
+/* The slices a swmi_global_full_affine call of n alignments cuts its batch into (traceback = 0: ends-only), in order; returns
+ * how many there are and writes the first `cap` sizes (NULL to count).  The budgets are swmi_semiglobal_full_affine_slices_for's:
+ * with a traceback what 256 alignments of 16384 x 16384 take (about 32.1 GiB: 128.5 MiB of codes each, 4 bits per cell),
+ * ends-only 256 MiB; at most 2^20 alignments per slice.  Needs no device.  0 for a length outside [1, 16384]. */
+SWMI_API size_t swmi_global_full_affine_slices_for(size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap);
+/* Same with every buffer in device memory (16-byte aligned), asynchronous on `stream`.  The traceback codes go to a workspace
+ * of the library's per (GPU, stream), grown on demand up to one slice and kept until
+ * swmi_global_full_affine_release_workspaces() / swmi_shutdown(): calls on one stream serialise by themselves, calls on
+ * different streams may be in flight together. */
+SWMI_API int swmi_global_full_affine_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
+                                            const int8_t score_matrix[16], int gap_open, int gap_extend, unsigned free_ends,
+                                            void *d_scores, void *d_ends, void *d_moves, void *d_steps, void *stream);
+/* Free the device buffers of both entries above on the current GPU (synchronises the device first). */
+SWMI_API int swmi_global_full_affine_release_workspaces(void);
+/* Measurement helper: `iters` swmi_global_full_affine_device calls back to back on `stream`, bracketed by HIP events;
+ * *avg_ms = the average time of one call.  Synchronous. */
+SWMI_API int swmi_global_full_affine_time_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
+                                                 const int8_t score_matrix[16], int gap_open, int gap_extend,
+                                                 unsigned free_ends, void *d_scores, void *d_ends, void *d_moves, void *d_steps,
+                                                 void *stream, int iters, float *avg_ms);
+
 /* ---- deferred queue behind the per-pair signature -------------------------------------
  * Lets a per-pair caller (the reference's timing loop) keep its call shape while the
  * library batches: submit() copies the pair into pinned staging memory and returns its

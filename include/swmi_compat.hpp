@@ -93,6 +93,16 @@ inline std::pair<int, std::vector<std::pair<int, int>>> NeedlemanWunsch_mi355x(c
                                                                               const int8_t gap_penalty,
                                                                               unsigned free_ends = SWMI_ENDS_GLOBAL);
 
+// The same with affine gaps (swmi_global_full_affine: no reference counterpart), a gap of length k costing
+// gap_open + (k-1) gap_extend, both in [0, 127]: Gotoh's global alignment under SWMI_ENDS_GLOBAL, fit and overlap alignment
+// under the other masks.  NeedlemanWunsch_affine_mi355x(a, b, m, g, g, mask) == NeedlemanWunsch_mi355x(a, b, m, g, mask).
+// One synchronous call per alignment; swmi::NeedlemanWunsch_affine_mi355x_batch is the throughput form.
+inline std::pair<int, std::vector<std::pair<int, int>>> NeedlemanWunsch_affine_mi355x(const std::vector<uint8_t> &seq1,
+                                                                                     const std::vector<uint8_t> &seq2,
+                                                                                     const std::array<int8_t, 16> &score_matrix,
+                                                                                     int gap_open, int gap_extend,
+                                                                                     unsigned free_ends = SWMI_ENDS_GLOBAL);
+
 namespace swmi {
 
 // match 1, mismatch -1 (source.cpp:1786)
@@ -524,6 +534,25 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> NeedlemanWu
         detail::local_full_path);
 }
 
+// Affine global / free-end-gap alignment of seq1s[k] against seq2s[k], every seq1 of one length and every seq2 of one length:
+// result[k] == NeedlemanWunsch_affine_mi355x(seq1s[k], seq2s[k], score_matrix, gap_open, gap_extend, free_ends).  The batch goes
+// to the GPU in pieces of `piece` alignments, at most one traceback slice of swmi_global_full_affine (0 = one slice: 256 at
+// 16384 x 16384); only two pieces' moves are held at a time, and the paths of one piece are rebuilt on `threads` host threads
+// (0 = as many as the machine reports, at most 64) while the GPU aligns the next.
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> NeedlemanWunsch_affine_mi355x_batch(
+    const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::vector<uint8_t>> &seq2s,
+    const std::array<int8_t, 16> &score_matrix, int gap_open, int gap_extend, unsigned free_ends = SWMI_ENDS_GLOBAL, size_t piece = 0,
+    unsigned threads = 0)
+{
+    return detail::shaped_batch(
+        "NeedlemanWunsch_affine_mi355x_batch", "swmi_global_full_affine", seq1s, seq2s, piece, threads, 4,
+        SWMI_GLOBAL_FULL_MOVE_WORDS(detail::common_length(seq1s), detail::common_length(seq2s)), swmi_global_full_affine_slices_for,
+        [&](const uint8_t *a, size_t len1, const uint8_t *b, size_t len2, size_t m, auto... out) {
+            return swmi_global_full_affine(a, len1, b, len2, m, score_matrix.data(), gap_open, gap_extend, free_ends, out...);
+        },
+        detail::local_full_path);
+}
+
 // Any-length affine local alignment of seq1s[k] against seq2s[k], every seq1 of one length and every seq2 of one length:
 // result[k] == SmithWaterman_long_affine_mi355x(seq1s[k], seq2s[k], score_matrix, gap_open, gap_extend).  The batch goes to the
 // GPU in pieces of `piece` alignments, at most one traceback slice of swmi_local_full_affine (0 = one slice: 256 at
@@ -744,6 +773,20 @@ inline std::pair<int, std::vector<std::pair<int, int>>> NeedlemanWunsch_mi355x(c
         [&](auto... out) {
             return swmi_global_full(seq1.data(), seq1.size(), seq2.data(), seq2.size(), 1, score_matrix.data(), gap_penalty, free_ends,
                                     out...);
+        },
+        swmi::detail::local_full_path);
+}
+
+inline std::pair<int, std::vector<std::pair<int, int>>> NeedlemanWunsch_affine_mi355x(const std::vector<uint8_t> &seq1,
+                                                                                     const std::vector<uint8_t> &seq2,
+                                                                                     const std::array<int8_t, 16> &score_matrix,
+                                                                                     int gap_open, int gap_extend, unsigned free_ends)
+{
+    return swmi::detail::one_alignment(
+        "swmi_global_full_affine", SWMI_GLOBAL_FULL_MOVE_WORDS(seq1.size(), seq2.size()),
+        [&](auto... out) {
+            return swmi_global_full_affine(seq1.data(), seq1.size(), seq2.data(), seq2.size(), 1, score_matrix.data(), gap_open,
+                                           gap_extend, free_ends, out...);
         },
         swmi::detail::local_full_path);
 }

@@ -176,6 +176,7 @@ struct Context {
     std::shared_ptr<void> local_full_state;     // the any-length local aligner's (local_full_api.cpp, likewise)
     std::shared_ptr<void> local_full_affine_state;  // the any-length affine local aligner's (local_full_affine_api.cpp, likewise)
     std::shared_ptr<void> global_full_state;    // the global / free-end-gap aligner's (global_full_api.cpp, likewise)
+    std::shared_ptr<void> global_full_affine_state;  // the affine global / free-end-gap aligner's (global_full_affine_api.cpp, likewise)
     std::mutex mu;                      // serialises use of the slots, the sg sets and the pinned buffer
 };
 
@@ -240,7 +241,7 @@ struct Table {
     const int8_t *sm;
     int gap, gap_extend;        // gap_extend: the affine aligner's (gap is then the open cost)
     const RaggedPlan *plan = nullptr;   // a ragged batch: len1, code_words and move_words unused, slices as the plan says
-    unsigned free_ends = 0;             // the global aligner's mask of SWMI_FREE_*, which its slice launcher reads
+    unsigned free_ends = 0;             // the global aligners' mask of SWMI_FREE_*, which their slice launchers read
 };
 constexpr size_t kTableSliceBytes = size_t(256) << 20;
 constexpr size_t kTableMaxSlice = size_t(1) << 20;     // alignments per slice (and per launch)
@@ -258,6 +259,8 @@ Table affine_table(size_t len1, const int8_t *sm, int gap_open, int gap_extend);
 Table local_full_table(size_t len1, size_t len2, const int8_t *sm, int gap);             // local_full_api.cpp
 Table local_full_affine_table(size_t len1, size_t len2, const int8_t *sm, int gap_open, int gap_extend);   // local_full_affine_api.cpp
 Table global_full_table(size_t len1, size_t len2, const int8_t *sm, int gap, unsigned free_ends);         // global_full_api.cpp
+Table global_full_affine_table(size_t len1, size_t len2, const int8_t *sm, int gap_open, int gap_extend,
+                               unsigned free_ends);                                                        // global_full_affine_api.cpp
 // local_full_ragged_api.cpp: the plan of a ragged any-length batch alone (no device), for tests of its arithmetic -- per slice
 // its alignments and device bytes; true when every code base equals the 64-bit running sum of the code words before it
 bool local_full_ragged_plan_check(const uint64_t *seq1_offsets, const uint64_t *seq2_offsets, size_t n, bool affine, bool tb,

@@ -194,3 +194,14 @@ hipError_t launch_global_full(const uint8_t *d_seq1s, const uint8_t *d_seq2s, in
                               unsigned free_ends, int32_t *d_scores, int32_t *d_ends, uint32_t *d_codes, unsigned long long *d_moves,
                               uint32_t *d_steps, size_t move_words, hipStream_t stream);
 }  // namespace swmi
+
+namespace swmi {
+// Global and free-end-gap aligner with AFFINE gaps (global_full_affine_kernels.hip): launch_global_full's shapes, workgroups,
+// d_ends and mask, with global_full_affine_code_qwords(len1, len2) qwords of codes per alignment of the launch (4 bits per
+// cell).  d_moves NULL: the ends-only kernel (no codes, no walk; d_codes and d_steps unused).
+size_t global_full_affine_code_qwords(int len1, int len2);
+hipError_t launch_global_full_affine(const uint8_t *d_seq1s, const uint8_t *d_seq2s, int len1, int len2, size_t n, const int8_t *sm,
+                                     int gap_open, int gap_extend, unsigned free_ends, int32_t *d_scores, int32_t *d_ends,
+                                     unsigned long long *d_codes, unsigned long long *d_moves, uint32_t *d_steps, size_t move_words,
+                                     hipStream_t stream);
+}  // namespace swmi

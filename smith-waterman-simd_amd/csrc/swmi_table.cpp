@@ -6,7 +6,8 @@
 // local_full_ragged_api.cpp, section 19) run through.  What differs between them is data (struct Table, swmi_host.h).
 //
 // Their device buffers hang off Context::local_state, sgfull_state, local_affine_state, sgfull_affine_state and
-// local_full_state, local_full_affine_state and global_full_state (global_full_api.cpp, section 20), which
+// local_full_state, local_full_affine_state, global_full_state (global_full_api.cpp, section 20) and global_full_affine_state
+// (global_full_affine_api.cpp, section 21), which
 // destroy_context (swmi_api.cpp) drops at swmi_shutdown: that file names no symbol of this one, so the host-only builds of swmi_api.cpp /
 // swmi_multi.cpp (tests/test_multi_fake.py, tests/test_sanitizers.py) link without these kernels -- and this file names no
 // launcher but launch_local and launch_sgfull, so that the fake-GPU build of every swmi_*.cpp (tests/test_table_host_fake.py)

@@ -1,7 +1,7 @@
 // tile_sweep.h -- what the any-length aligners share (sgfull_kernels.hip, sgfull_affine_kernels.hip,
-// local_full_kernels.hip, local_full_affine_kernels.hip, global_full_kernels.hip): the mapping and its constants, the helpers,
-// the geometry and the launcher; the few helpers that the 16-lane local aligners take from here as well.  The sweep and the
-// walk of the two linear-gap kernels are tile_sweep_body.inc, those of the two affine kernels tile_sweep_affine_body.inc.
+// local_full_kernels.hip, local_full_affine_kernels.hip, global_full_kernels.hip, global_full_affine_kernels.hip; DESIGN.md
+// section 13): the mapping and its constants, the helpers, the geometry and the launcher; the few helpers that the 16-lane local aligners take from here as well.  The sweep and the
+// walk of the linear-gap kernels are tile_sweep_body.inc, those of the affine kernels tile_sweep_affine_body.inc.
 //
 // Mapping: ONE workgroup per alignment, W = ceil(len2 / 1024) wavefronts; lane l of wave w owns the 16 columns
 // 16 G + 1 .. 16 G + 16 of G = 64 w + l.  Inside a wave, lane l computes row s - l + 1 at the wave's local step s; what
@@ -48,9 +48,9 @@
 //     kWalkStops                    whether a code can stop the walk (else it goes on to (0, 0), forced on the border)
 // The borders take the NEGATED row or column so that the caller's sum folds into the negation as it did before the split.
 //
-// The END RULE (global_full_kernels.hip): a variant with a static member kFreeEnds = true -- the other
-// variants have no such member, and kEndRule<V> is then false -- asks the body for another best cell and another end of the
-// walk.  Its kernel has an argument `free_ends` (uniform, so in SGPRs; a kernel without one finds tile::free_ends = 0 below),
+// The END RULE (global_full_kernels.hip, global_full_affine_kernels.hip; DESIGN.md sections 20 and 21): a variant with a
+// static member kFreeEnds = true -- the other variants have no such member, and kEndRule<V> is then false -- asks the body
+// for another best cell and another end of the walk.  Its kernel has an argument `free_ends` (uniform, so in SGPRs; a kernel without one finds tile::free_ends = 0 below),
 // a mask of kFreeBegin1 / kFreeBegin2 (column 0 / row 0 hold 0: the variant's left_border / row0 and border follow them) and
 // kFreeEnd1 / kFreeEnd2 (the end cell may lie anywhere in column len2 / row len1).  Such a variant has kWalkStops = false,
 // kEnds = 4 and kRowMin below every key.  With it
@@ -74,6 +74,11 @@
 //     row0(jj, j, open, extend)     the stored key of row 0 in the lane's column jj (global column j)
 //     border(j, open, extend)       the stored key of H(0, j) = H(j, 0), column bits aside
 //     floor(m)                      H's largest candidate m with the zero floor joined, or m itself
+// With the end rule (a variant with kFreeEnds = true; its kernel names free_ends) the affine body keeps one (open, extend) per
+// border, (0, 0) where the mask frees it, and hands border() and row0() that border's pair; E on row 0 and F on column 0 stay
+// -inf.  It reads the last column's key of row i - 1 before it computes row i, through the same uniform switch, where the
+// linear body reads row i's from the finished row: the body says why.  Thread 0 packs the two border cells before the sweep
+// and keeps them in VGPRs.  The last row, the corner, the reduction and the walk's tail are the linear body's.
 //
 // Ragged launches (the two local kernels): a kernel with a template parameter RAGGED has a last
 // parameter `work` (NULL and unread in a fixed launch; last, so that every other argument lies where it did), and with RAGGED

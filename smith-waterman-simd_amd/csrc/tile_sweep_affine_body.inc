@@ -2,7 +2,8 @@
 // tells the mapping and what an affine variant V supplies).  Included INSIDE the kernel, after `using V = <variant>;`,
 // where the kernel's parameters are named seq1s, seq2s, len1, len2, cols, gap_open, gap_extend, scores, ends, codes, moves,
 // counts, move_words, n_trips and its template parameter TB.  A kernel with a ragged form also names RAGGED and slot, and
-// then len1, len2 and n_trips are the slot's (tile_sweep.h).  Text and not a function on purpose: tile_sweep.h says why.
+// then len1, len2 and n_trips are the slot's (tile_sweep.h).  A kernel whose variant has the end rule (kEndRule<V>,
+// tile_sweep.h) also names free_ends.  Text and not a function on purpose: tile_sweep.h says why.
 //
 // E runs down a column and stays with the lane; F runs along the row, so what lane l - 1 hands over (and lane 63 through
 // the ring) is its H(i, 16 G) AND its F(i, 16 G): two v_mov_b32_dpp wave_shr:1 per step, (H, F) pairs in the ring.  With a
@@ -42,6 +43,12 @@
         }
     }
     const int jbase = kCols * G;                        // the lane's columns are jbase + 1 .. jbase + 16
+    // what a gap along row 0 / column 0 costs: the kernel's, or with the end rule 0 where that border is free
+    int open_row0 = gap_open, ext_row0 = gap_extend, open_col0 = gap_open, ext_col0 = gap_extend;
+    if constexpr (kEndRule<V>) {
+        if (free_ends & kFreeBegin2) open_row0 = ext_row0 = 0;
+        if (free_ends & kFreeBegin1) open_col0 = ext_col0 = 0;
+    }
 
     uint32_t prof[kCols];
     int key[kCols], e[kCols];                           // H's stored keys and E of the row the lane computed last
@@ -50,14 +57,29 @@
         const int j = jbase + jj + 1;
         const uint32_t b = s2[j <= len2 ? j - 1 : 0] & 3u;
         prof[jj] = j > len2 ? 0x80808080u : b == 0 ? cols.c[0] : b == 1 ? cols.c[1] : b == 2 ? cols.c[2] : cols.c[3];
-        key[jj] = V::row0(jj, j, gap_open, gap_extend);
+        key[jj] = V::row0(jj, j, open_row0, ext_row0);
         e[jj] = kMinusInf;
+    }
+    // end rule: the border cells (0, len2) and (len1, 0) are closed forms; thread 0 holds them as candidates from here on (in
+    // two VGPRs: kept as scalars until after the sweep, the borders' gaps cost SGPRs that the traceback kernel has not got)
+    [[maybe_unused]] unsigned long long r_border = 0;
+    if constexpr (kEndRule<V>) {
+        if (tid == 0) {
+            if (free_ends & kFreeEnd1) r_border = end_pack(V::border(len2, open_row0, ext_row0) >> 6, 0, len2);
+            if (free_ends & kFreeEnd2) r_border = umax64(r_border, end_pack(V::border(len1, open_col0, ext_col0) >> 6, len1, 0));
+        }
     }
     const int g_open = -(gap_open << 6);
     const int g_ext = -(gap_extend << 6);
-    int diag_in = V::border(jbase, gap_open, gap_extend);   // key(0, jbase)
+    int diag_in = V::border(jbase, open_row0, ext_row0);   // key(0, jbase)
     int f_last = kMinusInf;                             // F(i, jbase + 16) of the lane's last row, for lane l + 1
-    int best = V::kTagH, best_row = 0;                  // H = 0 at (0, 0)
+    int best = kEndRule<V> ? V::kRowMin : V::kTagH, best_row = 0;   // H = 0 at (0, 0); end rule: no last-column cell yet
+    // end rule: the lane that owns column len2 keeps the best cell of that column, if seq1's end is free.  end_sel is that
+    // column's jj in the last wave and -1 anywhere else (uniform, made scalar here).  Every lane of the last wave tracks its
+    // column jj = end_sel, and only the owner's is read after the sweep, so the loop holds no lane mask.
+    [[maybe_unused]] int end_sel = -1;
+    if constexpr (kEndRule<V>)
+        end_sel = __builtin_amdgcn_readfirstlane((free_ends & kFreeEnd1) && w == W - 1 ? (len2 - 1) & (kCols - 1) : -1);
 
     const int local_chunks = (len1 + 63 + kChunk - 1) / kChunk;
     const int total_chunks = local_chunks + kDelay * (W - 1);
@@ -88,7 +110,7 @@
                         bound_h[t] = v.x;
                         bound_f[t] = v.y;
                     } else {
-                        bound_h[t] = V::border(s0 + t + 1, gap_open, gap_extend);
+                        bound_h[t] = V::border(s0 + t + 1, open_col0, ext_col0);
                         bound_f[t] = kMinusInf;
                     }
                     cw[t] = 0;
@@ -101,6 +123,39 @@
                     const int row = s0 + t - l + 1;
                     if (row >= 1 && row <= len1) {
                         int d = diag_in, lft = left_in, f = f_in, rk = V::kRowMin;
+                        if constexpr (kEndRule<V>) {
+                            // H(row - 1, len2), read BEFORE the row is computed, while key[] still holds the row above: one
+                            // register of one lane through a uniform switch, in a branch that only the last wave takes and
+                            // only with kFreeEnd1, so the loop has no chain over the cells.  (Read from the FINISHED row, as
+                            // the linear body does it, the old row's keys live on beside the new row's and the traceback
+                            // kernel spills 32 VGPRs; a select per cell costs every mask 64 v_cndmask_b32 per trip.  DESIGN.md
+                            // section 21.)  Row 0 is read at row 1; row len1's cell is the corner, a candidate of its own
+                            if (end_sel >= 0) {
+                                int end_key;
+                                switch (end_sel) {
+                                case 0: end_key = key[0]; break;
+                                case 1: end_key = key[1]; break;
+                                case 2: end_key = key[2]; break;
+                                case 3: end_key = key[3]; break;
+                                case 4: end_key = key[4]; break;
+                                case 5: end_key = key[5]; break;
+                                case 6: end_key = key[6]; break;
+                                case 7: end_key = key[7]; break;
+                                case 8: end_key = key[8]; break;
+                                case 9: end_key = key[9]; break;
+                                case 10: end_key = key[10]; break;
+                                case 11: end_key = key[11]; break;
+                                case 12: end_key = key[12]; break;
+                                case 13: end_key = key[13]; break;
+                                case 14: end_key = key[14]; break;
+                                default: end_key = key[15]; break;
+                                }
+                                if (end_key > best) {
+                                    best = end_key;
+                                    best_row = row - 1;
+                                }
+                            }
+                        }
 #pragma unroll
                         for (int jj = 0; jj < kCols; ++jj) {
                             const int sc = __builtin_amdgcn_sbfe((int)prof[jj], sh[t], 8);
@@ -123,12 +178,14 @@
                             e[jj] = ec;
                             f = fc;
                             lft = nk;
-                            rk = rk > nk ? rk : nk;
+                            if constexpr (!kEndRule<V>) rk = rk > nk ? rk : nk;
                         }
                         f_last = f;
-                        if (rk > (best | 63)) {
-                            best = rk;
-                            best_row = row;
+                        if constexpr (!kEndRule<V>) {
+                            if (rk > (best | 63)) {
+                                best = rk;
+                                best_row = row;
+                            }
                         }
                     }
                     edge_h[t] = key[kCols - 1];
@@ -153,10 +210,30 @@
     }
 
     // best cell: (H desc, row asc, column asc) over the lanes, then over the waves
-    const int h = best >> 6;
-    const int col = h > 0 ? jbase + (kCols - 1 - (best & 15)) + 1 : 0;
-    unsigned long long r = ((unsigned long long)(uint32_t)h << 34) | ((unsigned long long)(0x1FFFF - best_row) << 17) |
-                           (unsigned long long)(0x1FFFF - col);
+    unsigned long long r;
+    if constexpr (kEndRule<V>) {
+        // the lane's candidates (tile_sweep.h): key[] holds row len1 now.  Last row, columns past len2 masked out; the
+        // corner; the last column's best over rows 0 .. len1 - 1; thread 0's two border cells
+        r = 0;
+        int last = V::kRowMin, corner = V::kRowMin;
+#pragma unroll
+        for (int jj = 0; jj < kCols; ++jj) {
+            const int j = jbase + jj + 1;
+            if (j <= len2 && key[jj] > last) last = key[jj];
+            if (j == len2) corner = key[jj];
+        }
+        if ((free_ends & kFreeEnd2) && jbase < len2) r = end_pack(last >> 6, len1, jbase + (kCols - 1 - (last & 15)) + 1);
+        if (G == (len2 - 1) >> 4) {
+            r = umax64(r, end_pack(corner >> 6, len1, len2));
+            if (end_sel >= 0) r = umax64(r, end_pack(best >> 6, best_row, len2));
+        }
+        r = umax64(r, r_border);
+    } else {
+        const int h = best >> 6;
+        const int col = h > 0 ? jbase + (kCols - 1 - (best & 15)) + 1 : 0;
+        r = ((unsigned long long)(uint32_t)h << 34) | ((unsigned long long)(0x1FFFF - best_row) << 17) |
+            (unsigned long long)(0x1FFFF - col);
+    }
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
         const unsigned long long v = __shfl_xor(r, o, 64);
@@ -167,9 +244,9 @@
     __syncthreads();
     r = red[0];
     for (int x = 1; x < W; ++x) r = red[x] > r ? red[x] : r;
-    const int score = (int)(r >> 34);
-    const int end_i = score > 0 ? 0x1FFFF - (int)((r >> 17) & 0x1FFFF) : 0;
-    const int end_j = score > 0 ? 0x1FFFF - (int)(r & 0x1FFFF) : 0;
+    const int score = kEndRule<V> ? (int)(r >> 34) - kEndBias : (int)(r >> 34);
+    const int end_i = kEndRule<V> || score > 0 ? 0x1FFFF - (int)((r >> 17) & 0x1FFFF) : 0;
+    const int end_j = kEndRule<V> || score > 0 ? 0x1FFFF - (int)(r & 0x1FFFF) : 0;
     if (tid == 0) {
         scores[k] = score;
         ends[V::kEnds * k + 0] = end_i;
@@ -241,6 +318,25 @@
         if (tid == 0) {
             if constexpr (V::kWalkStops) {
                 // the walk ended on its start cell: the count is the moves
+                if (t & 31) mv[t >> 5] = acc;
+                counts[k] = t;
+                ends[V::kEnds * k + 2] = i;
+                ends[V::kEnds * k + 3] = j;
+            } else if constexpr (kEndRule<V>) {
+                // the walk reached a border (in state H): it ends there if that border is free, else it goes on to (0, 0) by
+                // forced moves (up along column 0, left along row 0); the count is the moves, the start cell where it ended
+                const uint32_t m = i > 0 ? 2u : 1u;
+                if (!(free_ends & (i > 0 ? kFreeBegin1 : kFreeBegin2))) {
+                    for (; i > 0 || j > 0; ++t) {
+                        acc |= (unsigned long long)m << (2 * (t & 31));
+                        i -= m == 2u;
+                        j -= m == 1u;
+                        if (((t + 1) & 31) == 0) {
+                            mv[t >> 5] = acc;
+                            acc = 0;
+                        }
+                    }
+                }
                 if (t & 31) mv[t >> 5] = acc;
                 counts[k] = t;
                 ends[V::kEnds * k + 2] = i;

@@ -136,7 +136,9 @@ def load():
             ("swmi_local_full_affine", "swmi_local_full_affine_time_device", "swmi_local_full_affine_slices_for", two_lens, [ci, ci]),
             ("swmi_local_full_ragged", None, None, ragged2, [i8]),
             ("swmi_local_full_affine_ragged", None, None, ragged2, [ci, ci]),
-            ("swmi_global_full", "swmi_global_full_time_device", "swmi_global_full_slices_for", two_lens, [i8, cu])):
+            ("swmi_global_full", "swmi_global_full_time_device", "swmi_global_full_slices_for", two_lens, [i8, cu]),
+            ("swmi_global_full_affine", "swmi_global_full_affine_time_device", "swmi_global_full_affine_slices_for", two_lens,
+             [ci, ci, cu])):
         args = shape + [vp] + gap + [vp, vp, vp, vp]
         getattr(lib, host).argtypes = args
         getattr(lib, host + "_device").argtypes = args + [vp]
@@ -1175,3 +1177,8 @@ class Queue:
             self.close()
         except Exception:
             pass
+
+
+# The affine global / free-end-gap aligner's wrappers live in a submodule, swmi.global_affine.<name>: imported as a module
+# (last, when every helper it takes from here is defined), its functions stay out of this namespace.
+from . import global_affine    # noqa: E402
