@@ -793,6 +793,63 @@ SWMI_API int swmi_global_full_affine_time_device(const void *d_seq1s, size_t len
                                                  unsigned free_ends, void *d_scores, void *d_ends, void *d_moves, void *d_steps,
                                                  void *stream, int iters, float *avg_ms);
 
+/* ---- the global / fit / overlap aligners on a batch of MIXED (len1, len2) ----------------------------
+ * swmi_global_full and swmi_global_full_affine with one (len1, len2) per alignment and one mask and one set of gaps per
+ * call.  Alignment k is seq1 = bytes [seq1_offsets[k], seq1_offsets[k+1]) of seq1s against seq2 = bytes
+ * [seq2_offsets[k], seq2_offsets[k+1]) of seq2s; both offset arrays hold n + 1 non-decreasing entries, and every length is in
+ * [0, 16384].  scores, ends = (end_i, end_j, start_i, start_j) and steps are those of the fixed-length entries, in caller
+ * order, with the same semantics, tie rules, forced border steps and move encoding, under every one of the 16 masks.
+ * Alignment k's moves start at word move_offsets[k].  SWMI_GLOBAL_FULL_MOVE_WORDS is SWMI_LOCAL_FULL_MOVE_WORDS, so
+ * swmi_local_full_ragged_move_offsets gives the layout, and there is no second function for it;
+ * swmi_local_full_expand_moves(moves + move_offsets[k], ...) rebuilds a path.  moves and steps both NULL: ends-only, the
+ * start cell reported as (-1, -1).
+ * ZERO LENGTHS follow from the definitions above extended to an empty sequence -- they are NOT the local aligners' "score 0".
+ * The table is then one border.  Let L be the non-empty sequence's length and cost(L) = L gap (linear gaps) or
+ * open + (L - 1) extend (affine gaps).  For len2 == 0 the border is column 0: BEGIN = SWMI_FREE_BEGIN1, END = SWMI_FREE_END1,
+ * the forced move is "up" (2).  For len1 == 0 it is row 0: BEGIN = SWMI_FREE_BEGIN2, END = SWMI_FREE_END2, the move "left" (1).
+ *     case                    score      ends                                      steps
+ *     both lengths 0          0          (0, 0, 0, 0)                              0
+ *     END set                 0          (0, 0, 0, 0)                              0
+ *     END clear, BEGIN set    0          end = start = (L, 0) or (0, L)            0
+ *     neither                 -cost(L)   end (L, 0) or (0, L), start (0, 0)        L forced moves
+ * With END set the first border cell in row-major order, (0, 0), holds the largest H (0), also at gap 0.  In the last row
+ * the L forced moves are all the same code: whole words of 0xAAAA... (up) or 0x5555... (left); bits past step L are
+ * unspecified, as everywhere.  Ends-only gives the same score and end cell, with start (-1, -1).  No byte of either sequence
+ * is read.
+ * Host buffers.  The batch runs in slices (swmi_global_full_ragged_slices_for) on two sets of device buffers.  One workgroup of
+ * ceil(len2 / 1024) wavefronts computes an alignment (one wavefront when a length is 0), so a slice runs as one launch per
+ * wave count present in it, the widest first, and inside a launch the longest seq1 first; results go to caller positions.
+ * Errors: SWMI_ERR_INVALID_ARGUMENT for decreasing offsets, a length above 16384, free_ends above 15, a NULL buffer, or only
+ * one of moves / steps; SWMI_ERR_DOMAIN as in the fixed-length entries.  n = 0 is a no-op that needs no device.  Every argument
+ * is checked before any device is touched. */
+SWMI_API int swmi_global_full_ragged(const uint8_t *seq1s, const uint64_t *seq1_offsets, const uint8_t *seq2s,
+                                     const uint64_t *seq2_offsets, size_t n, const int8_t score_matrix[16], int8_t gap_penalty,
+                                     unsigned free_ends, int32_t *scores, int32_t *ends, uint64_t *moves, uint32_t *steps);
+SWMI_API int swmi_global_full_affine_ragged(const uint8_t *seq1s, const uint64_t *seq1_offsets, const uint8_t *seq2s,
+                                            const uint64_t *seq2_offsets, size_t n, const int8_t score_matrix[16], int gap_open,
+                                            int gap_extend, unsigned free_ends, int32_t *scores, int32_t *ends, uint64_t *moves,
+                                            uint32_t *steps);
+/* The slices a ragged call of n alignments cuts its batch into (affine = 0: swmi_global_full_ragged, else the affine one;
+ * traceback = 0: ends-only), in order; returns how many there are and writes the first `cap` sizes (NULL to count).  Each is
+ * the longest run of the alignments left, in caller order, whose device bytes -- inputs, slots and results, plus codes, moves
+ * and steps with a traceback -- fit the fixed-length aligner's budget for one slice (swmi_global_full_slices_for's or
+ * swmi_global_full_affine_slices_for's with a traceback; 256 MiB ends-only), at most 2^20 alignments and at least one.  An
+ * alignment with a zero length takes no codes, but its move words.  Needs no device.  0 for invalid offsets. */
+SWMI_API size_t swmi_global_full_ragged_slices_for(const uint64_t *seq1_offsets, const uint64_t *seq2_offsets, size_t n, int affine,
+                                                   int traceback, size_t *sizes, size_t cap);
+/* Same with every data buffer in device memory (16-byte aligned at its base; an alignment's offsets need no alignment),
+ * asynchronous on `stream`; d_moves uses the move_offsets layout.  Both offset arrays stay HOST arrays, read during the call
+ * only.  The codes and slots go to the workspace of the fixed-length entry per (GPU, stream)
+ * (swmi_global_full_release_workspaces / swmi_global_full_affine_release_workspaces free it). */
+SWMI_API int swmi_global_full_ragged_device(const void *d_seq1s, const uint64_t *seq1_offsets, const void *d_seq2s,
+                                            const uint64_t *seq2_offsets, size_t n, const int8_t score_matrix[16],
+                                            int8_t gap_penalty, unsigned free_ends, void *d_scores, void *d_ends, void *d_moves,
+                                            void *d_steps, void *stream);
+SWMI_API int swmi_global_full_affine_ragged_device(const void *d_seq1s, const uint64_t *seq1_offsets, const void *d_seq2s,
+                                                   const uint64_t *seq2_offsets, size_t n, const int8_t score_matrix[16],
+                                                   int gap_open, int gap_extend, unsigned free_ends, void *d_scores,
+                                                   void *d_ends, void *d_moves, void *d_steps, void *stream);
+
 /* ---- deferred queue behind the per-pair signature -------------------------------------
  * Lets a per-pair caller (the reference's timing loop) keep its call shape while the
  * library batches: submit() copies the pair into pinned staging memory and returns its

@@ -86,7 +86,9 @@ inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_long_affin
 // gap (swmi_global_full: no reference counterpart): (score, path of (i, j) from the start cell to the end cell), forced steps
 // along a border that is not free included.  free_ends is a mask of SWMI_FREE_*: SWMI_ENDS_GLOBAL (end to end, from (0, 0) to
 // (len1, len2)), SWMI_ENDS_FIT (all of seq1 against a stretch of seq2), SWMI_ENDS_OVERLAP, or any other of the 16.  The score
-// may be negative.  One synchronous call per alignment; swmi::NeedlemanWunsch_mi355x_batch is the throughput form.
+// may be negative.  One synchronous call per alignment; swmi::NeedlemanWunsch_mi355x_batch is the throughput form, and
+// swmi::NeedlemanWunsch_mi355x_ragged_batch the one for mixed lengths.  An empty sequence is taken too (through the ragged
+// entry): the table is then one border, and the result the closed form of include/swmi.h.
 inline std::pair<int, std::vector<std::pair<int, int>>> NeedlemanWunsch_mi355x(const std::vector<uint8_t> &seq1,
                                                                               const std::vector<uint8_t> &seq2,
                                                                               const std::array<int8_t, 16> &score_matrix,
@@ -641,6 +643,39 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SmithWaterm
                                    });
 }
 
+// Global / free-end-gap alignment of seq1s[k] against seq2s[k], every sequence of a length of its own in [0, 16384]
+// (swmi_global_full_ragged): result[k] == NeedlemanWunsch_mi355x(seq1s[k], seq2s[k], score_matrix, gap_penalty, free_ends), also
+// for an empty sequence, whose table is one border (include/swmi.h has the closed form: not the local aligners' score 0).
+// Pieces, moves and threads as in SmithWaterman_long_mi355x_ragged_batch, whose move layout this shares.
+// NeedlemanWunsch_mi355x_batch keeps requiring one shape and throws on differing lengths.
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> NeedlemanWunsch_mi355x_ragged_batch(
+    const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::vector<uint8_t>> &seq2s,
+    const std::array<int8_t, 16> &score_matrix, const int8_t gap_penalty, unsigned free_ends = SWMI_ENDS_GLOBAL, size_t piece = 0,
+    unsigned threads = 0)
+{
+    return local_full_ragged_batch("NeedlemanWunsch_mi355x_ragged_batch", seq1s, seq2s, piece, threads,
+                                   [&](const uint8_t *a, const uint64_t *oa, const uint8_t *b, const uint64_t *ob, size_t m, int32_t *sc,
+                                       int32_t *e, uint64_t *mv, uint32_t *st) {
+                                       return swmi_global_full_ragged(a, oa, b, ob, m, score_matrix.data(), gap_penalty, free_ends, sc, e,
+                                                                      mv, st);
+                                   });
+}
+
+// The same with affine gaps: result[k] == NeedlemanWunsch_affine_mi355x(seq1s[k], seq2s[k], score_matrix, gap_open, gap_extend,
+// free_ends), also for an empty sequence.
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> NeedlemanWunsch_affine_mi355x_ragged_batch(
+    const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::vector<uint8_t>> &seq2s,
+    const std::array<int8_t, 16> &score_matrix, int gap_open, int gap_extend, unsigned free_ends = SWMI_ENDS_GLOBAL, size_t piece = 0,
+    unsigned threads = 0)
+{
+    return local_full_ragged_batch("NeedlemanWunsch_affine_mi355x_ragged_batch", seq1s, seq2s, piece, threads,
+                                   [&](const uint8_t *a, const uint64_t *oa, const uint8_t *b, const uint64_t *ob, size_t m, int32_t *sc,
+                                       int32_t *e, uint64_t *mv, uint32_t *st) {
+                                       return swmi_global_full_affine_ragged(a, oa, b, ob, m, score_matrix.data(), gap_open, gap_extend,
+                                                                             free_ends, sc, e, mv, st);
+                                   });
+}
+
 // The reference's 1M-call loop (source.cpp:3074-3082) over arrays of pairs, on every GPU the library is bound to:
 // scores[k] == SmithWaterman(seq1s[k], seq2s[k], score_matrix, gap_penalty).  std::array<uint8_t,128> has no padding, so a
 // vector of them IS the concatenated layout the C ABI takes.  With swmi_init(device) it runs on that one GPU, with
@@ -768,6 +803,9 @@ inline std::pair<int, std::vector<std::pair<int, int>>> NeedlemanWunsch_mi355x(c
                                                                               const std::array<int8_t, 16> &score_matrix,
                                                                               const int8_t gap_penalty, unsigned free_ends)
 {
+    // an empty sequence: the fixed-length entry takes no length 0, the ragged one does (one border, include/swmi.h)
+    if (seq1.empty() || seq2.empty())
+        return swmi::NeedlemanWunsch_mi355x_ragged_batch({seq1}, {seq2}, score_matrix, gap_penalty, free_ends, 1, 1).front();
     return swmi::detail::one_alignment(
         "swmi_global_full", SWMI_GLOBAL_FULL_MOVE_WORDS(seq1.size(), seq2.size()),
         [&](auto... out) {
@@ -782,6 +820,8 @@ inline std::pair<int, std::vector<std::pair<int, int>>> NeedlemanWunsch_affine_m
                                                                                      const std::array<int8_t, 16> &score_matrix,
                                                                                      int gap_open, int gap_extend, unsigned free_ends)
 {
+    if (seq1.empty() || seq2.empty())                       // as in NeedlemanWunsch_mi355x
+        return swmi::NeedlemanWunsch_affine_mi355x_ragged_batch({seq1}, {seq2}, score_matrix, gap_open, gap_extend, free_ends, 1, 1).front();
     return swmi::detail::one_alignment(
         "swmi_global_full_affine", SWMI_GLOBAL_FULL_MOVE_WORDS(seq1.size(), seq2.size()),
         [&](auto... out) {

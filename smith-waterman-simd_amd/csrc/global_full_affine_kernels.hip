@@ -84,15 +84,20 @@ struct GlobalAffine {
     static __device__ __forceinline__ int floor(int m) { return m; }
 };
 
-// free_ends is an argument, not a template parameter: it is uniform, stays in SGPRs, and one pair of kernels serves all 16 masks
-template <bool TB>
+// free_ends is an argument, not a template parameter: it is uniform, stays in SGPRs, and one pair of kernels serves all 16 masks.
+// RAGGED: one TileWork per workgroup (work[blockIdx.x]) names the alignment, and the launch's own shape (fixed_*, move_words)
+// is unused; else `work` is NULL and unread (tile_sweep.h).  The mask and the gaps stay the launch's: one call has one of each.
+template <bool TB, bool RAGGED = false>
 __global__ __launch_bounds__(64 * kMaxWaves) void global_full_affine_kernel(
-    const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ seq2s, int len1, int len2, SmCols cols, int gap_open,
+    const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ seq2s, int fixed_len1, int fixed_len2, SmCols cols, int gap_open,
     int gap_extend, unsigned free_ends, int32_t *__restrict__ scores, int32_t *__restrict__ ends,
     unsigned long long *__restrict__ codes, unsigned long long *__restrict__ moves, uint32_t *__restrict__ counts,
-    uint32_t move_words, uint32_t n_trips)
+    uint32_t move_words, uint32_t fixed_trips, const TileWork *__restrict__ work)
 {
     using V = GlobalAffine;
+    const TileWork slot = load_slot<RAGGED>(work);
+    const int len1 = RAGGED ? (int)slot.len1 : fixed_len1, len2 = RAGGED ? (int)slot.len2 : fixed_len2;
+    const uint32_t n_trips = RAGGED ? (uint32_t)trips(len1) : fixed_trips;
 #include "tile_sweep_affine_body.inc"
 }
 
@@ -110,6 +115,16 @@ hipError_t launch_global_full_affine(const uint8_t *d_seq1s, const uint8_t *d_se
     return tile::launch<global_full_affine_kernel<true>, global_full_affine_kernel<false>>(
         d_seq1s, d_seq2s, len1, len2, n, sm, d_scores, d_ends, d_codes, d_moves, d_steps, move_words, stream, gap_open, gap_extend,
         free_ends);
+}
+
+hipError_t launch_global_full_affine_ragged(const uint8_t *d_seq1s, const uint8_t *d_seq2s, const TileWork *d_work, size_t n,
+                                            int waves, const int8_t *sm, int gap_open, int gap_extend, unsigned free_ends,
+                                            int32_t *d_scores, int32_t *d_ends, unsigned long long *d_codes,
+                                            unsigned long long *d_moves, uint32_t *d_steps, hipStream_t stream)
+{
+    if (free_ends > 15u) return hipErrorInvalidValue;
+    return tile::launch_ragged<global_full_affine_kernel<true, true>, global_full_affine_kernel<false, true>>(
+        d_seq1s, d_seq2s, d_work, n, waves, sm, d_scores, d_ends, d_codes, d_moves, d_steps, stream, gap_open, gap_extend, free_ends);
 }
 
 }  // namespace swmi

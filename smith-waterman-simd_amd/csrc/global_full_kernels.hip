@@ -88,16 +88,23 @@ struct GlobalLinear {
     static __device__ __forceinline__ uint32_t step(uint32_t wd, int cc) { return (wd >> (2 * cc)) & 3u; }
 };
 
-// free_ends is an argument, not a template parameter: it is uniform, stays in SGPRs, and one pair of kernels serves all 16 masks
-template <bool TB>
+// free_ends is an argument, not a template parameter: it is uniform, stays in SGPRs, and one pair of kernels serves all 16 masks.
+// RAGGED: one TileWork per workgroup (work[blockIdx.x]) names the alignment, and the launch's own shape (fixed_*, move_words)
+// is unused; else `work` is NULL and unread (tile_sweep.h).  The mask and the gap stay the launch's: one call has one of each.
+template <bool TB, bool RAGGED = false>
 __global__ __launch_bounds__(64 * kMaxWaves) void global_full_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ seq2s,
-                                                                      int len1, int len2, SmCols cols, int gap, unsigned free_ends,
-                                                                      int32_t *__restrict__ scores, int32_t *__restrict__ ends,
-                                                                      uint32_t *__restrict__ codes, unsigned long long *__restrict__ moves,
-                                                                      uint32_t *__restrict__ counts, uint32_t move_words, uint32_t n_trips)
+                                                                      int fixed_len1, int fixed_len2, SmCols cols, int gap,
+                                                                      unsigned free_ends, int32_t *__restrict__ scores,
+                                                                      int32_t *__restrict__ ends, uint32_t *__restrict__ codes,
+                                                                      unsigned long long *__restrict__ moves, uint32_t *__restrict__ counts,
+                                                                      uint32_t move_words, uint32_t fixed_trips,
+                                                                      const TileWork *__restrict__ work)
 {
     using V = GlobalLinear;
     const V::Gaps gaps{gap, free_ends};
+    const TileWork slot = load_slot<RAGGED>(work);
+    const int len1 = RAGGED ? (int)slot.len1 : fixed_len1, len2 = RAGGED ? (int)slot.len2 : fixed_len2;
+    const uint32_t n_trips = RAGGED ? (uint32_t)trips(len1) : fixed_trips;
 #include "tile_sweep_body.inc"
 }
 
@@ -112,6 +119,17 @@ hipError_t launch_global_full(const uint8_t *d_seq1s, const uint8_t *d_seq2s, in
     if (free_ends > 15u) return hipErrorInvalidValue;
     return tile::launch<global_full_kernel<true>, global_full_kernel<false>>(d_seq1s, d_seq2s, len1, len2, n, sm, d_scores, d_ends, d_codes,
                                                                              d_moves, d_steps, move_words, stream, gap, free_ends);
+}
+
+int global_full_ragged_waves(int len1, int len2) { return len1 > 0 && len2 > 0 ? tile::waves(len2) : 1; }
+
+hipError_t launch_global_full_ragged(const uint8_t *d_seq1s, const uint8_t *d_seq2s, const TileWork *d_work, size_t n, int waves,
+                                     const int8_t *sm, int gap, unsigned free_ends, int32_t *d_scores, int32_t *d_ends,
+                                     uint32_t *d_codes, unsigned long long *d_moves, uint32_t *d_steps, hipStream_t stream)
+{
+    if (free_ends > 15u) return hipErrorInvalidValue;
+    return tile::launch_ragged<global_full_kernel<true, true>, global_full_kernel<false, true>>(
+        d_seq1s, d_seq2s, d_work, n, waves, sm, d_scores, d_ends, d_codes, d_moves, d_steps, stream, gap, free_ends);
 }
 
 }  // namespace swmi

@@ -1,170 +1,40 @@
 // local_full_ragged_api.cpp -- C entries of the two any-length local aligners on a batch of mixed (len1, len2)
-// (swmi_local_full_ragged*, swmi_local_full_affine_ragged*, include/swmi.h).  A batch becomes a TilePlan:
-// a RaggedPlan (swmi_host.h) whose slices are cut in caller order within the fixed-length aligner's budget, with one TileWork
-// per alignment and, per slice, where each wave count's slots start.  Inside a slice the slots are ordered by wave count
-// descending (one launch serves one wave count), then len1 descending (the hardware starts workgroups in order, and longest
-// first evens out the tail), then caller order.  The plan then runs through the slice pipeline of swmi_table.cpp.  This file
-// is the only host source that names the ragged any-length launchers; its name lies outside csrc/swmi_*.cpp, and
+// (swmi_local_full_ragged*, swmi_local_full_affine_ragged*, include/swmi.h).  A batch becomes a TilePlan
+// (tile_ragged_plan.h, which the global aligners' ragged entries share) and runs through the slice pipeline of swmi_table.cpp.
+// This file is the only host source that names the ragged local any-length launchers; its name lies outside csrc/swmi_*.cpp, and
 // local_full_api.cpp and local_full_affine_api.cpp do not refer to it, so the fake-GPU builds of those link without them.
-#include "swmi_host.h"
-
-#include <algorithm>
-#include <array>
+#include "tile_ragged_plan.h"
 
 namespace swmi {
 namespace host {
 namespace {
 
-constexpr int kMaxWaves = 16;            // wave counts of a slot: 1 .. 16 (local_full_ragged_waves)
-
-struct TilePlan : RaggedPlan {
-    bool affine = false;
-    std::vector<TileWork> tiles;                                 // [n]: slice s's slots at [first[s], first[s + 1])
-    // per slice: the slots of wave count W lie at [start[kMaxWaves - W], start[kMaxWaves - W + 1]) of the slice's slots
-    std::vector<std::array<uint32_t, kMaxWaves + 1>> start;
-};
+using namespace tile_plan;
 
 // The launches of one slice: one per wave count present, in descending wave count, on the one stream
 hipError_t launch_tiles(const Table &t, size_t slice, const uint8_t *s1, const uint8_t *s2, const void *work, size_t n, int32_t *scores,
                         int32_t *ends, uint32_t *codes, unsigned long long *moves, uint32_t *counts, hipStream_t st)
 {
     const TilePlan &p = *static_cast<const TilePlan *>(t.plan);
-    const TileWork *slots = static_cast<const TileWork *>(work);
-    const auto &start = p.start[slice];
-    if (start[kMaxWaves] != n) return hipErrorInvalidValue;
-    for (int waves = kMaxWaves; waves >= 1; --waves) {
-        const uint32_t a = start[kMaxWaves - waves], b = start[kMaxWaves - waves + 1];
-        if (a == b) continue;
-        const hipError_t e =
-            p.affine ? swmi::launch_local_full_affine_ragged(s1, s2, slots + a, b - a, waves, t.sm, t.gap, t.gap_extend, scores, ends,
-                                                             reinterpret_cast<unsigned long long *>(codes), moves, counts, st)
-                     : swmi::launch_local_full_ragged(s1, s2, slots + a, b - a, waves, t.sm, t.gap, scores, ends, codes, moves, counts, st);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return for_each_wave_count(p, slice, work, n, [&](const TileWork *slots, size_t m, int waves) {
+        return p.affine ? swmi::launch_local_full_affine_ragged(s1, s2, slots, m, waves, t.sm, t.gap, t.gap_extend, scores, ends,
+                                                                reinterpret_cast<unsigned long long *>(codes), moves, counts, st)
+                        : swmi::launch_local_full_ragged(s1, s2, slots, m, waves, t.sm, t.gap, scores, ends, codes, moves, counts, st);
+    });
 }
 
-// code words of one alignment in the kernel's unit (dwords; affine: qwords); none when a length is 0 (nothing is swept)
-size_t code_words(bool affine, size_t len1, size_t len2)
+size_t family_code_words(bool affine, int len1, int len2)
 {
-    if (!len1 || !len2) return 0;
-    return affine ? swmi::local_full_affine_code_qwords((int)len1, (int)len2) : swmi::local_full_code_words((int)len1, (int)len2);
+    return affine ? swmi::local_full_affine_code_qwords(len1, len2) : swmi::local_full_code_words(len1, len2);
 }
 
-// device bytes one alignment of a ragged slice takes: inputs, its slot, results, and with a traceback codes, moves and count
-size_t ragged_bytes(bool affine, bool tb, size_t len1, size_t len2)
+size_t family_tb_slice_bytes(bool affine)
 {
-    size_t b = len1 + len2 + sizeof(TileWork) + 5 * sizeof(int32_t);
-    if (tb)
-        b += code_words(affine, len1, len2) * (affine ? sizeof(uint64_t) : sizeof(uint32_t)) +
-             SWMI_LOCAL_FULL_MOVE_WORDS(len1, len2) * sizeof(uint64_t) + sizeof(uint32_t);
-    return b;
-}
-
-// the fixed-length aligner's budget for one slice's device buffers
-size_t budget(bool affine, bool tb)
-{
-    if (!tb) return kTableSliceBytes;
     return (affine ? local_full_affine_table(1, 1, nullptr, 0, 0) : local_full_table(1, 1, nullptr, 0)).tb_slice_bytes;
 }
 
-int check_offsets(const char *name, const uint64_t *off, size_t n)
-{
-    if (!off) return fail(SWMI_ERR_INVALID_ARGUMENT, "%s is NULL", name);
-    for (size_t k = 0; k < n; ++k) {
-        if (off[k + 1] < off[k]) return fail(SWMI_ERR_INVALID_ARGUMENT, "%s decrease at %zu", name, k);
-        if (off[k + 1] - off[k] > SWMI_LOCAL_FULL_MAX_LEN)
-            return fail(SWMI_ERR_INVALID_ARGUMENT, "%s: sequence %zu has length %llu > %d", name, k,
-                        (unsigned long long)(off[k + 1] - off[k]), SWMI_LOCAL_FULL_MAX_LEN);
-    }
-    return SWMI_OK;
-}
-
-int check_both(const uint64_t *off1, const uint64_t *off2, size_t n)
-{
-    const int rc = check_offsets("seq1_offsets", off1, n);
-    return rc != SWMI_OK ? rc : check_offsets("seq2_offsets", off2, n);
-}
-
-int check_affine_gaps(const int8_t *sm, int gap_open, int gap_extend)
-{
-    if (!sm) return fail(SWMI_ERR_INVALID_ARGUMENT, "score_matrix is NULL");
-    if (gap_open < 0 || gap_open > 127 || gap_extend < 0 || gap_extend > 127)
-        return fail(SWMI_ERR_DOMAIN, "gap_open %d / gap_extend %d outside [0,127]", gap_open, gap_extend);
-    return SWMI_OK;
-}
-
-// Slices of checked offsets: each the longest run from where the last one ended whose ragged_bytes fit the budget, at most
-// kTableMaxSlice alignments and at least one.  first = {0, ..., n}.
-std::vector<size_t> cut(const uint64_t *off1, const uint64_t *off2, size_t n, bool affine, bool tb)
-{
-    const size_t cap = budget(affine, tb);
-    std::vector<size_t> first{0};
-    size_t bytes = 0, m = 0;
-    for (size_t k = 0; k < n; ++k) {
-        const size_t b = ragged_bytes(affine, tb, size_t(off1[k + 1] - off1[k]), size_t(off2[k + 1] - off2[k]));
-        if (m && (bytes + b > cap || m == kTableMaxSlice)) {
-            first.push_back(k);
-            bytes = m = 0;
-        }
-        bytes += b;
-        ++m;
-    }
-    if (n) first.push_back(n);
-    return first;
-}
-
-void fill_move_offsets(const uint64_t *off1, const uint64_t *off2, size_t n, uint64_t *out)
-{
-    out[0] = 0;
-    for (size_t k = 0; k < n; ++k) out[k + 1] = out[k] + SWMI_LOCAL_FULL_MOVE_WORDS(off1[k + 1] - off1[k], off2[k + 1] - off2[k]);
-}
-
-// The plan of a checked batch.  Every TileWork offset and base is a 64-bit running sum relative to its slice (swmi_internal.h
-// says why 32 bits would not do); code bases run in caller order, so a slice's codes are one block of code_words[s] dwords.
-void make_plan(TilePlan &p, const uint64_t *off1, const uint64_t *off2, size_t n, bool affine, bool tb)
-{
-    p.launch = launch_tiles;
-    p.affine = affine;
-    p.seq1_offsets = off1;
-    p.seq2_offsets = off2;
-    p.move_offsets.resize(n + 1);
-    fill_move_offsets(off1, off2, n, p.move_offsets.data());
-    p.first = cut(off1, off2, n, affine, tb);
-    p.tiles.resize(n);
-    p.slots = p.tiles.data();
-    p.slot_bytes = sizeof(TileWork);
-    const size_t slices = p.first.size() - 1;
-    p.code_words.assign(slices, 0);
-    p.start.resize(slices);
-    // counting sort on (wave count, len1), both descending, equal keys in caller order: bucket = (16 - W) * 16385 + (16384 - len1)
-    constexpr size_t kLens = SWMI_LOCAL_FULL_MAX_LEN + 1;
-    std::vector<uint32_t> at(kMaxWaves * kLens + 1);
-    for (size_t s = 0; s < slices; ++s) {
-        const size_t a = p.first[s], b = p.first[s + 1];
-        auto bucket = [&](size_t k) {
-            const int len1 = int(off1[k + 1] - off1[k]), len2 = int(off2[k + 1] - off2[k]);
-            return size_t(kMaxWaves - swmi::local_full_ragged_waves(len1, len2)) * kLens + size_t(SWMI_LOCAL_FULL_MAX_LEN - len1);
-        };
-        std::fill(at.begin(), at.end(), 0u);
-        for (size_t k = a; k < b; ++k) ++at[bucket(k) + 1];
-        for (size_t x = 1; x < at.size(); ++x) at[x] += at[x - 1];
-        for (int j = 0; j <= kMaxWaves; ++j) p.start[s][j] = at[size_t(j) * kLens];
-        uint64_t codes = 0;
-        for (size_t k = a; k < b; ++k) {
-            const uint32_t len1 = uint32_t(off1[k + 1] - off1[k]), len2 = uint32_t(off2[k + 1] - off2[k]);
-            p.tiles[a + at[bucket(k)]++] = {off1[k] - off1[a], off2[k] - off2[a], codes, p.move_offsets[k] - p.move_offsets[a],
-                                            uint32_t(k - a), len1, len2, 0};
-            if (tb) codes += code_words(affine, len1, len2);
-        }
-        p.code_words[s] = size_t(codes) * (affine ? 2 : 1);
-        p.max_m = std::max(p.max_m, b - a);
-        p.max_seq1 = std::max(p.max_seq1, size_t(off1[b] - off1[a]));
-        p.max_seq2 = std::max(p.max_seq2, size_t(off2[b] - off2[a]));
-        p.max_codes = std::max(p.max_codes, p.code_words[s]);
-        p.max_moves = std::max(p.max_moves, size_t(p.move_offsets[b] - p.move_offsets[a]));
-    }
-}
+// what the planner of tile_ragged_plan.h takes from this family
+constexpr TileFamily kLocal{launch_tiles, swmi::local_full_ragged_waves, family_code_words, family_tb_slice_bytes};
 
 // checks shared by the host and the device entries, in the order of the fixed-length ones; then the call
 int ragged(bool affine, bool device, const char *entry, const void *seq1s, const uint64_t *off1, const void *seq2s, const uint64_t *off2,
@@ -178,7 +48,7 @@ int ragged(bool affine, bool device, const char *entry, const void *seq1s, const
     rc = check_both(off1, off2, n);
     if (rc != SWMI_OK) return rc;
     TilePlan plan;
-    make_plan(plan, off1, off2, n, affine, moves != nullptr);
+    make_plan(plan, kLocal, off1, off2, n, affine, moves != nullptr);
     Table t = affine ? local_full_affine_table(1, 1, sm, gap, gap_extend) : local_full_table(1, 1, sm, gap);
     t.plan = &plan;
     if (device) return table_device(t, seq1s, seq2s, n, scores, ends, moves, steps, stream);
@@ -189,37 +59,18 @@ int ragged(bool affine, bool device, const char *entry, const void *seq1s, const
 
 }  // namespace
 
-// The plan alone, for a test of its arithmetic at sizes no test can allocate: per slice its alignments and device bytes, and
-// whether every code base equals the 64-bit running sum of the code words before it.  Not part of the C ABI.
+// The plan alone, for a test of its arithmetic at sizes no test can allocate (tile_ragged_plan.h).  Not part of the C ABI.
 bool local_full_ragged_plan_check(const uint64_t *off1, const uint64_t *off2, size_t n, bool affine, bool tb,
                                   std::vector<size_t> *slice_sizes, std::vector<size_t> *slice_bytes)
 {
-    TilePlan p;
-    make_plan(p, off1, off2, n, affine, tb);
-    bool ok = true;
-    for (size_t s = 0; s + 1 < p.first.size(); ++s) {
-        const size_t a = p.first[s], b = p.first[s + 1];
-        std::vector<uint64_t> base(b - a);
-        size_t bytes = 0;
-        uint64_t codes = 0;
-        for (size_t k = a; k < b; ++k) {
-            const size_t len1 = size_t(off1[k + 1] - off1[k]), len2 = size_t(off2[k + 1] - off2[k]);
-            base[k - a] = codes;
-            if (tb) codes += code_words(affine, len1, len2);
-            bytes += ragged_bytes(affine, tb, len1, len2);
-        }
-        for (size_t x = a; x < b; ++x) ok = ok && p.tiles[x].k < b - a && p.tiles[x].code_base == base[p.tiles[x].k];
-        ok = ok && p.code_words[s] == codes * (affine ? 2 : 1);
-        slice_sizes->push_back(b - a);
-        slice_bytes->push_back(bytes);
-    }
-    return ok;
+    return plan_check(kLocal, off1, off2, n, affine, tb, slice_sizes, slice_bytes);
 }
 
 }  // namespace host
 }  // namespace swmi
 
 using namespace swmi::host;
+using namespace swmi::host::tile_plan;
 
 extern "C" {
 
@@ -235,10 +86,7 @@ int swmi_local_full_ragged_move_offsets(const uint64_t *seq1_offsets, const uint
 size_t swmi_local_full_ragged_slices_for(const uint64_t *seq1_offsets, const uint64_t *seq2_offsets, size_t n, int affine,
                                          int traceback, size_t *sizes, size_t cap)
 {
-    if (check_both(seq1_offsets, seq2_offsets, n) != SWMI_OK) return 0;
-    const std::vector<size_t> first = cut(seq1_offsets, seq2_offsets, n, affine != 0, traceback != 0);
-    for (size_t s = 0; sizes && s + 1 < first.size() && s < cap; ++s) sizes[s] = first[s + 1] - first[s];
-    return first.size() - 1;
+    return slices_for(kLocal, seq1_offsets, seq2_offsets, n, affine != 0, traceback != 0, sizes, cap);
 }
 
 int swmi_local_full_ragged(const uint8_t *seq1s, const uint64_t *seq1_offsets, const uint8_t *seq2s, const uint64_t *seq2_offsets,

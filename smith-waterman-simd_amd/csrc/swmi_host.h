@@ -213,7 +213,7 @@ using RaggedLaunch = hipError_t (*)(const Table &t, size_t slice, const uint8_t 
                                     int32_t *scores, int32_t *ends, uint32_t *codes, unsigned long long *moves, uint32_t *counts,
                                     hipStream_t st);
 // A batch with lengths of its own per alignment: the local aligners' with a seq1 length each (local_ragged_api.cpp), the
-// any-length local aligners' with a seq1 and a seq2 length each (local_full_ragged_api.cpp).  Its slices, contiguous in caller
+// any-length local and global aligners' with a seq1 and a seq2 length each (local_full_ragged_api.cpp, global_full_ragged_api.cpp).  Its slices, contiguous in caller
 // order, and one slot per alignment (LocalWork or TileWork: the pipeline copies slots as bytes and hands them to `launch`),
 // slice-relative, in the order the plan's owner gave the slots of each slice.
 struct RaggedPlan {
@@ -265,6 +265,9 @@ Table global_full_affine_table(size_t len1, size_t len2, const int8_t *sm, int g
 // its alignments and device bytes; true when every code base equals the 64-bit running sum of the code words before it
 bool local_full_ragged_plan_check(const uint64_t *seq1_offsets, const uint64_t *seq2_offsets, size_t n, bool affine, bool tb,
                                   std::vector<size_t> *slice_sizes, std::vector<size_t> *slice_bytes);
+// global_full_ragged_api.cpp: the same for a ragged batch of the global aligners (one planner, tile_ragged_plan.h)
+bool global_full_ragged_plan_check(const uint64_t *seq1_offsets, const uint64_t *seq2_offsets, size_t n, bool affine, bool tb,
+                                   std::vector<size_t> *slice_sizes, std::vector<size_t> *slice_bytes);
 // Free one aligner's device buffers on the current GPU (synchronises the device first): the body of the *_release_workspaces entries
 int table_release_workspaces(std::shared_ptr<void> Context::*member);
 

@@ -205,3 +205,17 @@ hipError_t launch_global_full_affine(const uint8_t *d_seq1s, const uint8_t *d_se
                                      unsigned long long *d_codes, unsigned long long *d_moves, uint32_t *d_steps, size_t move_words,
                                      hipStream_t stream);
 }  // namespace swmi
+
+namespace swmi {
+// The ragged launches of the two global aligners: launch_local_full_ragged's slots, wave counts and
+// buffers, with the call's one mask.  A slot with a zero length runs in a workgroup of one wavefront and writes the closed
+// form of its one border (tile_sweep.h, end_rule_zero_length): it takes no code words, but its move words.
+int global_full_ragged_waves(int len1, int len2);
+hipError_t launch_global_full_ragged(const uint8_t *d_seq1s, const uint8_t *d_seq2s, const TileWork *d_work, size_t n, int waves,
+                                     const int8_t *sm, int gap, unsigned free_ends, int32_t *d_scores, int32_t *d_ends,
+                                     uint32_t *d_codes, unsigned long long *d_moves, uint32_t *d_steps, hipStream_t stream);
+hipError_t launch_global_full_affine_ragged(const uint8_t *d_seq1s, const uint8_t *d_seq2s, const TileWork *d_work, size_t n,
+                                            int waves, const int8_t *sm, int gap_open, int gap_extend, unsigned free_ends,
+                                            int32_t *d_scores, int32_t *d_ends, unsigned long long *d_codes,
+                                            unsigned long long *d_moves, uint32_t *d_steps, hipStream_t stream);
+}  // namespace swmi

@@ -80,7 +80,7 @@
 // linear body reads row i's from the finished row: the body says why.  Thread 0 packs the two border cells before the sweep
 // and keeps them in VGPRs.  The last row, the corner, the reduction and the walk's tail are the linear body's.
 //
-// Ragged launches (the two local kernels): a kernel with a template parameter RAGGED has a last
+// Ragged launches (the two local and the two global kernels; DESIGN.md sections 19 and 22): a kernel with a template parameter RAGGED has a last
 // parameter `work` (NULL and unread in a fixed launch; last, so that every other argument lies where it did), and with RAGGED
 // takes its alignment from one TileWork per workgroup, `slot` = work[blockIdx.x], instead of from k = blockIdx.x and the
 // launch's one (len1, len2): its sequences, lengths, trips, code block, move row and result index.  The slot is loaded through an address
@@ -88,7 +88,8 @@
 // a ragged form (the semi-global pair) finds tile::RAGGED = false and an empty tile::slot below, and a kernel with one shadows both.  One
 // launch serves one wave count: every slot of a launch has W = blockDim.x >> 6, so no wave ever leaves before the
 // workgroup's last barrier -- except that a slot with a zero length, which runs in a W = 1 launch, returns as a whole
-// workgroup, on a uniform test, before the first barrier and before any load from either sequence.
+// workgroup, on a uniform test, before the first barrier and before any load from either sequence.  What it writes first is
+// the local aligners' "score 0", or with the end rule the closed form of end_rule_zero_length below.
 //
 // Why the bodies are includes, and why there are two: this compiler optimises a function on its own before it inlines it.
 // A body behind a call -- even the unchanged kernel moved into a forceinline function -- is optimised twice and came out
@@ -189,12 +190,53 @@ __device__ __forceinline__ uint4 code_quad(const unsigned long long *c)
     return make_uint4((uint32_t)c[0], (uint32_t)(c[0] >> 32), (uint32_t)c[1], (uint32_t)(c[1] >> 32));
 }
 
+// v itself, which with ON the compiler may not look through: nothing derived from the result is computed before this point.
+// The end rule's ragged kernels read len2 through it after the sweep.  Without it the compiler evaluates the last row's sixteen
+// column tests (j <= len2, j == len2) before the sweep and keeps the lane masks in SGPR pairs across it; the fixed-length
+// kernels fit that in their SGPRs with none to spare, the ragged ones, with a slot to hold, spilled up to 7 SGPRs into a VGPR.
+template <bool ON>
+__device__ __forceinline__ int opaque(int v)
+{
+    if constexpr (ON) asm volatile("" : "+s"(v));
+    return v;
+}
+
 // the slot of a ragged launch's workgroup; nothing is loaded for a fixed launch
 template <bool RAGGED>
 __device__ __forceinline__ TileWork load_slot(const TileWork *work)
 {
     if constexpr (RAGGED) return work[blockIdx.x];
     else return TileWork{};
+}
+
+// A ragged slot with a zero length under the end rule: the table is one border, `steps` = the other
+// sequence's length cells long, and everything is a closed form of the mask.  With len2 == 0 the border is column 0 (its
+// begin flag kFreeBegin1, its end flag kFreeEnd1, the forced move "up" = 2), with len1 == 0 row 0 (kFreeBegin2, kFreeEnd2,
+// "left" = 1); `cost` is what the whole border costs as one gap.  A free end: every border cell holds at most 0 and (0, 0)
+// holds 0 and comes first, so the end cell is (0, 0) -- also at gap 0.  Else the end cell is the far corner: with a free
+// begin it holds 0 and the walk ends on it, else it holds -cost and the walk is `steps` forced moves, whole words of one
+// code (bits past the last step are unspecified).  The slot's workgroup is one wavefront; it writes the words lane-strided,
+// with vector stores, inside the slot's move row.  No byte of either sequence is read.
+template <bool TB>
+__device__ __forceinline__ void end_rule_zero_length(int len1, int len2, unsigned free_ends, int cost, size_t k, int32_t *scores,
+                                                     int32_t *ends, unsigned long long *mv, uint32_t *counts)
+{
+    const bool up = len2 == 0;
+    const bool forced = (len1 | len2) != 0 && !(free_ends & (up ? kFreeEnd1 : kFreeEnd2));   // the end cell is the far corner
+    const bool walks = forced && !(free_ends & (up ? kFreeBegin1 : kFreeBegin2));
+    const uint32_t steps = walks ? (uint32_t)(len1 + len2) : 0u;
+    if (threadIdx.x == 0) {
+        scores[k] = walks ? -cost : 0;
+        ends[4 * k + 0] = forced ? len1 : 0;
+        ends[4 * k + 1] = forced ? len2 : 0;
+        ends[4 * k + 2] = !TB ? -1 : forced && !walks ? len1 : 0;
+        ends[4 * k + 3] = !TB ? -1 : forced && !walks ? len2 : 0;
+        if constexpr (TB) counts[k] = steps;
+    }
+    if constexpr (TB) {
+        const unsigned long long word = up ? 0xAAAAAAAAAAAAAAAAull : 0x5555555555555555ull;
+        for (uint32_t x = threadIdx.x; x < (steps + 31) >> 5; x += blockDim.x) mv[x] = word;
+    }
 }
 
 // launches k with `args`, and with a last argument of nullptr when k takes one more (the `work` of a kernel with a ragged form)

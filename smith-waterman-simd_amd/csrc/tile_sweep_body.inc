@@ -17,7 +17,11 @@
     if constexpr (RAGGED) {
         // a slot with a zero length: the whole workgroup (one wavefront) leaves here, before any barrier and any sequence load
         if (len1 == 0 || len2 == 0) {
-            if (tid == 0) {
+            if constexpr (kEndRule<V>) {
+                // the end rule's closed form of one border (tile_sweep.h); a linear gap run of L cells costs L gap
+                end_rule_zero_length<TB>(len1, len2, free_ends, (len1 + len2) * gaps.gap, k, scores, ends,
+                                         TB ? moves + (size_t)slot.move_base : nullptr, counts);
+            } else if (tid == 0) {
                 scores[k] = 0;
                 ends[V::kEnds * k + 0] = 0;
                 ends[V::kEnds * k + 1] = 0;
@@ -145,20 +149,21 @@
         // the lane's candidates (tile_sweep.h): key[] holds row len1 now.  Last row, columns past len2 masked out; the
         // corner; the last column's best; thread 0 adds the two border cells, which are closed forms
         r = 0;
+        const int len2_e = opaque<RAGGED>(len2);   // len2, not before the sweep in a ragged kernel (tile_sweep.h)
         int last = V::kRowMin, corner = V::kRowMin;
 #pragma unroll
         for (int jj = 0; jj < kCols; ++jj) {
             const int j = jbase + jj + 1;
-            if (j <= len2 && key[jj] > last) last = key[jj];
-            if (j == len2) corner = key[jj];
+            if (j <= len2_e && key[jj] > last) last = key[jj];
+            if (j == len2_e) corner = key[jj];
         }
-        if ((free_ends & kFreeEnd2) && jbase < len2) r = end_pack(last >> 6, len1, jbase + (kCols - 1 - (last & 15)) + 1);
-        if (G == (len2 - 1) >> 4) {
-            r = umax64(r, end_pack(corner >> 6, len1, len2));
-            if (end_col_lane) r = umax64(r, end_pack(best >> 6, best_row, len2));
+        if ((free_ends & kFreeEnd2) && jbase < len2_e) r = end_pack(last >> 6, len1, jbase + (kCols - 1 - (last & 15)) + 1);
+        if (G == (len2_e - 1) >> 4) {
+            r = umax64(r, end_pack(corner >> 6, len1, len2_e));
+            if (end_col_lane) r = umax64(r, end_pack(best >> 6, best_row, len2_e));
         }
         if (tid == 0) {
-            if (free_ends & kFreeEnd1) r = umax64(r, end_pack(lane.border(-len2) >> 6, 0, len2));
+            if (free_ends & kFreeEnd1) r = umax64(r, end_pack(lane.border(-len2_e) >> 6, 0, len2_e));
             if (free_ends & kFreeEnd2) r = umax64(r, end_pack(lane.left_border(-len1) >> 6, len1, 0));
         }
     } else {

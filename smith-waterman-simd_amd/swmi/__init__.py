@@ -138,7 +138,9 @@ def load():
             ("swmi_local_full_affine_ragged", None, None, ragged2, [ci, ci]),
             ("swmi_global_full", "swmi_global_full_time_device", "swmi_global_full_slices_for", two_lens, [i8, cu]),
             ("swmi_global_full_affine", "swmi_global_full_affine_time_device", "swmi_global_full_affine_slices_for", two_lens,
-             [ci, ci, cu])):
+             [ci, ci, cu]),
+            ("swmi_global_full_ragged", None, None, ragged2, [i8, cu]),
+            ("swmi_global_full_affine_ragged", None, None, ragged2, [ci, ci, cu])):
         args = shape + [vp] + gap + [vp, vp, vp, vp]
         getattr(lib, host).argtypes = args
         getattr(lib, host + "_device").argtypes = args + [vp]
@@ -154,6 +156,8 @@ def load():
     lib.swmi_local_full_ragged_move_offsets.argtypes = [vp, vp, sz, vp]
     lib.swmi_local_full_ragged_slices_for.argtypes = [vp, vp, sz, ci, ci, vp, sz]
     lib.swmi_local_full_ragged_slices_for.restype = sz
+    lib.swmi_global_full_ragged_slices_for.argtypes = [vp, vp, sz, ci, ci, vp, sz]
+    lib.swmi_global_full_ragged_slices_for.restype = sz
     _lib = lib
     return lib
 
@@ -1182,3 +1186,4 @@ class Queue:
 # The affine global / free-end-gap aligner's wrappers live in a submodule, swmi.global_affine.<name>: imported as a module
 # (last, when every helper it takes from here is defined), its functions stay out of this namespace.
 from . import global_affine    # noqa: E402
+from . import global_ragged    # noqa: E402  (the global aligners on mixed-shape batches, likewise a submodule)
