@@ -105,6 +105,21 @@ inline std::pair<int, std::vector<std::pair<int, int>>> NeedlemanWunsch_affine_m
                                                                                      int gap_open, int gap_extend,
                                                                                      unsigned free_ends = SWMI_ENDS_GLOBAL);
 
+// NeedlemanWunsch_mi355x and NeedlemanWunsch_affine_mi355x for lengths in [1, 65536] (swmi_global_long, swmi_global_long_affine):
+// the same results, accepted iff max(1, |score|, gaps) * (len1 + len2) <= 2^23 (include/swmi.h), which holds for every shape
+// up to 32768 x 32768.  One synchronous call per alignment; swmi::NeedlemanWunsch_long_mi355x_batch and
+// swmi::NeedlemanWunsch_long_affine_mi355x_batch are the throughput forms.
+inline std::pair<int, std::vector<std::pair<int, int>>> NeedlemanWunsch_long_mi355x(const std::vector<uint8_t> &seq1,
+                                                                                   const std::vector<uint8_t> &seq2,
+                                                                                   const std::array<int8_t, 16> &score_matrix,
+                                                                                   const int8_t gap_penalty,
+                                                                                   unsigned free_ends = SWMI_ENDS_GLOBAL);
+inline std::pair<int, std::vector<std::pair<int, int>>> NeedlemanWunsch_long_affine_mi355x(const std::vector<uint8_t> &seq1,
+                                                                                          const std::vector<uint8_t> &seq2,
+                                                                                          const std::array<int8_t, 16> &score_matrix,
+                                                                                          int gap_open, int gap_extend,
+                                                                                          unsigned free_ends = SWMI_ENDS_GLOBAL);
+
 namespace swmi {
 
 // match 1, mismatch -1 (source.cpp:1786)
@@ -328,6 +343,14 @@ inline std::vector<std::pair<int, int>> semiglobal_path(const uint64_t *moves, u
 inline std::vector<std::pair<int, int>> local_full_path(const uint64_t *moves, uint32_t steps, const int32_t *ends)
 {
     return expand_local_full_moves(moves, steps, ends[0], ends[1]);
+}
+// ... and the long global aligners' (end cells up to (65536, 65536))
+inline std::vector<std::pair<int, int>> global_long_path(const uint64_t *moves, uint32_t steps, const int32_t *ends)
+{
+    std::vector<std::pair<int, int>> path(size_t(steps) + 1);
+    detail::check(swmi_global_long_expand_moves(moves, steps, ends[0], ends[1], reinterpret_cast<int32_t *>(path.data()), path.size()),
+                  "swmi_global_long_expand_moves");
+    return path;
 }
 
 }  // namespace detail
@@ -553,6 +576,38 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> NeedlemanWu
             return swmi_global_full_affine(a, len1, b, len2, m, score_matrix.data(), gap_open, gap_extend, free_ends, out...);
         },
         detail::local_full_path);
+}
+
+// NeedlemanWunsch_mi355x_batch for lengths in [1, 65536]: result[k] == NeedlemanWunsch_long_mi355x(seq1s[k], seq2s[k], ...).  A
+// piece is at most one traceback slice of swmi_global_long (0 = one slice: 16 at 65536 x 65536).
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> NeedlemanWunsch_long_mi355x_batch(
+    const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::vector<uint8_t>> &seq2s,
+    const std::array<int8_t, 16> &score_matrix, const int8_t gap_penalty, unsigned free_ends = SWMI_ENDS_GLOBAL, size_t piece = 0,
+    unsigned threads = 0)
+{
+    return detail::shaped_batch(
+        "NeedlemanWunsch_long_mi355x_batch", "swmi_global_long", seq1s, seq2s, piece, threads, 4,
+        SWMI_GLOBAL_LONG_MOVE_WORDS(detail::common_length(seq1s), detail::common_length(seq2s)), swmi_global_long_slices_for,
+        [&](const uint8_t *a, size_t len1, const uint8_t *b, size_t len2, size_t m, auto... out) {
+            return swmi_global_long(a, len1, b, len2, m, score_matrix.data(), gap_penalty, free_ends, out...);
+        },
+        detail::global_long_path);
+}
+
+// NeedlemanWunsch_affine_mi355x_batch for lengths in [1, 65536]: result[k] == NeedlemanWunsch_long_affine_mi355x(seq1s[k],
+// seq2s[k], ...).  A piece is at most one traceback slice of swmi_global_long_affine.
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> NeedlemanWunsch_long_affine_mi355x_batch(
+    const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::vector<uint8_t>> &seq2s,
+    const std::array<int8_t, 16> &score_matrix, int gap_open, int gap_extend, unsigned free_ends = SWMI_ENDS_GLOBAL, size_t piece = 0,
+    unsigned threads = 0)
+{
+    return detail::shaped_batch(
+        "NeedlemanWunsch_long_affine_mi355x_batch", "swmi_global_long_affine", seq1s, seq2s, piece, threads, 4,
+        SWMI_GLOBAL_LONG_MOVE_WORDS(detail::common_length(seq1s), detail::common_length(seq2s)), swmi_global_long_affine_slices_for,
+        [&](const uint8_t *a, size_t len1, const uint8_t *b, size_t len2, size_t m, auto... out) {
+            return swmi_global_long_affine(a, len1, b, len2, m, score_matrix.data(), gap_open, gap_extend, free_ends, out...);
+        },
+        detail::global_long_path);
 }
 
 // Any-length affine local alignment of seq1s[k] against seq2s[k], every seq1 of one length and every seq2 of one length:
@@ -829,6 +884,34 @@ inline std::pair<int, std::vector<std::pair<int, int>>> NeedlemanWunsch_affine_m
                                            gap_extend, free_ends, out...);
         },
         swmi::detail::local_full_path);
+}
+
+inline std::pair<int, std::vector<std::pair<int, int>>> NeedlemanWunsch_long_mi355x(const std::vector<uint8_t> &seq1,
+                                                                                   const std::vector<uint8_t> &seq2,
+                                                                                   const std::array<int8_t, 16> &score_matrix,
+                                                                                   const int8_t gap_penalty, unsigned free_ends)
+{
+    return swmi::detail::one_alignment(
+        "swmi_global_long", SWMI_GLOBAL_LONG_MOVE_WORDS(seq1.size(), seq2.size()),
+        [&](auto... out) {
+            return swmi_global_long(seq1.data(), seq1.size(), seq2.data(), seq2.size(), 1, score_matrix.data(), gap_penalty, free_ends,
+                                    out...);
+        },
+        swmi::detail::global_long_path);
+}
+
+inline std::pair<int, std::vector<std::pair<int, int>>> NeedlemanWunsch_long_affine_mi355x(const std::vector<uint8_t> &seq1,
+                                                                                          const std::vector<uint8_t> &seq2,
+                                                                                          const std::array<int8_t, 16> &score_matrix,
+                                                                                          int gap_open, int gap_extend, unsigned free_ends)
+{
+    return swmi::detail::one_alignment(
+        "swmi_global_long_affine", SWMI_GLOBAL_LONG_MOVE_WORDS(seq1.size(), seq2.size()),
+        [&](auto... out) {
+            return swmi_global_long_affine(seq1.data(), seq1.size(), seq2.data(), seq2.size(), 1, score_matrix.data(), gap_open,
+                                           gap_extend, free_ends, out...);
+        },
+        swmi::detail::global_long_path);
 }
 
 inline std::pair<int, std::vector<std::pair<int, int>>> SemiGlobal_111_mi355x(const std::array<uint8_t, 16384> &seq1,

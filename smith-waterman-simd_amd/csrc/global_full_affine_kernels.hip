@@ -43,7 +43,7 @@
 //
 // Walk: no code stops it; E(1,j) and F(i,1) always open, so it reaches row 0 or column 0 in state H, and there the end rule's
 // tail takes over.  An end cell on a border never enters the staged loop.
-#include "tile_sweep.h"
+#include "global_full_affine_variant.h"
 
 namespace swmi {
 namespace {
@@ -62,27 +62,6 @@ constexpr int kStageRows = 128;
 static_assert(kCols == tile::kCols && kMaxWaves == tile::kMaxWaves && kUnroll == tile::kUnroll && kChunk == tile::kChunk &&
               kDelay == tile::kDelay && kRing == tile::kRing && kStageRows == tile::kStageRows);
 }  // namespace written_for
-
-struct GlobalAffine {
-    static constexpr bool kWalkStops = false;
-    static constexpr bool kFreeEnds = true;        // the end rule of tile_sweep.h
-    static constexpr int kEnds = 4;
-    static constexpr int kRowMin = (int)0x80000000;
-    static constexpr int kTagH = 3 << 4;
-    static constexpr int kTagE = 2 << 4;
-    static constexpr int kTagF = 1 << 4;
-    static constexpr int kOpenBitE = 4;            // kTagH has it, kTagE has not
-    static constexpr int kOpenBitF = 5;            // kTagH has it, kTagF has not
-
-    // H(0, j) or H(j, 0) for j >= 1 (and 0 at j = 0) as a stored key, from THAT border's open and extend (0, 0 where it is free)
-    static __device__ __forceinline__ int border(int j, int gap_open, int gap_extend)
-    {
-        const int h = j > 0 ? -(gap_open + (j - 1) * gap_extend) : 0;
-        return (h << 6) | kTagH;
-    }
-    static __device__ __forceinline__ int row0(int, int j, int gap_open, int gap_extend) { return border(j, gap_open, gap_extend); }
-    static __device__ __forceinline__ int floor(int m) { return m; }
-};
 
 // free_ends is an argument, not a template parameter: it is uniform, stays in SGPRs, and one pair of kernels serves all 16 masks.
 // RAGGED: one TileWork per workgroup (work[blockIdx.x]) names the alignment, and the launch's own shape (fixed_*, move_words)

@@ -24,7 +24,7 @@
 //
 // Codes: 2 bits per cell, one dword per lane and row, column jj at bits 2 jj: the move itself (3 / 2 / 1).  A staging block
 // of the walk is 128 rows x 64 lanes (1024 columns).
-#include "tile_sweep.h"
+#include "global_full_variant.h"
 
 namespace swmi {
 namespace {
@@ -43,50 +43,6 @@ constexpr int kStageRows = 128;
 static_assert(kCols == tile::kCols && kMaxWaves == tile::kMaxWaves && kUnroll == tile::kUnroll && kChunk == tile::kChunk &&
               kDelay == tile::kDelay && kRing == tile::kRing && kStageRows == tile::kStageRows);
 }  // namespace written_for
-
-constexpr int kTag3 = 3 << 4;
-
-// the stored key of -n gap from nn = -n, column bits aside
-__device__ __forceinline__ int border_key(int nn, int gap) { return ((nn * gap) << 6) | kTag3; }
-
-struct GlobalLinear {
-    static constexpr bool kWalkStops = false;
-    static constexpr bool kFreeEnds = true;      // the end rule of tile_sweep.h
-    static constexpr int kEnds = 4;
-    static constexpr int kStageLanes = 64;
-    static constexpr int kRowMin = (int)0x80000000;
-    static constexpr int kZeroKey = kTag3;       // the stored key of H = 0, column bits aside
-
-    struct Gaps {
-        int gap;
-        unsigned free_ends;
-    };
-    int g_up, g_left, gap_row0, gap_col0;        // gap_row0, gap_col0: what a step along row 0 / column 0 costs
-
-    __device__ __forceinline__ explicit GlobalLinear(Gaps g)
-        : g_up(-(g.gap << 6) - (1 << 4)), g_left(-(g.gap << 6) - (2 << 4)), gap_row0(g.free_ends & kFreeBegin2 ? 0 : g.gap),
-          gap_col0(g.free_ends & kFreeBegin1 ? 0 : g.gap)
-    {
-    }
-
-    static __device__ __forceinline__ int row0(int, int nj, Gaps g) { return border_key(nj, g.free_ends & kFreeBegin2 ? 0 : g.gap); }
-    __device__ __forceinline__ int border(int nj) const { return border_key(nj, gap_row0); }
-    __device__ __forceinline__ int left_border(int nrow) const { return border_key(nrow, gap_col0); }
-
-    template <bool TB>
-    __device__ __forceinline__ int cell(int jj, int sc, int &d, int &lft, int &key, uint32_t &code) const
-    {
-        const int m = max3(d + (sc << 6), key + g_up, lft + g_left);
-        const int nk = (m & ~63) | (kTag3 | (kCols - 1 - jj));
-        if constexpr (TB) code = ((uint32_t)(m >> 4) & 3u) << (2 * jj);
-        d = key;
-        key = nk;
-        lft = nk;
-        return nk;
-    }
-
-    static __device__ __forceinline__ uint32_t step(uint32_t wd, int cc) { return (wd >> (2 * cc)) & 3u; }
-};
 
 // free_ends is an argument, not a template parameter: it is uniform, stays in SGPRs, and one pair of kernels serves all 16 masks.
 // RAGGED: one TileWork per workgroup (work[blockIdx.x]) names the alignment, and the launch's own shape (fixed_*, move_words)

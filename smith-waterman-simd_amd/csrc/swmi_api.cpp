@@ -677,6 +677,8 @@ void destroy_context(Context &c)
     c.local_full_affine_state.reset();
     c.global_full_state.reset();
     c.global_full_affine_state.reset();
+    c.global_long_state.reset();
+    c.global_long_affine_state.reset();
     if (c.pin) (void)hipHostFree(c.pin);
     c.pin = nullptr;
     c.pin_dev = nullptr;

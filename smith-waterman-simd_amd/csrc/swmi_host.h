@@ -177,6 +177,8 @@ struct Context {
     std::shared_ptr<void> local_full_affine_state;  // the any-length affine local aligner's (local_full_affine_api.cpp, likewise)
     std::shared_ptr<void> global_full_state;    // the global / free-end-gap aligner's (global_full_api.cpp, likewise)
     std::shared_ptr<void> global_full_affine_state;  // the affine global / free-end-gap aligner's (global_full_affine_api.cpp, likewise)
+    std::shared_ptr<void> global_long_state;         // the striped global aligner's (global_long_api.cpp, likewise)
+    std::shared_ptr<void> global_long_affine_state;  // the striped affine global aligner's (global_long_affine_api.cpp, likewise)
     std::mutex mu;                      // serialises use of the slots, the sg sets and the pinned buffer
 };
 
@@ -242,6 +244,11 @@ struct Table {
     int gap, gap_extend;        // gap_extend: the affine aligner's (gap is then the open cost)
     const RaggedPlan *plan = nullptr;   // a ragged batch: len1, code_words and move_words unused, slices as the plan says
     unsigned free_ends = 0;             // the global aligners' mask of SWMI_FREE_*, which their slice launchers read
+    // The striped global aligners' carry (global_long_api.cpp): dwords per alignment of device scratch that a slice's kernel needs
+    // with or without a traceback, counted in a slice's bytes; the pipeline allocates it beside the codes and hands the launcher
+    // a copy of the Table whose `carry` points at the slice's (NULL where carry_words is 0).
+    size_t carry_words = 0;
+    int32_t *carry = nullptr;
 };
 constexpr size_t kTableSliceBytes = size_t(256) << 20;
 constexpr size_t kTableMaxSlice = size_t(1) << 20;     // alignments per slice (and per launch)
@@ -261,6 +268,11 @@ Table local_full_affine_table(size_t len1, size_t len2, const int8_t *sm, int ga
 Table global_full_table(size_t len1, size_t len2, const int8_t *sm, int gap, unsigned free_ends);         // global_full_api.cpp
 Table global_full_affine_table(size_t len1, size_t len2, const int8_t *sm, int gap_open, int gap_extend,
                                unsigned free_ends);                                                        // global_full_affine_api.cpp
+Table global_long_table(size_t len1, size_t len2, const int8_t *sm, int gap, unsigned free_ends);         // global_long_api.cpp
+Table global_long_affine_table(size_t len1, size_t len2, const int8_t *sm, int gap_open, int gap_extend,
+                               unsigned free_ends);                                                        // global_long_affine_api.cpp
+// the striped aligners' domain rule (include/swmi.h): P (len1 + len2) <= 2^23 with P = max(1, max |sm|, gaps...)
+bool global_long_domain_ok(size_t len1, size_t len2, const int8_t *sm, int gap_a, int gap_b);             // global_long_api.cpp
 // local_full_ragged_api.cpp: the plan of a ragged any-length batch alone (no device), for tests of its arithmetic -- per slice
 // its alignments and device bytes; true when every code base equals the 64-bit running sum of the code words before it
 bool local_full_ragged_plan_check(const uint64_t *seq1_offsets, const uint64_t *seq2_offsets, size_t n, bool affine, bool tb,

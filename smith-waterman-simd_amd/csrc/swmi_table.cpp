@@ -7,7 +7,8 @@
 //
 // Their device buffers hang off Context::local_state, sgfull_state, local_affine_state, sgfull_affine_state and
 // local_full_state, local_full_affine_state, global_full_state (global_full_api.cpp, section 20) and global_full_affine_state
-// (global_full_affine_api.cpp, section 21), which
+// (global_full_affine_api.cpp, section 21), global_long_state and global_long_affine_state (global_long_api.cpp,
+// global_long_affine_api.cpp, section 23), which
 // destroy_context (swmi_api.cpp) drops at swmi_shutdown: that file names no symbol of this one, so the host-only builds of swmi_api.cpp /
 // swmi_multi.cpp (tests/test_multi_fake.py, tests/test_sanitizers.py) link without these kernels -- and this file names no
 // launcher but launch_local and launch_sgfull, so that the fake-GPU build of every swmi_*.cpp (tests/test_table_host_fake.py)
@@ -74,11 +75,12 @@ struct HostSet {
     uint32_t *d_codes = nullptr, *d_counts = nullptr;
     unsigned long long *d_moves = nullptr;
     unsigned char *d_work = nullptr;                                         // a ragged batch's slots, as bytes
-    struct { size_t d1, d2, scores, ends, codes, counts, moves, work; } have{};   // capacity in elements
+    int32_t *d_carry = nullptr;                                              // a striped aligner's carry (Table::carry_words)
+    struct { size_t d1, d2, scores, ends, codes, counts, moves, work, carry; } have{};   // capacity in elements
     size_t off = 0, m = 0;                                                   // slice in flight
     void release()
     {
-        for (void *p : std::initializer_list<void *>{d1, d2, d_scores, d_ends, d_codes, d_counts, d_moves, d_work})
+        for (void *p : std::initializer_list<void *>{d1, d2, d_scores, d_ends, d_codes, d_counts, d_moves, d_work, d_carry})
             if (p) (void)hipFree(p);
         *this = HostSet{};
     }
@@ -143,10 +145,14 @@ struct Slices {
 };
 
 hipError_t launch_table(const Table &t, size_t slice, const uint8_t *s1, const uint8_t *s2, const void *work, size_t m,
-                        int32_t *scores, int32_t *ends, uint32_t *codes, unsigned long long *moves, uint32_t *counts, hipStream_t st)
+                        int32_t *scores, int32_t *ends, uint32_t *codes, unsigned long long *moves, uint32_t *counts, int32_t *carry,
+                        hipStream_t st)
 {
     if (t.plan) return t.plan->launch(t, slice, s1, s2, work, m, scores, ends, codes, moves, counts, st);
-    return t.launch(t, s1, s2, m, scores, ends, codes, moves, counts, st);
+    if (!t.carry_words) return t.launch(t, s1, s2, m, scores, ends, codes, moves, counts, st);
+    Table with_carry = t;                       // the slice's carry rides in the Table (swmi_host.h)
+    with_carry.carry = carry;
+    return t.launch(with_carry, s1, s2, m, scores, ends, codes, moves, counts, st);
 }
 
 int check_local(size_t len1, const int8_t *sm, int gap)
@@ -173,7 +179,7 @@ Table local_table(size_t len1, const int8_t *sm, int gap)
 // device bytes one alignment of a slice takes: inputs, results, and with a traceback the codes, the moves and the count
 size_t table_slice_bytes(const Table &t, bool tb)
 {
-    size_t b = t.len1 + t.len2 + sizeof(int32_t) + t.ends * sizeof(int32_t);
+    size_t b = t.len1 + t.len2 + sizeof(int32_t) + t.ends * sizeof(int32_t) + t.carry_words * sizeof(int32_t);
     if (tb) b += t.code_words * sizeof(uint32_t) + t.move_words * sizeof(uint64_t) + sizeof(uint32_t);
     return b;
 }
@@ -217,7 +223,10 @@ int table_device(const Table &t, const void *d_seq1s, const void *d_seq2s, size_
     unsigned char *work = nullptr;
     const size_t code_bytes = ((tb ? sl.max_codes() * sizeof(uint32_t) : 0) + 15) & ~size_t(15);
     const size_t slot_bytes = t.plan ? t.plan->slot_bytes : 0;
-    const size_t need = code_bytes + n * slot_bytes;
+    // a striped aligner's carry lies behind the codes (never with a plan: carry_words is a fixed-length Table's)
+    const size_t carry_bytes = (sl.max_m() * t.carry_words * sizeof(int32_t) + 15) & ~size_t(15);
+    int32_t *carry = nullptr;
+    const size_t need = code_bytes + carry_bytes + n * slot_bytes;
     if (need) {
         Workspace &ws = ts.workspaces[st];
         if (need > ws.bytes) {
@@ -229,9 +238,10 @@ int table_device(const Table &t, const void *d_seq1s, const void *d_seq2s, size_
             ws.bytes = need;
         }
         codes = tb ? static_cast<uint32_t *>(ws.ptr) : nullptr;
+        if (carry_bytes) carry = reinterpret_cast<int32_t *>(static_cast<unsigned char *>(ws.ptr) + code_bytes);
         if (t.plan) {
             // the slots go up from pinned memory that the stream's last ragged upload has finished reading
-            work = static_cast<unsigned char *>(ws.ptr) + code_bytes;
+            work = static_cast<unsigned char *>(ws.ptr) + code_bytes + carry_bytes;
             Staging &g = ts.staging[st];
             if (g.done) SWMI_HIP_TRY(hipEventSynchronize(g.done));
             else SWMI_HIP_TRY(hipEventCreateWithFlags(&g.done, hipEventDisableTiming));
@@ -253,7 +263,7 @@ int table_device(const Table &t, const void *d_seq1s, const void *d_seq2s, size_
         SWMI_HIP_TRY(launch_table(t, s, s1 + sl.seq1(off), s2 + sl.seq2(off), work ? work + off * slot_bytes : nullptr, sl.size(s),
                                   static_cast<int32_t *>(d_scores) + off, static_cast<int32_t *>(d_ends) + t.ends * off, codes,
                                   tb ? static_cast<unsigned long long *>(d_moves) + sl.moves(off) : nullptr,
-                                  tb ? static_cast<uint32_t *>(d_counts) + off : nullptr, st));
+                                  tb ? static_cast<uint32_t *>(d_counts) + off : nullptr, carry, st));
     }
     return SWMI_OK;
 }
@@ -288,6 +298,7 @@ int table_host(const Table &t, const char *entry, const uint8_t *seq1s, const ui
         if (rc == SWMI_OK && tb) rc = grow(s.d_codes, s.have.codes, sl.max_codes());
         if (rc == SWMI_OK && tb) rc = grow(s.d_moves, s.have.moves, sl.max_moves());
         if (rc == SWMI_OK && t.plan) rc = grow(s.d_work, s.have.work, slice * slot_bytes);
+        if (rc == SWMI_OK && t.carry_words) rc = grow(s.d_carry, s.have.carry, slice * t.carry_words);
         if (rc != SWMI_OK) return rc;
     }
     // results of the slice a set holds -> host; only as many move words per alignment as the slice's longest walk needs (a
@@ -337,7 +348,7 @@ int table_host(const Table &t, const char *entry, const uint8_t *seq1s, const ui
                                hipMemcpyHostToDevice, st);
         if (e == hipSuccess)
             e = launch_table(t, sc, s.d1, s.d2, s.d_work, s.m, s.d_scores, s.d_ends, tb ? s.d_codes : nullptr, tb ? s.d_moves : nullptr,
-                             tb ? s.d_counts : nullptr, st);
+                             tb ? s.d_counts : nullptr, s.d_carry, st);
         if (e == hipSuccess && n_sets == 2) e = drain(turn ^ 1);         // the previous slice, while this one computes
     }
     for (int k = 0; k < n_sets; ++k) {

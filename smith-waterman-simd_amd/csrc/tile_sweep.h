@@ -1,5 +1,6 @@
 // tile_sweep.h -- what the any-length aligners share (sgfull_kernels.hip, sgfull_affine_kernels.hip,
-// local_full_kernels.hip, local_full_affine_kernels.hip, global_full_kernels.hip, global_full_affine_kernels.hip; DESIGN.md
+// local_full_kernels.hip, local_full_affine_kernels.hip, global_full_kernels.hip, global_full_affine_kernels.hip,
+// global_long_kernels.hip, global_long_affine_kernels.hip; DESIGN.md
 // section 13): the mapping and its constants, the helpers, the geometry and the launcher; the few helpers that the 16-lane local aligners take from here as well.  The sweep and the
 // walk of the linear-gap kernels are tile_sweep_body.inc, those of the affine kernels tile_sweep_affine_body.inc.
 //
@@ -139,10 +140,21 @@ constexpr int kStageRows = 128;        // rows of a walk staging block
 constexpr bool RAGGED = false;         // what a kernel without a ragged form sees (above)
 constexpr TileWork slot{};
 
+// Column stripes (global_long_kernels.hip, global_long_affine_kernels.hip): a kernel that shadows STRIPED
+// with true sweeps len2 > kStripeCols columns as stripes of kStripeCols, one after another, in the same workgroup; it names
+// `carry` (linear body: int per row) or `carry_hf` (affine body: int2 per row), the per-alignment device buffer through which
+// a stripe's last column reaches the next stripe's wave 0.  What every other kernel sees:
+constexpr bool STRIPED = false;
+constexpr int *carry = nullptr;
+constexpr int2 *carry_hf = nullptr;
+constexpr int kStripeCols = 64 * 16 * 16;   // kMaxWaves x 64 lanes x kCols columns (asserted below)
+
 // The end rule (above).  The flags are SWMI_FREE_* of include/swmi.h, which no kernel file includes.
 constexpr unsigned kFreeBegin1 = 1, kFreeBegin2 = 2, kFreeEnd1 = 4, kFreeEnd2 = 8;
 constexpr unsigned free_ends = 0;      // what a kernel without the argument sees
 constexpr int kEndBias = 1 << 22;      // |H| <= 128 * 32768 = 2^22, and the bound is never met: H + kEndBias > 0
+                                       // (a striped kernel shadows it: its |H| reaches 2^23)
+static_assert(kStripeCols == kMaxWaves * 64 * kCols);
 
 template <class V, class = void>
 constexpr bool kEndRule = false;
@@ -150,9 +162,10 @@ template <class V>
 constexpr bool kEndRule<V, std::void_t<decltype(V::kFreeEnds)>> = V::kFreeEnds;
 
 // a candidate end cell for the reduction's maximum: H descending, row ascending, column ascending; above 0, which no cell packs to
-__device__ __forceinline__ unsigned long long end_pack(int h, int row, int col)
+// (`bias`: the kEndBias that the calling kernel sees)
+__device__ __forceinline__ unsigned long long end_pack(int h, int row, int col, int bias)
 {
-    return ((unsigned long long)(uint32_t)(h + kEndBias) << 34) | ((unsigned long long)(0x1FFFF - row) << 17) |
+    return ((unsigned long long)(uint32_t)(h + bias) << 34) | ((unsigned long long)(0x1FFFF - row) << 17) |
            (unsigned long long)(0x1FFFF - col);
 }
 
@@ -185,6 +198,11 @@ __device__ __forceinline__ int base_shift(const uint8_t *s1, int idx, int len1)
     return 8 * (s1[c] & 3);
 }
 
+// The carry entry that a lane of a striped kernel's wave 0 loads for the row `idx` + 1, clamped into the buffer.  Only lane
+// 0's value is used (it is from_left's `edge`), and lane 0 asks for the row it needs; the other lanes' indices run backwards
+// from it, so that the load is one coalesced vector load and not a scalar load of memory that this kernel writes.
+__device__ __forceinline__ int carry_row(int idx, int len1) { return idx < 0 ? 0 : idx >= len1 ? len1 - 1 : idx; }
+
 __device__ __forceinline__ uint4 code_quad(const unsigned long long *c)
 {
     return make_uint4((uint32_t)c[0], (uint32_t)(c[0] >> 32), (uint32_t)c[1], (uint32_t)(c[1] >> 32));
@@ -198,6 +216,16 @@ template <bool ON>
 __device__ __forceinline__ int opaque(int v)
 {
     if constexpr (ON) asm volatile("" : "+s"(v));
+    return v;
+}
+
+// The same for a per-lane value.  A striped kernel re-derives its lane and wave from it in every stripe, so that nothing made
+// of them -- the first rows' base shifts, addresses, the border candidates -- is hoisted out of the stripe loop and kept in
+// registers across the sweep.
+template <bool ON>
+__device__ __forceinline__ int opaque_lane(int v)
+{
+    if constexpr (ON) asm volatile("" : "+v"(v));
     return v;
 }
 
@@ -284,6 +312,30 @@ hipError_t launch_ragged(const uint8_t *d_seq1s, const uint8_t *d_seq2s, const T
     else
         hipLaunchKernelGGL(KEnds, grid, block, 0, stream, d_seq1s, d_seq2s, 0, 0, cols, gaps..., d_scores, d_ends, (Code *)nullptr,
                            (unsigned long long *)nullptr, (uint32_t *)nullptr, 0u, 0u, d_work);
+    return hipGetLastError();
+}
+
+// The striped sibling (a kernel with STRIPED, whose last parameter is its carry buffer): one workgroup of
+// min(waves(len2), kMaxWaves) wavefronts per alignment, which sweeps ceil(len2 / kStripeCols) stripes.  d_carry: len1 entries
+// per alignment of the launch, unused (may be NULL) when len2 <= kStripeCols.
+template <auto KTb, auto KEnds, class Code, class Carry, class... Gaps>
+hipError_t launch_striped(const uint8_t *d_seq1s, const uint8_t *d_seq2s, int len1, int len2, size_t n, const int8_t *sm,
+                          int32_t *d_scores, int32_t *d_ends, Code *d_codes, unsigned long long *d_moves, uint32_t *d_counts,
+                          size_t move_words, Carry *d_carry, hipStream_t stream, Gaps... gaps)
+{
+    if (n == 0) return hipSuccess;
+    if (len1 < 1 || len2 < 1 || len1 > 4 * kStripeCols || len2 > 4 * kStripeCols || (len2 > kStripeCols && !d_carry))
+        return hipErrorInvalidValue;
+    const SmCols cols = sm_cols(sm);
+    const int w = waves(len2);
+    const dim3 grid((unsigned)n), block(64 * (w < kMaxWaves ? w : kMaxWaves));
+    const uint32_t n_trips = (uint32_t)trips(len1);
+    if (d_moves)
+        hipLaunchKernelGGL(KTb, grid, block, 0, stream, d_seq1s, d_seq2s, len1, len2, cols, gaps..., d_scores, d_ends, d_codes, d_moves,
+                           d_counts, (uint32_t)move_words, n_trips, d_carry);
+    else
+        hipLaunchKernelGGL(KEnds, grid, block, 0, stream, d_seq1s, d_seq2s, len1, len2, cols, gaps..., d_scores, d_ends,
+                           (Code *)nullptr, (unsigned long long *)nullptr, (uint32_t *)nullptr, 0u, n_trips, d_carry);
     return hipGetLastError();
 }
 

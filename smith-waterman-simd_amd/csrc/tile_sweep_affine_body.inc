@@ -3,7 +3,9 @@
 // where the kernel's parameters are named seq1s, seq2s, len1, len2, cols, gap_open, gap_extend, scores, ends, codes, moves,
 // counts, move_words, n_trips and its template parameter TB.  A kernel with a ragged form also names RAGGED and slot, and
 // then len1, len2 and n_trips are the slot's (tile_sweep.h).  A kernel whose variant has the end rule (kEndRule<V>,
-// tile_sweep.h) also names free_ends.  Text and not a function on purpose: tile_sweep.h says why.
+// tile_sweep.h) also names free_ends.  A kernel that sweeps column stripes shadows STRIPED and kEndBias and names `carry_hf`
+// (tile_sweep.h; tile_sweep_body.inc tells the stripe loop, which is the same here with (H, F) pairs in the carry).  Text and
+// not a function on purpose: tile_sweep.h says why.
 //
 // E runs down a column and stays with the lane; F runs along the row, so what lane l - 1 hands over (and lane 63 through
 // the ring) is its H(i, 16 G) AND its F(i, 16 G): two v_mov_b32_dpp wave_shr:1 per step, (H, F) pairs in the ring.  With a
@@ -25,7 +27,7 @@
     __shared__ unsigned long long stage[TB ? kStageRows * kStageLanes : 1];
 
     const int W = blockDim.x >> 6;
-    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, G = tid;
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
     const size_t k = RAGGED ? (size_t)slot.k : (size_t)blockIdx.x;
     const uint8_t *s1 = seq1s + (RAGGED ? (size_t)slot.s1_off : k * (size_t)len1);
     const uint8_t *s2 = seq2s + (RAGGED ? (size_t)slot.s2_off : k * (size_t)len2);
@@ -46,6 +48,21 @@
             return;
         }
     }
+    // STRIPED: tile_sweep_body.inc's stripe loop, carry ordering and BARRIER INVARIANT (every wave executes total_chunks + 1
+    // barriers in every stripe but the last and total_chunks in the last, whatever w and the stripe's valid width); the
+    // carry holds the last column's stored key AND its F, so a gap that opened left of the stripe's edge extends across it.
+    static_assert(!STRIPED || kEndRule<V>, "column stripes fold end-rule candidates");
+    [[maybe_unused]] int2 *const carry_k = STRIPED ? carry_hf + k * (size_t)len1 : nullptr;
+    unsigned long long r = 0;                           // best cell so far: (H desc, row asc, column asc)
+    int stripe = 0;
+    do {
+    // (a striped kernel's per-stripe tid, w and l: opaque_lane, tile_sweep.h; they shadow the workgroup's, which they equal)
+    const int tid = opaque_lane<STRIPED>((int)threadIdx.x), w = tid >> 6, l = tid & 63;
+    const int G = STRIPED ? stripe * (64 * kMaxWaves) + tid : tid;
+    const int gw = STRIPED ? G >> 6 : w;                // the wave of G in the code layout
+    // whether another stripe follows (nothing but len2 and `stripe` is kept across the sweep: the kernels have no SGPRs to spare)
+    const bool more_stripes = STRIPED && (stripe + 1) * kStripeCols < len2;
+    const int code_waves = STRIPED ? waves(len2) : W;   // the wave count of the code layout: all stripes' waves
     const int jbase = kCols * G;                        // the lane's columns are jbase + 1 .. jbase + 16
     // what a gap along row 0 / column 0 costs: the kernel's, or with the end rule 0 where that border is free
     int open_row0 = gap_open, ext_row0 = gap_extend, open_col0 = gap_open, ext_col0 = gap_extend;
@@ -69,8 +86,9 @@
     [[maybe_unused]] unsigned long long r_border = 0;
     if constexpr (kEndRule<V>) {
         if (tid == 0) {
-            if (free_ends & kFreeEnd1) r_border = end_pack(V::border(len2, open_row0, ext_row0) >> 6, 0, len2);
-            if (free_ends & kFreeEnd2) r_border = umax64(r_border, end_pack(V::border(len1, open_col0, ext_col0) >> 6, len1, 0));
+            if (free_ends & kFreeEnd1) r_border = end_pack(V::border(len2, open_row0, ext_row0) >> 6, 0, len2, kEndBias);
+            if (free_ends & kFreeEnd2)
+                r_border = umax64(r_border, end_pack(V::border(len1, open_col0, ext_col0) >> 6, len1, 0, kEndBias));
         }
     }
     const int g_open = -(gap_open << 6);
@@ -83,14 +101,18 @@
     // column jj = end_sel, and only the owner's is read after the sweep, so the loop holds no lane mask.
     [[maybe_unused]] int end_sel = -1;
     if constexpr (kEndRule<V>)
-        end_sel = __builtin_amdgcn_readfirstlane((free_ends & kFreeEnd1) && w == W - 1 ? (len2 - 1) & (kCols - 1) : -1);
+        end_sel = __builtin_amdgcn_readfirstlane((free_ends & kFreeEnd1) && (STRIPED ? gw == (len2 - 1) >> 10 : w == W - 1)
+                                                     ? (len2 - 1) & (kCols - 1)
+                                                     : -1);
 
     const int local_chunks = (len1 + 63 + kChunk - 1) / kChunk;
+    // a striped kernel's wave with no column in the (last) stripe: no chunk of work, every barrier
+    const int my_chunks = STRIPED && jbase - (l << 4) >= len2 ? 0 : local_chunks;
     const int total_chunks = local_chunks + kDelay * (W - 1);
     const int2 *ring_in = ring + (w > 0 ? w - 1 : 0) * kRing;  // read by waves 1.. (wave 0's left column is the border)
     int2 *ring_out = ring + (w < W - 1 ? w : 0) * kRing;       // written by waves ..W-2
-    unsigned long long *cw_out = TB ? codes + (RAGGED ? (size_t)slot.code_base : k * ((size_t)W * n_trips * 256)) +
-                                          ((size_t)w * n_trips * 64 + l) * 4
+    unsigned long long *cw_out = TB ? codes + (RAGGED ? (size_t)slot.code_base : k * ((size_t)code_waves * n_trips * 256)) +
+                                          ((size_t)gw * n_trips * 64 + l) * 4
                                     : nullptr;
 
     int sh_next[kUnroll];
@@ -99,7 +121,7 @@
 
     for (int c = 0; c < total_chunks; ++c) {
         const int lc = c - kDelay * w;
-        if (lc >= 0 && lc < local_chunks) {
+        if (lc >= 0 && lc < my_chunks) {
             for (int q = 0; q < kChunk / kUnroll; ++q) {
                 const int s0 = lc * kChunk + q * kUnroll;
                 int sh[kUnroll], bound_h[kUnroll], bound_f[kUnroll], edge_h[kUnroll], edge_f[kUnroll];
@@ -111,6 +133,11 @@
                     // lane 0's left column for row s0 + t + 1: the ring, or the border's H and F = -inf
                     if (w > 0) {
                         const int2 v = ring_in[(s0 + t) & (kRing - 1)];
+                        bound_h[t] = v.x;
+                        bound_f[t] = v.y;
+                    } else if (STRIPED && stripe > 0) {
+                        // ... the previous stripe's last column (carry_row, tile_sweep.h)
+                        const int2 v = carry_k[carry_row(s0 + t - l, len1)];
                         bound_h[t] = v.x;
                         bound_f[t] = v.y;
                     } else {
@@ -203,6 +230,16 @@
                         if (row >= 1 && row <= len1) ring_out[(row - 1) & (kRing - 1)] = make_int2(edge_h[t], edge_f[t]);
                     }
                 }
+                if constexpr (STRIPED) {
+                    // the stripe's last column, for the next stripe's wave 0 (vector stores; every stripe but the last is full)
+                    if (more_stripes && w == W - 1 && l == 63) {
+#pragma unroll
+                        for (int t = 0; t < kUnroll; ++t) {
+                            const int row = s0 + t - 62;
+                            if (row >= 1 && row <= len1) carry_k[row - 1] = make_int2(edge_h[t], edge_f[t]);
+                        }
+                    }
+                }
                 if constexpr (TB) {
                     uint4 *o = reinterpret_cast<uint4 *>(cw_out + (size_t)(s0 >> 2) * 256);
                     o[0] = make_uint4(cw[0], co[0], cw[1], co[1]);
@@ -214,12 +251,11 @@
     }
 
     // best cell: (H desc, row asc, column asc) over the lanes, then over the waves
-    unsigned long long r;
     if constexpr (kEndRule<V>) {
         // the lane's candidates (tile_sweep.h): key[] holds row len1 now.  Last row, columns past len2 masked out; the
-        // corner; the last column's best over rows 0 .. len1 - 1; thread 0's two border cells
-        r = 0;
-        const int len2_e = opaque<RAGGED>(len2);   // len2, not before the sweep in a ragged kernel (tile_sweep.h)
+        // corner; the last column's best over rows 0 .. len1 - 1; thread 0's two border cells.  (STRIPED: a wave that skipped
+        // the stripe still holds row 0 in key[], and jbase >= len2 masks all of it)
+        const int len2_e = opaque<RAGGED || STRIPED>(len2);   // len2, not before the sweep in a ragged or striped kernel (tile_sweep.h)
         int last = V::kRowMin, corner = V::kRowMin;
 #pragma unroll
         for (int jj = 0; jj < kCols; ++jj) {
@@ -227,10 +263,11 @@
             if (j <= len2_e && key[jj] > last) last = key[jj];
             if (j == len2_e) corner = key[jj];
         }
-        if ((free_ends & kFreeEnd2) && jbase < len2_e) r = end_pack(last >> 6, len1, jbase + (kCols - 1 - (last & 15)) + 1);
+        if ((free_ends & kFreeEnd2) && jbase < len2_e)
+            r = umax64(r, end_pack(last >> 6, len1, jbase + (kCols - 1 - (last & 15)) + 1, kEndBias));
         if (G == (len2_e - 1) >> 4) {
-            r = umax64(r, end_pack(corner >> 6, len1, len2_e));
-            if (end_sel >= 0) r = umax64(r, end_pack(best >> 6, best_row, len2_e));
+            r = umax64(r, end_pack(corner >> 6, len1, len2_e, kEndBias));
+            if (end_sel >= 0) r = umax64(r, end_pack(best >> 6, best_row, len2_e, kEndBias));
         }
         r = umax64(r, r_border);
     } else {
@@ -239,6 +276,16 @@
         r = ((unsigned long long)(uint32_t)h << 34) | ((unsigned long long)(0x1FFFF - best_row) << 17) |
             (unsigned long long)(0x1FFFF - col);
     }
+    if constexpr (STRIPED) {
+        if (more_stripes) {
+            // between two stripes: this wave's carry stores have reached L2, every wave is past its last ring read, and the
+            // next stripe's carry loads miss this CU's L1, which may hold the rows as the previous stripe left them
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        }
+    }
+    } while (STRIPED && ++stripe * kStripeCols < len2);
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
         const unsigned long long v = __shfl_xor(r, o, 64);
@@ -261,7 +308,7 @@
     }
     if constexpr (TB) {
         constexpr uint32_t kCodeH = V::kTagH >> 4, kCodeE = V::kTagE >> 4;
-        const unsigned long long *cd = codes + (RAGGED ? (size_t)slot.code_base : k * ((size_t)W * n_trips * 256));
+        const unsigned long long *cd = codes + (RAGGED ? (size_t)slot.code_base : k * ((size_t)(STRIPED ? waves(len2) : W) * n_trips * 256));
         unsigned long long *mv = moves + (RAGGED ? (size_t)slot.move_base : k * (size_t)move_words);
         int i = end_i, j = end_j, stopped = 0;
         int state = 0;                                  // 0 = H, 1 = E, 2 = F (thread 0's only)

@@ -3,14 +3,15 @@
 // `const V::Gaps gaps{<gap argument>};`, where the kernel's parameters are named seq1s, seq2s, len1, len2, cols, scores,
 // ends, codes, moves, counts, move_words, n_trips and its template parameter TB.  A kernel with a ragged form also names
 // RAGGED and slot, and then len1, len2 and n_trips are the slot's (tile_sweep.h).  A kernel whose variant has the end rule
-// (kEndRule<V>, tile_sweep.h) also names free_ends.  Text and not a function on purpose: tile_sweep.h says why.
+// (kEndRule<V>, tile_sweep.h) also names free_ends.  A kernel that sweeps column stripes shadows STRIPED and kEndBias and names
+// `carry` (tile_sweep.h; the stripe loop below says what a stripe adds).  Text and not a function on purpose: tile_sweep.h says why.
     __shared__ int ring[(kMaxWaves - 1) * kRing];
     __shared__ unsigned long long red[kMaxWaves];
     __shared__ int walk_at[V::kWalkStops ? 3 : 2];
     __shared__ uint32_t stage[TB ? kStageRows * V::kStageLanes : 1];
 
     const int W = blockDim.x >> 6;
-    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, G = tid;
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
     const size_t k = RAGGED ? (size_t)slot.k : (size_t)blockIdx.x;
     const uint8_t *s1 = seq1s + (RAGGED ? (size_t)slot.s1_off : k * (size_t)len1);
     const uint8_t *s2 = seq2s + (RAGGED ? (size_t)slot.s2_off : k * (size_t)len2);
@@ -31,6 +32,33 @@
             return;
         }
     }
+    // STRIPED (needs the end rule): the workgroup sweeps the stripes of kStripeCols columns one after another over all of seq1.
+    // A stripe re-initialises everything from here to the sweep with the lane's GLOBAL index G; wave 0 takes its left column
+    // from `carry`, which lane 63 of the previous stripe's last wave wrote (row i at carry[i - 1]: that lane's stored key, what
+    // the ring would have carried), and the last row's candidates are folded into r after each stripe -- end_pack orders them,
+    // so a tie between stripes goes to the earlier column.  ONE carry buffer, in place: row i is read by wave 0 in chunk
+    // (i - 1) / 32 of a stripe and overwritten by wave 15 in chunk 45 + (i + 62) / 32 of the SAME stripe, 45 barriers after
+    // its value was consumed, and read again only behind the stripe's closing drain, barrier and L1 invalidate.
+    // BARRIER INVARIANT: every wave of the workgroup executes total_chunks + 1 barriers in every stripe but the last and
+    // total_chunks in the last; total_chunks is made of len1 and blockDim alone, never of w, the stripe or its valid width.  A
+    // wave with no column in the last stripe (my_chunks = 0 below) skips the chunk's work, not its barrier.
+    static_assert(!STRIPED || kEndRule<V>, "column stripes fold end-rule candidates");
+    [[maybe_unused]] int *const carry_k = STRIPED ? carry + k * (size_t)len1 : nullptr;
+    unsigned long long r = 0;                           // best cell so far: (H desc, row asc, column asc)
+    // the matrix columns, which every stripe's profile needs: a striped kernel keeps them in VGPRs across the sweep (it has
+    // some to spare and no SGPR: as scalars they were spilled)
+    SmCols pc = cols;
+    if constexpr (STRIPED)
+        for (int b = 0; b < 4; ++b) pc.c[b] = (uint32_t)opaque_lane<true>((int)pc.c[b]);
+    int stripe = 0;
+    do {
+    // (a striped kernel's per-stripe tid, w and l: opaque_lane, tile_sweep.h; they shadow the workgroup's, which they equal)
+    const int tid = opaque_lane<STRIPED>((int)threadIdx.x), w = tid >> 6, l = tid & 63;
+    const int G = STRIPED ? stripe * (64 * kMaxWaves) + tid : tid;
+    const int gw = STRIPED ? G >> 6 : w;                // the wave of G in the code layout
+    // whether another stripe follows (nothing but len2 and `stripe` is kept across the sweep: the kernels have no SGPRs to spare)
+    const bool more_stripes = STRIPED && (stripe + 1) * kStripeCols < len2;
+    const int code_waves = STRIPED ? waves(len2) : W;   // the wave count of the code layout: all stripes' waves
     const int jbase = kCols * G;                        // the lane's columns are jbase + 1 .. jbase + 16
 
     uint32_t prof[kCols];
@@ -39,7 +67,7 @@
     for (int jj = 0; jj < kCols; ++jj) {
         const int j = jbase + jj + 1;
         const uint32_t b = s2[j <= len2 ? j - 1 : 0] & 3u;
-        prof[jj] = j > len2 ? 0x80808080u : b == 0 ? cols.c[0] : b == 1 ? cols.c[1] : b == 2 ? cols.c[2] : cols.c[3];
+        prof[jj] = j > len2 ? 0x80808080u : b == 0 ? pc.c[0] : b == 1 ? pc.c[1] : b == 2 ? pc.c[2] : pc.c[3];
         key[jj] = V::row0(jj, -j, gaps);
     }
     V lane(gaps);
@@ -47,15 +75,17 @@
     int best = kEndRule<V> ? V::kRowMin : V::kZeroKey, best_row = 0;   // H = 0 at (0, 0); end rule: no last-column cell yet
     // end rule: the lane that owns column len2 keeps the best cell of that column, if seq1's end is free
     const int end_jj = (len2 - 1) & (kCols - 1);
-    const bool end_col_wave = kEndRule<V> && (free_ends & kFreeEnd1) && w == W - 1;
+    const bool end_col_wave = kEndRule<V> && (free_ends & kFreeEnd1) && (STRIPED ? gw == (len2 - 1) >> 10 : w == W - 1);
     const bool end_col_lane = end_col_wave && G == (len2 - 1) >> 4;
 
     const int local_chunks = (len1 + 63 + kChunk - 1) / kChunk;
+    // a striped kernel's wave with no column in the (last) stripe: no chunk of work, every barrier
+    const int my_chunks = STRIPED && jbase - (l << 4) >= len2 ? 0 : local_chunks;
     const int total_chunks = local_chunks + kDelay * (W - 1);
     const int *ring_in = ring + (w > 0 ? w - 1 : 0) * kRing;   // read by waves 1.. (wave 0's left column is the border)
     int *ring_out = ring + (w < W - 1 ? w : 0) * kRing;        // written by waves ..W-2
-    uint32_t *cw_out = TB ? codes + (RAGGED ? (size_t)slot.code_base : k * ((size_t)W * n_trips * 256)) +
-                                ((size_t)w * n_trips * 64 + l) * 4
+    uint32_t *cw_out = TB ? codes + (RAGGED ? (size_t)slot.code_base : k * ((size_t)code_waves * n_trips * 256)) +
+                                ((size_t)gw * n_trips * 64 + l) * 4
                           : nullptr;
 
     int sh_next[kUnroll];
@@ -64,7 +94,7 @@
 
     for (int c = 0; c < total_chunks; ++c) {
         const int lc = c - kDelay * w;
-        if (lc >= 0 && lc < local_chunks) {
+        if (lc >= 0 && lc < my_chunks) {
             for (int q = 0; q < kChunk / kUnroll; ++q) {
                 const int s0 = lc * kChunk + q * kUnroll;
                 int sh[kUnroll];
@@ -75,7 +105,10 @@
                     sh[t] = sh_next[t];
                     sh_next[t] = base_shift(s1, s0 + kUnroll + t - l, len1);
                     // lane 0's left column for row s0 + t + 1
-                    bound[t] = w > 0 ? ring_in[(s0 + t) & (kRing - 1)] : lane.left_border(-(s0 + t + 1));
+                    if (STRIPED && stripe > 0)          // ... the previous stripe's last column (carry_row, tile_sweep.h)
+                        bound[t] = w > 0 ? ring_in[(s0 + t) & (kRing - 1)] : carry_k[carry_row(s0 + t - l, len1)];
+                    else
+                        bound[t] = w > 0 ? ring_in[(s0 + t) & (kRing - 1)] : lane.left_border(-(s0 + t + 1));
                     cw[t] = 0;
                 }
 #pragma unroll
@@ -135,6 +168,16 @@
                         if (row >= 1 && row <= len1) ring_out[(row - 1) & (kRing - 1)] = edge[t];
                     }
                 }
+                if constexpr (STRIPED) {
+                    // the stripe's last column, for the next stripe's wave 0 (vector stores; every stripe but the last is full)
+                    if (more_stripes && w == W - 1 && l == 63) {
+#pragma unroll
+                        for (int t = 0; t < kUnroll; ++t) {
+                            const int row = s0 + t - 62;
+                            if (row >= 1 && row <= len1) carry_k[row - 1] = edge[t];
+                        }
+                    }
+                }
                 if constexpr (TB) {
                     *reinterpret_cast<uint4 *>(cw_out + (size_t)(s0 >> 2) * 256) = make_uint4(cw[0], cw[1], cw[2], cw[3]);
                 }
@@ -144,12 +187,11 @@
     }
 
     // best cell: (H desc, row asc, column asc) over the lanes, then over the waves
-    unsigned long long r;
     if constexpr (kEndRule<V>) {
         // the lane's candidates (tile_sweep.h): key[] holds row len1 now.  Last row, columns past len2 masked out; the
-        // corner; the last column's best; thread 0 adds the two border cells, which are closed forms
-        r = 0;
-        const int len2_e = opaque<RAGGED>(len2);   // len2, not before the sweep in a ragged kernel (tile_sweep.h)
+        // corner; the last column's best; thread 0 adds the two border cells, which are closed forms.  (STRIPED: a wave that
+        // skipped the stripe still holds row 0 in key[], and jbase >= len2 masks all of it)
+        const int len2_e = opaque<RAGGED || STRIPED>(len2);   // len2, not before the sweep in a ragged or striped kernel (tile_sweep.h)
         int last = V::kRowMin, corner = V::kRowMin;
 #pragma unroll
         for (int jj = 0; jj < kCols; ++jj) {
@@ -157,14 +199,15 @@
             if (j <= len2_e && key[jj] > last) last = key[jj];
             if (j == len2_e) corner = key[jj];
         }
-        if ((free_ends & kFreeEnd2) && jbase < len2_e) r = end_pack(last >> 6, len1, jbase + (kCols - 1 - (last & 15)) + 1);
+        if ((free_ends & kFreeEnd2) && jbase < len2_e)
+            r = umax64(r, end_pack(last >> 6, len1, jbase + (kCols - 1 - (last & 15)) + 1, kEndBias));
         if (G == (len2_e - 1) >> 4) {
-            r = umax64(r, end_pack(corner >> 6, len1, len2_e));
-            if (end_col_lane) r = umax64(r, end_pack(best >> 6, best_row, len2_e));
+            r = umax64(r, end_pack(corner >> 6, len1, len2_e, kEndBias));
+            if (end_col_lane) r = umax64(r, end_pack(best >> 6, best_row, len2_e, kEndBias));
         }
         if (tid == 0) {
-            if (free_ends & kFreeEnd1) r = umax64(r, end_pack(lane.border(-len2_e) >> 6, 0, len2_e));
-            if (free_ends & kFreeEnd2) r = umax64(r, end_pack(lane.left_border(-len1) >> 6, len1, 0));
+            if (free_ends & kFreeEnd1) r = umax64(r, end_pack(lane.border(-len2_e) >> 6, 0, len2_e, kEndBias));
+            if (free_ends & kFreeEnd2) r = umax64(r, end_pack(lane.left_border(-len1) >> 6, len1, 0, kEndBias));
         }
     } else {
         const int h = best >> 6;
@@ -172,6 +215,16 @@
         r = ((unsigned long long)(uint32_t)h << 34) | ((unsigned long long)(0x1FFFF - best_row) << 17) |
             (unsigned long long)(0x1FFFF - col);
     }
+    if constexpr (STRIPED) {
+        if (more_stripes) {
+            // between two stripes: this wave's carry stores have reached L2, every wave is past its last ring read, and the
+            // next stripe's carry loads miss this CU's L1, which may hold the rows as the previous stripe left them
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        }
+    }
+    } while (STRIPED && ++stripe * kStripeCols < len2);
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
         const unsigned long long v = __shfl_xor(r, o, 64);
@@ -193,7 +246,7 @@
             for (int x = 2; x < V::kEnds; ++x) ends[V::kEnds * k + x] = -1;
     }
     if constexpr (TB) {
-        const uint32_t *cd = codes + (RAGGED ? (size_t)slot.code_base : k * ((size_t)W * n_trips * 256));
+        const uint32_t *cd = codes + (RAGGED ? (size_t)slot.code_base : k * ((size_t)(STRIPED ? waves(len2) : W) * n_trips * 256));
         unsigned long long *mv = moves + (RAGGED ? (size_t)slot.move_base : k * (size_t)move_words);
         int i = end_i, j = end_j, stopped = 0;
         uint32_t t = 0;
