@@ -1,9 +1,9 @@
 // global_full_ragged_api.cpp -- C entries of the two global / fit / overlap aligners on a batch of mixed (len1, len2)
 // (swmi_global_full_ragged*, swmi_global_full_affine_ragged*, include/swmi.h).  A batch becomes a TilePlan
 // (tile_ragged_plan.h, shared with the local aligners' ragged entries) and runs through the slice pipeline of swmi_table.cpp,
-// on the fixed-length entries' own workspaces (Context::global_full_state and the affine one) and within their slice budgets.
-// This file is the only host source that names the ragged global launchers; its name lies outside csrc/swmi_*.cpp, and
-// global_full_api.cpp and global_full_affine_api.cpp do not refer to it, so the fake-GPU builds of those link without them.
+// on the fixed-length entries' Table (table_api.cpp): their workspaces and their slice budgets.  This file is the only host
+// source that names the ragged global launchers, and table_api.cpp does not refer to it, so the fake-GPU build of the
+// fixed-length entries links without them.
 #include "tile_ragged_plan.h"
 
 namespace swmi {
@@ -32,7 +32,7 @@ size_t family_code_words(bool affine, int len1, int len2)
 
 size_t family_tb_slice_bytes(bool affine)
 {
-    return (affine ? global_full_affine_table(1, 1, nullptr, 0, 0, 0) : global_full_table(1, 1, nullptr, 0, 0)).tb_slice_bytes;
+    return family_table(affine ? kTableGlobalFullAffine : kTableGlobalFull, 1, 1, nullptr, 0, 0, 0).tb_slice_bytes;
 }
 
 // what the planner of tile_ragged_plan.h takes from this family
@@ -54,7 +54,7 @@ int ragged(bool affine, bool device, const char *entry, const void *seq1s, const
     if (rc != SWMI_OK) return rc;
     TilePlan plan;
     make_plan(plan, kGlobal, off1, off2, n, affine, moves != nullptr);
-    Table t = affine ? global_full_affine_table(1, 1, sm, gap, gap_extend, free_ends) : global_full_table(1, 1, sm, gap, free_ends);
+    Table t = family_table(affine ? kTableGlobalFullAffine : kTableGlobalFull, 1, 1, sm, gap, gap_extend, free_ends);
     t.plan = &plan;
     if (device) return table_device(t, seq1s, seq2s, n, scores, ends, moves, steps, stream);
     return table_host(t, entry, static_cast<const uint8_t *>(seq1s), static_cast<const uint8_t *>(seq2s), n,

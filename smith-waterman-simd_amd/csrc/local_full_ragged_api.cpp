@@ -1,8 +1,8 @@
 // local_full_ragged_api.cpp -- C entries of the two any-length local aligners on a batch of mixed (len1, len2)
 // (swmi_local_full_ragged*, swmi_local_full_affine_ragged*, include/swmi.h).  A batch becomes a TilePlan
-// (tile_ragged_plan.h, which the global aligners' ragged entries share) and runs through the slice pipeline of swmi_table.cpp.
-// This file is the only host source that names the ragged local any-length launchers; its name lies outside csrc/swmi_*.cpp, and
-// local_full_api.cpp and local_full_affine_api.cpp do not refer to it, so the fake-GPU builds of those link without them.
+// (tile_ragged_plan.h, which the global aligners' ragged entries share) and runs through the slice pipeline of swmi_table.cpp,
+// on the fixed-length entries' Table (table_api.cpp).  This file is the only host source that names the ragged local any-length
+// launchers, and table_api.cpp does not refer to it, so the fake-GPU build of the fixed-length entries links without them.
 #include "tile_ragged_plan.h"
 
 namespace swmi {
@@ -30,7 +30,7 @@ size_t family_code_words(bool affine, int len1, int len2)
 
 size_t family_tb_slice_bytes(bool affine)
 {
-    return (affine ? local_full_affine_table(1, 1, nullptr, 0, 0) : local_full_table(1, 1, nullptr, 0)).tb_slice_bytes;
+    return family_table(affine ? kTableLocalFullAffine : kTableLocalFull, 1, 1, nullptr, 0, 0, 0).tb_slice_bytes;
 }
 
 // what the planner of tile_ragged_plan.h takes from this family
@@ -49,7 +49,7 @@ int ragged(bool affine, bool device, const char *entry, const void *seq1s, const
     if (rc != SWMI_OK) return rc;
     TilePlan plan;
     make_plan(plan, kLocal, off1, off2, n, affine, moves != nullptr);
-    Table t = affine ? local_full_affine_table(1, 1, sm, gap, gap_extend) : local_full_table(1, 1, sm, gap);
+    Table t = family_table(affine ? kTableLocalFullAffine : kTableLocalFull, 1, 1, sm, gap, gap_extend, 0);
     t.plan = &plan;
     if (device) return table_device(t, seq1s, seq2s, n, scores, ends, moves, steps, stream);
     return table_host(t, entry, static_cast<const uint8_t *>(seq1s), static_cast<const uint8_t *>(seq2s), n,

@@ -2,8 +2,8 @@
 // swmi_local_align_affine_ragged*, include/swmi.h).  A batch becomes a RaggedPlan (swmi_host.h): slices
 // cut in caller order within the aligner's budget, and per slice one LocalWork per alignment, longest first, so that the 4
 // alignments of a wavefront and the 16 of a workgroup have similar lengths.  The plan then runs through the slice pipeline of
-// swmi_table.cpp.  This file is the only host source that names the ragged launchers; its name lies outside csrc/swmi_*.cpp,
-// which tests/test_table_host_fake.py links against a fake GPU that knows the fixed-length launchers only.
+// swmi_table.cpp, on the fixed-length entries' Table (table_api.cpp).  This file is the only host source that names the ragged
+// launchers, so that the fake-GPU build of the fixed-length entries (tests/test_table_host_fake.py) links without them.
 #include "swmi_host.h"
 
 #include <algorithm>
@@ -43,7 +43,7 @@ size_t ragged_bytes(bool affine, bool tb, size_t len1)
 size_t budget(bool affine, bool tb)
 {
     if (!tb) return kTableSliceBytes;
-    return (affine ? affine_table(1, nullptr, 0, 0) : local_table(1, nullptr, 0)).tb_slice_bytes;
+    return family_table(affine ? kTableLocalAffine : kTableLocal, 1, SWMI_LOCAL_SEQ2_LEN, nullptr, 0, 0, 0).tb_slice_bytes;
 }
 
 int check_offsets(const uint64_t *off, size_t n)
@@ -145,7 +145,7 @@ int ragged(bool affine, bool device, const char *entry, const void *seq1s, const
     if (rc != SWMI_OK) return rc;
     RaggedPlan plan;
     make_plan(plan, off, n, affine, moves != nullptr);
-    Table t = affine ? affine_table(1, sm, gap, gap_extend) : local_table(1, sm, gap);
+    Table t = family_table(affine ? kTableLocalAffine : kTableLocal, 1, SWMI_LOCAL_SEQ2_LEN, sm, gap, gap_extend, 0);
     t.plan = &plan;
     if (device) return table_device(t, seq1s, seq2s, n, scores, ends, moves, steps, stream);
     return table_host(t, entry, static_cast<const uint8_t *>(seq1s), static_cast<const uint8_t *>(seq2s), n,

@@ -669,16 +669,7 @@ void destroy_context(Context &c)
         (void)hipFree(g.d_moves);
         g = SgSet{};
     }
-    c.local_state.reset();              // (after the synchronisation above: its deleter frees device memory)
-    c.sgfull_state.reset();
-    c.local_affine_state.reset();
-    c.sgfull_affine_state.reset();
-    c.local_full_state.reset();
-    c.local_full_affine_state.reset();
-    c.global_full_state.reset();
-    c.global_full_affine_state.reset();
-    c.global_long_state.reset();
-    c.global_long_affine_state.reset();
+    for (auto &state : c.table_states) state.reset();      // (after the synchronisation above: their deleters free device memory)
     if (c.pin) (void)hipHostFree(c.pin);
     c.pin = nullptr;
     c.pin_dev = nullptr;

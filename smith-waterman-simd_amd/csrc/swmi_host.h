@@ -139,6 +139,12 @@ struct Workspace {
     size_t bytes = 0;
 };
 
+// The aligners that run through the slice pipeline of swmi_table.cpp, one row of table_api.cpp each
+enum TableFamily {
+    kTableLocal, kTableSgfull, kTableLocalAffine, kTableSgfullAffine, kTableLocalFull, kTableLocalFullAffine, kTableGlobalFull,
+    kTableGlobalFullAffine, kTableGlobalLong, kTableGlobalLongAffine, kTableFamilies
+};
+
 // Everything the library owns on ONE bound GPU.  A GPU may be bound twice (swmi_init_devices({0, 0})): two contexts,
 // two stream sets, the same hardware.
 struct Context {
@@ -166,19 +172,10 @@ struct Context {
     uint8_t *pin = nullptr;             // [kPinPairs * 128] seq1s, [kPinPairs * 128] seq2s, [kPinPairs] int32 scores
     void *pin_dev = nullptr;            // the same memory as the device sees it
     unsigned extra_lds = 0;             // SWMI_EXTRA_LDS: occupancy sweep knob (BASELINE config 3)
-    // Device buffers of the local and the exact semi-global aligner, one state each, which live in another translation
-    // unit (swmi_table.cpp) and are created there on first use under ws_mu.  destroy_context drops the last reference after
+    // Device buffers of the table aligners, one state per family (TableFamily), which live in another translation unit
+    // (swmi_table.cpp) and are created there on first use under ws_mu.  destroy_context drops the last reference after
     // synchronising the device, and the owner's deleter frees what it holds -- so this file needs no symbol of that one.
-    std::shared_ptr<void> local_state;
-    std::shared_ptr<void> sgfull_state;
-    std::shared_ptr<void> local_affine_state;   // the affine local aligner's (local_affine_api.cpp through the same pipeline)
-    std::shared_ptr<void> sgfull_affine_state;  // the affine exact semi-global aligner's (sgfull_affine_api.cpp, likewise)
-    std::shared_ptr<void> local_full_state;     // the any-length local aligner's (local_full_api.cpp, likewise)
-    std::shared_ptr<void> local_full_affine_state;  // the any-length affine local aligner's (local_full_affine_api.cpp, likewise)
-    std::shared_ptr<void> global_full_state;    // the global / free-end-gap aligner's (global_full_api.cpp, likewise)
-    std::shared_ptr<void> global_full_affine_state;  // the affine global / free-end-gap aligner's (global_full_affine_api.cpp, likewise)
-    std::shared_ptr<void> global_long_state;         // the striped global aligner's (global_long_api.cpp, likewise)
-    std::shared_ptr<void> global_long_affine_state;  // the striped affine global aligner's (global_long_affine_api.cpp, likewise)
+    std::shared_ptr<void> table_states[kTableFamilies];
     std::mutex mu;                      // serialises use of the slots, the sg sets and the pinned buffer
 };
 
@@ -205,7 +202,7 @@ int score_host_batch(Context &ctx, const uint8_t *s1, const uint8_t *s2, size_t 
 
 // ---- the table aligners' slice pipeline (swmi_table.cpp) ----
 // One call of an aligner that fills the whole table, writes codes and walks them: its lengths and parameters checked, and
-// what differs between the aligners as data -- how a slice launches, which Context member holds its device buffers, and
+// what differs between the aligners as data -- how a slice launches, which family's state holds its device buffers, and
 // how much device memory a traceback slice may take.  Ends-only slices always take at most kTableSliceBytes.
 struct Table;
 using TableLaunch = hipError_t (*)(const Table &t, const uint8_t *s1, const uint8_t *s2, size_t n, int32_t *scores, int32_t *ends,
@@ -215,9 +212,10 @@ using RaggedLaunch = hipError_t (*)(const Table &t, size_t slice, const uint8_t 
                                     int32_t *scores, int32_t *ends, uint32_t *codes, unsigned long long *moves, uint32_t *counts,
                                     hipStream_t st);
 // A batch with lengths of its own per alignment: the local aligners' with a seq1 length each (local_ragged_api.cpp), the
-// any-length local and global aligners' with a seq1 and a seq2 length each (local_full_ragged_api.cpp, global_full_ragged_api.cpp).  Its slices, contiguous in caller
-// order, and one slot per alignment (LocalWork or TileWork: the pipeline copies slots as bytes and hands them to `launch`),
-// slice-relative, in the order the plan's owner gave the slots of each slice.
+// any-length local and global aligners' with a seq1 and a seq2 length each (local_full_ragged_api.cpp,
+// global_full_ragged_api.cpp).  Its slices, contiguous in caller order, and one slot per alignment (LocalWork or TileWork:
+// the pipeline copies slots as bytes and hands them to `launch`), slice-relative, in the order the plan's owner gave the
+// slots of each slice.
 struct RaggedPlan {
     RaggedLaunch launch;
     const uint64_t *seq1_offsets;               // the caller's n + 1
@@ -233,7 +231,7 @@ struct RaggedPlan {
 };
 struct Table {
     TableLaunch launch;
-    std::shared_ptr<void> Context::*state;      // created on first use under Context::ws_mu, dropped by destroy_context
+    TableFamily state;          // Context::table_states[state]: created on first use under Context::ws_mu, dropped by destroy_context
     size_t tb_slice_bytes;      // device bytes of one traceback slice's buffers
     const char *count;          // name of the per-alignment count array: "steps" (= moves) or "lengths" (= moves + 1)
     size_t len1, len2;          // len2 = SWMI_LOCAL_SEQ2_LEN for the local aligners
@@ -244,7 +242,7 @@ struct Table {
     int gap, gap_extend;        // gap_extend: the affine aligner's (gap is then the open cost)
     const RaggedPlan *plan = nullptr;   // a ragged batch: len1, code_words and move_words unused, slices as the plan says
     unsigned free_ends = 0;             // the global aligners' mask of SWMI_FREE_*, which their slice launchers read
-    // The striped global aligners' carry (global_long_api.cpp): dwords per alignment of device scratch that a slice's kernel needs
+    // The striped global aligners' carry (table_api.cpp): dwords per alignment of device scratch that a slice's kernel needs
     // with or without a traceback, counted in a slice's bytes; the pipeline allocates it beside the codes and hands the launcher
     // a copy of the Table whose `carry` points at the slice's (NULL where carry_words is 0).
     size_t carry_words = 0;
@@ -261,18 +259,9 @@ int table_host(const Table &t, const char *entry, const uint8_t *seq1s, const ui
 int table_time_device(const Table &t, const char *entry, const void *d_seq1s, const void *d_seq2s, size_t n, void *d_scores,
                       void *d_ends, void *d_moves, void *d_counts, void *stream, int iters, float *avg_ms);
 int table_check_timer(size_t n, int iters, const float *avg_ms);   // what the timers check before their first call
-Table local_table(size_t len1, const int8_t *sm, int gap);                               // swmi_table.cpp
-Table affine_table(size_t len1, const int8_t *sm, int gap_open, int gap_extend);         // local_affine_api.cpp
-Table local_full_table(size_t len1, size_t len2, const int8_t *sm, int gap);             // local_full_api.cpp
-Table local_full_affine_table(size_t len1, size_t len2, const int8_t *sm, int gap_open, int gap_extend);   // local_full_affine_api.cpp
-Table global_full_table(size_t len1, size_t len2, const int8_t *sm, int gap, unsigned free_ends);         // global_full_api.cpp
-Table global_full_affine_table(size_t len1, size_t len2, const int8_t *sm, int gap_open, int gap_extend,
-                               unsigned free_ends);                                                        // global_full_affine_api.cpp
-Table global_long_table(size_t len1, size_t len2, const int8_t *sm, int gap, unsigned free_ends);         // global_long_api.cpp
-Table global_long_affine_table(size_t len1, size_t len2, const int8_t *sm, int gap_open, int gap_extend,
-                               unsigned free_ends);                                                        // global_long_affine_api.cpp
-// the striped aligners' domain rule (include/swmi.h): P (len1 + len2) <= 2^23 with P = max(1, max |sm|, gaps...)
-bool global_long_domain_ok(size_t len1, size_t len2, const int8_t *sm, int gap_a, int gap_b);             // global_long_api.cpp
+// table_api.cpp: the Table of one call of a family, from its row (len2 = SWMI_LOCAL_SEQ2_LEN for the two local families;
+// gap_extend is read by the affine families and free_ends by those with a mask)
+Table family_table(TableFamily f, size_t len1, size_t len2, const int8_t *sm, int gap, int gap_extend, unsigned free_ends);
 // local_full_ragged_api.cpp: the plan of a ragged any-length batch alone (no device), for tests of its arithmetic -- per slice
 // its alignments and device bytes; true when every code base equals the 64-bit running sum of the code words before it
 bool local_full_ragged_plan_check(const uint64_t *seq1_offsets, const uint64_t *seq2_offsets, size_t n, bool affine, bool tb,
@@ -281,7 +270,7 @@ bool local_full_ragged_plan_check(const uint64_t *seq1_offsets, const uint64_t *
 bool global_full_ragged_plan_check(const uint64_t *seq1_offsets, const uint64_t *seq2_offsets, size_t n, bool affine, bool tb,
                                    std::vector<size_t> *slice_sizes, std::vector<size_t> *slice_bytes);
 // Free one aligner's device buffers on the current GPU (synchronises the device first): the body of the *_release_workspaces entries
-int table_release_workspaces(std::shared_ptr<void> Context::*member);
+int table_release_workspaces(TableFamily family);
 
 #define SWMI_HIP_TRY(expr)                                                                                          \
     do {                                                                                                            \

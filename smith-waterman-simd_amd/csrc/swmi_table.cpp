@@ -1,18 +1,9 @@
-// swmi_table.cpp -- host side of the aligners that fill the whole table, write codes and walk them (include/swmi.h): the local
-// aligner with end cell, start cell and traceback (swmi_local_*) and the exact semi-global aligner with
-// traceback (swmi_semiglobal_full*, section 13) here, and the one slice pipeline that they and the affine aligners
-// (local_affine_api.cpp, section 14; sgfull_affine_api.cpp, section 16), the any-length local aligners (local_full_api.cpp,
-// section 17; local_full_affine_api.cpp, section 18) and the ragged batches (local_ragged_api.cpp, section 15;
-// local_full_ragged_api.cpp, section 19) run through.  What differs between them is data (struct Table, swmi_host.h).
-//
-// Their device buffers hang off Context::local_state, sgfull_state, local_affine_state, sgfull_affine_state and
-// local_full_state, local_full_affine_state, global_full_state (global_full_api.cpp, section 20) and global_full_affine_state
-// (global_full_affine_api.cpp, section 21), global_long_state and global_long_affine_state (global_long_api.cpp,
-// global_long_affine_api.cpp, section 23), which
-// destroy_context (swmi_api.cpp) drops at swmi_shutdown: that file names no symbol of this one, so the host-only builds of swmi_api.cpp /
-// swmi_multi.cpp (tests/test_multi_fake.py, tests/test_sanitizers.py) link without these kernels -- and this file names no
-// launcher but launch_local and launch_sgfull, so that the fake-GPU build of every swmi_*.cpp (tests/test_table_host_fake.py)
-// links without the affine kernels and the any-length local ones.
+// swmi_table.cpp -- the one slice pipeline of the aligners that fill the whole table, write codes and walk them: host
+// entry, device entry, timer, slice arithmetic and the per-family device buffers (DESIGN.md sections 12 to 23).  What
+// differs between the aligners is data (struct Table, swmi_host.h), which table_api.cpp builds per family and the ragged
+// api files extend with a plan.  The buffers hang off Context::table_states, which destroy_context (swmi_api.cpp) drops at
+// swmi_shutdown: that file names no symbol of this one, so the host-only builds of swmi_api.cpp / swmi_multi.cpp
+// (tests/test_multi_fake.py, tests/test_sanitizers.py) link without the table code -- and this file names no launcher.
 #include "swmi_host.h"
 
 #include <algorithm>
@@ -21,32 +12,6 @@
 namespace swmi {
 namespace host {
 namespace {
-
-hipError_t launch_local_slice(const Table &t, const uint8_t *s1, const uint8_t *s2, size_t n, int32_t *scores, int32_t *ends,
-                              uint32_t *codes, unsigned long long *moves, uint32_t *counts, hipStream_t st)
-{
-    return swmi::launch_local(s1, s2, (int)t.len1, n, t.sm, t.gap, scores, ends, codes, moves, counts, t.move_words, st);
-}
-
-hipError_t launch_sgfull_slice(const Table &t, const uint8_t *s1, const uint8_t *s2, size_t n, int32_t *scores, int32_t *ends,
-                               uint32_t *codes, unsigned long long *moves, uint32_t *counts, hipStream_t st)
-{
-    return swmi::launch_sgfull(s1, s2, (int)t.len1, (int)t.len2, n, t.sm, t.gap, scores, ends, codes, moves, counts, t.move_words, st);
-}
-
-// An exact semi-global traceback slice holds as many alignments as 256 of 16384 x 16384 (about 16.1 GiB): one workgroup per
-// alignment, so that a full-size batch occupies every CU of an MI355X.
-Table sgfull_table(size_t len1, size_t len2, const int8_t *sm, int gap)
-{
-    Table t{launch_sgfull_slice, &Context::sgfull_state, 0, "lengths", len1, len2, 2, swmi::sgfull_code_words((int)len1, (int)len2),
-            SWMI_SGFULL_MOVE_WORDS(len1, len2), 1, sm, gap, 0};
-    Table full = t;
-    full.len1 = full.len2 = SWMI_SGFULL_MAX_LEN;
-    full.code_words = swmi::sgfull_code_words(SWMI_SGFULL_MAX_LEN, SWMI_SGFULL_MAX_LEN);
-    full.move_words = SWMI_SGFULL_MOVE_WORDS(SWMI_SGFULL_MAX_LEN, SWMI_SGFULL_MAX_LEN);
-    t.tb_slice_bytes = 256 * table_slice_bytes(full, true);
-    return t;
-}
 
 size_t slice_size(const Table &t, size_t n, bool tb)
 {
@@ -114,15 +79,13 @@ struct TableState {
     ~TableState() { release(); }
 };
 
-TableState &state(Context &ctx, std::shared_ptr<void> Context::*member)
+TableState &state(Context &ctx, TableFamily family)
 {
     std::lock_guard<std::mutex> lock(ctx.ws_mu);
-    std::shared_ptr<void> &p = ctx.*member;
+    std::shared_ptr<void> &p = ctx.table_states[family];
     if (!p) p = std::make_shared<TableState>();
     return *static_cast<TableState *>(p.get());
 }
-
-bool len_ok(size_t len, size_t max) { return len >= 1 && len <= max; }
 
 // Where slice by slice a batch's data lie: evenly cut for one length, as the plan says for a ragged batch.  Offsets count
 // alignments (first), seq1 and seq2 bytes (seq1, seq2) and move words (moves) from the start of the caller's arrays.
@@ -155,26 +118,7 @@ hipError_t launch_table(const Table &t, size_t slice, const uint8_t *s1, const u
     return t.launch(with_carry, s1, s2, m, scores, ends, codes, moves, counts, st);
 }
 
-int check_local(size_t len1, const int8_t *sm, int gap)
-{
-    if (!len_ok(len1, SWMI_LOCAL_MAX_LEN)) return fail(SWMI_ERR_INVALID_ARGUMENT, "len1 %zu outside [1, %d]", len1, SWMI_LOCAL_MAX_LEN);
-    return check_params(sm, gap);
-}
-
-int check_sgfull(size_t len1, size_t len2, const int8_t *sm, int gap)
-{
-    if (!len_ok(len1, SWMI_SGFULL_MAX_LEN) || !len_ok(len2, SWMI_SGFULL_MAX_LEN))
-        return fail(SWMI_ERR_INVALID_ARGUMENT, "lengths (%zu, %zu) outside [1, %d]", len1, len2, SWMI_SGFULL_MAX_LEN);
-    return check_params(sm, gap);
-}
-
 }  // namespace
-
-Table local_table(size_t len1, const int8_t *sm, int gap)
-{
-    return {launch_local_slice, &Context::local_state, kTableSliceBytes, "steps", len1, SWMI_LOCAL_SEQ2_LEN, 4,
-            swmi::local_code_words((int)len1), SWMI_LOCAL_MOVE_WORDS(len1), 0, sm, gap, 0};
-}
 
 // device bytes one alignment of a slice takes: inputs, results, and with a traceback the codes, the moves and the count
 size_t table_slice_bytes(const Table &t, bool tb)
@@ -384,12 +328,12 @@ int table_time_device(const Table &t, const char *entry, const void *d_seq1s, co
     return rc;
 }
 
-int table_release_workspaces(std::shared_ptr<void> Context::*member)
+int table_release_workspaces(TableFamily family)
 {
     Context *ctx = current();
     if (!ctx) return last_status();
     SWMI_HIP_TRY(hipDeviceSynchronize());
-    TableState &ts = state(*ctx, member);
+    TableState &ts = state(*ctx, family);
     std::lock_guard<std::mutex> host_lock(ctx->mu);
     std::lock_guard<std::mutex> lock(ts.mu);
     ts.release();
@@ -398,109 +342,3 @@ int table_release_workspaces(std::shared_ptr<void> Context::*member)
 
 }  // namespace host
 }  // namespace swmi
-
-using namespace swmi::host;
-
-extern "C" {
-
-size_t swmi_local_slices_for(size_t n, size_t len1, int traceback, size_t *sizes, size_t cap)
-{
-    return len_ok(len1, SWMI_LOCAL_MAX_LEN) ? table_slices_for(local_table(len1, nullptr, 0), n, traceback != 0, sizes, cap) : 0;
-}
-
-int swmi_local_align_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t n, const int8_t score_matrix[16],
-                            int8_t gap_penalty, void *d_scores, void *d_ends, void *d_moves, void *d_steps, void *stream)
-{
-    const int rc = check_local(len1, score_matrix, gap_penalty);
-    if (rc != SWMI_OK) return rc;
-    return table_device(local_table(len1, score_matrix, gap_penalty), d_seq1s, d_seq2s, n, d_scores, d_ends, d_moves, d_steps, stream);
-}
-
-int swmi_local_align(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t n, const int8_t score_matrix[16],
-                     int8_t gap_penalty, int32_t *scores, int32_t *ends, uint64_t *moves, uint32_t *steps)
-{
-    const int rc = check_local(len1, score_matrix, gap_penalty);
-    if (rc != SWMI_OK) return rc;
-    return table_host(local_table(len1, score_matrix, gap_penalty), __func__, seq1s, seq2s, n, scores, ends, moves, steps);
-}
-
-int swmi_local_time_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t n, const int8_t score_matrix[16],
-                           int8_t gap_penalty, void *d_scores, void *d_ends, void *d_moves, void *d_steps, void *stream, int iters,
-                           float *avg_ms)
-{
-    int rc = table_check_timer(n, iters, avg_ms);
-    if (rc == SWMI_OK) rc = check_local(len1, score_matrix, gap_penalty);
-    if (rc != SWMI_OK) return rc;
-    return table_time_device(local_table(len1, score_matrix, gap_penalty), __func__, d_seq1s, d_seq2s, n, d_scores, d_ends, d_moves,
-                             d_steps, stream, iters, avg_ms);
-}
-
-// The reference's list (source.cpp:1571-1572: from the start cell to the end cell) from the walk's moves: the start cell is
-// the end cell less the moves' row / column steps, and the list applies the moves last to first.
-int swmi_local_expand_moves(const uint64_t *moves, uint32_t steps, int32_t end_i, int32_t end_j, int32_t *positions, size_t cap)
-{
-    if ((!moves && steps) || (!positions && cap)) return fail(SWMI_ERR_INVALID_ARGUMENT, "NULL buffer");
-    if (end_i < 0 || end_j < 0 || end_i > SWMI_LOCAL_MAX_LEN || end_j > SWMI_LOCAL_SEQ2_LEN)
-        return fail(SWMI_ERR_INVALID_ARGUMENT, "end cell (%d, %d) outside the matrix", end_i, end_j);
-    if (steps > (uint32_t)end_i + (uint32_t)end_j) return fail(SWMI_ERR_INVALID_ARGUMENT, "%u steps cannot start inside the matrix from (%d, %d)", steps, end_i, end_j);
-    int32_t i = end_i, j = end_j;
-    for (uint32_t t = 0; t < steps; ++t) {
-        const unsigned c = unsigned(moves[t >> 5] >> (2 * (t & 31))) & 3u;
-        if (c == 0) return fail(SWMI_ERR_INVALID_ARGUMENT, "move %u is 0", t);
-        i -= c != 1;
-        j -= c != 2;
-    }
-    if (i < 0 || j < 0) return fail(SWMI_ERR_INVALID_ARGUMENT, "the moves leave the matrix");
-    const size_t count = size_t(steps) + 1 < cap ? size_t(steps) + 1 : cap;
-    for (size_t k = 0; k < count; ++k) {
-        positions[2 * k] = i;
-        positions[2 * k + 1] = j;
-        if (k + 1 < count) {
-            const uint32_t t = steps - 1 - uint32_t(k);          // the move that leads from list position k to k + 1
-            const unsigned c = unsigned(moves[t >> 5] >> (2 * (t & 31))) & 3u;
-            i += c != 1;
-            j += c != 2;
-        }
-    }
-    return SWMI_OK;
-}
-
-size_t swmi_semiglobal_full_slices_for(size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap)
-{
-    if (!len_ok(len1, SWMI_SGFULL_MAX_LEN) || !len_ok(len2, SWMI_SGFULL_MAX_LEN)) return 0;
-    return table_slices_for(sgfull_table(len1, len2, nullptr, 0), n, traceback != 0, sizes, cap);
-}
-
-int swmi_semiglobal_full_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
-                                const int8_t score_matrix[16], int8_t gap_penalty, void *d_scores, void *d_ends, void *d_moves,
-                                void *d_lengths, void *stream)
-{
-    const int rc = check_sgfull(len1, len2, score_matrix, gap_penalty);
-    if (rc != SWMI_OK) return rc;
-    return table_device(sgfull_table(len1, len2, score_matrix, gap_penalty), d_seq1s, d_seq2s, n, d_scores, d_ends, d_moves,
-                        d_lengths, stream);
-}
-
-int swmi_semiglobal_full(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t len2, size_t n,
-                         const int8_t score_matrix[16], int8_t gap_penalty, int32_t *scores, int32_t *ends, uint64_t *moves,
-                         uint32_t *lengths)
-{
-    const int rc = check_sgfull(len1, len2, score_matrix, gap_penalty);
-    if (rc != SWMI_OK) return rc;
-    return table_host(sgfull_table(len1, len2, score_matrix, gap_penalty), __func__, seq1s, seq2s, n, scores, ends, moves, lengths);
-}
-
-int swmi_semiglobal_full_release_workspaces(void) { return table_release_workspaces(&Context::sgfull_state); }
-
-int swmi_semiglobal_full_time_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
-                                     const int8_t score_matrix[16], int8_t gap_penalty, void *d_scores, void *d_ends, void *d_moves,
-                                     void *d_lengths, void *stream, int iters, float *avg_ms)
-{
-    int rc = table_check_timer(n, iters, avg_ms);
-    if (rc == SWMI_OK) rc = check_sgfull(len1, len2, score_matrix, gap_penalty);
-    if (rc != SWMI_OK) return rc;
-    return table_time_device(sgfull_table(len1, len2, score_matrix, gap_penalty), __func__, d_seq1s, d_seq2s, n, d_scores, d_ends,
-                             d_moves, d_lengths, stream, iters, avg_ms);
-}
-
-}  // extern "C"

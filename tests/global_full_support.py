@@ -1,5 +1,5 @@
 """Helpers of the global / free-end-gap aligner's tests (test_global_full_cpu.py, test_global_full_gpu.py,
-test_global_full_host_fake.py): the C restatement tests/native/global_full_oracle.c, compiled into a temporary directory
+test_table_host_fake.py): the C restatement tests/native/global_full_oracle.c, compiled into a temporary directory
 (these semantics have no reference counterpart, so the restatement is their definition), an independent numpy formulation
 for small shapes, and the checks every path has to pass whatever the tie rules."""
 import ctypes

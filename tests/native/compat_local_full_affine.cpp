@@ -1,6 +1,6 @@
 // compat_local_full_affine.cpp -- the C++ overloads of the any-length affine local aligner (include/swmi_compat.hpp):
 // SmithWaterman_long_affine_mi355x and swmi::SmithWaterman_long_affine_mi355x_batch.  Compiled by
-// tests/test_local_full_affine_host_fake.py (no device needed to compile and link), run by tests/test_local_full_affine_gpu.py.
+// tests/test_table_host_fake.py (no device needed to compile and link), run by tests/test_local_full_affine_gpu.py.
 //
 //   compat_local_full_affine <file> [piece]
 //

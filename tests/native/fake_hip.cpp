@@ -1,5 +1,5 @@
 // fake_hip.cpp -- TEST INFRASTRUCTURE ONLY: a recording stand-in for the HIP runtime and for the kernel launchers, so that the
-// product's HOST code (swmi_api.cpp, swmi_multi.cpp, swmi_table.cpp) can run on a machine with no GPU at all:
+// product's HOST code (swmi_api.cpp, swmi_multi.cpp, swmi_table.cpp, table_api.cpp) can run on a machine with no GPU at all:
 // FAKE_HIP_DEVICES "gfx950" devices whose memory is host memory, copies that happen at once -- EXCEPT device-to-host copies on
 // a stream (hipMemcpyAsync and hipMemcpy2DAsync), which are held back until that stream (or the device, or an event) is
 // synchronised and read the device buffer
@@ -227,7 +227,7 @@ hipError_t hipDeviceCanAccessPeer(int *can, int a, int b) { *can = a != b; retur
 hipError_t hipDeviceEnablePeerAccess(int peer, unsigned) { log("dev%d enable_peer dev%d", t_device, peer); return hipSuccess; }
 }  // extern "C"
 
-// ---- stand-ins for the kernel launchers (sw_kernels.hip, sg_kernels.hip, local_kernels.hip, sgfull_kernels.hip) -------------
+// ---- stand-ins for the kernel launchers (sw_kernels.hip, sg_kernels.hip and the ten fixed-shape table aligners') ------------
 namespace swmi {
 bool schedule_supported(int L) { return L == 64 || L == 32 || L == 16 || L == 8 || L == 4 || L == 2; }
 static void fake_scores(const uint8_t *s1, size_t stride, int32_t *out, size_t n)
@@ -275,54 +275,159 @@ hipError_t launch_semiglobal(const uint8_t *, const uint8_t *, size_t, void *, i
 size_t semiglobal_move_words() { return 1040; }
 void semiglobal_kernel_names(size_t, int, char *a, size_t an, char *b, size_t bn, SgTuning) { if (a && an) a[0] = 0; if (b && bn) b[0] = 0; }
 
-// The table aligners (local_kernels.hip, sgfull_kernels.hip).  Their code workspaces take a constant kFakeCodeWords dwords per
-// alignment, not the kernels' formula: a slice is then a few thousand alignments (the exact semi-global traceback budget,
-// 256 alignments of 16384 x 16384, about 11 MiB), so multi-slice batches stay small.  Alignment k of a launch reads its
-// index `id` from the first (up to) four bytes of its seq1 and writes score 2 id + 1, ends[e] = 8 id + e + 3, and with a
-// traceback (id >> 20) % (32 move_words + 1) moves, reported as that + count_offset (local steps: 0, semi-global lengths: 1),
-// and move word w = 0xC0DE << 48 | id << 16 | w in EVERY word of its row.  tests/native/table_host_fake.cpp states the same.
+// The ten fixed-shape table aligners (table_api.cpp names their launchers), all through fake_table.  Their code workspaces take
+// a constant kFakeCodeWords dwords (half as many qwords with affine gaps) per alignment, not the kernels' formula: a slice is then
+// a few thousand alignments at a small shape and the real 256 at 16384 x 16384, and the buffers stay small -- except while
+// fake_hip_real_code_sizes(1) holds, for slice sizes worked out by hand (nothing may launch then: fake_table checks its codes
+// against the constant).  Alignment k of a launch reads its index `id` from the first (up to) four bytes of its seq1 and writes
+// score 2 id + 1, ends[e] = 8 id + e + 3, and with a traceback (id >> 20) % (32 move_words + 1) moves, reported as that +
+// count_offset (steps: 0, the semi-global lengths: 1), and move word w = 0xC0DE << 48 | id << 16 | w in EVERY word of its row.
+// Every operand must lie inside one live device block, the carry of a striped launch (carry_words dwords per alignment, 8-byte
+// aligned) included; the carry's first and last dword are written.  One log line per launch states what the launcher was
+// handed: tests/native/table_host_fake.cpp reads it back.
 constexpr size_t kFakeCodeWords = 1024;
-static void fake_table(const char *name, const uint8_t *s1, size_t len1, const uint8_t *s2, size_t len2, size_t n, int32_t *scores,
-                       int32_t *ends, size_t n_ends, uint32_t *codes, unsigned long long *moves, uint32_t *counts, uint32_t count_offset,
-                       size_t move_words, hipStream_t st)
+static bool g_real_code_sizes = false;
+extern "C" void fake_hip_real_code_sizes(int on) { g_real_code_sizes = on != 0; }
+// the kernels' own sizes: local_kernels.hip / local_affine_kernels.hip (16 lanes, trips of 8 steps) and tile_sweep.h
+static size_t local_words(int len1, size_t per_step) { return size_t((len1 + 15 + 7) / 8) * 8 * per_step; }
+static size_t tile_words(int len1, int len2) { return size_t((len2 + 1023) / 1024) * size_t((len1 + 63 + 31) / 32 * 8) * 256; }
+static size_t tile_or_fake(int len1, int len2, size_t fake) { return g_real_code_sizes ? tile_words(len1, len2) : fake; }
+extern "C" unsigned fake_hip_matrix_sum(const int8_t *sm)        // what a launch line prints for its matrix
 {
-    log("dev%d %s n%zu stream%d", t_device, name, n, stream_id(st));
+    unsigned h = 0;
+    for (int x = 0; x < 16; ++x) h = h * 31 + uint8_t(sm[x]);
+    return h;
+}
+
+struct TableArgs {
+    const char *name;
+    const uint8_t *s1, *s2;
+    int len1, len2;
+    size_t n;
+    const int8_t *sm;
+    int gap, extend;
+    unsigned mask;
+    int32_t *scores, *ends;
+    size_t n_ends;
+    void *codes;
+    unsigned long long *moves;
+    uint32_t *counts;
+    uint32_t count_offset;
+    size_t move_words;
+    int32_t *carry;
+    size_t carry_words;         // dwords per alignment that the launch needs at `carry`
+    hipStream_t st;
+};
+static hipError_t fake_table(const TableArgs &a)
+{
+    log("dev%d %s n%zu stream%d len%dx%d tb%d mask%u gap%d extend%d sm%u mw%zu carry%p", t_device, a.name, a.n, stream_id(a.st), a.len1,
+        a.len2, a.moves != nullptr, a.mask, a.gap, a.extend, a.sm ? fake_hip_matrix_sum(a.sm) : 0u, a.move_words,
+        static_cast<void *>(a.carry));
     char what[96];
     const auto check = [&](const char *operand, const void *p, size_t bytes) {
-        snprintf(what, sizeof what, "%s %s", name, operand);
+        snprintf(what, sizeof what, "%s %s", a.name, operand);
         check_range(what, p, bytes);
     };
-    check("seq1 reads", s1, n * len1);
-    check("seq2 reads", s2, n * len2);
-    check("score writes", scores, n * sizeof(int32_t));
-    check("end writes", ends, n * n_ends * sizeof(int32_t));
-    if (moves) {
-        check("code writes", codes, n * kFakeCodeWords * sizeof(uint32_t));
-        check("move writes", moves, n * move_words * sizeof(uint64_t));
-        check("count writes", counts, n * sizeof(uint32_t));
+    const size_t n = a.n, len1 = size_t(a.len1), len2 = size_t(a.len2);
+    check("seq1 reads", a.s1, n * len1);
+    check("seq2 reads", a.s2, n * len2);
+    check("score writes", a.scores, n * sizeof(int32_t));
+    check("end writes", a.ends, n * a.n_ends * sizeof(int32_t));
+    if (a.moves) {
+        check("code writes", a.codes, n * kFakeCodeWords * sizeof(uint32_t));
+        check("move writes", a.moves, n * a.move_words * sizeof(uint64_t));
+        check("count writes", a.counts, n * sizeof(uint32_t));
+    }
+    if (a.carry_words && n) {
+        if (!a.carry || (reinterpret_cast<uintptr_t>(a.carry) & 7)) {
+            fprintf(stderr, "fake_hip: %s: carry %p is NULL or not 8-byte aligned\n", a.name, static_cast<void *>(a.carry));
+            abort();
+        }
+        check("carry writes", a.carry, n * a.carry_words * sizeof(int32_t));
+        a.carry[0] = a.carry[n * a.carry_words - 1] = 1;
     }
     for (size_t k = 0; k < n; ++k) {
         uint32_t id = 0;
-        memcpy(&id, s1 + k * len1, len1 < 4 ? len1 : 4);
-        scores[k] = int32_t(2 * id + 1);
-        for (size_t e = 0; e < n_ends; ++e) ends[k * n_ends + e] = int32_t(8 * id + e + 3);
-        if (!moves) continue;
-        counts[k] = uint32_t((id >> 20) % (32 * move_words + 1)) + count_offset;
-        for (size_t w = 0; w < move_words; ++w) moves[k * move_words + w] = 0xC0DEull << 48 | uint64_t(id) << 16 | w;
+        memcpy(&id, a.s1 + k * len1, len1 < 4 ? len1 : 4);
+        a.scores[k] = int32_t(2 * id + 1);
+        for (size_t e = 0; e < a.n_ends; ++e) a.ends[k * a.n_ends + e] = int32_t(8 * id + e + 3);
+        if (!a.moves) continue;
+        a.counts[k] = uint32_t((id >> 20) % (32 * a.move_words + 1)) + a.count_offset;
+        for (size_t w = 0; w < a.move_words; ++w) a.moves[k * a.move_words + w] = 0xC0DEull << 48 | uint64_t(id) << 16 | w;
     }
-}
-size_t local_code_words(int) { return kFakeCodeWords; }
-hipError_t launch_local(const uint8_t *s1, const uint8_t *s2, int len1, size_t n, const int8_t *, int, int32_t *scores, int32_t *ends,
-                        uint32_t *codes, unsigned long long *moves, uint32_t *steps, size_t move_words, hipStream_t st)
-{
-    fake_table("launch_local", s1, len1, s2, 128, n, scores, ends, 4, codes, moves, steps, 0, move_words, st);
     return hipSuccess;
 }
-size_t sgfull_code_words(int, int) { return kFakeCodeWords; }
-hipError_t launch_sgfull(const uint8_t *s1, const uint8_t *s2, int len1, int len2, size_t n, const int8_t *, int, int32_t *scores,
-                         int32_t *ends, uint32_t *codes, unsigned long long *moves, uint32_t *lengths, size_t move_words, hipStream_t st)
+size_t local_code_words(int len1) { return g_real_code_sizes ? local_words(len1, 8) : kFakeCodeWords; }
+size_t local_affine_code_words(int len1) { return g_real_code_sizes ? local_words(len1, 16) : kFakeCodeWords; }
+size_t sgfull_code_words(int len1, int len2) { return tile_or_fake(len1, len2, kFakeCodeWords); }
+size_t local_full_code_words(int len1, int len2) { return tile_or_fake(len1, len2, kFakeCodeWords); }
+size_t global_full_code_words(int len1, int len2) { return tile_or_fake(len1, len2, kFakeCodeWords); }
+size_t global_long_code_words(int len1, int len2) { return tile_or_fake(len1, len2, kFakeCodeWords); }
+size_t sgfull_affine_code_qwords(int len1, int len2) { return tile_or_fake(len1, len2, kFakeCodeWords / 2); }
+size_t local_full_affine_code_qwords(int len1, int len2) { return tile_or_fake(len1, len2, kFakeCodeWords / 2); }
+size_t global_full_affine_code_qwords(int len1, int len2) { return tile_or_fake(len1, len2, kFakeCodeWords / 2); }
+size_t global_long_affine_code_qwords(int len1, int len2) { return tile_or_fake(len1, len2, kFakeCodeWords / 2); }
+
+hipError_t launch_local(const uint8_t *s1, const uint8_t *s2, int len1, size_t n, const int8_t *sm, int gap, int32_t *scores, int32_t *ends,
+                        uint32_t *codes, unsigned long long *moves, uint32_t *steps, size_t mw, hipStream_t st)
 {
-    fake_table("launch_sgfull", s1, len1, s2, len2, n, scores, ends, 2, codes, moves, lengths, 1, move_words, st);
-    return hipSuccess;
+    return fake_table({"launch_local", s1, s2, len1, 128, n, sm, gap, 0, 0, scores, ends, 4, codes, moves, steps, 0, mw, nullptr, 0, st});
+}
+hipError_t launch_local_affine(const uint8_t *s1, const uint8_t *s2, int len1, size_t n, const int8_t *sm, int go, int ge, int32_t *scores,
+                               int32_t *ends, uint32_t *codes, unsigned long long *moves, uint32_t *steps, size_t mw, hipStream_t st)
+{
+    return fake_table({"launch_local_affine", s1, s2, len1, 128, n, sm, go, ge, 0, scores, ends, 4, codes, moves, steps, 0, mw, nullptr, 0, st});
+}
+hipError_t launch_sgfull(const uint8_t *s1, const uint8_t *s2, int len1, int len2, size_t n, const int8_t *sm, int gap, int32_t *scores,
+                         int32_t *ends, uint32_t *codes, unsigned long long *moves, uint32_t *lengths, size_t mw, hipStream_t st)
+{
+    return fake_table({"launch_sgfull", s1, s2, len1, len2, n, sm, gap, 0, 0, scores, ends, 2, codes, moves, lengths, 1, mw, nullptr, 0, st});
+}
+hipError_t launch_sgfull_affine(const uint8_t *s1, const uint8_t *s2, int len1, int len2, size_t n, const int8_t *sm, int go, int ge,
+                                int32_t *scores, int32_t *ends, unsigned long long *codes, unsigned long long *moves, uint32_t *lengths,
+                                size_t mw, hipStream_t st)
+{
+    return fake_table({"launch_sgfull_affine", s1, s2, len1, len2, n, sm, go, ge, 0, scores, ends, 2, codes, moves, lengths, 1, mw, nullptr,
+                       0, st});
+}
+hipError_t launch_local_full(const uint8_t *s1, const uint8_t *s2, int len1, int len2, size_t n, const int8_t *sm, int gap, int32_t *scores,
+                             int32_t *ends, uint32_t *codes, unsigned long long *moves, uint32_t *steps, size_t mw, hipStream_t st)
+{
+    return fake_table({"launch_local_full", s1, s2, len1, len2, n, sm, gap, 0, 0, scores, ends, 4, codes, moves, steps, 0, mw, nullptr, 0, st});
+}
+hipError_t launch_local_full_affine(const uint8_t *s1, const uint8_t *s2, int len1, int len2, size_t n, const int8_t *sm, int go, int ge,
+                                    int32_t *scores, int32_t *ends, unsigned long long *codes, unsigned long long *moves, uint32_t *steps,
+                                    size_t mw, hipStream_t st)
+{
+    return fake_table({"launch_local_full_affine", s1, s2, len1, len2, n, sm, go, ge, 0, scores, ends, 4, codes, moves, steps, 0, mw,
+                       nullptr, 0, st});
+}
+hipError_t launch_global_full(const uint8_t *s1, const uint8_t *s2, int len1, int len2, size_t n, const int8_t *sm, int gap, unsigned fe,
+                              int32_t *scores, int32_t *ends, uint32_t *codes, unsigned long long *moves, uint32_t *steps, size_t mw,
+                              hipStream_t st)
+{
+    return fake_table({"launch_global_full", s1, s2, len1, len2, n, sm, gap, 0, fe, scores, ends, 4, codes, moves, steps, 0, mw, nullptr, 0,
+                       st});
+}
+hipError_t launch_global_full_affine(const uint8_t *s1, const uint8_t *s2, int len1, int len2, size_t n, const int8_t *sm, int go, int ge,
+                                     unsigned fe, int32_t *scores, int32_t *ends, unsigned long long *codes, unsigned long long *moves,
+                                     uint32_t *steps, size_t mw, hipStream_t st)
+{
+    return fake_table({"launch_global_full_affine", s1, s2, len1, len2, n, sm, go, ge, fe, scores, ends, 4, codes, moves, steps, 0, mw,
+                       nullptr, 0, st});
+}
+hipError_t launch_global_long(const uint8_t *s1, const uint8_t *s2, int len1, int len2, size_t n, const int8_t *sm, int gap, unsigned fe,
+                              int32_t *scores, int32_t *ends, uint32_t *codes, unsigned long long *moves, uint32_t *steps, size_t mw,
+                              int32_t *carry, hipStream_t st)
+{
+    return fake_table({"launch_global_long", s1, s2, len1, len2, n, sm, gap, 0, fe, scores, ends, 4, codes, moves, steps, 0, mw, carry,
+                       len2 > 16384 ? size_t(len1) : 0, st});
+}
+hipError_t launch_global_long_affine(const uint8_t *s1, const uint8_t *s2, int len1, int len2, size_t n, const int8_t *sm, int go, int ge,
+                                     unsigned fe, int32_t *scores, int32_t *ends, unsigned long long *codes, unsigned long long *moves,
+                                     uint32_t *steps, size_t mw, int32_t *carry, hipStream_t st)
+{
+    return fake_table({"launch_global_long_affine", s1, s2, len1, len2, n, sm, go, ge, fe, scores, ends, 4, codes, moves, steps, 0, mw,
+                       carry, len2 > 16384 ? 2 * size_t(len1) : 0, st});
 }
 }  // namespace swmi

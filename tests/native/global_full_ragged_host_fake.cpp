@@ -1,7 +1,8 @@
 // global_full_ragged_host_fake.cpp -- the host side of the ragged global / fit / overlap aligners (swmi_global_full_ragged*,
 // swmi_global_full_affine_ragged*: global_full_ragged_api.cpp through the slice pipeline of swmi_table.cpp) on a fake GPU
-// (fake_hip.cpp), plus the stand-ins for the launchers that fake_hip.cpp does not know.  As in global_full_host_fake.cpp the
-// code workspaces take a constant 1024 code words per alignment, so a traceback slice is a few thousand alignments.
+// (fake_hip.cpp), plus the stand-ins for the ragged launchers (fake_hip.cpp holds the fixed-length ones and the code sizes).  The code
+// workspaces take fake_hip.cpp's constant 1024 dwords (512 qwords with affine gaps) per alignment, so a traceback slice is a few
+// thousand alignments.
 // Built and run by tests/test_global_full_ragged_host_fake.py (g++, ASan + UBSan, no GPU).
 //
 // A stand-in launch checks that the matrix, the gaps and the mask are the call's, copies its slots and computes every slot's
@@ -37,6 +38,7 @@
 extern "C" size_t fake_hip_log_size();
 extern "C" const char *fake_hip_log_at(size_t);
 extern "C" void fake_hip_log_clear();
+extern "C" void fake_hip_real_code_sizes(int on);
 
 namespace swmi {
 namespace host {
@@ -54,10 +56,10 @@ bool global_full_ragged_plan_check(const uint64_t *seq1_offsets, const uint64_t 
     } while (0)
 
 constexpr uint64_t kSentinel = 0x5E5E5E5E5E5E5E5Eull;
-constexpr size_t kCodeWords = 1024;
+constexpr size_t kCodeDwords = 1024;     // fake_hip.cpp kFakeCodeWords
+static size_t code_words(bool affine) { return affine ? kCodeDwords / 2 : kCodeDwords; }     // in the family's unit: dwords, qwords
 constexpr int kMax = SWMI_GLOBAL_FULL_MAX_LEN;
 static int8_t g_sm[16];
-static bool g_real_code_words = false;
 // what the call under test was given: the launchers must see exactly this
 static unsigned g_mask = 0;
 constexpr int kGap = 3, kOpen = 5, kExtend = 2;
@@ -148,26 +150,13 @@ static hipError_t fake_launch(bool affine, const uint8_t *s1, const uint8_t *s2,
         steps[w.k] = uint32_t(sums % (32 * mw + 1));
         for (size_t v = 0; v < mw; ++v) moves[w.move_base + v] = 0xC0DEull << 48 | uint64_t(uint32_t(sc)) << 16 | v;
         codes[w.code_base] = 1;
-        codes[w.code_base + kCodeWords - 1] = 1;
+        codes[w.code_base + kCodeDwords * 4 / sizeof(Code) - 1] = 1;
     }
     return hipSuccess;
 }
 
 namespace swmi {
-size_t global_full_code_words(int len1, int len2) { return g_real_code_words ? real_code_words(len1, len2) : kCodeWords; }
-size_t global_full_affine_code_qwords(int len1, int len2) { return g_real_code_words ? real_code_words(len1, len2) : kCodeWords; }
 int global_full_ragged_waves(int len1, int len2) { return len1 > 0 && len2 > 0 ? (len2 + 1023) / 1024 : 1; }
-// the fixed-length launchers, which global_full_api.cpp and global_full_affine_api.cpp name: never called here
-hipError_t launch_global_full(const uint8_t *, const uint8_t *, int, int, size_t, const int8_t *, int, unsigned, int32_t *, int32_t *,
-                              uint32_t *, unsigned long long *, uint32_t *, size_t, hipStream_t)
-{
-    return hipErrorUnknown;
-}
-hipError_t launch_global_full_affine(const uint8_t *, const uint8_t *, int, int, size_t, const int8_t *, int, int, unsigned, int32_t *,
-                                     int32_t *, unsigned long long *, unsigned long long *, uint32_t *, size_t, hipStream_t)
-{
-    return hipErrorUnknown;
-}
 hipError_t launch_global_full_ragged(const uint8_t *s1, const uint8_t *s2, const TileWork *work, size_t n, int waves, const int8_t *sm,
                                      int gap, unsigned free_ends, int32_t *scores, int32_t *ends, uint32_t *codes,
                                      unsigned long long *moves, uint32_t *steps, hipStream_t st)
@@ -238,6 +227,7 @@ static std::vector<Launch> take_launches()
 static size_t check_launches(const Batch &b, const std::vector<size_t> &sizes, const std::vector<Launch> &l, bool affine, bool tb,
                              hipStream_t only_stream)
 {
+    for (size_t k = 0; k < fake_hip_log_size(); ++k) CHECK(!strstr(fake_hip_log_at(k), " launch_"));     // no fixed-length launcher ran
     size_t at = 0, first = 0, max_codes = 0;
     std::vector<hipStream_t> slice_streams;
     for (size_t s = 0; s < sizes.size(); ++s) {
@@ -268,7 +258,7 @@ static size_t check_launches(const Batch &b, const std::vector<size_t> &sizes, c
                 CHECK(w.len1 <= last_len1);                                                               // longest first
                 last_len1 = w.len1;
                 CHECK(w.move_base == b.mo[k] - b.mo[first]);
-                if (tb && w.len1 && w.len2) code_ranges.push_back({w.code_base, w.code_base + kCodeWords});
+                if (tb && w.len1 && w.len2) code_ranges.push_back({w.code_base, w.code_base + code_words(affine)});
                 if (tb && mw_of(w.len1, w.len2)) move_ranges.push_back({w.move_base, w.move_base + mw_of(w.len1, w.len2)});
             }
             covered += x.slots.size();
@@ -279,7 +269,7 @@ static size_t check_launches(const Batch &b, const std::vector<size_t> &sizes, c
             for (size_t i = 1; i < r->size(); ++i) CHECK((*r)[i - 1].second <= (*r)[i].first);
         }
         if (!code_ranges.empty()) {
-            CHECK(code_ranges.back().second == code_ranges.size() * kCodeWords);                          // one block, no holes
+            CHECK(code_ranges.back().second == code_ranges.size() * code_words(affine));                          // one block, no holes
             max_codes = std::max(max_codes, size_t(code_ranges.back().second));
         }
         if (!move_ranges.empty()) CHECK(move_ranges.back().second <= b.mo[first + sizes[s]] - b.mo[first]);
@@ -407,7 +397,7 @@ static std::string workspace_malloc(size_t max_codes, bool affine, size_t n)
 
 static void plan_only_case()
 {
-    g_real_code_words = true;
+    fake_hip_real_code_sizes(1);
     const size_t n = 300;
     std::vector<uint64_t> off(n + 1);
     for (size_t k = 0; k <= n; ++k) off[k] = k * uint64_t(kMax);
@@ -425,7 +415,7 @@ static void plan_only_case()
     CHECK(uint64_t(sizes[0] - 1) * qwords * 2 > (uint64_t(1) << 32) && uint64_t(sizes[0]) * qwords > (uint64_t(1) << 31));
     CHECK(swmi_global_full_ragged_slices_for(off.data(), off.data(), n, 1, 1, nullptr, 0) == 2);
     CHECK(fake_hip_log_size() == 0);                                          // no device was touched
-    g_real_code_words = false;
+    fake_hip_real_code_sizes(0);
     printf("  plan only, 300 x (16384 x 16384) affine traceback: slices 255 + 45, code bases past 2^32 dwords: ok\n");
 }
 

@@ -1,6 +1,6 @@
 // ragged_host_fake.cpp -- the host side of the ragged local aligners (swmi_local_align_ragged*, local_ragged_api.cpp through
 // the slice pipeline of swmi_table.cpp) on the fake GPU of fake_hip.cpp.  This file holds the stand-ins of the ragged
-// launchers and of the affine ones (fake_hip.cpp knows the fixed-length linear launcher only).  Alignment k's seq2 carries k
+// launchers (fake_hip.cpp holds the fixed-length ones and the code sizes).  Alignment k's seq2 carries k
 // in its first four bytes and its seq1 byte j is (k + j) & 255; a stand-in checks every slot of a launch (lengths longest
 // first, equal lengths in caller order, each result index once, its seq1 where the slot says) and writes score 2 k + 1,
 // ends[e] = 8 k + e + 3, steps k % (32 move_words + 1) and move word w = 0xC0DE << 48 | k << 16 | w in every word of its row.
@@ -40,14 +40,6 @@ struct Launch {
 static std::vector<Launch> g_launches;
 
 namespace swmi {
-size_t local_affine_code_words(int) { return 2048; }
-hipError_t launch_local_affine(const uint8_t *, const uint8_t *, int, size_t, const int8_t *, int, int, int32_t *, int32_t *, uint32_t *,
-                               unsigned long long *, uint32_t *, size_t, hipStream_t)
-{
-    fprintf(stderr, "the fixed-length affine launcher ran\n");
-    exit(1);
-}
-
 static hipError_t fake_ragged(bool affine, const uint8_t *s1, const uint8_t *s2, const LocalWork *work, size_t n, int32_t *scores,
                               int32_t *ends, uint32_t *codes, unsigned long long *moves, uint32_t *steps, hipStream_t st)
 {
@@ -155,6 +147,7 @@ static void host_case(const char *name, const std::vector<uint32_t> &lens, bool 
     check_results(b, scores.data(), ends.data(), tb ? moves.data() : nullptr, steps.data());
     // one launch per slice, of the slice's size, alternating between the two sets' streams when there are several
     CHECK(g_launches.size() == sizes.size());
+    for (size_t k = 0; k < fake_hip_log_size(); ++k) CHECK(!strstr(fake_hip_log_at(k), " launch_local"));     // no fixed-length launcher ran
     for (size_t s = 0; s < sizes.size(); ++s) {
         CHECK(g_launches[s].n == sizes[s] && g_launches[s].affine == affine);
         if (s) CHECK(g_launches[s].st != g_launches[s - 1].st);

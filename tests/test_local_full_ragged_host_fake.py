@@ -1,7 +1,7 @@
 """The host side of the ragged any-length local aligners (swmi_local_full_ragged*: local_full_ragged_api.cpp through the slice
-pipeline of swmi_table.cpp) on a fake GPU, no device needed: the real host sources (every csrc/swmi_*.cpp, local_full_api.cpp,
-local_full_affine_api.cpp and local_full_ragged_api.cpp), compiled with g++ and ASan + UBSan against tests/native/fake_hip.cpp
-and tests/native/local_full_ragged_host_fake.cpp, which holds the stand-ins for the launchers that fake_hip.cpp does not know
+pipeline of swmi_table.cpp) on a fake GPU, no device needed: the real host sources (every csrc/swmi_*.cpp, table_api.cpp
+and local_full_ragged_api.cpp), compiled with g++ and ASan + UBSan against tests/native/fake_hip.cpp
+and tests/native/local_full_ragged_host_fake.cpp, which holds the stand-ins for the ragged launchers
 and the checks: every result at its caller position; the slots of every launch (inside the sequences, of the launch's wave
 count, disjoint code and move ranges inside their buffers); a slice's launches in descending wave count covering each slot
 once; one move copy per slice of exactly its words; the device entry growing its workspace on two streams; and the plan alone,
@@ -26,7 +26,7 @@ def fake_exe(tmp_path_factory):
     flags = ["-O1", "-g", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-fsanitize=address,undefined",
              "-fno-sanitize-recover=all"]
     host_sources = sorted(glob.glob(os.path.join(PKG, "csrc", "swmi_*.cpp"))) + [
-        os.path.join(PKG, "csrc", name) for name in ("local_full_api.cpp", "local_full_affine_api.cpp", "local_full_ragged_api.cpp")]
+        os.path.join(PKG, "csrc", name) for name in ("table_api.cpp", "local_full_ragged_api.cpp")]
     b = subprocess.run(["g++"] + flags + ["-o", exe, os.path.join(native, "local_full_ragged_host_fake.cpp"),
                                           os.path.join(native, "fake_hip.cpp")] + host_sources + ["-ldl", "-lpthread"],
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)

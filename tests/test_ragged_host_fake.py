@@ -23,7 +23,7 @@ def ragged_exe(tmp_path_factory):
     flags = ["-O1", "-g", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-fsanitize=address,undefined",
              "-fno-sanitize-recover=all"]
     host_sources = sorted(glob.glob(os.path.join(PKG, "csrc", "swmi_*.cpp"))) + [
-        os.path.join(PKG, "csrc", "local_affine_api.cpp"), os.path.join(PKG, "csrc", "local_ragged_api.cpp")]
+        os.path.join(PKG, "csrc", "table_api.cpp"), os.path.join(PKG, "csrc", "local_ragged_api.cpp")]
     b = subprocess.run(["g++"] + flags + ["-o", exe, os.path.join(native, "ragged_host_fake.cpp"), os.path.join(native, "fake_hip.cpp")]
                        + host_sources + ["-ldl", "-lpthread"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if b.returncode != 0 and "asan" in b.stdout.lower() and "cannot find" in b.stdout.lower():
