@@ -901,6 +901,56 @@ SWMI_API int swmi_global_long_affine_time_device(const void *d_seq1s, size_t len
                                                  unsigned free_ends, void *d_scores, void *d_ends, void *d_moves, void *d_steps,
                                                  void *stream, int iters, float *avg_ms);
 
+/* ---- local alignment of sequences up to 65536 long ---------------------------------------------------
+ * swmi_local_full and swmi_local_full_affine for 1 <= len1, len2 <= 65536 (SWMI_LOCAL_LONG_MAX_LEN): the same recurrences, zero
+ * floor, end cell (the first cell in row-major order holding max H; (0, 0) when that is 0), walk (it stops on the first cell
+ * holding 0) and tie order, and the same scores / ends[4] / moves / steps layout, field for field; ends-only (moves and steps
+ * both NULL) ends[4 k + 2] = ends[4 k + 3] = -1.  moves + k * SWMI_LOCAL_LONG_MOVE_WORDS(len1, len2) receives alignment k's
+ * steps (the formula of SWMI_LOCAL_FULL_MOVE_WORDS); swmi_local_long_expand_moves rebuilds the list of steps[k] + 1 positions
+ * (swmi_local_full_expand_moves with end cells up to (65536, 65536)).  On a shape with both lengths <= 16384 the fixed-length
+ * kernel runs, so every field equals the fixed-length entry's.
+ * DOMAIN.  Bytes are taken modulo 4.  There is NO domain rule: 0 <= H <= 127 * 65536 < 2^23 whatever the parameters, so every
+ * int8 matrix and gap (affine: gap_open and gap_extend each in [0, 127]) is accepted at every shape.  0 <= score < 2^23.
+ * Errors: SWMI_ERR_INVALID_ARGUMENT for a length outside [1, 65536], a NULL buffer, or only one of moves / steps; with affine
+ * gaps SWMI_ERR_DOMAIN for a gap outside [0, 127]; n = 0 is a no-op that needs no device.  Every argument is checked before
+ * any device is touched and before any launch.
+ * One workgroup aligns one pair and sweeps len2 in stripes of 16384 columns (the kernels' files tell how); where len2 > 16384
+ * a column of len1 values (affine: 2 len1) per alignment waits between two stripes in device memory, which the library keeps
+ * beside the traceback codes and counts in a slice.
+ * SLICES (swmi_local_long_slices_for, swmi_local_long_affine_slices_for): the budgets are the fixed-length local entries' --
+ * with a traceback what 256 alignments of 16384 x 16384 take, ends-only 256 MiB, at most 2^20 alignments and never fewer than
+ * one.  KNOWN LIMIT: at 65536 x 65536 a traceback slice holds 16 alignments (about 1 GiB of codes each, 2 GiB with affine
+ * gaps, whose budget is twice as large), fewer than an MI355X has CUs.  0 for a length outside [1, 65536].
+ * The _device, _release_workspaces and _time_device forms are the fixed-length entries' (16-byte aligned device buffers,
+ * asynchronous on `stream`, a workspace of the library's per (GPU, stream)). */
+#define SWMI_LOCAL_LONG_MAX_LEN 65536
+#define SWMI_LOCAL_LONG_MOVE_WORDS(len1, len2) ((((((size_t)(len1)) + ((size_t)(len2)) + 31) / 32) + 1) & ~(size_t)1)   /* 16-byte rows */
+SWMI_API int swmi_local_long(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t len2, size_t n,
+                             const int8_t score_matrix[16], int8_t gap_penalty, int32_t *scores, int32_t *ends, uint64_t *moves,
+                             uint32_t *steps);
+SWMI_API size_t swmi_local_long_slices_for(size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap);
+SWMI_API int swmi_local_long_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
+                                    const int8_t score_matrix[16], int8_t gap_penalty, void *d_scores, void *d_ends,
+                                    void *d_moves, void *d_steps, void *stream);
+SWMI_API int swmi_local_long_release_workspaces(void);
+SWMI_API int swmi_local_long_time_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
+                                         const int8_t score_matrix[16], int8_t gap_penalty, void *d_scores, void *d_ends,
+                                         void *d_moves, void *d_steps, void *stream, int iters, float *avg_ms);
+SWMI_API int swmi_local_long_expand_moves(const uint64_t *moves, uint32_t steps, int32_t end_i, int32_t end_j, int32_t *positions,
+                                          size_t cap);
+SWMI_API int swmi_local_long_affine(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t len2, size_t n,
+                                    const int8_t score_matrix[16], int gap_open, int gap_extend, int32_t *scores, int32_t *ends,
+                                    uint64_t *moves, uint32_t *steps);
+SWMI_API size_t swmi_local_long_affine_slices_for(size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap);
+SWMI_API int swmi_local_long_affine_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
+                                           const int8_t score_matrix[16], int gap_open, int gap_extend, void *d_scores,
+                                           void *d_ends, void *d_moves, void *d_steps, void *stream);
+SWMI_API int swmi_local_long_affine_release_workspaces(void);
+SWMI_API int swmi_local_long_affine_time_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
+                                                const int8_t score_matrix[16], int gap_open, int gap_extend, void *d_scores,
+                                                void *d_ends, void *d_moves, void *d_steps, void *stream, int iters,
+                                                float *avg_ms);
+
 /* ---- deferred queue behind the per-pair signature -------------------------------------
  * Lets a per-pair caller (the reference's timing loop) keep its call shape while the
  * library batches: submit() copies the pair into pinned staging memory and returns its

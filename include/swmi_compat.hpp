@@ -120,6 +120,19 @@ inline std::pair<int, std::vector<std::pair<int, int>>> NeedlemanWunsch_long_aff
                                                                                           int gap_open, int gap_extend,
                                                                                           unsigned free_ends = SWMI_ENDS_GLOBAL);
 
+// SmithWaterman_long_mi355x and SmithWaterman_long_affine_mi355x for lengths in [1, 65536] (swmi_local_long,
+// swmi_local_long_affine): the same results, with every int8 matrix and gap at every shape (no domain rule).  One synchronous
+// call per alignment; swmi::SmithWaterman_xlong_mi355x_batch and swmi::SmithWaterman_xlong_affine_mi355x_batch are the
+// throughput forms.
+inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_xlong_mi355x(const std::vector<uint8_t> &seq1,
+                                                                                  const std::vector<uint8_t> &seq2,
+                                                                                  const std::array<int8_t, 16> &score_matrix,
+                                                                                  const int8_t gap_penalty);
+inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_xlong_affine_mi355x(const std::vector<uint8_t> &seq1,
+                                                                                         const std::vector<uint8_t> &seq2,
+                                                                                         const std::array<int8_t, 16> &score_matrix,
+                                                                                         int gap_open, int gap_extend);
+
 namespace swmi {
 
 // match 1, mismatch -1 (source.cpp:1786)
@@ -350,6 +363,15 @@ inline std::vector<std::pair<int, int>> global_long_path(const uint64_t *moves, 
     std::vector<std::pair<int, int>> path(size_t(steps) + 1);
     detail::check(swmi_global_long_expand_moves(moves, steps, ends[0], ends[1], reinterpret_cast<int32_t *>(path.data()), path.size()),
                   "swmi_global_long_expand_moves");
+    return path;
+}
+
+// ... and the long local aligners'
+inline std::vector<std::pair<int, int>> local_long_path(const uint64_t *moves, uint32_t steps, const int32_t *ends)
+{
+    std::vector<std::pair<int, int>> path(size_t(steps) + 1);
+    detail::check(swmi_local_long_expand_moves(moves, steps, ends[0], ends[1], reinterpret_cast<int32_t *>(path.data()), path.size()),
+                  "swmi_local_long_expand_moves");
     return path;
 }
 
@@ -628,6 +650,36 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SmithWaterm
         detail::local_full_path);
 }
 
+// SmithWaterman_long_mi355x_batch for lengths in [1, 65536]: result[k] == SmithWaterman_xlong_mi355x(seq1s[k], seq2s[k], ...).  A
+// piece is at most one traceback slice of swmi_local_long (0 = one slice: 16 at 65536 x 65536).
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SmithWaterman_xlong_mi355x_batch(
+    const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::vector<uint8_t>> &seq2s,
+    const std::array<int8_t, 16> &score_matrix, const int8_t gap_penalty, size_t piece = 0, unsigned threads = 0)
+{
+    return detail::shaped_batch(
+        "SmithWaterman_xlong_mi355x_batch", "swmi_local_long", seq1s, seq2s, piece, threads, 4,
+        SWMI_LOCAL_LONG_MOVE_WORDS(detail::common_length(seq1s), detail::common_length(seq2s)), swmi_local_long_slices_for,
+        [&](const uint8_t *a, size_t len1, const uint8_t *b, size_t len2, size_t m, auto... out) {
+            return swmi_local_long(a, len1, b, len2, m, score_matrix.data(), gap_penalty, out...);
+        },
+        detail::local_long_path);
+}
+
+// SmithWaterman_long_affine_mi355x_batch for lengths in [1, 65536]: result[k] == SmithWaterman_xlong_affine_mi355x(seq1s[k],
+// seq2s[k], ...).  A piece is at most one traceback slice of swmi_local_long_affine.
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SmithWaterman_xlong_affine_mi355x_batch(
+    const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::vector<uint8_t>> &seq2s,
+    const std::array<int8_t, 16> &score_matrix, int gap_open, int gap_extend, size_t piece = 0, unsigned threads = 0)
+{
+    return detail::shaped_batch(
+        "SmithWaterman_xlong_affine_mi355x_batch", "swmi_local_long_affine", seq1s, seq2s, piece, threads, 4,
+        SWMI_LOCAL_LONG_MOVE_WORDS(detail::common_length(seq1s), detail::common_length(seq2s)), swmi_local_long_affine_slices_for,
+        [&](const uint8_t *a, size_t len1, const uint8_t *b, size_t len2, size_t m, auto... out) {
+            return swmi_local_long_affine(a, len1, b, len2, m, score_matrix.data(), gap_open, gap_extend, out...);
+        },
+        detail::local_long_path);
+}
+
 // Any-length local alignments of mixed shapes (swmi_local_full_ragged and its affine twin): seq1s[k] and seq2s[k] each of any
 // length in [0, 16384], in pieces of at most `piece` alignments (0 counts as 4096), each one ragged call, so only two pieces'
 // inputs and moves are held at a time; the paths of one piece are rebuilt on `threads` host threads (0 = as many as the
@@ -851,6 +903,33 @@ inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_long_affin
                                           out...);
         },
         swmi::detail::local_full_path);
+}
+
+inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_xlong_mi355x(const std::vector<uint8_t> &seq1,
+                                                                                  const std::vector<uint8_t> &seq2,
+                                                                                  const std::array<int8_t, 16> &score_matrix,
+                                                                                  const int8_t gap_penalty)
+{
+    return swmi::detail::one_alignment(
+        "swmi_local_long", SWMI_LOCAL_LONG_MOVE_WORDS(seq1.size(), seq2.size()),
+        [&](auto... out) {
+            return swmi_local_long(seq1.data(), seq1.size(), seq2.data(), seq2.size(), 1, score_matrix.data(), gap_penalty, out...);
+        },
+        swmi::detail::local_long_path);
+}
+
+inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_xlong_affine_mi355x(const std::vector<uint8_t> &seq1,
+                                                                                         const std::vector<uint8_t> &seq2,
+                                                                                         const std::array<int8_t, 16> &score_matrix,
+                                                                                         int gap_open, int gap_extend)
+{
+    return swmi::detail::one_alignment(
+        "swmi_local_long_affine", SWMI_LOCAL_LONG_MOVE_WORDS(seq1.size(), seq2.size()),
+        [&](auto... out) {
+            return swmi_local_long_affine(seq1.data(), seq1.size(), seq2.data(), seq2.size(), 1, score_matrix.data(), gap_open, gap_extend,
+                                          out...);
+        },
+        swmi::detail::local_long_path);
 }
 
 inline std::pair<int, std::vector<std::pair<int, int>>> NeedlemanWunsch_mi355x(const std::vector<uint8_t> &seq1,

@@ -13,7 +13,8 @@
 //
 // Mapping, ring timing, best-cell rule and code layout: tile_sweep.h, which also holds the constants, the helpers and the
 // launcher.  The sweep and the walk (the (H, F) hand-over, the code word, the walk's states) are
-// tile_sweep_affine_body.inc, shared with sgfull_affine_kernels.hip; this file holds what depends on the recurrence.
+// tile_sweep_affine_body.inc, shared with sgfull_affine_kernels.hip; what depends on the recurrence is LocalAffine,
+// local_full_affine_variant.h (shared with local_long_affine_kernels.hip); this comment tells it.
 //
 // The cell as KEYS: key = value << 6 | tag << 4 | low.  A stored H key has tag 2 and low = 15 - jj (jj = the column within
 // the lane); with a traceback E is kept masked to tag 1 and F to tag 0 (one v_and_or_b32 after their max).  Every candidate
@@ -52,7 +53,7 @@
 //
 // Walk: it ends on a stop code read in state H (inside E or F the cell's H code is not consulted), on row 0 or on column 0
 // (border cells hold 0 and have no code), where it arrives in state H.
-#include "tile_sweep.h"
+#include "local_full_affine_variant.h"
 
 namespace swmi {
 namespace {
@@ -72,22 +73,6 @@ constexpr int kStageRows = 128;
 static_assert(kCols == tile::kCols && kMaxWaves == tile::kMaxWaves && kUnroll == tile::kUnroll && kChunk == tile::kChunk &&
               kDelay == tile::kDelay && kRing == tile::kRing && kStageRows == tile::kStageRows);
 }  // namespace written_for
-
-struct LocalAffine {
-    static constexpr bool kWalkStops = true;       // on the floor's code, kTagH's + 1
-    static constexpr int kEnds = 4;
-    static constexpr int kRowMin = 0;
-    static constexpr int kTagH = 2 << 4;           // of a stored H key (= the diagonal's and both open candidates')
-    static constexpr int kTagE = 1 << 4;
-    static constexpr int kTagF = 0 << 4;
-    static constexpr int kFloor = 3 << 4;          // the floor candidate: H = 0, tag 3
-    static constexpr int kOpenBitE = 5;            // kTagH has it, kTagE and kTagF have not
-    static constexpr int kOpenBitF = 5;
-
-    static __device__ __forceinline__ int border(int, int, int) { return kTagH; }                          // the borders hold 0
-    static __device__ __forceinline__ int row0(int jj, int, int, int) { return kTagH | (kCols - 1 - jj); }
-    static __device__ __forceinline__ int floor(int m) { return imax(m, kFloor); }
-};
 
 // RAGGED: one TileWork per workgroup (work[blockIdx.x]) names the alignment, and the launch's own shape (fixed_*, move_words)
 // is unused; else `work` is NULL and unread (tile_sweep.h).

@@ -8,7 +8,8 @@
 // The end cell is the first cell in row-major order holding max H ((0,0) when that is 0); the walk from it stops at the
 // first cell holding 0 (the test comes first), else takes a diagonal, else an up, else a left step.  DESIGN.md section 17.
 //
-// Mapping, ring timing, best-cell reduction, code layout and staged walk: tile_sweep.h.  This file holds the recurrence.
+// Mapping, ring timing, best-cell reduction, code layout and staged walk: tile_sweep.h.  The recurrence is LocalLinear,
+// local_full_variant.h (shared with local_long_kernels.hip); this comment tells it.
 //
 // The cell as KEYS: key = H << 6 | tag << 4 | (15 - jj) (jj = the column within the lane).  H >= 0 and
 // H <= 127 * 16384 < 2^21, so every stored key is positive and below 2^27.  A stored key has tag 2; the four candidates are
@@ -36,7 +37,7 @@
 //
 // Codes: 2 bits per cell, one dword per lane and row, column jj at bits 2 jj.  A staging block of the walk is 128 rows x
 // 64 lanes (1024 columns); the walk inside it ends on a stop code, on row 0 or on column 0.
-#include "tile_sweep.h"
+#include "local_full_variant.h"
 
 namespace swmi {
 namespace {
@@ -56,48 +57,6 @@ constexpr int kStageRows = 128;
 static_assert(kCols == tile::kCols && kMaxWaves == tile::kMaxWaves && kUnroll == tile::kUnroll && kChunk == tile::kChunk &&
               kDelay == tile::kDelay && kRing == tile::kRing && kStageRows == tile::kStageRows);
 }  // namespace written_for
-
-constexpr int kFloor = 3 << 4;         // the floor candidate: H = 0, tag 3
-constexpr int kStored = 2 << 4;        // tag of a stored key (= the diagonal candidate's)
-constexpr uint32_t kStop = 3;          // code of a cell whose floor won
-
-struct LocalLinear {
-    static constexpr bool kWalkStops = true;
-    static constexpr int kEnds = 4;
-    static constexpr int kStageLanes = 64;
-    static constexpr int kRowMin = 0;
-    static constexpr int kZeroKey = kStored;       // the stored key of H = 0, column bits aside
-
-    struct Gaps {
-        int gap;
-    };
-    int g_up, g_left;
-
-    __device__ __forceinline__ explicit LocalLinear(Gaps g) : g_up(-(g.gap << 6) - (1 << 4)), g_left(-(g.gap << 6) - (2 << 4)) {}
-
-    static __device__ __forceinline__ int row0(int jj, int, Gaps) { return kStored | (kCols - 1 - jj); }
-    __device__ __forceinline__ int border(int) const { return kStored; }                    // the borders hold 0
-    __device__ __forceinline__ int left_border(int) const { return kStored; }
-
-    template <bool TB>
-    __device__ __forceinline__ int cell(int jj, int sc, int &d, int &lft, int &key, uint32_t &code) const
-    {
-        const int m = imax(max3(d + (sc << 6), key + g_up, lft + g_left), kFloor);
-        const int nk = (m & ~63) | (kStored | (kCols - 1 - jj));
-        if constexpr (TB) code = ((uint32_t)(m >> 4) & 3u) << (2 * jj);
-        d = key;
-        key = nk;
-        lft = nk;
-        return nk;
-    }
-
-    // a stop code: the cell holds 0, the start cell; else the move is code + 1
-    static __device__ __forceinline__ uint32_t step(uint32_t wd, int cc)
-    {
-        const uint32_t code = (wd >> (2 * cc)) & 3u;
-        return code == kStop ? 0u : code + 1;
-    }
-};
 
 // RAGGED: one TileWork per workgroup (work[blockIdx.x]) names the alignment, and the launch's own shape (fixed_*, move_words)
 // is unused; else `work` is NULL and unread (tile_sweep.h).

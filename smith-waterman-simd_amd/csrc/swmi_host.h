@@ -139,11 +139,13 @@ struct Workspace {
     size_t bytes = 0;
 };
 
-// The aligners that run through the slice pipeline of swmi_table.cpp, one row of table_api.cpp each
+// The aligners that run through the slice pipeline of swmi_table.cpp: one FamilyRow each, the first kTableApiFamilies in
+// table_api.cpp, the two long local ones in local_long_api.cpp
 enum TableFamily {
     kTableLocal, kTableSgfull, kTableLocalAffine, kTableSgfullAffine, kTableLocalFull, kTableLocalFullAffine, kTableGlobalFull,
-    kTableGlobalFullAffine, kTableGlobalLong, kTableGlobalLongAffine, kTableFamilies
+    kTableGlobalFullAffine, kTableGlobalLong, kTableGlobalLongAffine, kTableLocalLong, kTableLocalLongAffine, kTableFamilies
 };
+constexpr int kTableApiFamilies = kTableLocalLong;     // the families whose rows table_api.cpp holds
 
 // Everything the library owns on ONE bound GPU.  A GPU may be bound twice (swmi_init_devices({0, 0})): two contexts,
 // two stream sets, the same hardware.
@@ -242,7 +244,7 @@ struct Table {
     int gap, gap_extend;        // gap_extend: the affine aligner's (gap is then the open cost)
     const RaggedPlan *plan = nullptr;   // a ragged batch: len1, code_words and move_words unused, slices as the plan says
     unsigned free_ends = 0;             // the global aligners' mask of SWMI_FREE_*, which their slice launchers read
-    // The striped global aligners' carry (table_api.cpp): dwords per alignment of device scratch that a slice's kernel needs
+    // The striped aligners' carry (FamilyRow::carry): dwords per alignment of device scratch that a slice's kernel needs
     // with or without a traceback, counted in a slice's bytes; the pipeline allocates it beside the codes and hands the launcher
     // a copy of the Table whose `carry` points at the slice's (NULL where carry_words is 0).
     size_t carry_words = 0;
@@ -259,9 +261,53 @@ int table_host(const Table &t, const char *entry, const uint8_t *seq1s, const ui
 int table_time_device(const Table &t, const char *entry, const void *d_seq1s, const void *d_seq2s, size_t n, void *d_scores,
                       void *d_ends, void *d_moves, void *d_counts, void *stream, int iters, float *avg_ms);
 int table_check_timer(size_t n, int iters, const float *avg_ms);   // what the timers check before their first call
-// table_api.cpp: the Table of one call of a family, from its row (len2 = SWMI_LOCAL_SEQ2_LEN for the two local families;
-// gap_extend is read by the affine families and free_ends by those with a mask)
+// ---- one aligner family as data, and one body per kind of entry (table_api.cpp) ----
+// What differs between the aligners.  Code sizes are in the Table's unit, dwords: twice the affine launchers' qwords.
+struct FamilyRow {
+    TableLaunch launch;
+    TableFamily family;         // Table::state: whose device buffers a call uses
+    size_t max_len;             // per axis
+    bool fixed_len2;            // len2 is SWMI_LOCAL_SEQ2_LEN, whatever the caller's
+    const char *count;          // Table::count, and
+    uint32_t count_offset;      //   Table::count_offset
+    size_t ends;                // int32 of `ends` per alignment
+    size_t (*code_words)(size_t len1, size_t len2);
+    size_t (*move_words)(size_t len1, size_t len2);
+    // A traceback slice holds as many alignments as `budget` of `budget_as`'s maximum shape (0: kTableSliceBytes); budget_as is
+    // one of table_api.cpp's families.  256 of 16384 x 16384 (16.1 GiB of 2-bit codes, 32.1 GiB of 4-bit ones) are one
+    // workgroup per alignment for every CU of an MI355X; 4096 of len1 = 16384 (4.1 GiB) give every CU a workgroup of 16
+    // alignments.  A striped pair takes its fixed-length pair's budget, and counts its carry in a slice.
+    size_t budget;
+    TableFamily budget_as;
+    bool affine;                // gap_extend is read; gaps within [0, 127] instead of check_params
+    bool mask;                  // free_ends is read
+    bool carry;                 // column stripes: a carry of len1 dwords (affine: 2 len1) per alignment where len2 > 16384
+    bool domain;                // the striped global aligners' domain rule, P (len1 + len2) <= 2^23 (include/swmi.h)
+    bool timer_first;           // the timer checks its own arguments (and binds the context) before the call's
+};
+// the arguments of one call that the families read
+struct Call {
+    size_t len1, len2;          // len2 = SWMI_LOCAL_SEQ2_LEN from the two local families' entries
+    const int8_t *sm;
+    int gap, gap_extend;        // gap_extend 0 from the linear families' entries
+    unsigned free_ends;         // 0 from the families without a mask
+};
+// in the order include/swmi.h gives: the lengths, the mask, the matrix and the gaps, the domain rule
+int family_check(const FamilyRow &r, const Call &c);
+// The Table of one call of a family, from its row (len2 = SWMI_LOCAL_SEQ2_LEN for the two local families; gap_extend is read
+// by the affine families and free_ends by those with a mask); by TableFamily for table_api.cpp's own families
+Table family_table(const FamilyRow &r, size_t len1, size_t len2, const int8_t *sm, int gap, int gap_extend, unsigned free_ends);
 Table family_table(TableFamily f, size_t len1, size_t len2, const int8_t *sm, int gap, int gap_extend, unsigned free_ends);
+size_t family_slices_for(const FamilyRow &r, size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap);
+int family_device(const FamilyRow &r, const Call &c, const void *d_seq1s, const void *d_seq2s, size_t n, void *d_scores, void *d_ends,
+                  void *d_moves, void *d_counts, void *stream);
+int family_host(const FamilyRow &r, const char *entry, const Call &c, const uint8_t *seq1s, const uint8_t *seq2s, size_t n,
+                int32_t *scores, int32_t *ends, uint64_t *moves, uint32_t *counts);
+int family_time_device(const FamilyRow &r, const char *entry, const Call &c, const void *d_seq1s, const void *d_seq2s, size_t n,
+                       void *d_scores, void *d_ends, void *d_moves, void *d_counts, void *stream, int iters, float *avg_ms);
+// the reference's list of positions from a walk's moves, for end cells up to (max_i, max_j): the body of the *_expand_moves entries
+int family_expand_moves(int32_t max_i, int32_t max_j, const uint64_t *moves, uint32_t steps, int32_t end_i, int32_t end_j,
+                        int32_t *positions, size_t cap);
 // local_full_ragged_api.cpp: the plan of a ragged any-length batch alone (no device), for tests of its arithmetic -- per slice
 // its alignments and device bytes; true when every code base equals the 64-bit running sum of the code words before it
 bool local_full_ragged_plan_check(const uint64_t *seq1_offsets, const uint64_t *seq2_offsets, size_t n, bool affine, bool tb,

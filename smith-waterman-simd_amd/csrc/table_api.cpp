@@ -1,8 +1,9 @@
 // table_api.cpp -- C entries of the ten fixed-shape aligners that run through the slice pipeline of swmi_table.cpp (struct Table,
 // swmi_host.h; include/swmi.h, DESIGN.md sections 12 to 14, 16 to 18, 20, 21 and 23): one row of data per family, one body for the
 // argument check, the Table and each of the five kinds of entry, and one explicit extern "C" definition per exported name.
-// This is the only host source that names the fixed-shape launchers.  Its name lies outside csrc/swmi_*.cpp, so that the
-// host-only builds of swmi_api.cpp + swmi_multi.cpp stay free of the table kernels.
+// The bodies are declared in swmi_host.h (family_*) and take a FamilyRow, so that local_long_api.cpp, which holds the two long
+// local families, runs through them too.  This file's name lies outside csrc/swmi_*.cpp, so that the host-only builds of
+// swmi_api.cpp + swmi_multi.cpp stay free of the table kernels.
 #include "swmi_host.h"
 
 #include <algorithm>
@@ -75,82 +76,53 @@ hipError_t launch_global_long_affine_slice(SLICE_ARGS)
 #undef SLICE_ARGS
 
 // ---- the families ----
-// What differs between the aligners.  Code sizes are in the Table's unit, dwords: twice the affine launchers' qwords.
-struct FamilyRow {
-    TableLaunch launch;
-    size_t max_len;             // per axis
-    bool fixed_len2;            // len2 is SWMI_LOCAL_SEQ2_LEN, whatever the caller's
-    const char *count;          // Table::count, and
-    uint32_t count_offset;      //   Table::count_offset
-    size_t ends;                // int32 of `ends` per alignment
-    size_t (*code_words)(size_t len1, size_t len2);
-    size_t (*move_words)(size_t len1, size_t len2);
-    // A traceback slice holds as many alignments as `budget` of `budget_as`'s maximum shape (0: kTableSliceBytes).  256 of
-    // 16384 x 16384 (16.1 GiB of 2-bit codes, 32.1 GiB of 4-bit ones) are one workgroup per alignment for every CU of an
-    // MI355X; 4096 of len1 = 16384 (4.1 GiB) give every CU a workgroup of 16 alignments.  The striped pair takes the fixed
-    // global pair's budget, and counts its carry in a slice.
-    size_t budget;
-    TableFamily budget_as;
-    bool affine;                // gap_extend is read; gaps within [0, 127] instead of check_params
-    bool mask;                  // free_ends is read
-    bool striped;               // lengths above kStripe: the domain rule, and a carry where len2 > kStripe
-    bool timer_first;           // the timer checks its own arguments (and binds the context) before the call's
-};
-
-constexpr FamilyRow kRows[kTableFamilies] = {
+// One FamilyRow (swmi_host.h) each; local_long_api.cpp holds the two long local families' rows.
+constexpr FamilyRow kRows[kTableApiFamilies] = {
     /* kTableLocal */
-    {launch_local_slice, SWMI_LOCAL_MAX_LEN, true, "steps", 0, 4, [](size_t a, size_t) { return swmi::local_code_words((int)a); },
-     [](size_t a, size_t) { return size_t(SWMI_LOCAL_MOVE_WORDS(a)); }, 0, kTableLocal, false, false, false, true},
+    {launch_local_slice, kTableLocal, SWMI_LOCAL_MAX_LEN, true, "steps", 0, 4, [](size_t a, size_t) { return swmi::local_code_words((int)a); },
+     [](size_t a, size_t) { return size_t(SWMI_LOCAL_MOVE_WORDS(a)); }, 0, kTableLocal, false, false, false, false, true},
     /* kTableSgfull */
-    {launch_sgfull_slice, SWMI_SGFULL_MAX_LEN, false, "lengths", 1, 2,
+    {launch_sgfull_slice, kTableSgfull, SWMI_SGFULL_MAX_LEN, false, "lengths", 1, 2,
      [](size_t a, size_t b) { return swmi::sgfull_code_words((int)a, (int)b); },
-     [](size_t a, size_t b) { return size_t(SWMI_SGFULL_MOVE_WORDS(a, b)); }, 256, kTableSgfull, false, false, false, true},
+     [](size_t a, size_t b) { return size_t(SWMI_SGFULL_MOVE_WORDS(a, b)); }, 256, kTableSgfull, false, false, false, false, true},
     /* kTableLocalAffine */
-    {launch_local_affine_slice, SWMI_LOCAL_MAX_LEN, true, "steps", 0, 4,
+    {launch_local_affine_slice, kTableLocalAffine, SWMI_LOCAL_MAX_LEN, true, "steps", 0, 4,
      [](size_t a, size_t) { return swmi::local_affine_code_words((int)a); },
-     [](size_t a, size_t) { return size_t(SWMI_LOCAL_MOVE_WORDS(a)); }, 4096, kTableLocalAffine, true, false, false, true},
+     [](size_t a, size_t) { return size_t(SWMI_LOCAL_MOVE_WORDS(a)); }, 4096, kTableLocalAffine, true, false, false, false, true},
     /* kTableSgfullAffine */
-    {launch_sgfull_affine_slice, SWMI_SGFULL_MAX_LEN, false, "lengths", 1, 2,
+    {launch_sgfull_affine_slice, kTableSgfullAffine, SWMI_SGFULL_MAX_LEN, false, "lengths", 1, 2,
      [](size_t a, size_t b) { return 2 * swmi::sgfull_affine_code_qwords((int)a, (int)b); },
-     [](size_t a, size_t b) { return size_t(SWMI_SGFULL_MOVE_WORDS(a, b)); }, 256, kTableSgfullAffine, true, false, false, false},
+     [](size_t a, size_t b) { return size_t(SWMI_SGFULL_MOVE_WORDS(a, b)); }, 256, kTableSgfullAffine, true, false, false, false, false},
     /* kTableLocalFull */
-    {launch_local_full_slice, SWMI_LOCAL_FULL_MAX_LEN, false, "steps", 0, 4,
+    {launch_local_full_slice, kTableLocalFull, SWMI_LOCAL_FULL_MAX_LEN, false, "steps", 0, 4,
      [](size_t a, size_t b) { return swmi::local_full_code_words((int)a, (int)b); },
-     [](size_t a, size_t b) { return size_t(SWMI_LOCAL_FULL_MOVE_WORDS(a, b)); }, 256, kTableLocalFull, false, false, false, false},
+     [](size_t a, size_t b) { return size_t(SWMI_LOCAL_FULL_MOVE_WORDS(a, b)); }, 256, kTableLocalFull, false, false, false, false, false},
     /* kTableLocalFullAffine */
-    {launch_local_full_affine_slice, SWMI_LOCAL_FULL_MAX_LEN, false, "steps", 0, 4,
+    {launch_local_full_affine_slice, kTableLocalFullAffine, SWMI_LOCAL_FULL_MAX_LEN, false, "steps", 0, 4,
      [](size_t a, size_t b) { return 2 * swmi::local_full_affine_code_qwords((int)a, (int)b); },
-     [](size_t a, size_t b) { return size_t(SWMI_LOCAL_FULL_MOVE_WORDS(a, b)); }, 256, kTableLocalFullAffine, true, false, false,
+     [](size_t a, size_t b) { return size_t(SWMI_LOCAL_FULL_MOVE_WORDS(a, b)); }, 256, kTableLocalFullAffine, true, false, false, false,
      false},
     /* kTableGlobalFull */
-    {launch_global_full_slice, SWMI_GLOBAL_FULL_MAX_LEN, false, "steps", 0, 4,
+    {launch_global_full_slice, kTableGlobalFull, SWMI_GLOBAL_FULL_MAX_LEN, false, "steps", 0, 4,
      [](size_t a, size_t b) { return swmi::global_full_code_words((int)a, (int)b); },
-     [](size_t a, size_t b) { return size_t(SWMI_GLOBAL_FULL_MOVE_WORDS(a, b)); }, 256, kTableGlobalFull, false, true, false, false},
+     [](size_t a, size_t b) { return size_t(SWMI_GLOBAL_FULL_MOVE_WORDS(a, b)); }, 256, kTableGlobalFull, false, true, false, false, false},
     /* kTableGlobalFullAffine */
-    {launch_global_full_affine_slice, SWMI_GLOBAL_FULL_MAX_LEN, false, "steps", 0, 4,
+    {launch_global_full_affine_slice, kTableGlobalFullAffine, SWMI_GLOBAL_FULL_MAX_LEN, false, "steps", 0, 4,
      [](size_t a, size_t b) { return 2 * swmi::global_full_affine_code_qwords((int)a, (int)b); },
-     [](size_t a, size_t b) { return size_t(SWMI_GLOBAL_FULL_MOVE_WORDS(a, b)); }, 256, kTableGlobalFullAffine, true, true, false,
+     [](size_t a, size_t b) { return size_t(SWMI_GLOBAL_FULL_MOVE_WORDS(a, b)); }, 256, kTableGlobalFullAffine, true, true, false, false,
      false},
     /* kTableGlobalLong */
-    {launch_global_long_slice, SWMI_GLOBAL_LONG_MAX_LEN, false, "steps", 0, 4,
+    {launch_global_long_slice, kTableGlobalLong, SWMI_GLOBAL_LONG_MAX_LEN, false, "steps", 0, 4,
      [](size_t a, size_t b) { return swmi::global_long_code_words((int)a, (int)b); },
-     [](size_t a, size_t b) { return size_t(SWMI_GLOBAL_LONG_MOVE_WORDS(a, b)); }, 256, kTableGlobalFull, false, true, true, false},
+     [](size_t a, size_t b) { return size_t(SWMI_GLOBAL_LONG_MOVE_WORDS(a, b)); }, 256, kTableGlobalFull, false, true, true, true, false},
     /* kTableGlobalLongAffine */
-    {launch_global_long_affine_slice, SWMI_GLOBAL_LONG_MAX_LEN, false, "steps", 0, 4,
+    {launch_global_long_affine_slice, kTableGlobalLongAffine, SWMI_GLOBAL_LONG_MAX_LEN, false, "steps", 0, 4,
      [](size_t a, size_t b) { return 2 * swmi::global_long_affine_code_qwords((int)a, (int)b); },
-     [](size_t a, size_t b) { return size_t(SWMI_GLOBAL_LONG_MOVE_WORDS(a, b)); }, 256, kTableGlobalFullAffine, true, true, true,
+     [](size_t a, size_t b) { return size_t(SWMI_GLOBAL_LONG_MOVE_WORDS(a, b)); }, 256, kTableGlobalFullAffine, true, true, true, true,
      false},
 };
 
 // ---- one body each ----
-// the arguments of one call that the families read
-struct Call {
-    size_t len1, len2;          // len2 = SWMI_LOCAL_SEQ2_LEN from the two local families' entries
-    const int8_t *sm;
-    int gap, gap_extend;        // gap_extend 0 from the linear families' entries
-    unsigned free_ends;         // 0 from the families without a mask
-};
-
 bool lens_ok(const FamilyRow &r, size_t len1, size_t len2)
 {
     return len1 >= 1 && len1 <= r.max_len && (r.fixed_len2 || (len2 >= 1 && len2 <= r.max_len));
@@ -166,8 +138,10 @@ bool domain_ok(const Call &c)
     return p * (c.len1 + c.len2) <= (size_t(1) << 23);
 }
 
-// in the order include/swmi.h gives: the lengths, the mask, the matrix and the gaps, the striped families' domain rule
-int check(const FamilyRow &r, const Call &c)
+}  // namespace
+
+// in the order include/swmi.h gives: the lengths, the mask, the matrix and the gaps, the domain rule
+int family_check(const FamilyRow &r, const Call &c)
 {
     if (!lens_ok(r, c.len1, c.len2)) {
         if (r.fixed_len2) return fail(SWMI_ERR_INVALID_ARGUMENT, "len1 %zu outside [1, %zu]", c.len1, r.max_len);
@@ -183,7 +157,7 @@ int check(const FamilyRow &r, const Call &c)
         if (c.gap < 0 || c.gap > 127 || c.gap_extend < 0 || c.gap_extend > 127)
             return fail(SWMI_ERR_DOMAIN, "gap_open %d / gap_extend %d outside [0,127]", c.gap, c.gap_extend);
     }
-    if (r.striped && !domain_ok(c)) {
+    if (r.domain && !domain_ok(c)) {
         if (r.affine)
             return fail(SWMI_ERR_INVALID_ARGUMENT, "max(1, |score|, gap_open, gap_extend) * (len1 + len2) = P * %zu above 2^23",
                         c.len1 + c.len2);
@@ -192,45 +166,46 @@ int check(const FamilyRow &r, const Call &c)
     return SWMI_OK;
 }
 
-Table call_table(TableFamily f, const Call &c) { return family_table(f, c.len1, c.len2, c.sm, c.gap, c.gap_extend, c.free_ends); }
+namespace {
+Table call_table(const FamilyRow &r, const Call &c) { return family_table(r, c.len1, c.len2, c.sm, c.gap, c.gap_extend, c.free_ends); }
+}  // namespace
 
-size_t slices_for(TableFamily f, size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap)
+size_t family_slices_for(const FamilyRow &r, size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap)
 {
-    if (!lens_ok(kRows[f], len1, len2)) return 0;
-    return table_slices_for(family_table(f, len1, len2, nullptr, 0, 0, 0), n, traceback != 0, sizes, cap);
+    if (!lens_ok(r, len1, len2)) return 0;
+    return table_slices_for(family_table(r, len1, len2, nullptr, 0, 0, 0), n, traceback != 0, sizes, cap);
 }
 
-int device(TableFamily f, const Call &c, const void *d_seq1s, const void *d_seq2s, size_t n, void *d_scores, void *d_ends, void *d_moves,
-           void *d_counts, void *stream)
+int family_device(const FamilyRow &r, const Call &c, const void *d_seq1s, const void *d_seq2s, size_t n, void *d_scores, void *d_ends,
+                  void *d_moves, void *d_counts, void *stream)
 {
-    const int rc = check(kRows[f], c);
+    const int rc = family_check(r, c);
     if (rc != SWMI_OK) return rc;
-    return table_device(call_table(f, c), d_seq1s, d_seq2s, n, d_scores, d_ends, d_moves, d_counts, stream);
+    return table_device(call_table(r, c), d_seq1s, d_seq2s, n, d_scores, d_ends, d_moves, d_counts, stream);
 }
 
-int host(TableFamily f, const char *entry, const Call &c, const uint8_t *seq1s, const uint8_t *seq2s, size_t n, int32_t *scores,
-         int32_t *ends, uint64_t *moves, uint32_t *counts)
+int family_host(const FamilyRow &r, const char *entry, const Call &c, const uint8_t *seq1s, const uint8_t *seq2s, size_t n,
+                int32_t *scores, int32_t *ends, uint64_t *moves, uint32_t *counts)
 {
-    const int rc = check(kRows[f], c);
+    const int rc = family_check(r, c);
     if (rc != SWMI_OK) return rc;
-    return table_host(call_table(f, c), entry, seq1s, seq2s, n, scores, ends, moves, counts);
+    return table_host(call_table(r, c), entry, seq1s, seq2s, n, scores, ends, moves, counts);
 }
 
-int time_device(TableFamily f, const char *entry, const Call &c, const void *d_seq1s, const void *d_seq2s, size_t n, void *d_scores,
-                void *d_ends, void *d_moves, void *d_counts, void *stream, int iters, float *avg_ms)
+int family_time_device(const FamilyRow &r, const char *entry, const Call &c, const void *d_seq1s, const void *d_seq2s, size_t n,
+                       void *d_scores, void *d_ends, void *d_moves, void *d_counts, void *stream, int iters, float *avg_ms)
 {
-    const FamilyRow &r = kRows[f];
     int rc = r.timer_first ? table_check_timer(n, iters, avg_ms) : SWMI_OK;       // (its last check makes the context current)
-    if (rc == SWMI_OK) rc = check(r, c);
+    if (rc == SWMI_OK) rc = family_check(r, c);
     if (rc == SWMI_OK && !r.timer_first) rc = table_check_timer(n, iters, avg_ms);
     if (rc != SWMI_OK) return rc;
-    return table_time_device(call_table(f, c), entry, d_seq1s, d_seq2s, n, d_scores, d_ends, d_moves, d_counts, stream, iters, avg_ms);
+    return table_time_device(call_table(r, c), entry, d_seq1s, d_seq2s, n, d_scores, d_ends, d_moves, d_counts, stream, iters, avg_ms);
 }
 
 // The reference's list (source.cpp:1571-1572: from the start cell to the end cell) from the walk's moves: the start cell is
 // the end cell less the moves' row / column steps, and the list applies the moves last to first.
-int expand_moves(int32_t max_i, int32_t max_j, const uint64_t *moves, uint32_t steps, int32_t end_i, int32_t end_j, int32_t *positions,
-                 size_t cap)
+int family_expand_moves(int32_t max_i, int32_t max_j, const uint64_t *moves, uint32_t steps, int32_t end_i, int32_t end_j,
+                        int32_t *positions, size_t cap)
 {
     if ((!moves && steps) || (!positions && cap)) return fail(SWMI_ERR_INVALID_ARGUMENT, "NULL buffer");
     if (end_i < 0 || end_j < 0 || end_i > max_i || end_j > max_j)
@@ -259,12 +234,10 @@ int expand_moves(int32_t max_i, int32_t max_j, const uint64_t *moves, uint32_t s
     return SWMI_OK;
 }
 
-}  // namespace
-
-Table family_table(TableFamily f, size_t len1, size_t len2, const int8_t *sm, int gap, int gap_extend, unsigned free_ends)
+Table family_table(const FamilyRow &r, size_t len1, size_t len2, const int8_t *sm, int gap, int gap_extend, unsigned free_ends)
 {
-    const FamilyRow &r = kRows[f], &b = kRows[r.budget_as];
-    Table t{r.launch, f, kTableSliceBytes, r.count, len1, len2, r.ends, r.code_words(len1, len2), r.move_words(len1, len2),
+    const FamilyRow &b = kRows[r.budget_as];
+    Table t{r.launch, r.family, kTableSliceBytes, r.count, len1, len2, r.ends, r.code_words(len1, len2), r.move_words(len1, len2),
             r.count_offset, sm, gap, gap_extend};
     t.free_ends = free_ends;
     if (r.budget) {
@@ -275,9 +248,48 @@ Table family_table(TableFamily f, size_t len1, size_t len2, const int8_t *sm, in
         full.move_words = b.move_words(full.len1, full.len2);
         t.tb_slice_bytes = r.budget * table_slice_bytes(full, true);
     }
-    if (r.striped && len2 > kStripe) t.carry_words = r.affine ? 2 * len1 : len1;       // a row of H, or of (H, F)
+    if (r.carry && len2 > kStripe) t.carry_words = r.affine ? 2 * len1 : len1;       // a row of H, or of (H, F)
     return t;
 }
+
+Table family_table(TableFamily f, size_t len1, size_t len2, const int8_t *sm, int gap, int gap_extend, unsigned free_ends)
+{
+    return family_table(kRows[f], len1, len2, sm, gap, gap_extend, free_ends);
+}
+
+// ---- the exported definitions below name a family of kRows ----
+namespace {
+
+size_t slices_for(TableFamily f, size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap)
+{
+    return family_slices_for(kRows[f], n, len1, len2, traceback, sizes, cap);
+}
+
+int device(TableFamily f, const Call &c, const void *d_seq1s, const void *d_seq2s, size_t n, void *d_scores, void *d_ends, void *d_moves,
+           void *d_counts, void *stream)
+{
+    return family_device(kRows[f], c, d_seq1s, d_seq2s, n, d_scores, d_ends, d_moves, d_counts, stream);
+}
+
+int host(TableFamily f, const char *entry, const Call &c, const uint8_t *seq1s, const uint8_t *seq2s, size_t n, int32_t *scores,
+         int32_t *ends, uint64_t *moves, uint32_t *counts)
+{
+    return family_host(kRows[f], entry, c, seq1s, seq2s, n, scores, ends, moves, counts);
+}
+
+int time_device(TableFamily f, const char *entry, const Call &c, const void *d_seq1s, const void *d_seq2s, size_t n, void *d_scores,
+                void *d_ends, void *d_moves, void *d_counts, void *stream, int iters, float *avg_ms)
+{
+    return family_time_device(kRows[f], entry, c, d_seq1s, d_seq2s, n, d_scores, d_ends, d_moves, d_counts, stream, iters, avg_ms);
+}
+
+int expand_moves(int32_t max_i, int32_t max_j, const uint64_t *moves, uint32_t steps, int32_t end_i, int32_t end_j, int32_t *positions,
+                 size_t cap)
+{
+    return family_expand_moves(max_i, max_j, moves, steps, end_i, end_j, positions, cap);
+}
+
+}  // namespace
 
 }  // namespace host
 }  // namespace swmi

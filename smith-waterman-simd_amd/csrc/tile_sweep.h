@@ -1,6 +1,6 @@
 // tile_sweep.h -- what the any-length aligners share (sgfull_kernels.hip, sgfull_affine_kernels.hip,
 // local_full_kernels.hip, local_full_affine_kernels.hip, global_full_kernels.hip, global_full_affine_kernels.hip,
-// global_long_kernels.hip, global_long_affine_kernels.hip; DESIGN.md
+// global_long_kernels.hip, global_long_affine_kernels.hip, local_long_kernels.hip, local_long_affine_kernels.hip; DESIGN.md
 // section 13): the mapping and its constants, the helpers, the geometry and the launcher; the few helpers that the 16-lane local aligners take from here as well.  The sweep and the
 // walk of the linear-gap kernels are tile_sweep_body.inc, those of the affine kernels tile_sweep_affine_body.inc.
 //
@@ -140,7 +140,8 @@ constexpr int kStageRows = 128;        // rows of a walk staging block
 constexpr bool RAGGED = false;         // what a kernel without a ragged form sees (above)
 constexpr TileWork slot{};
 
-// Column stripes (global_long_kernels.hip, global_long_affine_kernels.hip): a kernel that shadows STRIPED
+// Column stripes (global_long_kernels.hip, global_long_affine_kernels.hip, and with a local variant local_long_kernels.hip,
+// local_long_affine_kernels.hip; DESIGN.md sections 23 and 25): a kernel that shadows STRIPED
 // with true sweeps len2 > kStripeCols columns as stripes of kStripeCols, one after another, in the same workgroup; it names
 // `carry` (linear body: int per row) or `carry_hf` (affine body: int2 per row), the per-alignment device buffer through which
 // a stripe's last column reaches the next stripe's wave 0.  What every other kernel sees:

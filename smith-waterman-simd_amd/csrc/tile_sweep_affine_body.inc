@@ -51,9 +51,15 @@
     // STRIPED: tile_sweep_body.inc's stripe loop, carry ordering and BARRIER INVARIANT (every wave executes total_chunks + 1
     // barriers in every stripe but the last and total_chunks in the last, whatever w and the stripe's valid width); the
     // carry holds the last column's stored key AND its F, so a gap that opened left of the stripe's edge extends across it.
-    static_assert(!STRIPED || kEndRule<V>, "column stripes fold end-rule candidates");
+    // A local variant's best cell of each stripe is folded into r as in the linear body.
     [[maybe_unused]] int2 *const carry_k = STRIPED ? carry_hf + k * (size_t)len1 : nullptr;
     unsigned long long r = 0;                           // best cell so far: (H desc, row asc, column asc)
+    // A striped kernel without the end rule (a local variant) keeps its best cell so far per wave in red[w], not in r: two VGPRs
+    // that it has not got across the sweep.  Only lane 0 of wave w touches red[w] before the last barrier.
+    constexpr bool kFoldInLds = STRIPED && !kEndRule<V>;
+    if constexpr (kFoldInLds) {
+        if (l == 0) red[w] = 0;
+    }
     int stripe = 0;
     do {
     // (a striped kernel's per-stripe tid, w and l: opaque_lane, tile_sweep.h; they shadow the workgroup's, which they equal)
@@ -73,12 +79,16 @@
 
     uint32_t prof[kCols];
     int key[kCols], e[kCols];                           // H's stored keys and E of the row the lane computed last
+    // (a striped local kernel's row 0 is sixteen constants: made of a 0 that the compiler cannot see through, so that they are
+    // set up anew in every stripe and not kept across the sweeps, tile_sweep_body.inc)
+    [[maybe_unused]] const int row0_zero = opaque_lane<STRIPED && !kEndRule<V>>(0);
 #pragma unroll
     for (int jj = 0; jj < kCols; ++jj) {
         const int j = jbase + jj + 1;
         const uint32_t b = s2[j <= len2 ? j - 1 : 0] & 3u;
         prof[jj] = j > len2 ? 0x80808080u : b == 0 ? cols.c[0] : b == 1 ? cols.c[1] : b == 2 ? cols.c[2] : cols.c[3];
         key[jj] = V::row0(jj, j, open_row0, ext_row0);
+        if constexpr (STRIPED && !kEndRule<V>) key[jj] |= row0_zero;
         e[jj] = kMinusInf;
     }
     // end rule: the border cells (0, len2) and (len1, 0) are closed forms; thread 0 holds them as candidates from here on (in
@@ -273,8 +283,17 @@
     } else {
         const int h = best >> 6;
         const int col = h > 0 ? jbase + (kCols - 1 - (best & 15)) + 1 : 0;
-        r = ((unsigned long long)(uint32_t)h << 34) | ((unsigned long long)(0x1FFFF - best_row) << 17) |
-            (unsigned long long)(0x1FFFF - col);
+        const unsigned long long cand = ((unsigned long long)(uint32_t)h << 34) | ((unsigned long long)(0x1FFFF - best_row) << 17) |
+                                        (unsigned long long)(0x1FFFF - col);
+        // the stripe's best cell joins the earlier stripes' (a wave that skipped the stripe folds (0, 0) with H = 0: harmless)
+        if constexpr (kFoldInLds) {
+            unsigned long long c = cand;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) c = umax64(c, __shfl_xor(c, o, 64));
+            if (l == 0) red[w] = umax64(red[w], c);
+        } else {
+            r = cand;
+        }
     }
     if constexpr (STRIPED) {
         if (more_stripes) {
@@ -286,12 +305,14 @@
         }
     }
     } while (STRIPED && ++stripe * kStripeCols < len2);
+    if constexpr (!kFoldInLds) {
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long v = __shfl_xor(r, o, 64);
-        r = v > r ? v : r;
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned long long v = __shfl_xor(r, o, 64);
+            r = v > r ? v : r;
+        }
+        if (l == 0) red[w] = r;
     }
-    if (l == 0) red[w] = r;
     if constexpr (TB) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's code stores have reached L2
     __syncthreads();
     r = red[0];

@@ -32,23 +32,31 @@
             return;
         }
     }
-    // STRIPED (needs the end rule): the workgroup sweeps the stripes of kStripeCols columns one after another over all of seq1.
+    // STRIPED: the workgroup sweeps the stripes of kStripeCols columns one after another over all of seq1.
     // A stripe re-initialises everything from here to the sweep with the lane's GLOBAL index G; wave 0 takes its left column
     // from `carry`, which lane 63 of the previous stripe's last wave wrote (row i at carry[i - 1]: that lane's stored key, what
-    // the ring would have carried), and the last row's candidates are folded into r after each stripe -- end_pack orders them,
-    // so a tie between stripes goes to the earlier column.  ONE carry buffer, in place: row i is read by wave 0 in chunk
+    // the ring would have carried), and each stripe's candidates are folded into r after it with a 64-bit maximum: the end
+    // rule's last-row and last-column cells (end_pack orders them, so a tie between stripes goes to the earlier column), or a
+    // local variant's best cell of the stripe (best and best_row start anew in every stripe, the column comes from the lane's
+    // GLOBAL jbase; the pack orders H descending, row ascending, column ascending, which is "first in row-major order" over
+    // all stripes -- not "the earlier stripe": a later stripe's cell in a lower row beats an equal cell of stripe 0).  ONE carry buffer, in place: row i is read by wave 0 in chunk
     // (i - 1) / 32 of a stripe and overwritten by wave 15 in chunk 45 + (i + 62) / 32 of the SAME stripe, 45 barriers after
     // its value was consumed, and read again only behind the stripe's closing drain, barrier and L1 invalidate.
     // BARRIER INVARIANT: every wave of the workgroup executes total_chunks + 1 barriers in every stripe but the last and
     // total_chunks in the last; total_chunks is made of len1 and blockDim alone, never of w, the stripe or its valid width.  A
     // wave with no column in the last stripe (my_chunks = 0 below) skips the chunk's work, not its barrier.
-    static_assert(!STRIPED || kEndRule<V>, "column stripes fold end-rule candidates");
     [[maybe_unused]] int *const carry_k = STRIPED ? carry + k * (size_t)len1 : nullptr;
     unsigned long long r = 0;                           // best cell so far: (H desc, row asc, column asc)
+    // A striped kernel without the end rule (a local variant) keeps its best cell so far per wave in red[w], not in r: two VGPRs
+    // that it has not got across the sweep.  Only lane 0 of wave w touches red[w] before the last barrier.
+    constexpr bool kFoldInLds = STRIPED && !kEndRule<V>;
+    if constexpr (kFoldInLds) {
+        if (l == 0) red[w] = 0;
+    }
     // the matrix columns, which every stripe's profile needs: a striped kernel keeps them in VGPRs across the sweep (it has
     // some to spare and no SGPR: as scalars they were spilled)
     SmCols pc = cols;
-    if constexpr (STRIPED)
+    if constexpr (STRIPED && kEndRule<V>)
         for (int b = 0; b < 4; ++b) pc.c[b] = (uint32_t)opaque_lane<true>((int)pc.c[b]);
     int stripe = 0;
     do {
@@ -63,12 +71,16 @@
 
     uint32_t prof[kCols];
     int key[kCols];                                     // H's stored keys of the row the lane computed last
+    // (a striped local kernel's row 0 is sixteen constants, which the compiler would set up once before the stripe loop and keep --
+    // spilled -- across every sweep: made of a 0 it cannot see through, they are set up anew in every stripe)
+    [[maybe_unused]] const int row0_zero = opaque_lane<STRIPED && !kEndRule<V>>(0);
 #pragma unroll
     for (int jj = 0; jj < kCols; ++jj) {
         const int j = jbase + jj + 1;
         const uint32_t b = s2[j <= len2 ? j - 1 : 0] & 3u;
         prof[jj] = j > len2 ? 0x80808080u : b == 0 ? pc.c[0] : b == 1 ? pc.c[1] : b == 2 ? pc.c[2] : pc.c[3];
         key[jj] = V::row0(jj, -j, gaps);
+        if constexpr (STRIPED && !kEndRule<V>) key[jj] |= row0_zero;
     }
     V lane(gaps);
     int diag_in = lane.border(-jbase);                   // key(0, jbase)
@@ -212,8 +224,17 @@
     } else {
         const int h = best >> 6;
         const int col = h > 0 ? jbase + (kCols - 1 - (best & 15)) + 1 : 0;
-        r = ((unsigned long long)(uint32_t)h << 34) | ((unsigned long long)(0x1FFFF - best_row) << 17) |
-            (unsigned long long)(0x1FFFF - col);
+        const unsigned long long cand = ((unsigned long long)(uint32_t)h << 34) | ((unsigned long long)(0x1FFFF - best_row) << 17) |
+                                        (unsigned long long)(0x1FFFF - col);
+        // the stripe's best cell joins the earlier stripes' (a wave that skipped the stripe folds (0, 0) with H = 0: harmless)
+        if constexpr (kFoldInLds) {
+            unsigned long long c = cand;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) c = umax64(c, __shfl_xor(c, o, 64));
+            if (l == 0) red[w] = umax64(red[w], c);
+        } else {
+            r = cand;
+        }
     }
     if constexpr (STRIPED) {
         if (more_stripes) {
@@ -225,12 +246,14 @@
         }
     }
     } while (STRIPED && ++stripe * kStripeCols < len2);
+    if constexpr (!kFoldInLds) {
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long v = __shfl_xor(r, o, 64);
-        r = v > r ? v : r;
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned long long v = __shfl_xor(r, o, 64);
+            r = v > r ? v : r;
+        }
+        if (l == 0) red[w] = r;
     }
-    if (l == 0) red[w] = r;
     if constexpr (TB) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's code stores have reached L2
     __syncthreads();
     r = red[0];

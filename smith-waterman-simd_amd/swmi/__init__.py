@@ -142,6 +142,8 @@ def load():
             ("swmi_global_long", "swmi_global_long_time_device", "swmi_global_long_slices_for", two_lens, [i8, cu]),
             ("swmi_global_long_affine", "swmi_global_long_affine_time_device", "swmi_global_long_affine_slices_for", two_lens,
              [ci, ci, cu]),
+            ("swmi_local_long", "swmi_local_long_time_device", "swmi_local_long_slices_for", two_lens, [i8]),
+            ("swmi_local_long_affine", "swmi_local_long_affine_time_device", "swmi_local_long_affine_slices_for", two_lens, [ci, ci]),
             ("swmi_global_full_ragged", None, None, ragged2, [i8, cu]),
             ("swmi_global_full_affine_ragged", None, None, ragged2, [ci, ci, cu])):
         args = shape + [vp] + gap + [vp, vp, vp, vp]
@@ -154,6 +156,7 @@ def load():
     lib.swmi_local_expand_moves.argtypes = [vp, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32, vp, sz]
     lib.swmi_local_full_expand_moves.argtypes = [vp, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32, vp, sz]
     lib.swmi_global_long_expand_moves.argtypes = [vp, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32, vp, sz]
+    lib.swmi_local_long_expand_moves.argtypes = [vp, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32, vp, sz]
     lib.swmi_local_ragged_move_offsets.argtypes = [vp, sz, vp]
     lib.swmi_local_ragged_slices_for.argtypes = [vp, sz, ci, ci, vp, sz]
     lib.swmi_local_ragged_slices_for.restype = sz
@@ -1192,3 +1195,4 @@ class Queue:
 from . import global_affine    # noqa: E402
 from . import global_ragged    # noqa: E402  (the global aligners on mixed-shape batches, likewise a submodule)
 from . import global_long      # noqa: E402  (the global aligners for lengths up to 65536, likewise a submodule)
+from . import local_long       # noqa: E402  (the local aligners for lengths up to 65536, likewise a submodule)
