@@ -951,6 +951,63 @@ SWMI_API int swmi_local_long_affine_time_device(const void *d_seq1s, size_t len1
                                                 void *d_ends, void *d_moves, void *d_steps, void *stream, int iters,
                                                 float *avg_ms);
 
+/* ---- exact semi-global alignment of sequences up to 65536 long ---------------------------------------
+ * swmi_semiglobal_full and swmi_semiglobal_full_affine for 1 <= len1, len2 <= 65536 (SWMI_SEMIGLOBAL_LONG_MAX_LEN): the same
+ * recurrences and charged borders (no zero floor), the same best cell (the first cell in row-major order over i = 0..len1,
+ * j = 0..len2 strictly above every earlier one, from 0 at (0, 0); (0, 0) when nothing is above 0), the same walk back to
+ * (0, 0), forced on row 0 and column 0, the same tie order (diagonal, up, left; affine: diagonal, E, F, and opening wins), and
+ * the same scores / ends[2] / moves / lengths layout, field for field: ends[2 k .. 2 k + 1] = the best cell, moves +
+ * k * SWMI_SEMIGLOBAL_LONG_MOVE_WORDS(len1, len2) alignment k's moves in WALKING order (the formula of SWMI_SGFULL_MOVE_WORDS),
+ * lengths[k] = steps + 1 <= SWMI_SEMIGLOBAL_LONG_MAX_TRACEBACK.  moves and lengths both NULL: ENDS-ONLY.
+ * swmi_semiglobal_long_expand_moves(moves_k, lengths[k], ...) rebuilds the (i, j) list from (0, 0) to the best cell; it is
+ * swmi_semiglobal_expand_moves for lengths up to 131073 (that one keeps refusing a length above 32769).  On a shape with both
+ * lengths <= 16384 the fixed-length kernel runs, so every field equals the fixed-length entry's.
+ * DOMAIN.  Bytes are taken modulo 4.  H is not floored, so swmi_global_long's rule applies: with P = max(1, max |score_matrix|,
+ * gap_penalty) (affine: gap_open and gap_extend in place of gap_penalty) a call is accepted iff P * (len1 + len2) <= 2^23.
+ * Every shape up to 32768 x 32768 passes with any int8 parameters, 65536 x 65536 with every magnitude <= 64.  0 <= score <
+ * 2^23.
+ * Errors: SWMI_ERR_INVALID_ARGUMENT for a length outside [1, 65536], a NULL buffer, only one of moves / lengths, or a call
+ * outside the domain rule; SWMI_ERR_DOMAIN for gap_penalty < 0 (affine: a gap outside [0, 127]); n = 0 is a no-op that needs
+ * no device.  Every argument is checked before any device is touched and before any launch.
+ * One workgroup aligns one pair and sweeps len2 in stripes of 16384 columns (the kernels' files tell how); where len2 > 16384
+ * a column of len1 values (affine: 2 len1) per alignment waits between two stripes in device memory, which the library keeps
+ * beside the traceback codes and counts in a slice.
+ * SLICES (swmi_semiglobal_long_slices_for, swmi_semiglobal_long_affine_slices_for): the budgets are the fixed-length
+ * semi-global entries' -- with a traceback what 256 alignments of 16384 x 16384 take, ends-only 256 MiB, at most 2^20
+ * alignments and never fewer than one.  KNOWN LIMIT: at 65536 x 65536 a traceback slice holds 16 alignments (about 1 GiB of
+ * codes each, 2 GiB with affine gaps, whose budget is twice as large), fewer than an MI355X has CUs.  0 for a length outside
+ * [1, 65536].
+ * The _device, _release_workspaces and _time_device forms are the fixed-length entries' (16-byte aligned device buffers,
+ * asynchronous on `stream`, a workspace of the library's per (GPU, stream)). */
+#define SWMI_SEMIGLOBAL_LONG_MAX_LEN 65536
+#define SWMI_SEMIGLOBAL_LONG_MOVE_WORDS(len1, len2) ((((((size_t)(len1)) + ((size_t)(len2)) + 31) / 32) + 1) & ~(size_t)1)   /* 16-byte rows */
+#define SWMI_SEMIGLOBAL_LONG_MAX_TRACEBACK 131073      /* 65536 + 65536 steps + 1 */
+SWMI_API int swmi_semiglobal_long(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t len2, size_t n,
+                                  const int8_t score_matrix[16], int8_t gap_penalty, int32_t *scores, int32_t *ends,
+                                  uint64_t *moves, uint32_t *lengths);
+SWMI_API size_t swmi_semiglobal_long_slices_for(size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap);
+SWMI_API int swmi_semiglobal_long_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
+                                         const int8_t score_matrix[16], int8_t gap_penalty, void *d_scores, void *d_ends,
+                                         void *d_moves, void *d_lengths, void *stream);
+SWMI_API int swmi_semiglobal_long_release_workspaces(void);
+SWMI_API int swmi_semiglobal_long_time_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
+                                              const int8_t score_matrix[16], int8_t gap_penalty, void *d_scores, void *d_ends,
+                                              void *d_moves, void *d_lengths, void *stream, int iters, float *avg_ms);
+SWMI_API int swmi_semiglobal_long_expand_moves(const uint64_t *moves, uint32_t length, int32_t *traceback, size_t cap);
+SWMI_API int swmi_semiglobal_long_affine(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t len2, size_t n,
+                                         const int8_t score_matrix[16], int gap_open, int gap_extend, int32_t *scores,
+                                         int32_t *ends, uint64_t *moves, uint32_t *lengths);
+SWMI_API size_t swmi_semiglobal_long_affine_slices_for(size_t n, size_t len1, size_t len2, int traceback, size_t *sizes,
+                                                       size_t cap);
+SWMI_API int swmi_semiglobal_long_affine_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
+                                                const int8_t score_matrix[16], int gap_open, int gap_extend, void *d_scores,
+                                                void *d_ends, void *d_moves, void *d_lengths, void *stream);
+SWMI_API int swmi_semiglobal_long_affine_release_workspaces(void);
+SWMI_API int swmi_semiglobal_long_affine_time_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2,
+                                                     size_t n, const int8_t score_matrix[16], int gap_open, int gap_extend,
+                                                     void *d_scores, void *d_ends, void *d_moves, void *d_lengths,
+                                                     void *stream, int iters, float *avg_ms);
+
 /* ---- deferred queue behind the per-pair signature -------------------------------------
  * Lets a per-pair caller (the reference's timing loop) keep its call shape while the
  * library batches: submit() copies the pair into pinned staging memory and returns its

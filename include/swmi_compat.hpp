@@ -133,6 +133,20 @@ inline std::pair<int, std::vector<std::pair<int, int>>> SmithWaterman_xlong_affi
                                                                                          const std::array<int8_t, 16> &score_matrix,
                                                                                          int gap_open, int gap_extend);
 
+// SemiGlobal_111's exact semi-global alignment for lengths in [1, 65536], any score matrix and gap (swmi_semiglobal_long,
+// swmi_semiglobal_long_affine): (score, path of (i, j) from (0, 0) to the best cell), the results of swmi_semiglobal_full and
+// swmi_semiglobal_full_affine field for field, accepted iff max(1, |score|, gaps) * (len1 + len2) <= 2^23 (include/swmi.h), which
+// holds for every shape up to 32768 x 32768.  One synchronous call per alignment; swmi::SemiGlobal_long_mi355x_batch and
+// swmi::SemiGlobal_long_affine_mi355x_batch are the throughput forms.
+inline std::pair<int, std::vector<std::pair<int, int>>> SemiGlobal_long_mi355x(const std::vector<uint8_t> &seq1,
+                                                                              const std::vector<uint8_t> &seq2,
+                                                                              const std::array<int8_t, 16> &score_matrix,
+                                                                              const int8_t gap_penalty);
+inline std::pair<int, std::vector<std::pair<int, int>>> SemiGlobal_long_affine_mi355x(const std::vector<uint8_t> &seq1,
+                                                                                     const std::vector<uint8_t> &seq2,
+                                                                                     const std::array<int8_t, 16> &score_matrix,
+                                                                                     int gap_open, int gap_extend);
+
 namespace swmi {
 
 // match 1, mismatch -1 (source.cpp:1786)
@@ -373,6 +387,15 @@ inline std::vector<std::pair<int, int>> local_long_path(const uint64_t *moves, u
     detail::check(swmi_local_long_expand_moves(moves, steps, ends[0], ends[1], reinterpret_cast<int32_t *>(path.data()), path.size()),
                   "swmi_local_long_expand_moves");
     return path;
+}
+
+// ... and the long semi-global aligners' (lengths up to 131073)
+inline std::vector<std::pair<int, int>> semiglobal_long_path(const uint64_t *moves, uint32_t length, const int32_t *)
+{
+    std::vector<std::pair<int, int>> tb(length);
+    detail::check(swmi_semiglobal_long_expand_moves(moves, length, reinterpret_cast<int32_t *>(tb.data()), length),
+                  "swmi_semiglobal_long_expand_moves");
+    return tb;
 }
 
 }  // namespace detail
@@ -678,6 +701,38 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SmithWaterm
             return swmi_local_long_affine(a, len1, b, len2, m, score_matrix.data(), gap_open, gap_extend, out...);
         },
         detail::local_long_path);
+}
+
+// Exact semi-global alignment of seq1s[k] against seq2s[k] for lengths in [1, 65536], every seq1 of one length and every seq2 of
+// one length: result[k] == SemiGlobal_long_mi355x(seq1s[k], seq2s[k], score_matrix, gap_penalty).  A piece is at most one
+// traceback slice of swmi_semiglobal_long (0 = one slice: 16 at 65536 x 65536).
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SemiGlobal_long_mi355x_batch(
+    const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::vector<uint8_t>> &seq2s,
+    const std::array<int8_t, 16> &score_matrix, const int8_t gap_penalty, size_t piece = 0, unsigned threads = 0)
+{
+    return detail::shaped_batch(
+        "SemiGlobal_long_mi355x_batch", "swmi_semiglobal_long", seq1s, seq2s, piece, threads, 2,
+        SWMI_SEMIGLOBAL_LONG_MOVE_WORDS(detail::common_length(seq1s), detail::common_length(seq2s)), swmi_semiglobal_long_slices_for,
+        [&](const uint8_t *a, size_t len1, const uint8_t *b, size_t len2, size_t m, auto... out) {
+            return swmi_semiglobal_long(a, len1, b, len2, m, score_matrix.data(), gap_penalty, out...);
+        },
+        detail::semiglobal_long_path);
+}
+
+// The same with affine gaps: result[k] == SemiGlobal_long_affine_mi355x(seq1s[k], seq2s[k], ...).  A piece is at most one
+// traceback slice of swmi_semiglobal_long_affine.
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SemiGlobal_long_affine_mi355x_batch(
+    const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::vector<uint8_t>> &seq2s,
+    const std::array<int8_t, 16> &score_matrix, int gap_open, int gap_extend, size_t piece = 0, unsigned threads = 0)
+{
+    return detail::shaped_batch(
+        "SemiGlobal_long_affine_mi355x_batch", "swmi_semiglobal_long_affine", seq1s, seq2s, piece, threads, 2,
+        SWMI_SEMIGLOBAL_LONG_MOVE_WORDS(detail::common_length(seq1s), detail::common_length(seq2s)),
+        swmi_semiglobal_long_affine_slices_for,
+        [&](const uint8_t *a, size_t len1, const uint8_t *b, size_t len2, size_t m, auto... out) {
+            return swmi_semiglobal_long_affine(a, len1, b, len2, m, score_matrix.data(), gap_open, gap_extend, out...);
+        },
+        detail::semiglobal_long_path);
 }
 
 // Any-length local alignments of mixed shapes (swmi_local_full_ragged and its affine twin): seq1s[k] and seq2s[k] each of any
@@ -1016,4 +1071,31 @@ inline std::pair<int, std::vector<std::pair<int, int>>> SemiGlobal_affine_mi355x
                                                gap_extend, out...);
         },
         swmi::detail::semiglobal_path);
+}
+
+inline std::pair<int, std::vector<std::pair<int, int>>> SemiGlobal_long_mi355x(const std::vector<uint8_t> &seq1,
+                                                                              const std::vector<uint8_t> &seq2,
+                                                                              const std::array<int8_t, 16> &score_matrix,
+                                                                              const int8_t gap_penalty)
+{
+    return swmi::detail::one_alignment(
+        "swmi_semiglobal_long", SWMI_SEMIGLOBAL_LONG_MOVE_WORDS(seq1.size(), seq2.size()),
+        [&](auto... out) {
+            return swmi_semiglobal_long(seq1.data(), seq1.size(), seq2.data(), seq2.size(), 1, score_matrix.data(), gap_penalty, out...);
+        },
+        swmi::detail::semiglobal_long_path);
+}
+
+inline std::pair<int, std::vector<std::pair<int, int>>> SemiGlobal_long_affine_mi355x(const std::vector<uint8_t> &seq1,
+                                                                                     const std::vector<uint8_t> &seq2,
+                                                                                     const std::array<int8_t, 16> &score_matrix,
+                                                                                     int gap_open, int gap_extend)
+{
+    return swmi::detail::one_alignment(
+        "swmi_semiglobal_long_affine", SWMI_SEMIGLOBAL_LONG_MOVE_WORDS(seq1.size(), seq2.size()),
+        [&](auto... out) {
+            return swmi_semiglobal_long_affine(seq1.data(), seq1.size(), seq2.data(), seq2.size(), 1, score_matrix.data(), gap_open,
+                                               gap_extend, out...);
+        },
+        swmi::detail::semiglobal_long_path);
 }

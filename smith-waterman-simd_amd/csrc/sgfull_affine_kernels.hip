@@ -12,7 +12,8 @@
 //
 // Mapping, ring timing, best-cell rule and code layout: tile_sweep.h, which also holds the constants, the helpers and the
 // launcher.  The sweep and the walk (the (H, F) hand-over, the code word, the walk's states) are
-// tile_sweep_affine_body.inc, shared with local_full_affine_kernels.hip; this file holds what depends on the recurrence.
+// tile_sweep_affine_body.inc, shared with local_full_affine_kernels.hip; what depends on the recurrence is the variant's
+// (sgfull_affine_variant.h, shared with sgfull_long_affine_kernels.hip), and this file tells it.
 //
 // The cell as KEYS: key = value << 6 | tag << 4 | low, |value| < 2^23 (below).  A stored H key has tag 3 and low = 15 - jj
 // (jj = the column within the lane); E and F are kept as keys of tag 2 and 1 with a traceback (one v_and_or_b32 after their
@@ -41,7 +42,7 @@
 // Codes: H's field of the low dword is the winner's tag (3 / 2 / 1 = diagonal / E / F), as sgfull_kernels.hip's codes.
 //
 // Walk: no code stops it; it reaches row 0 or column 0 in state H, and from there it is forced to (0, 0).
-#include "tile_sweep.h"
+#include "sgfull_affine_variant.h"
 
 namespace swmi {
 namespace {
@@ -61,26 +62,6 @@ constexpr int kStageRows = 128;
 static_assert(kCols == tile::kCols && kMaxWaves == tile::kMaxWaves && kUnroll == tile::kUnroll && kChunk == tile::kChunk &&
               kDelay == tile::kDelay && kRing == tile::kRing && kStageRows == tile::kStageRows);
 }  // namespace written_for
-
-struct SgAffine {
-    static constexpr bool kWalkStops = false;
-    static constexpr int kEnds = 2;
-    static constexpr int kRowMin = (int)0x80000000;
-    static constexpr int kTagH = 3 << 4;
-    static constexpr int kTagE = 2 << 4;
-    static constexpr int kTagF = 1 << 4;
-    static constexpr int kOpenBitE = 4;            // kTagH has it, kTagE has not
-    static constexpr int kOpenBitF = 5;            // kTagH has it, kTagF has not
-
-    // H(0, j) = H(j, 0) for j >= 1 (and 0 at j = 0) as a stored key
-    static __device__ __forceinline__ int border(int j, int gap_open, int gap_extend)
-    {
-        const int h = j > 0 ? -(gap_open + (j - 1) * gap_extend) : 0;
-        return (h << 6) | kTagH;
-    }
-    static __device__ __forceinline__ int row0(int, int j, int gap_open, int gap_extend) { return border(j, gap_open, gap_extend); }
-    static __device__ __forceinline__ int floor(int m) { return m; }
-};
 
 template <bool TB>
 __global__ __launch_bounds__(64 * kMaxWaves) void sg_full_affine_kernel(

@@ -6,7 +6,8 @@
 // for i = 1..len1, j = 1..len2.  The best cell is the first cell in row-major order strictly above every earlier one,
 // from 0 at (0,0); the walk goes back from it to (0,0), diagonal before up before left.  DESIGN.md section 13.
 //
-// Mapping, ring timing, best-cell reduction, code layout and staged walk: tile_sweep.h.  This file holds the recurrence.
+// Mapping, ring timing, best-cell reduction, code layout and staged walk: tile_sweep.h.  The recurrence is the variant's
+// (sgfull_variant.h, shared with sgfull_long_kernels.hip); this file tells it.
 //
 // The cell as KEYS: key = H << 6 | tag << 4 | (15 - jj) (jj = the column within the lane).  A stored key has tag 3; the
 // candidates come from the neighbours' keys by one add each:
@@ -26,7 +27,7 @@
 //
 // Codes: 2 bits per cell, one dword per lane and row, column jj at bits 2 jj: the move itself (3 / 2 / 1).  A staging block
 // of the walk is 128 rows x 64 lanes (1024 columns): at 16384 x 16384 a path needs at most 256 blocks.
-#include "tile_sweep.h"
+#include "sgfull_variant.h"
 
 namespace swmi {
 namespace {
@@ -46,44 +47,6 @@ constexpr int kStageRows = 128;
 static_assert(kCols == tile::kCols && kMaxWaves == tile::kMaxWaves && kUnroll == tile::kUnroll && kChunk == tile::kChunk &&
               kDelay == tile::kDelay && kRing == tile::kRing && kStageRows == tile::kStageRows);
 }  // namespace written_for
-
-constexpr int kTag3 = 3 << 4;
-
-// H(0, j) = H(j, 0) as a stored key, from nj = -j
-__device__ __forceinline__ int border_key(int nj, int gap) { return ((nj * gap) << 6) | kTag3; }
-
-struct SgLinear {
-    static constexpr bool kWalkStops = false;
-    static constexpr int kEnds = 2;
-    static constexpr int kStageLanes = 64;
-    static constexpr int kRowMin = (int)0x80000000;
-    static constexpr int kZeroKey = kTag3;       // the stored key of H = 0, column bits aside
-
-    struct Gaps {
-        int gap;
-    };
-    int gap, g_up, g_left;
-
-    __device__ __forceinline__ explicit SgLinear(Gaps g) : gap(g.gap), g_up(-(g.gap << 6) - (1 << 4)), g_left(-(g.gap << 6) - (2 << 4)) {}
-
-    static __device__ __forceinline__ int row0(int, int nj, Gaps g) { return border_key(nj, g.gap); }
-    __device__ __forceinline__ int border(int nj) const { return border_key(nj, gap); }
-    __device__ __forceinline__ int left_border(int nrow) const { return border(nrow); }
-
-    template <bool TB>
-    __device__ __forceinline__ int cell(int jj, int sc, int &d, int &lft, int &key, uint32_t &code) const
-    {
-        const int m = max3(d + (sc << 6), key + g_up, lft + g_left);
-        const int nk = (m & ~63) | (kTag3 | (kCols - 1 - jj));
-        if constexpr (TB) code = ((uint32_t)(m >> 4) & 3u) << (2 * jj);
-        d = key;
-        key = nk;
-        lft = nk;
-        return nk;
-    }
-
-    static __device__ __forceinline__ uint32_t step(uint32_t wd, int cc) { return (wd >> (2 * cc)) & 3u; }
-};
 
 template <bool TB>
 __global__ __launch_bounds__(64 * kMaxWaves) void sg_full_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ seq2s,

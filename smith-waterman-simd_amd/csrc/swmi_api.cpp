@@ -594,6 +594,28 @@ int score_host_batch(Context &ctx, const uint8_t *s1, const uint8_t *s2, size_t 
     return SWMI_OK;
 }
 
+// Host-side expansion of one alignment's moves into the reference's traceback (source.cpp:1962-1975: the (i, j) list in
+// ascending order from (0, 0)).  No device involved.  Move t sits at bits 2 (t % 32) of word t / 32, in WALKING order (move 0
+// leaves the best cell); the list therefore applies them last to first: 3 = diagonal, 2 = a row step, 1 = a column step.
+int semiglobal_expand_moves(uint32_t max_length, const uint64_t *moves, uint32_t length, int32_t *traceback, size_t cap)
+{
+    if (!moves || (!traceback && cap)) return fail(SWMI_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (length == 0 || length > max_length) return fail(SWMI_ERR_INVALID_ARGUMENT, "length %u outside [1, %u]", length, max_length);
+    const size_t count = length < cap ? length : cap;
+    if (count == 0) return SWMI_OK;
+    // position k as ONE 64-bit word (i in the low half, j in the high half: two int32 on a little-endian host); a step adds its
+    // row / column increment to it.  Step t of the walk produces position length - 1 - t of the list.
+    static const uint64_t kStep[4] = {0, uint64_t(1) << 32, 1, (uint64_t(1) << 32) | 1};
+    uint64_t pos = 0;
+    memcpy(traceback, &pos, sizeof pos);                 // (traceback need not be 8-byte aligned)
+    int64_t t = int64_t(length) - 2;
+    for (size_t k = 1; k < count; ++k, --t) {
+        pos += kStep[(moves[t >> 5] >> (2 * (t & 31))) & 3u];
+        memcpy(traceback + 2 * k, &pos, sizeof pos);
+    }
+    return SWMI_OK;
+}
+
 }  // namespace host
 }  // namespace swmi
 
@@ -1132,26 +1154,9 @@ int swmi_semiglobal_xdrop_moves_device(const void *d_seq1s, const void *d_seq2s,
     return semiglobal_device(d_seq1s, d_seq2s, n, d_scores, nullptr, 0, d_lengths, stream, nullptr, d_moves);
 }
 
-// Host-side expansion of one alignment's moves into the reference's traceback (source.cpp:1962-1975: the (i, j) list in
-// ascending order from (0, 0)).  No device involved.  Move t sits at bits 2 (t % 32) of word t / 32, in WALKING order (move 0
-// leaves the best cell); the list therefore applies them last to first: 3 = diagonal, 2 = a row step, 1 = a column step.
 int swmi_semiglobal_expand_moves(const uint64_t *moves, uint32_t length, int32_t *traceback, size_t cap)
 {
-    if (!moves || (!traceback && cap)) return fail(SWMI_ERR_INVALID_ARGUMENT, "NULL buffer");
-    if (length == 0 || length > SWMI_SG_MAX_TRACEBACK) return fail(SWMI_ERR_INVALID_ARGUMENT, "length %u outside [1, %d]", length, SWMI_SG_MAX_TRACEBACK);
-    const size_t count = length < cap ? length : cap;
-    if (count == 0) return SWMI_OK;
-    // position k as ONE 64-bit word (i in the low half, j in the high half: two int32 on a little-endian host); a step adds its
-    // row / column increment to it.  Step t of the walk produces position length - 1 - t of the list.
-    static const uint64_t kStep[4] = {0, uint64_t(1) << 32, 1, (uint64_t(1) << 32) | 1};
-    uint64_t pos = 0;
-    memcpy(traceback, &pos, sizeof pos);                 // (traceback need not be 8-byte aligned)
-    int64_t t = int64_t(length) - 2;
-    for (size_t k = 1; k < count; ++k, --t) {
-        pos += kStep[(moves[t >> 5] >> (2 * (t & 31))) & 3u];
-        memcpy(traceback + 2 * k, &pos, sizeof pos);
-    }
-    return SWMI_OK;
+    return semiglobal_expand_moves(SWMI_SG_MAX_TRACEBACK, moves, length, traceback, cap);
 }
 
 int swmi_semiglobal_xdrop_device(const void *d_seq1s, const void *d_seq2s, size_t n, void *d_scores, void *d_tracebacks,

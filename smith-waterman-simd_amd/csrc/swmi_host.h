@@ -140,10 +140,11 @@ struct Workspace {
 };
 
 // The aligners that run through the slice pipeline of swmi_table.cpp: one FamilyRow each, the first kTableApiFamilies in
-// table_api.cpp, the two long local ones in local_long_api.cpp
+// table_api.cpp, the two long local ones in local_long_api.cpp, the two long semi-global ones in semiglobal_long_api.cpp
 enum TableFamily {
     kTableLocal, kTableSgfull, kTableLocalAffine, kTableSgfullAffine, kTableLocalFull, kTableLocalFullAffine, kTableGlobalFull,
-    kTableGlobalFullAffine, kTableGlobalLong, kTableGlobalLongAffine, kTableLocalLong, kTableLocalLongAffine, kTableFamilies
+    kTableGlobalFullAffine, kTableGlobalLong, kTableGlobalLongAffine, kTableLocalLong, kTableLocalLongAffine, kTableSemiglobalLong,
+    kTableSemiglobalLongAffine, kTableFamilies
 };
 constexpr int kTableApiFamilies = kTableLocalLong;     // the families whose rows table_api.cpp holds
 
@@ -282,7 +283,7 @@ struct FamilyRow {
     bool affine;                // gap_extend is read; gaps within [0, 127] instead of check_params
     bool mask;                  // free_ends is read
     bool carry;                 // column stripes: a carry of len1 dwords (affine: 2 len1) per alignment where len2 > 16384
-    bool domain;                // the striped global aligners' domain rule, P (len1 + len2) <= 2^23 (include/swmi.h)
+    bool domain;                // the unfloored striped aligners' domain rule, P (len1 + len2) <= 2^23 (include/swmi.h)
     bool timer_first;           // the timer checks its own arguments (and binds the context) before the call's
 };
 // the arguments of one call that the families read
@@ -315,6 +316,9 @@ bool local_full_ragged_plan_check(const uint64_t *seq1_offsets, const uint64_t *
 // global_full_ragged_api.cpp: the same for a ragged batch of the global aligners (one planner, tile_ragged_plan.h)
 bool global_full_ragged_plan_check(const uint64_t *seq1_offsets, const uint64_t *seq2_offsets, size_t n, bool affine, bool tb,
                                    std::vector<size_t> *slice_sizes, std::vector<size_t> *slice_bytes);
+// the (i, j) list from (0, 0) of a semi-global walk's moves, for lengths up to max_length: the body of swmi_semiglobal_expand_moves
+// (swmi_api.cpp) and of swmi_semiglobal_long_expand_moves (semiglobal_long_api.cpp)
+int semiglobal_expand_moves(uint32_t max_length, const uint64_t *moves, uint32_t length, int32_t *traceback, size_t cap);
 // Free one aligner's device buffers on the current GPU (synchronises the device first): the body of the *_release_workspaces entries
 int table_release_workspaces(TableFamily family);
 

@@ -238,6 +238,22 @@ hipError_t launch_local_long_affine(const uint8_t *d_seq1s, const uint8_t *d_seq
 }  // namespace swmi
 
 namespace swmi {
+// The striped semi-global aligners for lengths up to 65536 (sgfull_long_kernels.hip, sgfull_long_affine_kernels.hip; DESIGN.md
+// section 26): launch_sgfull's / launch_sgfull_affine's arguments, shapes up to 65536 x 65536, and d_carry as for the striped
+// global aligners: len1 dwords (affine: 2 len1) per alignment of the launch, 8-byte aligned, needed when len2 > 16384 and else
+// unused (may be NULL).
+size_t sgfull_long_code_words(int len1, int len2);
+hipError_t launch_sgfull_long(const uint8_t *d_seq1s, const uint8_t *d_seq2s, int len1, int len2, size_t n, const int8_t *sm, int gap,
+                              int32_t *d_scores, int32_t *d_ends, uint32_t *d_codes, unsigned long long *d_moves, uint32_t *d_lengths,
+                              size_t move_words, int32_t *d_carry, hipStream_t stream);
+size_t sgfull_long_affine_code_qwords(int len1, int len2);
+hipError_t launch_sgfull_long_affine(const uint8_t *d_seq1s, const uint8_t *d_seq2s, int len1, int len2, size_t n, const int8_t *sm,
+                                     int gap_open, int gap_extend, int32_t *d_scores, int32_t *d_ends, unsigned long long *d_codes,
+                                     unsigned long long *d_moves, uint32_t *d_lengths, size_t move_words, int32_t *d_carry,
+                                     hipStream_t stream);
+}  // namespace swmi
+
+namespace swmi {
 // The ragged launches of the two global aligners: launch_local_full_ragged's slots, wave counts and
 // buffers, with the call's one mask.  A slot with a zero length runs in a workgroup of one wavefront and writes the closed
 // form of its one border (tile_sweep.h, end_rule_zero_length): it takes no code words, but its move words.

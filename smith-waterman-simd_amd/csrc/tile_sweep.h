@@ -1,7 +1,7 @@
 // tile_sweep.h -- what the any-length aligners share (sgfull_kernels.hip, sgfull_affine_kernels.hip,
 // local_full_kernels.hip, local_full_affine_kernels.hip, global_full_kernels.hip, global_full_affine_kernels.hip,
-// global_long_kernels.hip, global_long_affine_kernels.hip, local_long_kernels.hip, local_long_affine_kernels.hip; DESIGN.md
-// section 13): the mapping and its constants, the helpers, the geometry and the launcher; the few helpers that the 16-lane local aligners take from here as well.  The sweep and the
+// global_long_kernels.hip, global_long_affine_kernels.hip, local_long_kernels.hip, local_long_affine_kernels.hip,
+// sgfull_long_kernels.hip, sgfull_long_affine_kernels.hip): the mapping and its constants, the helpers, the geometry and the launcher; the few helpers that the 16-lane local aligners take from here as well.  The sweep and the
 // walk of the linear-gap kernels are tile_sweep_body.inc, those of the affine kernels tile_sweep_affine_body.inc.
 //
 // Mapping: ONE workgroup per alignment, W = ceil(len2 / 1024) wavefronts; lane l of wave w owns the 16 columns
@@ -140,8 +140,9 @@ constexpr int kStageRows = 128;        // rows of a walk staging block
 constexpr bool RAGGED = false;         // what a kernel without a ragged form sees (above)
 constexpr TileWork slot{};
 
-// Column stripes (global_long_kernels.hip, global_long_affine_kernels.hip, and with a local variant local_long_kernels.hip,
-// local_long_affine_kernels.hip; DESIGN.md sections 23 and 25): a kernel that shadows STRIPED
+// Column stripes (global_long_kernels.hip, global_long_affine_kernels.hip, with a local variant local_long_kernels.hip,
+// local_long_affine_kernels.hip, and with a semi-global one sgfull_long_kernels.hip, sgfull_long_affine_kernels.hip; DESIGN.md
+// sections 23, 25 and 26): a kernel that shadows STRIPED
 // with true sweeps len2 > kStripeCols columns as stripes of kStripeCols, one after another, in the same workgroup; it names
 // `carry` (linear body: int per row) or `carry_hf` (affine body: int2 per row), the per-alignment device buffer through which
 // a stripe's last column reaches the next stripe's wave 0.  What every other kernel sees:

@@ -85,6 +85,10 @@
     V lane(gaps);
     int diag_in = lane.border(-jbase);                   // key(0, jbase)
     int best = kEndRule<V> ? V::kRowMin : V::kZeroKey, best_row = 0;   // H = 0 at (0, 0); end rule: no last-column cell yet
+    // (a striped semi-global kernel, whose walk no code stops: with a literal 0 the compiler packs the candidate of a lane that
+    // took no row, (0x1FFFF - 0) << 17, once before the stripe loop and keeps the 64-bit constant -- spilled -- across every sweep;
+    // the row starts from the stripe's opaque 0 instead)
+    if constexpr (STRIPED && !kEndRule<V> && !V::kWalkStops) best_row = row0_zero;
     // end rule: the lane that owns column len2 keeps the best cell of that column, if seq1's end is free
     const int end_jj = (len2 - 1) & (kCols - 1);
     const bool end_col_wave = kEndRule<V> && (free_ends & kFreeEnd1) && (STRIPED ? gw == (len2 - 1) >> 10 : w == W - 1);

@@ -100,6 +100,7 @@ def load():
     lib.swmi_semiglobal_xdrop_moves.argtypes = [vp, vp, sz, vp, vp, vp]
     lib.swmi_semiglobal_xdrop_moves_device.argtypes = [vp, vp, sz, vp, vp, vp, vp]
     lib.swmi_semiglobal_expand_moves.argtypes = [vp, ctypes.c_uint32, vp, sz]
+    lib.swmi_semiglobal_long_expand_moves.argtypes = [vp, ctypes.c_uint32, vp, sz]
     lib.swmi_schedule_for_batch.argtypes = [sz]
     lib.swmi_semiglobal_time_device.argtypes = [vp, vp, sz, vp, vp, sz, vp, vp, ctypes.POINTER(ctypes.c_float)]
     lib.swmi_semiglobal_window_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
@@ -144,6 +145,9 @@ def load():
              [ci, ci, cu]),
             ("swmi_local_long", "swmi_local_long_time_device", "swmi_local_long_slices_for", two_lens, [i8]),
             ("swmi_local_long_affine", "swmi_local_long_affine_time_device", "swmi_local_long_affine_slices_for", two_lens, [ci, ci]),
+            ("swmi_semiglobal_long", "swmi_semiglobal_long_time_device", "swmi_semiglobal_long_slices_for", two_lens, [i8]),
+            ("swmi_semiglobal_long_affine", "swmi_semiglobal_long_affine_time_device", "swmi_semiglobal_long_affine_slices_for",
+             two_lens, [ci, ci]),
             ("swmi_global_full_ragged", None, None, ragged2, [i8, cu]),
             ("swmi_global_full_affine_ragged", None, None, ragged2, [ci, ci, cu])):
         args = shape + [vp] + gap + [vp, vp, vp, vp]
@@ -1196,3 +1200,4 @@ from . import global_affine    # noqa: E402
 from . import global_ragged    # noqa: E402  (the global aligners on mixed-shape batches, likewise a submodule)
 from . import global_long      # noqa: E402  (the global aligners for lengths up to 65536, likewise a submodule)
 from . import local_long       # noqa: E402  (the local aligners for lengths up to 65536, likewise a submodule)
+from . import semiglobal_long  # noqa: E402  (the exact semi-global aligners for lengths up to 65536, likewise a submodule)
