@@ -1008,6 +1008,53 @@ SWMI_API int swmi_semiglobal_long_affine_time_device(const void *d_seq1s, size_t
                                                      void *d_scores, void *d_ends, void *d_moves, void *d_lengths,
                                                      void *stream, int iters, float *avg_ms);
 
+/* ---- the exact semi-global aligners on a batch of MIXED (len1, len2) ----------------------------------
+ * swmi_semiglobal_full and swmi_semiglobal_full_affine with one (len1, len2) per alignment and one set of gaps per call.  The
+ * arguments are swmi_local_full_ragged's: alignment k is seq1 = bytes [seq1_offsets[k], seq1_offsets[k+1]) of seq1s against
+ * seq2 = bytes [seq2_offsets[k], seq2_offsets[k+1]) of seq2s; both offset arrays hold n + 1 non-decreasing entries, and every
+ * length is in [0, 16384].  For two non-zero lengths scores[k], ends[2 k .. 2 k + 1] = the best cell (TWO int32 per alignment),
+ * the moves in walking order (3 / 2 / 1 = diagonal / up / left) and lengths[k] = steps + 1 are, field for field, those of the
+ * fixed-length entry called with that pair, in caller order.  Alignment k's moves start at word move_offsets[k]:
+ * SWMI_SGFULL_MOVE_WORDS is SWMI_LOCAL_FULL_MOVE_WORDS, so swmi_local_full_ragged_move_offsets gives the layout, and there is
+ * no second function for it; swmi_semiglobal_expand_moves(moves + move_offsets[k], lengths[k], ...) rebuilds a path.  moves
+ * and lengths both NULL: ends-only.
+ * ZERO LENGTHS follow from the definition extended to an empty sequence: the table is one border, every cell of which is <= 0,
+ * and (0, 0) holds 0 and comes first.  So the score is 0, the best cell (0, 0), there is no move, and lengths[k] = 1 (the one
+ * position (0, 0)), also at gap 0 -- NOT the local aligners' count of 0.  Ends-only gives the same score and cell.  No byte of
+ * either sequence is read, and no move word is written.
+ * Host buffers.  The batch runs in slices (swmi_semiglobal_full_ragged_slices_for) on two sets of device buffers, one launch
+ * per wave count present in a slice, the widest first, and inside a launch the longest seq1 first; results go to caller
+ * positions.  The checks run in this order: the matrix and the gaps, moves / lengths given both or neither, n = 0 (a no-op that
+ * needs no device), the buffers, the offsets.  Errors: SWMI_ERR_INVALID_ARGUMENT for decreasing offsets, a length above 16384, a
+ * NULL buffer, or only one of moves / lengths; SWMI_ERR_DOMAIN as in the fixed-length entries.  Every argument is checked
+ * before any device is touched. */
+SWMI_API int swmi_semiglobal_full_ragged(const uint8_t *seq1s, const uint64_t *seq1_offsets, const uint8_t *seq2s,
+                                         const uint64_t *seq2_offsets, size_t n, const int8_t score_matrix[16], int8_t gap_penalty,
+                                         int32_t *scores, int32_t *ends, uint64_t *moves, uint32_t *lengths);
+SWMI_API int swmi_semiglobal_full_affine_ragged(const uint8_t *seq1s, const uint64_t *seq1_offsets, const uint8_t *seq2s,
+                                                const uint64_t *seq2_offsets, size_t n, const int8_t score_matrix[16], int gap_open,
+                                                int gap_extend, int32_t *scores, int32_t *ends, uint64_t *moves, uint32_t *lengths);
+/* The slices a ragged call of n alignments cuts its batch into (affine = 0: swmi_semiglobal_full_ragged, else the affine one;
+ * traceback = 0: ends-only), in order; returns how many there are and writes the first `cap` sizes (NULL to count).  Each is
+ * the longest run of the alignments left, in caller order, whose device bytes fit the fixed-length aligner's budget for one
+ * slice (swmi_semiglobal_full_slices_for's or swmi_semiglobal_full_affine_slices_for's with a traceback; 256 MiB ends-only), at
+ * most 2^20 alignments and at least one.  The bytes are counted as for the other ragged families (five result dwords per
+ * alignment, an upper bound here).  Needs no device.  0 for invalid offsets. */
+SWMI_API size_t swmi_semiglobal_full_ragged_slices_for(const uint64_t *seq1_offsets, const uint64_t *seq2_offsets, size_t n,
+                                                       int affine, int traceback, size_t *sizes, size_t cap);
+/* Same with every data buffer in device memory (16-byte aligned at its base; an alignment's offsets need no alignment),
+ * asynchronous on `stream`; d_moves uses the move_offsets layout.  Both offset arrays stay HOST arrays, read during the call
+ * only.  The codes and slots go to the workspace of the fixed-length entry per (GPU, stream)
+ * (swmi_semiglobal_full_release_workspaces / swmi_semiglobal_full_affine_release_workspaces free it). */
+SWMI_API int swmi_semiglobal_full_ragged_device(const void *d_seq1s, const uint64_t *seq1_offsets, const void *d_seq2s,
+                                                const uint64_t *seq2_offsets, size_t n, const int8_t score_matrix[16],
+                                                int8_t gap_penalty, void *d_scores, void *d_ends, void *d_moves, void *d_lengths,
+                                                void *stream);
+SWMI_API int swmi_semiglobal_full_affine_ragged_device(const void *d_seq1s, const uint64_t *seq1_offsets, const void *d_seq2s,
+                                                       const uint64_t *seq2_offsets, size_t n, const int8_t score_matrix[16],
+                                                       int gap_open, int gap_extend, void *d_scores, void *d_ends, void *d_moves,
+                                                       void *d_lengths, void *stream);
+
 /* ---- deferred queue behind the per-pair signature -------------------------------------
  * Lets a per-pair caller (the reference's timing loop) keep its call shape while the
  * library batches: submit() copies the pair into pinned staging memory and returns its

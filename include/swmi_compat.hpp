@@ -739,11 +739,12 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SemiGlobal_
 // length in [0, 16384], in pieces of at most `piece` alignments (0 counts as 4096), each one ragged call, so only two pieces'
 // inputs and moves are held at a time; the paths of one piece are rebuilt on `threads` host threads (0 = as many as the
 // machine reports, at most 64) while the GPU aligns the next.  call(seq1 bytes, offsets, seq2 bytes, offsets, m, scores,
-// ends, moves, steps) is the C entry with its parameters bound.
-template <class Call>
-inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> local_full_ragged_batch(
+// ends, moves, counts) is the C entry with its parameters bound; it writes `ends_width` int32 of ends per alignment, and
+// path(moves row, count, the alignment's ends) is the family's expander (detail::local_full_path, detail::semiglobal_path).
+template <class Call, class Path>
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> full_ragged_batch(
     const char *name, const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::vector<uint8_t>> &seq2s, size_t piece,
-    unsigned threads, Call call)
+    unsigned threads, size_t ends_width, Call call, Path path)
 {
     if (seq1s.size() != seq2s.size()) throw std::invalid_argument(std::string(name) + ": seq1s and seq2s differ in length");
     if (piece == 0) piece = 4096;
@@ -765,17 +766,25 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> local_full_
         if (swmi_local_full_ragged_move_offsets(p.seq1_offsets.data(), p.seq2_offsets.data(), m, p.move_offsets.data()) != SWMI_OK)
             throw std::invalid_argument(std::string(name) + ": " + swmi_last_error());
         p.scores.resize(m);
-        p.ends.resize(4 * m);
+        p.ends.resize(ends_width * m);
         p.moves.resize(p.move_offsets[m] ? p.move_offsets[m] : 1);
         p.counts.resize(m);
         detail::check(call(p.seq1s.data(), p.seq1_offsets.data(), p.seq2s.data(), p.seq2_offsets.data(), m, p.scores.data(),
                            p.ends.data(), p.moves.data(), p.counts.data()),
                       name);
     };
-    return detail::run_in_pieces(seq1s.size(), piece, threads, align, [](const detail::PieceBuffers &p, size_t k) {
-        return detail::Result{p.scores[k],
-                              expand_local_full_moves(p.moves.data() + p.move_offsets[k], p.counts[k], p.ends[4 * k], p.ends[4 * k + 1])};
+    return detail::run_in_pieces(seq1s.size(), piece, threads, align, [=](const detail::PieceBuffers &p, size_t k) {
+        return detail::Result{p.scores[k], path(p.moves.data() + p.move_offsets[k], p.counts[k], p.ends.data() + ends_width * k)};
     });
+}
+
+// The local and the global families: four ends per alignment, the path from the end cell (expand_local_full_moves).
+template <class Call>
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> local_full_ragged_batch(
+    const char *name, const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::vector<uint8_t>> &seq2s, size_t piece,
+    unsigned threads, Call call)
+{
+    return full_ragged_batch(name, seq1s, seq2s, piece, threads, 4, call, detail::local_full_path);
 }
 
 // Any-length local alignment of seq1s[k] against seq2s[k], every sequence of a length of its own in [0, 16384]: result[k] ==
@@ -836,6 +845,37 @@ inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> NeedlemanWu
                                        return swmi_global_full_affine_ragged(a, oa, b, ob, m, score_matrix.data(), gap_open, gap_extend,
                                                                              free_ends, sc, e, mv, st);
                                    });
+}
+
+// Exact semi-global alignment of seq1s[k] against seq2s[k], every sequence of a length of its own in [0, 16384]
+// (swmi_semiglobal_full_ragged): result[k] == SemiGlobal_long_mi355x(seq1s[k], seq2s[k], score_matrix, gap_penalty), which with
+// semiglobal_111_matrix() and gap 1 is the reference's SemiGlobal_111: the path from (0, 0) to the best cell, and
+// (0, {(0, 0)}) when either sequence is empty (one border, all <= 0: include/swmi.h).
+// Pieces, moves and threads as in SmithWaterman_long_mi355x_ragged_batch, whose move layout this shares.
+// SemiGlobal_111_mi355x_batch and SemiGlobal_affine_mi355x_batch keep requiring one shape.
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SemiGlobal_111_mi355x_ragged_batch(
+    const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::vector<uint8_t>> &seq2s,
+    const std::array<int8_t, 16> &score_matrix, const int8_t gap_penalty, size_t piece = 0, unsigned threads = 0)
+{
+    return full_ragged_batch(
+        "SemiGlobal_111_mi355x_ragged_batch", seq1s, seq2s, piece, threads, 2,
+        [&](const uint8_t *a, const uint64_t *oa, const uint8_t *b, const uint64_t *ob, size_t m, int32_t *sc, int32_t *e, uint64_t *mv,
+            uint32_t *ln) { return swmi_semiglobal_full_ragged(a, oa, b, ob, m, score_matrix.data(), gap_penalty, sc, e, mv, ln); },
+        detail::semiglobal_path);
+}
+
+// The same with affine gaps: result[k] == SemiGlobal_affine_mi355x(seq1s[k], seq2s[k], score_matrix, gap_open, gap_extend).
+inline std::vector<std::pair<int, std::vector<std::pair<int, int>>>> SemiGlobal_affine_mi355x_ragged_batch(
+    const std::vector<std::vector<uint8_t>> &seq1s, const std::vector<std::vector<uint8_t>> &seq2s,
+    const std::array<int8_t, 16> &score_matrix, int gap_open, int gap_extend, size_t piece = 0, unsigned threads = 0)
+{
+    return full_ragged_batch(
+        "SemiGlobal_affine_mi355x_ragged_batch", seq1s, seq2s, piece, threads, 2,
+        [&](const uint8_t *a, const uint64_t *oa, const uint8_t *b, const uint64_t *ob, size_t m, int32_t *sc, int32_t *e, uint64_t *mv,
+            uint32_t *ln) {
+            return swmi_semiglobal_full_affine_ragged(a, oa, b, ob, m, score_matrix.data(), gap_open, gap_extend, sc, e, mv, ln);
+        },
+        detail::semiglobal_path);
 }
 
 // The reference's 1M-call loop (source.cpp:3074-3082) over arrays of pairs, on every GPU the library is bound to:

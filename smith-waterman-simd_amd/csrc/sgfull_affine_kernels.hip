@@ -10,9 +10,9 @@
 // The best cell is that of sgfull_kernels.hip; the walk goes back from it in state H (diagonal, E, F) and through E / F runs
 // (opening wins a tie), forced along row 0 and column 0.
 //
-// Mapping, ring timing, best-cell rule and code layout: tile_sweep.h, which also holds the constants, the helpers and the
-// launcher.  The sweep and the walk (the (H, F) hand-over, the code word, the walk's states) are
-// tile_sweep_affine_body.inc, shared with local_full_affine_kernels.hip; what depends on the recurrence is the variant's
+// Mapping, ring timing, best-cell rule, code layout and ragged launches (swmi_semiglobal_full_affine_ragged*, DESIGN.md
+// section 27): tile_sweep.h, which also holds the constants, the helpers and the launchers.  The sweep and the walk (the
+// (H, F) hand-over, the code word, the walk's states) are tile_sweep_affine_body.inc, shared with local_full_affine_kernels.hip; what depends on the recurrence is the variant's
 // (sgfull_affine_variant.h, shared with sgfull_long_affine_kernels.hip), and this file tells it.
 //
 // The cell as KEYS: key = value << 6 | tag << 4 | low, |value| < 2^23 (below).  A stored H key has tag 3 and low = 15 - jj
@@ -63,13 +63,20 @@ static_assert(kCols == tile::kCols && kMaxWaves == tile::kMaxWaves && kUnroll ==
               kDelay == tile::kDelay && kRing == tile::kRing && kStageRows == tile::kStageRows);
 }  // namespace written_for
 
-template <bool TB>
+// RAGGED: one TileWork per workgroup (work[blockIdx.x]) names the alignment, and the launch's own shape (fixed_*, move_words)
+// is unused; else `work` is NULL and unread (tile_sweep.h).  The gaps stay the launch's: one call has one pair.  A slot with a
+// zero length is sgfull_kernels.hip's: score 0 at (0, 0), no move, a path of one position.
+template <bool TB, bool RAGGED = false>
 __global__ __launch_bounds__(64 * kMaxWaves) void sg_full_affine_kernel(
-    const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ seq2s, int len1, int len2, SmCols cols, int gap_open,
+    const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ seq2s, int fixed_len1, int fixed_len2, SmCols cols, int gap_open,
     int gap_extend, int32_t *__restrict__ scores, int32_t *__restrict__ ends, unsigned long long *__restrict__ codes,
-    unsigned long long *__restrict__ moves, uint32_t *__restrict__ counts, uint32_t move_words, uint32_t n_trips)
+    unsigned long long *__restrict__ moves, uint32_t *__restrict__ counts, uint32_t move_words, uint32_t fixed_trips,
+    const TileWork *__restrict__ work)
 {
     using V = SgAffine;
+    const TileWork slot = load_slot<RAGGED>(work);
+    const int len1 = RAGGED ? (int)slot.len1 : fixed_len1, len2 = RAGGED ? (int)slot.len2 : fixed_len2;
+    const uint32_t n_trips = RAGGED ? (uint32_t)trips(len1) : fixed_trips;
 #include "tile_sweep_affine_body.inc"
 }
 
@@ -84,6 +91,15 @@ hipError_t launch_sgfull_affine(const uint8_t *d_seq1s, const uint8_t *d_seq2s, 
 {
     return tile::launch<sg_full_affine_kernel<true>, sg_full_affine_kernel<false>>(d_seq1s, d_seq2s, len1, len2, n, sm, d_scores, d_ends, d_codes, d_moves, d_lengths,
         move_words, stream, gap_open, gap_extend);
+}
+
+hipError_t launch_sgfull_affine_ragged(const uint8_t *d_seq1s, const uint8_t *d_seq2s, const TileWork *d_work, size_t n, int waves,
+                                       const int8_t *sm, int gap_open, int gap_extend, int32_t *d_scores, int32_t *d_ends,
+                                       unsigned long long *d_codes, unsigned long long *d_moves, uint32_t *d_lengths,
+                                       hipStream_t stream)
+{
+    return tile::launch_ragged<sg_full_affine_kernel<true, true>, sg_full_affine_kernel<false, true>>(
+        d_seq1s, d_seq2s, d_work, n, waves, sm, d_scores, d_ends, d_codes, d_moves, d_lengths, stream, gap_open, gap_extend);
 }
 
 }  // namespace swmi

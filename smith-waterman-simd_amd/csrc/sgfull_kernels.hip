@@ -6,8 +6,9 @@
 // for i = 1..len1, j = 1..len2.  The best cell is the first cell in row-major order strictly above every earlier one,
 // from 0 at (0,0); the walk goes back from it to (0,0), diagonal before up before left.  DESIGN.md section 13.
 //
-// Mapping, ring timing, best-cell reduction, code layout and staged walk: tile_sweep.h.  The recurrence is the variant's
-// (sgfull_variant.h, shared with sgfull_long_kernels.hip); this file tells it.
+// Mapping, ring timing, best-cell reduction, code layout, staged walk and ragged launches (swmi_semiglobal_full_ragged*,
+// DESIGN.md section 27): tile_sweep.h.  The recurrence is the variant's (sgfull_variant.h, shared with
+// sgfull_long_kernels.hip); this file tells it.
 //
 // The cell as KEYS: key = H << 6 | tag << 4 | (15 - jj) (jj = the column within the lane).  A stored key has tag 3; the
 // candidates come from the neighbours' keys by one add each:
@@ -48,15 +49,22 @@ static_assert(kCols == tile::kCols && kMaxWaves == tile::kMaxWaves && kUnroll ==
               kDelay == tile::kDelay && kRing == tile::kRing && kStageRows == tile::kStageRows);
 }  // namespace written_for
 
-template <bool TB>
+// RAGGED: one TileWork per workgroup (work[blockIdx.x]) names the alignment, and the launch's own shape (fixed_*, move_words)
+// is unused; else `work` is NULL and unread (tile_sweep.h).  The gap stays the launch's: one call has one.  A slot with a
+// zero length is one border whose cells are all <= 0 with (0, 0) first: score 0 at (0, 0), no move, a path of one position.
+template <bool TB, bool RAGGED = false>
 __global__ __launch_bounds__(64 * kMaxWaves) void sg_full_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ seq2s,
-                                                                  int len1, int len2, SmCols cols, int gap, int32_t *__restrict__ scores,
-                                                                  int32_t *__restrict__ ends, uint32_t *__restrict__ codes,
-                                                                  unsigned long long *__restrict__ moves, uint32_t *__restrict__ counts,
-                                                                  uint32_t move_words, uint32_t n_trips)
+                                                                  int fixed_len1, int fixed_len2, SmCols cols, int gap,
+                                                                  int32_t *__restrict__ scores, int32_t *__restrict__ ends,
+                                                                  uint32_t *__restrict__ codes, unsigned long long *__restrict__ moves,
+                                                                  uint32_t *__restrict__ counts, uint32_t move_words, uint32_t fixed_trips,
+                                                                  const TileWork *__restrict__ work)
 {
     using V = SgLinear;
     const V::Gaps gaps{gap};
+    const TileWork slot = load_slot<RAGGED>(work);
+    const int len1 = RAGGED ? (int)slot.len1 : fixed_len1, len2 = RAGGED ? (int)slot.len2 : fixed_len2;
+    const uint32_t n_trips = RAGGED ? (uint32_t)trips(len1) : fixed_trips;
 #include "tile_sweep_body.inc"
 }
 
@@ -74,6 +82,16 @@ hipError_t launch_sgfull(const uint8_t *d_seq1s, const uint8_t *d_seq2s, int len
 {
     return tile::launch<sg_full_kernel<true>, sg_full_kernel<false>>(d_seq1s, d_seq2s, len1, len2, n, sm, d_scores, d_ends, d_codes,
                                                                      d_moves, d_lengths, move_words, stream, gap);
+}
+
+int sgfull_ragged_waves(int len1, int len2) { return len1 > 0 && len2 > 0 ? tile::waves(len2) : 1; }
+
+hipError_t launch_sgfull_ragged(const uint8_t *d_seq1s, const uint8_t *d_seq2s, const TileWork *d_work, size_t n, int waves,
+                                const int8_t *sm, int gap, int32_t *d_scores, int32_t *d_ends, uint32_t *d_codes,
+                                unsigned long long *d_moves, uint32_t *d_lengths, hipStream_t stream)
+{
+    return tile::launch_ragged<sg_full_kernel<true, true>, sg_full_kernel<false, true>>(d_seq1s, d_seq2s, d_work, n, waves, sm, d_scores,
+                                                                                        d_ends, d_codes, d_moves, d_lengths, stream, gap);
 }
 
 }  // namespace swmi

@@ -316,6 +316,10 @@ bool local_full_ragged_plan_check(const uint64_t *seq1_offsets, const uint64_t *
 // global_full_ragged_api.cpp: the same for a ragged batch of the global aligners (one planner, tile_ragged_plan.h)
 bool global_full_ragged_plan_check(const uint64_t *seq1_offsets, const uint64_t *seq2_offsets, size_t n, bool affine, bool tb,
                                    std::vector<size_t> *slice_sizes, std::vector<size_t> *slice_bytes);
+// sgfull_ragged_api.cpp: the same for a ragged batch of the exact semi-global aligners (the same planner; its bytes count five
+// result dwords per alignment, an upper bound for this family)
+bool semiglobal_full_ragged_plan_check(const uint64_t *seq1_offsets, const uint64_t *seq2_offsets, size_t n, bool affine, bool tb,
+                                       std::vector<size_t> *slice_sizes, std::vector<size_t> *slice_bytes);
 // the (i, j) list from (0, 0) of a semi-global walk's moves, for lengths up to max_length: the body of swmi_semiglobal_expand_moves
 // (swmi_api.cpp) and of swmi_semiglobal_long_expand_moves (semiglobal_long_api.cpp)
 int semiglobal_expand_moves(uint32_t max_length, const uint64_t *moves, uint32_t length, int32_t *traceback, size_t cap);

@@ -266,3 +266,17 @@ hipError_t launch_global_full_affine_ragged(const uint8_t *d_seq1s, const uint8_
                                             int32_t *d_scores, int32_t *d_ends, unsigned long long *d_codes,
                                             unsigned long long *d_moves, uint32_t *d_steps, hipStream_t stream);
 }  // namespace swmi
+
+namespace swmi {
+// The ragged launches of the two exact semi-global aligners: launch_local_full_ragged's slots, wave
+// counts and buffers, with d_ends two int32 per alignment and d_lengths the path's cells.  A slot with a zero length runs in a
+// workgroup of one wavefront and writes score 0, end cell (0, 0) and length 1: it takes no code words and writes no move word.
+int sgfull_ragged_waves(int len1, int len2);
+hipError_t launch_sgfull_ragged(const uint8_t *d_seq1s, const uint8_t *d_seq2s, const TileWork *d_work, size_t n, int waves,
+                                const int8_t *sm, int gap, int32_t *d_scores, int32_t *d_ends, uint32_t *d_codes,
+                                unsigned long long *d_moves, uint32_t *d_lengths, hipStream_t stream);
+hipError_t launch_sgfull_affine_ragged(const uint8_t *d_seq1s, const uint8_t *d_seq2s, const TileWork *d_work, size_t n, int waves,
+                                       const int8_t *sm, int gap_open, int gap_extend, int32_t *d_scores, int32_t *d_ends,
+                                       unsigned long long *d_codes, unsigned long long *d_moves, uint32_t *d_lengths,
+                                       hipStream_t stream);
+}  // namespace swmi

@@ -1,12 +1,13 @@
 // tile_ragged_plan.h -- the plan of a batch of mixed (len1, len2) for the any-length aligners on the wavefront-tiled sweep:
-// what local_full_ragged_api.cpp and global_full_ragged_api.cpp (section 22) share.  A batch becomes a
+// what local_full_ragged_api.cpp, global_full_ragged_api.cpp (section 22) and sgfull_ragged_api.cpp
+// (section 27) share.  A batch becomes a
 // TilePlan: a RaggedPlan (swmi_host.h) whose slices are cut in caller order within the fixed-length aligner's budget, with one
 // TileWork per alignment and, per slice, where each wave count's slots start.  Inside a slice the slots are ordered by wave
 // count descending (one launch serves one wave count), then len1 descending (the hardware starts workgroups in order, and
 // longest first evens out the tail), then caller order.  The plan then runs through the slice pipeline of swmi_table.cpp.
 //
 // A header and not a source file on purpose: the fake-GPU tests link an exact list of sources, and this one names no
-// launcher.  What differs between the two families -- the launchers, the wave count of a slot, the code words of an
+// launcher.  What differs between the three families -- the launchers, the wave count of a slot, the code words of an
 // alignment and the slice budget -- reaches the planner as a TileFamily of function pointers that each family's file fills.
 #pragma once
 #include "swmi_host.h"
@@ -20,8 +21,9 @@ namespace tile_plan {
 
 constexpr int kMaxWaves = 16;            // wave counts of a slot: 1 .. 16
 constexpr size_t kMaxLen = 16384;        // the largest length of either sequence
-static_assert(kMaxLen == SWMI_LOCAL_FULL_MAX_LEN && kMaxLen == SWMI_GLOBAL_FULL_MAX_LEN);
-static_assert(SWMI_GLOBAL_FULL_MOVE_WORDS(5, 70) == SWMI_LOCAL_FULL_MOVE_WORDS(5, 70));   // one move layout for both families
+static_assert(kMaxLen == SWMI_LOCAL_FULL_MAX_LEN && kMaxLen == SWMI_GLOBAL_FULL_MAX_LEN && kMaxLen == SWMI_SGFULL_MAX_LEN);
+static_assert(SWMI_GLOBAL_FULL_MOVE_WORDS(5, 70) == SWMI_LOCAL_FULL_MOVE_WORDS(5, 70));   // one move layout for all three families
+static_assert(SWMI_SGFULL_MOVE_WORDS(5, 70) == SWMI_LOCAL_FULL_MOVE_WORDS(5, 70));
 
 struct TileFamily {
     RaggedLaunch launch;                                         // the launches of one slice

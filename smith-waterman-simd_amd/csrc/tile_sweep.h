@@ -81,16 +81,17 @@
 // linear body reads row i's from the finished row: the body says why.  Thread 0 packs the two border cells before the sweep
 // and keeps them in VGPRs.  The last row, the corner, the reduction and the walk's tail are the linear body's.
 //
-// Ragged launches (the two local and the two global kernels; DESIGN.md sections 19 and 22): a kernel with a template parameter RAGGED has a last
+// Ragged launches (the two local, the two global and the two semi-global kernels; DESIGN.md sections 19, 22 and 27): a kernel with a template parameter RAGGED has a last
 // parameter `work` (NULL and unread in a fixed launch; last, so that every other argument lies where it did), and with RAGGED
 // takes its alignment from one TileWork per workgroup, `slot` = work[blockIdx.x], instead of from k = blockIdx.x and the
 // launch's one (len1, len2): its sequences, lengths, trips, code block, move row and result index.  The slot is loaded through an address
 // that is uniform by construction, so all of it stays in SGPRs.  Both bodies read the names RAGGED and slot; a kernel without
-// a ragged form (the semi-global pair) finds tile::RAGGED = false and an empty tile::slot below, and a kernel with one shadows both.  One
+// a ragged form (the striped kernels) finds tile::RAGGED = false and an empty tile::slot below, and a kernel with one shadows both.  One
 // launch serves one wave count: every slot of a launch has W = blockDim.x >> 6, so no wave ever leaves before the
 // workgroup's last barrier -- except that a slot with a zero length, which runs in a W = 1 launch, returns as a whole
 // workgroup, on a uniform test, before the first barrier and before any load from either sequence.  What it writes first is
-// the local aligners' "score 0", or with the end rule the closed form of end_rule_zero_length below.
+// "score 0 at (0, 0)" with the count that the variant's walk would write there -- the local aligners' 0 moves, the semi-global
+// pair's path of 1 position -- or with the end rule the closed form of end_rule_zero_length below.
 //
 // Why the bodies are includes, and why there are two: this compiler optimises a function on its own before it inlines it.
 // A body behind a call -- even the unchanged kernel moved into a forceinline function -- is optimised twice and came out
@@ -230,6 +231,12 @@ __device__ __forceinline__ int opaque_lane(int v)
     if constexpr (ON) asm volatile("" : "+v"(v));
     return v;
 }
+
+// Whether the thread is lane 0 of its wavefront, made of no register that lives anywhere else.  The zero-length arm of a
+// ragged semi-global kernel elects its writer with it (the slot's workgroup is one wavefront, so lane 0 is thread 0).  The
+// compiler places that arm behind the sweep in the structured control flow; elected by threadIdx.x, the arm kept the thread id
+// in a VGPR across the whole sweep, which made the affine ends-only kernel one VGPR larger than its fixed sibling.
+__device__ __forceinline__ bool first_lane() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0u; }
 
 // the slot of a ragged launch's workgroup; nothing is loaded for a fixed launch
 template <bool RAGGED>

@@ -38,12 +38,13 @@
                 // the end rule's closed form of one border (tile_sweep.h); an affine gap run of L >= 1 cells costs open + (L - 1) extend
                 end_rule_zero_length<TB>(len1, len2, free_ends, gap_open + (len1 + len2 - 1) * gap_extend, k, scores, ends,
                                          TB ? moves + (size_t)slot.move_base : nullptr, counts);
-            } else if (tid == 0) {
+            } else if (V::kWalkStops ? tid == 0 : first_lane()) {   // (first_lane: tile_sweep.h says why)
                 scores[k] = 0;
                 ends[V::kEnds * k + 0] = 0;
                 ends[V::kEnds * k + 1] = 0;
                 for (int x = 2; x < V::kEnds; ++x) ends[V::kEnds * k + x] = TB ? 0 : -1;
-                if constexpr (TB) counts[k] = 0;
+                // the count the variant's walk would write from (0, 0) (tile_sweep_body.inc): its moves, or the path's cells
+                if constexpr (TB) counts[k] = V::kWalkStops ? 0u : 1u;
             }
             return;
         }

@@ -22,12 +22,14 @@
                 // the end rule's closed form of one border (tile_sweep.h); a linear gap run of L cells costs L gap
                 end_rule_zero_length<TB>(len1, len2, free_ends, (len1 + len2) * gaps.gap, k, scores, ends,
                                          TB ? moves + (size_t)slot.move_base : nullptr, counts);
-            } else if (tid == 0) {
+            } else if (V::kWalkStops ? tid == 0 : first_lane()) {   // (first_lane: tile_sweep.h says why)
                 scores[k] = 0;
                 ends[V::kEnds * k + 0] = 0;
                 ends[V::kEnds * k + 1] = 0;
                 for (int x = 2; x < V::kEnds; ++x) ends[V::kEnds * k + x] = TB ? 0 : -1;
-                if constexpr (TB) counts[k] = 0;
+                // the count the variant's walk would write from (0, 0): its moves (none), or for a walk that no code stops the
+                // path's cells, moves + 1 (the one position (0, 0))
+                if constexpr (TB) counts[k] = V::kWalkStops ? 0u : 1u;
             }
             return;
         }

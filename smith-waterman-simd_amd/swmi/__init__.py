@@ -149,7 +149,9 @@ def load():
             ("swmi_semiglobal_long_affine", "swmi_semiglobal_long_affine_time_device", "swmi_semiglobal_long_affine_slices_for",
              two_lens, [ci, ci]),
             ("swmi_global_full_ragged", None, None, ragged2, [i8, cu]),
-            ("swmi_global_full_affine_ragged", None, None, ragged2, [ci, ci, cu])):
+            ("swmi_global_full_affine_ragged", None, None, ragged2, [ci, ci, cu]),
+            ("swmi_semiglobal_full_ragged", None, None, ragged2, [i8]),
+            ("swmi_semiglobal_full_affine_ragged", None, None, ragged2, [ci, ci])):
         args = shape + [vp] + gap + [vp, vp, vp, vp]
         getattr(lib, host).argtypes = args
         getattr(lib, host + "_device").argtypes = args + [vp]
@@ -169,6 +171,8 @@ def load():
     lib.swmi_local_full_ragged_slices_for.restype = sz
     lib.swmi_global_full_ragged_slices_for.argtypes = [vp, vp, sz, ci, ci, vp, sz]
     lib.swmi_global_full_ragged_slices_for.restype = sz
+    lib.swmi_semiglobal_full_ragged_slices_for.argtypes = [vp, vp, sz, ci, ci, vp, sz]
+    lib.swmi_semiglobal_full_ragged_slices_for.restype = sz
     _lib = lib
     return lib
 
@@ -1201,3 +1205,4 @@ from . import global_ragged    # noqa: E402  (the global aligners on mixed-shape
 from . import global_long      # noqa: E402  (the global aligners for lengths up to 65536, likewise a submodule)
 from . import local_long       # noqa: E402  (the local aligners for lengths up to 65536, likewise a submodule)
 from . import semiglobal_long  # noqa: E402  (the exact semi-global aligners for lengths up to 65536, likewise a submodule)
+from . import semiglobal_ragged  # noqa: E402  (the exact semi-global aligners on mixed-shape batches, likewise a submodule)
