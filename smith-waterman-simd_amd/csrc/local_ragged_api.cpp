@@ -2,8 +2,9 @@
 // swmi_local_align_affine_ragged*, include/swmi.h).  A batch becomes a RaggedPlan (swmi_host.h): slices
 // cut in caller order within the aligner's budget, and per slice one LocalWork per alignment, longest first, so that the 4
 // alignments of a wavefront and the 16 of a workgroup have similar lengths.  The plan then runs through the slice pipeline of
-// swmi_table.cpp, on the fixed-length entries' Table (table_api.cpp).  This file is the only host source that names the ragged
-// launchers, so that the fake-GPU build of the fixed-length entries (tests/test_table_host_fake.py) links without them.
+// swmi_table.cpp, on the fixed-length entries' Table (table_api.cpp: family_table).  The any-length aligners' mixed-shape
+// batches have a planner and slots of their own, tile_ragged_api.cpp.  This file is the only host source that names the two
+// ragged 128-column launchers, which tests/native/ragged_host_fake.cpp stands in for.
 #include "swmi_host.h"
 
 #include <algorithm>

@@ -139,14 +139,12 @@ struct Workspace {
     size_t bytes = 0;
 };
 
-// The aligners that run through the slice pipeline of swmi_table.cpp: one FamilyRow each, the first kTableApiFamilies in
-// table_api.cpp, the two long local ones in local_long_api.cpp, the two long semi-global ones in semiglobal_long_api.cpp
+// The aligners that run through the slice pipeline of swmi_table.cpp: one row of table_api.cpp's kRows each, in this order
 enum TableFamily {
     kTableLocal, kTableSgfull, kTableLocalAffine, kTableSgfullAffine, kTableLocalFull, kTableLocalFullAffine, kTableGlobalFull,
     kTableGlobalFullAffine, kTableGlobalLong, kTableGlobalLongAffine, kTableLocalLong, kTableLocalLongAffine, kTableSemiglobalLong,
     kTableSemiglobalLongAffine, kTableFamilies
 };
-constexpr int kTableApiFamilies = kTableLocalLong;     // the families whose rows table_api.cpp holds
 
 // Everything the library owns on ONE bound GPU.  A GPU may be bound twice (swmi_init_devices({0, 0})): two contexts,
 // two stream sets, the same hardware.
@@ -215,10 +213,9 @@ using RaggedLaunch = hipError_t (*)(const Table &t, size_t slice, const uint8_t 
                                     int32_t *scores, int32_t *ends, uint32_t *codes, unsigned long long *moves, uint32_t *counts,
                                     hipStream_t st);
 // A batch with lengths of its own per alignment: the local aligners' with a seq1 length each (local_ragged_api.cpp), the
-// any-length local and global aligners' with a seq1 and a seq2 length each (local_full_ragged_api.cpp,
-// global_full_ragged_api.cpp).  Its slices, contiguous in caller order, and one slot per alignment (LocalWork or TileWork:
-// the pipeline copies slots as bytes and hands them to `launch`), slice-relative, in the order the plan's owner gave the
-// slots of each slice.
+// any-length local, global and exact semi-global aligners' with a seq1 and a seq2 length each (tile_ragged_api.cpp).  Its
+// slices, contiguous in caller order, and one slot per alignment (LocalWork or TileWork: the pipeline copies slots as bytes
+// and hands them to `launch`), slice-relative, in the order the plan's owner gave the slots of each slice.
 struct RaggedPlan {
     RaggedLaunch launch;
     const uint64_t *seq1_offsets;               // the caller's n + 1
@@ -245,9 +242,9 @@ struct Table {
     int gap, gap_extend;        // gap_extend: the affine aligner's (gap is then the open cost)
     const RaggedPlan *plan = nullptr;   // a ragged batch: len1, code_words and move_words unused, slices as the plan says
     unsigned free_ends = 0;             // the global aligners' mask of SWMI_FREE_*, which their slice launchers read
-    // The striped aligners' carry (FamilyRow::carry): dwords per alignment of device scratch that a slice's kernel needs
-    // with or without a traceback, counted in a slice's bytes; the pipeline allocates it beside the codes and hands the launcher
-    // a copy of the Table whose `carry` points at the slice's (NULL where carry_words is 0).
+    // The striped aligners' carry (table_api.cpp, FamilyRow::carry): dwords per alignment of device scratch that a slice's kernel
+    // needs with or without a traceback, counted in a slice's bytes; the pipeline allocates it beside the codes and hands the
+    // launcher a copy of the Table whose `carry` points at the slice's (NULL where carry_words is 0).
     size_t carry_words = 0;
     int32_t *carry = nullptr;
 };
@@ -262,66 +259,19 @@ int table_host(const Table &t, const char *entry, const uint8_t *seq1s, const ui
 int table_time_device(const Table &t, const char *entry, const void *d_seq1s, const void *d_seq2s, size_t n, void *d_scores,
                       void *d_ends, void *d_moves, void *d_counts, void *stream, int iters, float *avg_ms);
 int table_check_timer(size_t n, int iters, const float *avg_ms);   // what the timers check before their first call
-// ---- one aligner family as data, and one body per kind of entry (table_api.cpp) ----
-// What differs between the aligners.  Code sizes are in the Table's unit, dwords: twice the affine launchers' qwords.
-struct FamilyRow {
-    TableLaunch launch;
-    TableFamily family;         // Table::state: whose device buffers a call uses
-    size_t max_len;             // per axis
-    bool fixed_len2;            // len2 is SWMI_LOCAL_SEQ2_LEN, whatever the caller's
-    const char *count;          // Table::count, and
-    uint32_t count_offset;      //   Table::count_offset
-    size_t ends;                // int32 of `ends` per alignment
-    size_t (*code_words)(size_t len1, size_t len2);
-    size_t (*move_words)(size_t len1, size_t len2);
-    // A traceback slice holds as many alignments as `budget` of `budget_as`'s maximum shape (0: kTableSliceBytes); budget_as is
-    // one of table_api.cpp's families.  256 of 16384 x 16384 (16.1 GiB of 2-bit codes, 32.1 GiB of 4-bit ones) are one
-    // workgroup per alignment for every CU of an MI355X; 4096 of len1 = 16384 (4.1 GiB) give every CU a workgroup of 16
-    // alignments.  A striped pair takes its fixed-length pair's budget, and counts its carry in a slice.
-    size_t budget;
-    TableFamily budget_as;
-    bool affine;                // gap_extend is read; gaps within [0, 127] instead of check_params
-    bool mask;                  // free_ends is read
-    bool carry;                 // column stripes: a carry of len1 dwords (affine: 2 len1) per alignment where len2 > 16384
-    bool domain;                // the unfloored striped aligners' domain rule, P (len1 + len2) <= 2^23 (include/swmi.h)
-    bool timer_first;           // the timer checks its own arguments (and binds the context) before the call's
-};
-// the arguments of one call that the families read
-struct Call {
-    size_t len1, len2;          // len2 = SWMI_LOCAL_SEQ2_LEN from the two local families' entries
-    const int8_t *sm;
-    int gap, gap_extend;        // gap_extend 0 from the linear families' entries
-    unsigned free_ends;         // 0 from the families without a mask
-};
-// in the order include/swmi.h gives: the lengths, the mask, the matrix and the gaps, the domain rule
-int family_check(const FamilyRow &r, const Call &c);
-// The Table of one call of a family, from its row (len2 = SWMI_LOCAL_SEQ2_LEN for the two local families; gap_extend is read
-// by the affine families and free_ends by those with a mask); by TableFamily for table_api.cpp's own families
-Table family_table(const FamilyRow &r, size_t len1, size_t len2, const int8_t *sm, int gap, int gap_extend, unsigned free_ends);
+// table_api.cpp: the Table of one call of a fixed-shape family, from its row of data (len2 = SWMI_LOCAL_SEQ2_LEN for the two
+// local families; gap_extend is read by the affine families and free_ends by those with a mask).  The mixed-shape entries
+// run on the fixed-length family's Table: its workspaces and its slice budget.
 Table family_table(TableFamily f, size_t len1, size_t len2, const int8_t *sm, int gap, int gap_extend, unsigned free_ends);
-size_t family_slices_for(const FamilyRow &r, size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap);
-int family_device(const FamilyRow &r, const Call &c, const void *d_seq1s, const void *d_seq2s, size_t n, void *d_scores, void *d_ends,
-                  void *d_moves, void *d_counts, void *stream);
-int family_host(const FamilyRow &r, const char *entry, const Call &c, const uint8_t *seq1s, const uint8_t *seq2s, size_t n,
-                int32_t *scores, int32_t *ends, uint64_t *moves, uint32_t *counts);
-int family_time_device(const FamilyRow &r, const char *entry, const Call &c, const void *d_seq1s, const void *d_seq2s, size_t n,
-                       void *d_scores, void *d_ends, void *d_moves, void *d_counts, void *stream, int iters, float *avg_ms);
-// the reference's list of positions from a walk's moves, for end cells up to (max_i, max_j): the body of the *_expand_moves entries
-int family_expand_moves(int32_t max_i, int32_t max_j, const uint64_t *moves, uint32_t steps, int32_t end_i, int32_t end_j,
-                        int32_t *positions, size_t cap);
-// local_full_ragged_api.cpp: the plan of a ragged any-length batch alone (no device), for tests of its arithmetic -- per slice
-// its alignments and device bytes; true when every code base equals the 64-bit running sum of the code words before it
-bool local_full_ragged_plan_check(const uint64_t *seq1_offsets, const uint64_t *seq2_offsets, size_t n, bool affine, bool tb,
-                                  std::vector<size_t> *slice_sizes, std::vector<size_t> *slice_bytes);
-// global_full_ragged_api.cpp: the same for a ragged batch of the global aligners (one planner, tile_ragged_plan.h)
-bool global_full_ragged_plan_check(const uint64_t *seq1_offsets, const uint64_t *seq2_offsets, size_t n, bool affine, bool tb,
-                                   std::vector<size_t> *slice_sizes, std::vector<size_t> *slice_bytes);
-// sgfull_ragged_api.cpp: the same for a ragged batch of the exact semi-global aligners (the same planner; its bytes count five
-// result dwords per alignment, an upper bound for this family)
-bool semiglobal_full_ragged_plan_check(const uint64_t *seq1_offsets, const uint64_t *seq2_offsets, size_t n, bool affine, bool tb,
-                                       std::vector<size_t> *slice_sizes, std::vector<size_t> *slice_bytes);
+// tile_ragged_api.cpp: the three kinds of aligner on the wavefront-tiled sweep that take a batch of mixed (len1, len2), and the
+// plan of such a batch alone (no device), for tests of its arithmetic -- per slice its alignments and device bytes; true when
+// every code base equals the 64-bit running sum of the code words before it.  (The bytes count five result dwords per
+// alignment, an upper bound for the semi-global kind.)
+enum TileKind { kTileLocal, kTileGlobal, kTileSemiglobal, kTileKinds };
+bool tile_ragged_plan_check(TileKind kind, const uint64_t *seq1_offsets, const uint64_t *seq2_offsets, size_t n, bool affine, bool tb,
+                            std::vector<size_t> *slice_sizes, std::vector<size_t> *slice_bytes);
 // the (i, j) list from (0, 0) of a semi-global walk's moves, for lengths up to max_length: the body of swmi_semiglobal_expand_moves
-// (swmi_api.cpp) and of swmi_semiglobal_long_expand_moves (semiglobal_long_api.cpp)
+// (swmi_api.cpp) and of swmi_semiglobal_long_expand_moves (table_api.cpp)
 int semiglobal_expand_moves(uint32_t max_length, const uint64_t *moves, uint32_t length, int32_t *traceback, size_t cap);
 // Free one aligner's device buffers on the current GPU (synchronises the device first): the body of the *_release_workspaces entries
 int table_release_workspaces(TableFamily family);

@@ -175,7 +175,7 @@ struct TileWork {
 // at once) in a workgroup of one wavefront.
 int local_full_ragged_waves(int len1, int len2);
 // n slots of d_work (device memory), ALL of wave count `waves`, one workgroup of that many wavefronts each: results at
-// d_scores[work.k] etc.  The slice launcher calls it once per wave count present (local_full_ragged_api.cpp).
+// d_scores[work.k] etc.  The slice launcher calls it once per wave count present (tile_ragged_api.cpp).
 hipError_t launch_local_full_ragged(const uint8_t *d_seq1s, const uint8_t *d_seq2s, const TileWork *d_work, size_t n, int waves,
                                     const int8_t *sm, int gap, int32_t *d_scores, int32_t *d_ends, uint32_t *d_codes,
                                     unsigned long long *d_moves, uint32_t *d_steps, hipStream_t stream);

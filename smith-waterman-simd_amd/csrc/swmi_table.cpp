@@ -1,7 +1,7 @@
 // swmi_table.cpp -- the one slice pipeline of the aligners that fill the whole table, write codes and walk them: host
 // entry, device entry, timer, slice arithmetic and the per-family device buffers (DESIGN.md sections 12 to 23).  What
 // differs between the aligners is data (struct Table, swmi_host.h), which table_api.cpp builds per family and the ragged
-// api files extend with a plan.  The buffers hang off Context::table_states, which destroy_context (swmi_api.cpp) drops at
+// api files (local_ragged_api.cpp, tile_ragged_api.cpp) extend with a plan.  The buffers hang off Context::table_states, which destroy_context (swmi_api.cpp) drops at
 // swmi_shutdown: that file names no symbol of this one, so the host-only builds of swmi_api.cpp / swmi_multi.cpp
 // (tests/test_multi_fake.py, tests/test_sanitizers.py) link without the table code -- and this file names no launcher.
 #include "swmi_host.h"

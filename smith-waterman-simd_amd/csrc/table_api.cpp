@@ -1,9 +1,9 @@
-// table_api.cpp -- C entries of the ten fixed-shape aligners that run through the slice pipeline of swmi_table.cpp (struct Table,
-// swmi_host.h; include/swmi.h, DESIGN.md sections 12 to 14, 16 to 18, 20, 21 and 23): one row of data per family, one body for the
-// argument check, the Table and each of the five kinds of entry, and one explicit extern "C" definition per exported name.
-// The bodies are declared in swmi_host.h (family_*) and take a FamilyRow, so that local_long_api.cpp, which holds the two long
-// local families, runs through them too.  This file's name lies outside csrc/swmi_*.cpp, so that the host-only builds of
-// swmi_api.cpp + swmi_multi.cpp stay free of the table kernels.
+// table_api.cpp -- C entries of the fourteen fixed-shape aligners that run through the slice pipeline of swmi_table.cpp (struct
+// Table, swmi_host.h; include/swmi.h, DESIGN.md sections 12 to 14, 16 to 18, 20, 21, 23, 25 and 26): one row of data per family
+// (kRows, in the order of TableFamily), one body for the argument check, the Table and each of the five kinds of entry, and
+// one explicit extern "C" definition per exported name.  Everything but family_table, which the mixed-shape entries
+// (local_ragged_api.cpp, tile_ragged_api.cpp) call for a fixed-length family's Table, is private to this file.  Its name lies
+// outside csrc/swmi_*.cpp, so that the host-only builds of swmi_api.cpp + swmi_multi.cpp stay free of the table kernels.
 #include "swmi_host.h"
 
 #include <algorithm>
@@ -13,7 +13,9 @@ namespace swmi {
 namespace host {
 namespace {
 
-constexpr size_t kStripe = SWMI_GLOBAL_FULL_MAX_LEN;      // columns of one stripe = what the fixed-length global kernels reach
+// columns of one stripe = what the fixed-length kernels of all three striped kinds reach
+constexpr size_t kStripe = SWMI_GLOBAL_FULL_MAX_LEN;
+static_assert(kStripe == SWMI_LOCAL_FULL_MAX_LEN && kStripe == SWMI_SGFULL_MAX_LEN);
 
 // ---- how a slice of each family launches ----
 #define SLICE_ARGS const Table &t, const uint8_t *s1, const uint8_t *s2, size_t n, int32_t *scores, int32_t *ends, uint32_t *codes, \
@@ -59,67 +61,157 @@ hipError_t launch_global_full_affine_slice(SLICE_ARGS)
     return swmi::launch_global_full_affine(s1, s2, (int)t.len1, (int)t.len2, n, t.sm, t.gap, t.gap_extend, t.free_ends, scores, ends,
                                            qwords(codes), moves, counts, t.move_words, st);
 }
-// A shape that the fixed-length kernel reaches goes to it: every field is then swmi_global_full's by construction.
+// The six striped families: a shape that the fixed-length kernel reaches goes to it, and every field is then the fixed-length
+// entry's by construction.
+bool fits_stripe(const Table &t) { return t.len1 <= kStripe && t.len2 <= kStripe; }
 hipError_t launch_global_long_slice(SLICE_ARGS)
 {
-    if (t.len1 <= kStripe && t.len2 <= kStripe) return launch_global_full_slice(t, s1, s2, n, scores, ends, codes, moves, counts, st);
+    if (fits_stripe(t)) return launch_global_full_slice(t, s1, s2, n, scores, ends, codes, moves, counts, st);
     return swmi::launch_global_long(s1, s2, (int)t.len1, (int)t.len2, n, t.sm, t.gap, t.free_ends, scores, ends, codes, moves, counts,
                                     t.move_words, t.carry, st);
 }
 hipError_t launch_global_long_affine_slice(SLICE_ARGS)
 {
-    if (t.len1 <= kStripe && t.len2 <= kStripe)
-        return launch_global_full_affine_slice(t, s1, s2, n, scores, ends, codes, moves, counts, st);
+    if (fits_stripe(t)) return launch_global_full_affine_slice(t, s1, s2, n, scores, ends, codes, moves, counts, st);
     return swmi::launch_global_long_affine(s1, s2, (int)t.len1, (int)t.len2, n, t.sm, t.gap, t.gap_extend, t.free_ends, scores, ends,
                                            qwords(codes), moves, counts, t.move_words, t.carry, st);
+}
+hipError_t launch_local_long_slice(SLICE_ARGS)
+{
+    if (fits_stripe(t)) return launch_local_full_slice(t, s1, s2, n, scores, ends, codes, moves, counts, st);
+    return swmi::launch_local_long(s1, s2, (int)t.len1, (int)t.len2, n, t.sm, t.gap, scores, ends, codes, moves, counts, t.move_words,
+                                   t.carry, st);
+}
+hipError_t launch_local_long_affine_slice(SLICE_ARGS)
+{
+    if (fits_stripe(t)) return launch_local_full_affine_slice(t, s1, s2, n, scores, ends, codes, moves, counts, st);
+    return swmi::launch_local_long_affine(s1, s2, (int)t.len1, (int)t.len2, n, t.sm, t.gap, t.gap_extend, scores, ends, qwords(codes),
+                                          moves, counts, t.move_words, t.carry, st);
+}
+hipError_t launch_semiglobal_long_slice(SLICE_ARGS)
+{
+    if (fits_stripe(t)) return launch_sgfull_slice(t, s1, s2, n, scores, ends, codes, moves, counts, st);
+    return swmi::launch_sgfull_long(s1, s2, (int)t.len1, (int)t.len2, n, t.sm, t.gap, scores, ends, codes, moves, counts, t.move_words,
+                                    t.carry, st);
+}
+hipError_t launch_semiglobal_long_affine_slice(SLICE_ARGS)
+{
+    if (fits_stripe(t)) return launch_sgfull_affine_slice(t, s1, s2, n, scores, ends, codes, moves, counts, st);
+    return swmi::launch_sgfull_long_affine(s1, s2, (int)t.len1, (int)t.len2, n, t.sm, t.gap, t.gap_extend, scores, ends, qwords(codes),
+                                           moves, counts, t.move_words, t.carry, st);
 }
 #undef SLICE_ARGS
 
 // ---- the families ----
-// One FamilyRow (swmi_host.h) each; local_long_api.cpp holds the two long local families' rows.
-constexpr FamilyRow kRows[kTableApiFamilies] = {
+// What differs between the aligners.  Code sizes are in the Table's unit, dwords: twice the affine launchers' qwords.
+struct FamilyRow {
+    TableLaunch launch;
+    TableFamily family;         // Table::state: whose device buffers a call uses; the row's own index in kRows
+    size_t max_len;             // per axis
+    bool fixed_len2;            // len2 is SWMI_LOCAL_SEQ2_LEN, whatever the caller's
+    const char *count;          // Table::count, and
+    uint32_t count_offset;      //   Table::count_offset
+    size_t ends;                // int32 of `ends` per alignment
+    size_t (*code_words)(size_t len1, size_t len2);
+    size_t (*move_words)(size_t len1, size_t len2);
+    // A traceback slice holds as many alignments as `budget` of `budget_as`'s maximum shape (0: kTableSliceBytes).  256 of
+    // 16384 x 16384 (16.1 GiB of 2-bit codes, 32.1 GiB of 4-bit ones) are one workgroup per alignment for every CU of an
+    // MI355X; 4096 of len1 = 16384 (4.1 GiB) give every CU a workgroup of 16 alignments.  A striped pair takes its
+    // fixed-length pair's budget, and counts its carry in a slice: on a shape that both reach the code sizes are equal
+    // (tile::code_words), so the slices are the fixed-length entries'.
+    size_t budget;
+    TableFamily budget_as;
+    bool affine;                // gap_extend is read; gaps within [0, 127] instead of check_params
+    bool mask;                  // free_ends is read
+    bool carry;                 // column stripes: a carry of len1 dwords (affine: 2 len1) per alignment where len2 > 16384
+    bool domain;                // the unfloored striped aligners' domain rule, P (len1 + len2) <= 2^23 (include/swmi.h); the long
+                                //   local pair has none: 0 <= H < 2^23 whatever the parameters (local_long_kernels.hip)
+    bool timer_first;           // the timer checks its own arguments (and binds the context) before the call's
+    bool timer_pair;            // the timer refuses a traceback given by half where the host and device entries do: behind the
+                                //   call's check and before a device is looked for (the others leave it to table_time_device)
+};
+constexpr FamilyRow kRows[] = {
     /* kTableLocal */
     {launch_local_slice, kTableLocal, SWMI_LOCAL_MAX_LEN, true, "steps", 0, 4, [](size_t a, size_t) { return swmi::local_code_words((int)a); },
-     [](size_t a, size_t) { return size_t(SWMI_LOCAL_MOVE_WORDS(a)); }, 0, kTableLocal, false, false, false, false, true},
+     [](size_t a, size_t) { return size_t(SWMI_LOCAL_MOVE_WORDS(a)); }, 0, kTableLocal, false, false, false, false, true, false},
     /* kTableSgfull */
     {launch_sgfull_slice, kTableSgfull, SWMI_SGFULL_MAX_LEN, false, "lengths", 1, 2,
      [](size_t a, size_t b) { return swmi::sgfull_code_words((int)a, (int)b); },
-     [](size_t a, size_t b) { return size_t(SWMI_SGFULL_MOVE_WORDS(a, b)); }, 256, kTableSgfull, false, false, false, false, true},
+     [](size_t a, size_t b) { return size_t(SWMI_SGFULL_MOVE_WORDS(a, b)); }, 256, kTableSgfull, false, false, false, false, true, false},
     /* kTableLocalAffine */
     {launch_local_affine_slice, kTableLocalAffine, SWMI_LOCAL_MAX_LEN, true, "steps", 0, 4,
      [](size_t a, size_t) { return swmi::local_affine_code_words((int)a); },
-     [](size_t a, size_t) { return size_t(SWMI_LOCAL_MOVE_WORDS(a)); }, 4096, kTableLocalAffine, true, false, false, false, true},
+     [](size_t a, size_t) { return size_t(SWMI_LOCAL_MOVE_WORDS(a)); }, 4096, kTableLocalAffine, true, false, false, false, true, false},
     /* kTableSgfullAffine */
     {launch_sgfull_affine_slice, kTableSgfullAffine, SWMI_SGFULL_MAX_LEN, false, "lengths", 1, 2,
      [](size_t a, size_t b) { return 2 * swmi::sgfull_affine_code_qwords((int)a, (int)b); },
-     [](size_t a, size_t b) { return size_t(SWMI_SGFULL_MOVE_WORDS(a, b)); }, 256, kTableSgfullAffine, true, false, false, false, false},
+     [](size_t a, size_t b) { return size_t(SWMI_SGFULL_MOVE_WORDS(a, b)); }, 256, kTableSgfullAffine, true, false, false, false, false,
+     false},
     /* kTableLocalFull */
     {launch_local_full_slice, kTableLocalFull, SWMI_LOCAL_FULL_MAX_LEN, false, "steps", 0, 4,
      [](size_t a, size_t b) { return swmi::local_full_code_words((int)a, (int)b); },
-     [](size_t a, size_t b) { return size_t(SWMI_LOCAL_FULL_MOVE_WORDS(a, b)); }, 256, kTableLocalFull, false, false, false, false, false},
+     [](size_t a, size_t b) { return size_t(SWMI_LOCAL_FULL_MOVE_WORDS(a, b)); }, 256, kTableLocalFull, false, false, false, false, false,
+     false},
     /* kTableLocalFullAffine */
     {launch_local_full_affine_slice, kTableLocalFullAffine, SWMI_LOCAL_FULL_MAX_LEN, false, "steps", 0, 4,
      [](size_t a, size_t b) { return 2 * swmi::local_full_affine_code_qwords((int)a, (int)b); },
      [](size_t a, size_t b) { return size_t(SWMI_LOCAL_FULL_MOVE_WORDS(a, b)); }, 256, kTableLocalFullAffine, true, false, false, false,
-     false},
+     false, false},
     /* kTableGlobalFull */
     {launch_global_full_slice, kTableGlobalFull, SWMI_GLOBAL_FULL_MAX_LEN, false, "steps", 0, 4,
      [](size_t a, size_t b) { return swmi::global_full_code_words((int)a, (int)b); },
-     [](size_t a, size_t b) { return size_t(SWMI_GLOBAL_FULL_MOVE_WORDS(a, b)); }, 256, kTableGlobalFull, false, true, false, false, false},
+     [](size_t a, size_t b) { return size_t(SWMI_GLOBAL_FULL_MOVE_WORDS(a, b)); }, 256, kTableGlobalFull, false, true, false, false, false,
+     false},
     /* kTableGlobalFullAffine */
     {launch_global_full_affine_slice, kTableGlobalFullAffine, SWMI_GLOBAL_FULL_MAX_LEN, false, "steps", 0, 4,
      [](size_t a, size_t b) { return 2 * swmi::global_full_affine_code_qwords((int)a, (int)b); },
      [](size_t a, size_t b) { return size_t(SWMI_GLOBAL_FULL_MOVE_WORDS(a, b)); }, 256, kTableGlobalFullAffine, true, true, false, false,
-     false},
+     false, false},
     /* kTableGlobalLong */
     {launch_global_long_slice, kTableGlobalLong, SWMI_GLOBAL_LONG_MAX_LEN, false, "steps", 0, 4,
      [](size_t a, size_t b) { return swmi::global_long_code_words((int)a, (int)b); },
-     [](size_t a, size_t b) { return size_t(SWMI_GLOBAL_LONG_MOVE_WORDS(a, b)); }, 256, kTableGlobalFull, false, true, true, true, false},
+     [](size_t a, size_t b) { return size_t(SWMI_GLOBAL_LONG_MOVE_WORDS(a, b)); }, 256, kTableGlobalFull, false, true, true, true, false,
+     false},
     /* kTableGlobalLongAffine */
     {launch_global_long_affine_slice, kTableGlobalLongAffine, SWMI_GLOBAL_LONG_MAX_LEN, false, "steps", 0, 4,
      [](size_t a, size_t b) { return 2 * swmi::global_long_affine_code_qwords((int)a, (int)b); },
      [](size_t a, size_t b) { return size_t(SWMI_GLOBAL_LONG_MOVE_WORDS(a, b)); }, 256, kTableGlobalFullAffine, true, true, true, true,
+     false, false},
+    /* kTableLocalLong */
+    {launch_local_long_slice, kTableLocalLong, SWMI_LOCAL_LONG_MAX_LEN, false, "steps", 0, 4,
+     [](size_t a, size_t b) { return swmi::local_long_code_words((int)a, (int)b); },
+     [](size_t a, size_t b) { return size_t(SWMI_LOCAL_LONG_MOVE_WORDS(a, b)); }, 256, kTableLocalFull, false, false, true, false, false,
      false},
+    /* kTableLocalLongAffine */
+    {launch_local_long_affine_slice, kTableLocalLongAffine, SWMI_LOCAL_LONG_MAX_LEN, false, "steps", 0, 4,
+     [](size_t a, size_t b) { return 2 * swmi::local_long_affine_code_qwords((int)a, (int)b); },
+     [](size_t a, size_t b) { return size_t(SWMI_LOCAL_LONG_MOVE_WORDS(a, b)); }, 256, kTableLocalFullAffine, true, false, true, false,
+     false, false},
+    /* kTableSemiglobalLong */
+    {launch_semiglobal_long_slice, kTableSemiglobalLong, SWMI_SEMIGLOBAL_LONG_MAX_LEN, false, "lengths", 1, 2,
+     [](size_t a, size_t b) { return swmi::sgfull_long_code_words((int)a, (int)b); },
+     [](size_t a, size_t b) { return size_t(SWMI_SEMIGLOBAL_LONG_MOVE_WORDS(a, b)); }, 256, kTableSgfull, false, false, true, true, false,
+     true},
+    /* kTableSemiglobalLongAffine */
+    {launch_semiglobal_long_affine_slice, kTableSemiglobalLongAffine, SWMI_SEMIGLOBAL_LONG_MAX_LEN, false, "lengths", 1, 2,
+     [](size_t a, size_t b) { return 2 * swmi::sgfull_long_affine_code_qwords((int)a, (int)b); },
+     [](size_t a, size_t b) { return size_t(SWMI_SEMIGLOBAL_LONG_MOVE_WORDS(a, b)); }, 256, kTableSgfullAffine, true, false, true, true,
+     false, true},
+};
+constexpr bool rows_in_enum_order()
+{
+    for (int f = 0; f < kTableFamilies; ++f)
+        if (kRows[f].family != f) return false;
+    return true;
+}
+static_assert(sizeof kRows / sizeof kRows[0] == kTableFamilies && rows_in_enum_order(), "kRows[f] is the row of TableFamily f");
+
+// the arguments of one call that the families read
+struct Call {
+    size_t len1, len2;          // len2 = SWMI_LOCAL_SEQ2_LEN from the two local families' entries
+    const int8_t *sm;
+    int gap, gap_extend;        // gap_extend 0 from the linear families' entries
+    unsigned free_ends;         // 0 from the families without a mask
 };
 
 // ---- one body each ----
@@ -138,10 +230,8 @@ bool domain_ok(const Call &c)
     return p * (c.len1 + c.len2) <= (size_t(1) << 23);
 }
 
-}  // namespace
-
 // in the order include/swmi.h gives: the lengths, the mask, the matrix and the gaps, the domain rule
-int family_check(const FamilyRow &r, const Call &c)
+int check(const FamilyRow &r, const Call &c)
 {
     if (!lens_ok(r, c.len1, c.len2)) {
         if (r.fixed_len2) return fail(SWMI_ERR_INVALID_ARGUMENT, "len1 %zu outside [1, %zu]", c.len1, r.max_len);
@@ -166,46 +256,47 @@ int family_check(const FamilyRow &r, const Call &c)
     return SWMI_OK;
 }
 
-namespace {
-Table call_table(const FamilyRow &r, const Call &c) { return family_table(r, c.len1, c.len2, c.sm, c.gap, c.gap_extend, c.free_ends); }
-}  // namespace
+Table call_table(TableFamily f, const Call &c) { return family_table(f, c.len1, c.len2, c.sm, c.gap, c.gap_extend, c.free_ends); }
 
-size_t family_slices_for(const FamilyRow &r, size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap)
+size_t slices_for(TableFamily f, size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap)
 {
-    if (!lens_ok(r, len1, len2)) return 0;
-    return table_slices_for(family_table(r, len1, len2, nullptr, 0, 0, 0), n, traceback != 0, sizes, cap);
+    if (!lens_ok(kRows[f], len1, len2)) return 0;
+    return table_slices_for(family_table(f, len1, len2, nullptr, 0, 0, 0), n, traceback != 0, sizes, cap);
 }
 
-int family_device(const FamilyRow &r, const Call &c, const void *d_seq1s, const void *d_seq2s, size_t n, void *d_scores, void *d_ends,
-                  void *d_moves, void *d_counts, void *stream)
+int device(TableFamily f, const Call &c, const void *d_seq1s, const void *d_seq2s, size_t n, void *d_scores, void *d_ends, void *d_moves,
+           void *d_counts, void *stream)
 {
-    const int rc = family_check(r, c);
+    const int rc = check(kRows[f], c);
     if (rc != SWMI_OK) return rc;
-    return table_device(call_table(r, c), d_seq1s, d_seq2s, n, d_scores, d_ends, d_moves, d_counts, stream);
+    return table_device(call_table(f, c), d_seq1s, d_seq2s, n, d_scores, d_ends, d_moves, d_counts, stream);
 }
 
-int family_host(const FamilyRow &r, const char *entry, const Call &c, const uint8_t *seq1s, const uint8_t *seq2s, size_t n,
-                int32_t *scores, int32_t *ends, uint64_t *moves, uint32_t *counts)
+int host(TableFamily f, const char *entry, const Call &c, const uint8_t *seq1s, const uint8_t *seq2s, size_t n, int32_t *scores,
+         int32_t *ends, uint64_t *moves, uint32_t *counts)
 {
-    const int rc = family_check(r, c);
+    const int rc = check(kRows[f], c);
     if (rc != SWMI_OK) return rc;
-    return table_host(call_table(r, c), entry, seq1s, seq2s, n, scores, ends, moves, counts);
+    return table_host(call_table(f, c), entry, seq1s, seq2s, n, scores, ends, moves, counts);
 }
 
-int family_time_device(const FamilyRow &r, const char *entry, const Call &c, const void *d_seq1s, const void *d_seq2s, size_t n,
-                       void *d_scores, void *d_ends, void *d_moves, void *d_counts, void *stream, int iters, float *avg_ms)
+int time_device(TableFamily f, const char *entry, const Call &c, const void *d_seq1s, const void *d_seq2s, size_t n, void *d_scores,
+                void *d_ends, void *d_moves, void *d_counts, void *stream, int iters, float *avg_ms)
 {
+    const FamilyRow &r = kRows[f];
     int rc = r.timer_first ? table_check_timer(n, iters, avg_ms) : SWMI_OK;       // (its last check makes the context current)
-    if (rc == SWMI_OK) rc = family_check(r, c);
+    if (rc == SWMI_OK) rc = check(r, c);
+    if (rc == SWMI_OK && r.timer_pair && !d_moves != !d_counts)
+        rc = fail(SWMI_ERR_INVALID_ARGUMENT, "moves and %s must both be given (traceback) or both be NULL (ends-only)", r.count);
     if (rc == SWMI_OK && !r.timer_first) rc = table_check_timer(n, iters, avg_ms);
     if (rc != SWMI_OK) return rc;
-    return table_time_device(call_table(r, c), entry, d_seq1s, d_seq2s, n, d_scores, d_ends, d_moves, d_counts, stream, iters, avg_ms);
+    return table_time_device(call_table(f, c), entry, d_seq1s, d_seq2s, n, d_scores, d_ends, d_moves, d_counts, stream, iters, avg_ms);
 }
 
-// The reference's list (source.cpp:1571-1572: from the start cell to the end cell) from the walk's moves: the start cell is
-// the end cell less the moves' row / column steps, and the list applies the moves last to first.
-int family_expand_moves(int32_t max_i, int32_t max_j, const uint64_t *moves, uint32_t steps, int32_t end_i, int32_t end_j,
-                        int32_t *positions, size_t cap)
+// The reference's list (source.cpp:1571-1572: from the start cell to the end cell) from the walk's moves, for end cells up to
+// (max_i, max_j): the start cell is the end cell less the moves' row / column steps, and the list applies the moves last to first.
+int expand_moves(int32_t max_i, int32_t max_j, const uint64_t *moves, uint32_t steps, int32_t end_i, int32_t end_j, int32_t *positions,
+                 size_t cap)
 {
     if ((!moves && steps) || (!positions && cap)) return fail(SWMI_ERR_INVALID_ARGUMENT, "NULL buffer");
     if (end_i < 0 || end_j < 0 || end_i > max_i || end_j > max_j)
@@ -234,9 +325,12 @@ int family_expand_moves(int32_t max_i, int32_t max_j, const uint64_t *moves, uin
     return SWMI_OK;
 }
 
-Table family_table(const FamilyRow &r, size_t len1, size_t len2, const int8_t *sm, int gap, int gap_extend, unsigned free_ends)
+}  // namespace
+
+// The Table of one call of a family, from its row (swmi_host.h)
+Table family_table(TableFamily f, size_t len1, size_t len2, const int8_t *sm, int gap, int gap_extend, unsigned free_ends)
 {
-    const FamilyRow &b = kRows[r.budget_as];
+    const FamilyRow &r = kRows[f], &b = kRows[r.budget_as];
     Table t{r.launch, r.family, kTableSliceBytes, r.count, len1, len2, r.ends, r.code_words(len1, len2), r.move_words(len1, len2),
             r.count_offset, sm, gap, gap_extend};
     t.free_ends = free_ends;
@@ -251,45 +345,6 @@ Table family_table(const FamilyRow &r, size_t len1, size_t len2, const int8_t *s
     if (r.carry && len2 > kStripe) t.carry_words = r.affine ? 2 * len1 : len1;       // a row of H, or of (H, F)
     return t;
 }
-
-Table family_table(TableFamily f, size_t len1, size_t len2, const int8_t *sm, int gap, int gap_extend, unsigned free_ends)
-{
-    return family_table(kRows[f], len1, len2, sm, gap, gap_extend, free_ends);
-}
-
-// ---- the exported definitions below name a family of kRows ----
-namespace {
-
-size_t slices_for(TableFamily f, size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap)
-{
-    return family_slices_for(kRows[f], n, len1, len2, traceback, sizes, cap);
-}
-
-int device(TableFamily f, const Call &c, const void *d_seq1s, const void *d_seq2s, size_t n, void *d_scores, void *d_ends, void *d_moves,
-           void *d_counts, void *stream)
-{
-    return family_device(kRows[f], c, d_seq1s, d_seq2s, n, d_scores, d_ends, d_moves, d_counts, stream);
-}
-
-int host(TableFamily f, const char *entry, const Call &c, const uint8_t *seq1s, const uint8_t *seq2s, size_t n, int32_t *scores,
-         int32_t *ends, uint64_t *moves, uint32_t *counts)
-{
-    return family_host(kRows[f], entry, c, seq1s, seq2s, n, scores, ends, moves, counts);
-}
-
-int time_device(TableFamily f, const char *entry, const Call &c, const void *d_seq1s, const void *d_seq2s, size_t n, void *d_scores,
-                void *d_ends, void *d_moves, void *d_counts, void *stream, int iters, float *avg_ms)
-{
-    return family_time_device(kRows[f], entry, c, d_seq1s, d_seq2s, n, d_scores, d_ends, d_moves, d_counts, stream, iters, avg_ms);
-}
-
-int expand_moves(int32_t max_i, int32_t max_j, const uint64_t *moves, uint32_t steps, int32_t end_i, int32_t end_j, int32_t *positions,
-                 size_t cap)
-{
-    return family_expand_moves(max_i, max_j, moves, steps, end_i, end_j, positions, cap);
-}
-
-}  // namespace
 
 }  // namespace host
 }  // namespace swmi
@@ -621,6 +676,139 @@ int swmi_global_long_affine_time_device(const void *d_seq1s, size_t len1, const 
 {
     return time_device(kTableGlobalLongAffine, __func__, {len1, len2, score_matrix, gap_open, gap_extend, free_ends}, d_seq1s, d_seq2s,
                        n, d_scores, d_ends, d_moves, d_steps, stream, iters, avg_ms);
+}
+
+// ---- local up to 65536 x 65536 (section 25) ----
+size_t swmi_local_long_slices_for(size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap)
+{
+    return slices_for(kTableLocalLong, n, len1, len2, traceback, sizes, cap);
+}
+
+int swmi_local_long_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n, const int8_t score_matrix[16],
+                           int8_t gap_penalty, void *d_scores, void *d_ends, void *d_moves, void *d_steps, void *stream)
+{
+    return device(kTableLocalLong, {len1, len2, score_matrix, gap_penalty, 0, 0}, d_seq1s, d_seq2s, n, d_scores, d_ends, d_moves,
+                  d_steps, stream);
+}
+
+int swmi_local_long(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t len2, size_t n, const int8_t score_matrix[16],
+                    int8_t gap_penalty, int32_t *scores, int32_t *ends, uint64_t *moves, uint32_t *steps)
+{
+    return host(kTableLocalLong, __func__, {len1, len2, score_matrix, gap_penalty, 0, 0}, seq1s, seq2s, n, scores, ends, moves, steps);
+}
+
+int swmi_local_long_release_workspaces(void) { return table_release_workspaces(kTableLocalLong); }
+
+int swmi_local_long_time_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
+                                const int8_t score_matrix[16], int8_t gap_penalty, void *d_scores, void *d_ends, void *d_moves,
+                                void *d_steps, void *stream, int iters, float *avg_ms)
+{
+    return time_device(kTableLocalLong, __func__, {len1, len2, score_matrix, gap_penalty, 0, 0}, d_seq1s, d_seq2s, n, d_scores, d_ends,
+                       d_moves, d_steps, stream, iters, avg_ms);
+}
+
+int swmi_local_long_expand_moves(const uint64_t *moves, uint32_t steps, int32_t end_i, int32_t end_j, int32_t *positions, size_t cap)
+{
+    return expand_moves(SWMI_LOCAL_LONG_MAX_LEN, SWMI_LOCAL_LONG_MAX_LEN, moves, steps, end_i, end_j, positions, cap);
+}
+
+// ---- the same with affine gaps (section 25) ----
+size_t swmi_local_long_affine_slices_for(size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap)
+{
+    return slices_for(kTableLocalLongAffine, n, len1, len2, traceback, sizes, cap);
+}
+
+int swmi_local_long_affine_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
+                                  const int8_t score_matrix[16], int gap_open, int gap_extend, void *d_scores, void *d_ends,
+                                  void *d_moves, void *d_steps, void *stream)
+{
+    return device(kTableLocalLongAffine, {len1, len2, score_matrix, gap_open, gap_extend, 0}, d_seq1s, d_seq2s, n, d_scores, d_ends,
+                  d_moves, d_steps, stream);
+}
+
+int swmi_local_long_affine(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t len2, size_t n,
+                           const int8_t score_matrix[16], int gap_open, int gap_extend, int32_t *scores, int32_t *ends,
+                           uint64_t *moves, uint32_t *steps)
+{
+    return host(kTableLocalLongAffine, __func__, {len1, len2, score_matrix, gap_open, gap_extend, 0}, seq1s, seq2s, n, scores, ends,
+                moves, steps);
+}
+
+int swmi_local_long_affine_release_workspaces(void) { return table_release_workspaces(kTableLocalLongAffine); }
+
+int swmi_local_long_affine_time_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
+                                       const int8_t score_matrix[16], int gap_open, int gap_extend, void *d_scores, void *d_ends,
+                                       void *d_moves, void *d_steps, void *stream, int iters, float *avg_ms)
+{
+    return time_device(kTableLocalLongAffine, __func__, {len1, len2, score_matrix, gap_open, gap_extend, 0}, d_seq1s, d_seq2s, n,
+                       d_scores, d_ends, d_moves, d_steps, stream, iters, avg_ms);
+}
+
+// ---- exact semi-global up to 65536 x 65536 (section 26) ----
+size_t swmi_semiglobal_long_slices_for(size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap)
+{
+    return slices_for(kTableSemiglobalLong, n, len1, len2, traceback, sizes, cap);
+}
+
+int swmi_semiglobal_long_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n, const int8_t score_matrix[16],
+                                int8_t gap_penalty, void *d_scores, void *d_ends, void *d_moves, void *d_lengths, void *stream)
+{
+    return device(kTableSemiglobalLong, {len1, len2, score_matrix, gap_penalty, 0, 0}, d_seq1s, d_seq2s, n, d_scores, d_ends, d_moves,
+                  d_lengths, stream);
+}
+
+int swmi_semiglobal_long(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t len2, size_t n, const int8_t score_matrix[16],
+                         int8_t gap_penalty, int32_t *scores, int32_t *ends, uint64_t *moves, uint32_t *lengths)
+{
+    return host(kTableSemiglobalLong, __func__, {len1, len2, score_matrix, gap_penalty, 0, 0}, seq1s, seq2s, n, scores, ends, moves,
+                lengths);
+}
+
+int swmi_semiglobal_long_release_workspaces(void) { return table_release_workspaces(kTableSemiglobalLong); }
+
+int swmi_semiglobal_long_time_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
+                                     const int8_t score_matrix[16], int8_t gap_penalty, void *d_scores, void *d_ends, void *d_moves,
+                                     void *d_lengths, void *stream, int iters, float *avg_ms)
+{
+    return time_device(kTableSemiglobalLong, __func__, {len1, len2, score_matrix, gap_penalty, 0, 0}, d_seq1s, d_seq2s, n, d_scores,
+                       d_ends, d_moves, d_lengths, stream, iters, avg_ms);
+}
+
+int swmi_semiglobal_long_expand_moves(const uint64_t *moves, uint32_t length, int32_t *traceback, size_t cap)
+{
+    return semiglobal_expand_moves(SWMI_SEMIGLOBAL_LONG_MAX_TRACEBACK, moves, length, traceback, cap);
+}
+
+// ---- the same with affine gaps (section 26) ----
+size_t swmi_semiglobal_long_affine_slices_for(size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap)
+{
+    return slices_for(kTableSemiglobalLongAffine, n, len1, len2, traceback, sizes, cap);
+}
+
+int swmi_semiglobal_long_affine_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
+                                       const int8_t score_matrix[16], int gap_open, int gap_extend, void *d_scores, void *d_ends,
+                                       void *d_moves, void *d_lengths, void *stream)
+{
+    return device(kTableSemiglobalLongAffine, {len1, len2, score_matrix, gap_open, gap_extend, 0}, d_seq1s, d_seq2s, n, d_scores,
+                  d_ends, d_moves, d_lengths, stream);
+}
+
+int swmi_semiglobal_long_affine(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t len2, size_t n,
+                                const int8_t score_matrix[16], int gap_open, int gap_extend, int32_t *scores, int32_t *ends,
+                                uint64_t *moves, uint32_t *lengths)
+{
+    return host(kTableSemiglobalLongAffine, __func__, {len1, len2, score_matrix, gap_open, gap_extend, 0}, seq1s, seq2s, n, scores,
+                ends, moves, lengths);
+}
+
+int swmi_semiglobal_long_affine_release_workspaces(void) { return table_release_workspaces(kTableSemiglobalLongAffine); }
+
+int swmi_semiglobal_long_affine_time_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n,
+                                            const int8_t score_matrix[16], int gap_open, int gap_extend, void *d_scores, void *d_ends,
+                                            void *d_moves, void *d_lengths, void *stream, int iters, float *avg_ms)
+{
+    return time_device(kTableSemiglobalLongAffine, __func__, {len1, len2, score_matrix, gap_open, gap_extend, 0}, d_seq1s, d_seq2s, n,
+                       d_scores, d_ends, d_moves, d_lengths, stream, iters, avg_ms);
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // fake_hip.cpp -- TEST INFRASTRUCTURE ONLY: a recording stand-in for the HIP runtime and for the kernel launchers, so that the
-// product's HOST code (swmi_api.cpp, swmi_multi.cpp, swmi_table.cpp, table_api.cpp) can run on a machine with no GPU at all:
+// product's HOST code (swmi_api.cpp, swmi_multi.cpp, swmi_table.cpp, table_api.cpp; with a driver's own stand-ins for the
+// ragged launchers also local_ragged_api.cpp and tile_ragged_api.cpp) can run on a machine with no GPU at all:
 // FAKE_HIP_DEVICES "gfx950" devices whose memory is host memory, copies that happen at once -- EXCEPT device-to-host copies on
 // a stream (hipMemcpyAsync and hipMemcpy2DAsync), which are held back until that stream (or the device, or an event) is
 // synchronised and read the device buffer
@@ -227,7 +228,7 @@ hipError_t hipDeviceCanAccessPeer(int *can, int a, int b) { *can = a != b; retur
 hipError_t hipDeviceEnablePeerAccess(int peer, unsigned) { log("dev%d enable_peer dev%d", t_device, peer); return hipSuccess; }
 }  // extern "C"
 
-// ---- stand-ins for the kernel launchers (sw_kernels.hip, sg_kernels.hip and the ten fixed-shape table aligners') ------------
+// ---- stand-ins for the kernel launchers (sw_kernels.hip, sg_kernels.hip and the fourteen fixed-shape table aligners') -------
 namespace swmi {
 bool schedule_supported(int L) { return L == 64 || L == 32 || L == 16 || L == 8 || L == 4 || L == 2; }
 static void fake_scores(const uint8_t *s1, size_t stride, int32_t *out, size_t n)
@@ -275,7 +276,7 @@ hipError_t launch_semiglobal(const uint8_t *, const uint8_t *, size_t, void *, i
 size_t semiglobal_move_words() { return 1040; }
 void semiglobal_kernel_names(size_t, int, char *a, size_t an, char *b, size_t bn, SgTuning) { if (a && an) a[0] = 0; if (b && bn) b[0] = 0; }
 
-// The ten fixed-shape table aligners (table_api.cpp names their launchers), all through fake_table.  Their code workspaces take
+// The fourteen fixed-shape table aligners (table_api.cpp names their launchers), all through fake_table.  Their code workspaces take
 // a constant kFakeCodeWords dwords (half as many qwords with affine gaps) per alignment, not the kernels' formula: a slice is then
 // a few thousand alignments at a small shape and the real 256 at 16384 x 16384, and the buffers stay small -- except while
 // fake_hip_real_code_sizes(1) holds, for slice sizes worked out by hand (nothing may launch then: fake_table checks its codes
@@ -363,10 +364,14 @@ size_t sgfull_code_words(int len1, int len2) { return tile_or_fake(len1, len2, k
 size_t local_full_code_words(int len1, int len2) { return tile_or_fake(len1, len2, kFakeCodeWords); }
 size_t global_full_code_words(int len1, int len2) { return tile_or_fake(len1, len2, kFakeCodeWords); }
 size_t global_long_code_words(int len1, int len2) { return tile_or_fake(len1, len2, kFakeCodeWords); }
+size_t local_long_code_words(int len1, int len2) { return tile_or_fake(len1, len2, kFakeCodeWords); }
+size_t sgfull_long_code_words(int len1, int len2) { return tile_or_fake(len1, len2, kFakeCodeWords); }
 size_t sgfull_affine_code_qwords(int len1, int len2) { return tile_or_fake(len1, len2, kFakeCodeWords / 2); }
 size_t local_full_affine_code_qwords(int len1, int len2) { return tile_or_fake(len1, len2, kFakeCodeWords / 2); }
 size_t global_full_affine_code_qwords(int len1, int len2) { return tile_or_fake(len1, len2, kFakeCodeWords / 2); }
 size_t global_long_affine_code_qwords(int len1, int len2) { return tile_or_fake(len1, len2, kFakeCodeWords / 2); }
+size_t local_long_affine_code_qwords(int len1, int len2) { return tile_or_fake(len1, len2, kFakeCodeWords / 2); }
+size_t sgfull_long_affine_code_qwords(int len1, int len2) { return tile_or_fake(len1, len2, kFakeCodeWords / 2); }
 
 hipError_t launch_local(const uint8_t *s1, const uint8_t *s2, int len1, size_t n, const int8_t *sm, int gap, int32_t *scores, int32_t *ends,
                         uint32_t *codes, unsigned long long *moves, uint32_t *steps, size_t mw, hipStream_t st)
@@ -428,6 +433,34 @@ hipError_t launch_global_long_affine(const uint8_t *s1, const uint8_t *s2, int l
                                      uint32_t *steps, size_t mw, int32_t *carry, hipStream_t st)
 {
     return fake_table({"launch_global_long_affine", s1, s2, len1, len2, n, sm, go, ge, fe, scores, ends, 4, codes, moves, steps, 0, mw,
+                       carry, len2 > 16384 ? 2 * size_t(len1) : 0, st});
+}
+hipError_t launch_local_long(const uint8_t *s1, const uint8_t *s2, int len1, int len2, size_t n, const int8_t *sm, int gap, int32_t *scores,
+                             int32_t *ends, uint32_t *codes, unsigned long long *moves, uint32_t *steps, size_t mw, int32_t *carry,
+                             hipStream_t st)
+{
+    return fake_table({"launch_local_long", s1, s2, len1, len2, n, sm, gap, 0, 0, scores, ends, 4, codes, moves, steps, 0, mw, carry,
+                       len2 > 16384 ? size_t(len1) : 0, st});
+}
+hipError_t launch_local_long_affine(const uint8_t *s1, const uint8_t *s2, int len1, int len2, size_t n, const int8_t *sm, int go, int ge,
+                                    int32_t *scores, int32_t *ends, unsigned long long *codes, unsigned long long *moves, uint32_t *steps,
+                                    size_t mw, int32_t *carry, hipStream_t st)
+{
+    return fake_table({"launch_local_long_affine", s1, s2, len1, len2, n, sm, go, ge, 0, scores, ends, 4, codes, moves, steps, 0, mw,
+                       carry, len2 > 16384 ? 2 * size_t(len1) : 0, st});
+}
+hipError_t launch_sgfull_long(const uint8_t *s1, const uint8_t *s2, int len1, int len2, size_t n, const int8_t *sm, int gap, int32_t *scores,
+                              int32_t *ends, uint32_t *codes, unsigned long long *moves, uint32_t *lengths, size_t mw, int32_t *carry,
+                              hipStream_t st)
+{
+    return fake_table({"launch_sgfull_long", s1, s2, len1, len2, n, sm, gap, 0, 0, scores, ends, 2, codes, moves, lengths, 1, mw, carry,
+                       len2 > 16384 ? size_t(len1) : 0, st});
+}
+hipError_t launch_sgfull_long_affine(const uint8_t *s1, const uint8_t *s2, int len1, int len2, size_t n, const int8_t *sm, int go, int ge,
+                                     int32_t *scores, int32_t *ends, unsigned long long *codes, unsigned long long *moves,
+                                     uint32_t *lengths, size_t mw, int32_t *carry, hipStream_t st)
+{
+    return fake_table({"launch_sgfull_long_affine", s1, s2, len1, len2, n, sm, go, ge, 0, scores, ends, 2, codes, moves, lengths, 1, mw,
                        carry, len2 > 16384 ? 2 * size_t(len1) : 0, st});
 }
 }  // namespace swmi

@@ -1,4 +1,4 @@
-// table_host_fake.cpp -- the host side of the ten fixed-shape table aligners (table_api.cpp through the slice pipeline of
+// table_host_fake.cpp -- the host side of the fourteen fixed-shape table aligners (table_api.cpp through the slice pipeline of
 // swmi_table.cpp) on a fake GPU (fake_hip.cpp), whose launcher stand-ins write results derived from an index in each seq1's
 // first four bytes, abort on any copy or launch that leaves its device block, and log what each launch was handed.  The index
 // is k | walk << 20 for alignment k: the fake makes `walk` its number of moves, so every slice of a batch gets a longest walk of
@@ -7,9 +7,14 @@
 //
 // Per family, each group printing one ": ok" line per case:
 //   refusals     before any device is bound and again after swmi_init, through the host entry, the device entry and the timer,
-//                each with its code and its swmi_last_error() text; n = 0; nothing logged or launched
+//                each with its code and its swmi_last_error() text -- one of moves / counts among them, which the long
+//                semi-global pair's timers refuse without a device too; n = 0; nothing logged or launched
 //   timer order  which of the timer's own arguments and the call's is checked first
-//   domain rule  (striped pair) P (len1 + len2) just over 2^23 refused, the boundary accepted and launched
+//   domain rule  (the striped families that have one) P (len1 + len2) just over 2^23 refused, by the matrix and by each gap, at
+//                (32769, 32768) and at 65536 x 65536 -- there (127, -127, 127), gap 65, extend 65, one matrix entry of 65 -- each
+//                with its code and text; the boundary (64, -64, 64) at 65536 x 65536 and 128 at 32768 x 32768 accepted: without
+//                a device the call then finds none, with one it is launched through the striped launcher with a carry
+//   no rule      (the long local pair) (127, -127, 127) at 65536 x 65536 passes the check in the same two ways
 //   slices_for   hand-computed sizes with the kernels' real code sizes, the full-slice value, the splits, 0 out of range
 //   host entry   traceback and ends-only at n = 1, S, S + 1 and 2.5 S: every score, end and count, every move word up to the
 //                slice's longest walk and the sentinel past it, one launch per slice alternating between two streams with the
@@ -17,7 +22,9 @@
 //   device entry two streams, a workspace that grows only after synchronising its stream; every result over the full rows
 //   timer        1 + iters launches on the caller's stream with the call's parameters
 //   release      (where there is one) then both entries again, which allocate again; the entries after swmi_shutdown
-//   striped pair which launcher a shape reaches, and the carry: NULL, or 8-byte aligned and of the stated size
+//   striped      which launcher a shape reaches -- the fixed one for (300, 16384) and (16384, 300), the striped one for
+//                (16385, 17) and (64, 16385) -- and the carry: NULL, or 8-byte aligned and of the stated size (fake_table checks
+//                it against the device blocks); the workspace of the device entry with and without a carry
 #include <hip/hip_runtime_api.h>
 
 #include <cstdio>
@@ -87,6 +94,8 @@ static size_t mw_sgfull(size_t len1, size_t len2) { return SWMI_SGFULL_MOVE_WORD
 static size_t mw_local_full(size_t len1, size_t len2) { return SWMI_LOCAL_FULL_MOVE_WORDS(len1, len2); }
 static size_t mw_global_full(size_t len1, size_t len2) { return SWMI_GLOBAL_FULL_MOVE_WORDS(len1, len2); }
 static size_t mw_global_long(size_t len1, size_t len2) { return SWMI_GLOBAL_LONG_MOVE_WORDS(len1, len2); }
+static size_t mw_local_long(size_t len1, size_t len2) { return SWMI_LOCAL_LONG_MOVE_WORDS(len1, len2); }
+static size_t mw_semiglobal_long(size_t len1, size_t len2) { return SWMI_SEMIGLOBAL_LONG_MOVE_WORDS(len1, len2); }
 
 // ---- the families ----
 struct Shape { size_t len1, len2; };
@@ -101,6 +110,8 @@ struct Family {
     uint32_t count_offset;          // count = moves + count_offset
     size_t budget;                  // a traceback slice: alignments of the maximum shape (0: 256 MiB)
     bool affine, mask, timer_first;
+    bool domain;                    // a striped family with the domain rule P (len1 + len2) <= 2^23
+    bool timer_pair;                // the timer refuses one of moves / counts itself, before it looks for a device
     Shape tb, eo;                   // the shapes of the traceback and the ends-only cases
     size_t (*move_words)(size_t, size_t);
     size_t (*slices_for)(size_t, size_t, size_t, int, size_t *, size_t);
@@ -111,49 +122,63 @@ struct Family {
 };
 
 static const Family kFamilies[] = {
-    {"local", "launch_local", nullptr, SWMI_LOCAL_MAX_LEN, true, 4, "steps", 0, 0, false, false, true, {200, 128}, {4, 128}, mw_local,
+    {"local", "launch_local", nullptr, SWMI_LOCAL_MAX_LEN, true, 4, "steps", 0, 0, false, false, true, false, false, {200, 128}, {4, 128}, mw_local,
      slices_1<swmi_local_slices_for>, host_1l<swmi_local_align>, dev_1l<swmi_local_align_device>, time_1l<swmi_local_time_device>, nullptr},
-    {"sgfull", "launch_sgfull", nullptr, SWMI_SGFULL_MAX_LEN, false, 2, "lengths", 1, 256, false, false, true, {300, 77}, {4, 1}, mw_sgfull,
+    {"sgfull", "launch_sgfull", nullptr, SWMI_SGFULL_MAX_LEN, false, 2, "lengths", 1, 256, false, false, true, false, false, {300, 77}, {4, 1}, mw_sgfull,
      slices_2<swmi_semiglobal_full_slices_for>, host_2l<swmi_semiglobal_full>, dev_2l<swmi_semiglobal_full_device>,
      time_2l<swmi_semiglobal_full_time_device>, swmi_semiglobal_full_release_workspaces},
-    {"local_affine", "launch_local_affine", nullptr, SWMI_LOCAL_MAX_LEN, true, 4, "steps", 0, 4096, true, false, true, {200, 128}, {4, 128},
+    {"local_affine", "launch_local_affine", nullptr, SWMI_LOCAL_MAX_LEN, true, 4, "steps", 0, 4096, true, false, true, false, false, {200, 128}, {4, 128},
      mw_local, slices_1<swmi_local_affine_slices_for>, host_1a<swmi_local_align_affine>, dev_1a<swmi_local_align_affine_device>,
      time_1a<swmi_local_affine_time_device>, nullptr},
-    {"sgfull_affine", "launch_sgfull_affine", nullptr, SWMI_SGFULL_MAX_LEN, false, 2, "lengths", 1, 256, true, false, false, {300, 77},
+    {"sgfull_affine", "launch_sgfull_affine", nullptr, SWMI_SGFULL_MAX_LEN, false, 2, "lengths", 1, 256, true, false, false, false, false, {300, 77},
      {4, 1}, mw_sgfull, slices_2<swmi_semiglobal_full_affine_slices_for>, host_2a<swmi_semiglobal_full_affine>,
      dev_2a<swmi_semiglobal_full_affine_device>, time_2a<swmi_semiglobal_full_affine_time_device>,
      swmi_semiglobal_full_affine_release_workspaces},
-    {"local_full", "launch_local_full", nullptr, SWMI_LOCAL_FULL_MAX_LEN, false, 4, "steps", 0, 256, false, false, false, {300, 777}, {4, 1},
+    {"local_full", "launch_local_full", nullptr, SWMI_LOCAL_FULL_MAX_LEN, false, 4, "steps", 0, 256, false, false, false, false, false, {300, 777}, {4, 1},
      mw_local_full, slices_2<swmi_local_full_slices_for>, host_2l<swmi_local_full>, dev_2l<swmi_local_full_device>,
      time_2l<swmi_local_full_time_device>, swmi_local_full_release_workspaces},
-    {"local_full_affine", "launch_local_full_affine", nullptr, SWMI_LOCAL_FULL_MAX_LEN, false, 4, "steps", 0, 256, true, false, false,
+    {"local_full_affine", "launch_local_full_affine", nullptr, SWMI_LOCAL_FULL_MAX_LEN, false, 4, "steps", 0, 256, true, false, false, false, false,
      {300, 777}, {4, 1}, mw_local_full, slices_2<swmi_local_full_affine_slices_for>, host_2a<swmi_local_full_affine>,
      dev_2a<swmi_local_full_affine_device>, time_2a<swmi_local_full_affine_time_device>, swmi_local_full_affine_release_workspaces},
-    {"global_full", "launch_global_full", nullptr, SWMI_GLOBAL_FULL_MAX_LEN, false, 4, "steps", 0, 256, false, true, false, {16384, 16384},
+    {"global_full", "launch_global_full", nullptr, SWMI_GLOBAL_FULL_MAX_LEN, false, 4, "steps", 0, 256, false, true, false, false, false, {16384, 16384},
      {4, 1}, mw_global_full, slices_2<swmi_global_full_slices_for>, host_2lm<swmi_global_full>, dev_2lm<swmi_global_full_device>,
      time_2lm<swmi_global_full_time_device>, swmi_global_full_release_workspaces},
-    {"global_full_affine", "launch_global_full_affine", nullptr, SWMI_GLOBAL_FULL_MAX_LEN, false, 4, "steps", 0, 256, true, true, false,
+    {"global_full_affine", "launch_global_full_affine", nullptr, SWMI_GLOBAL_FULL_MAX_LEN, false, 4, "steps", 0, 256, true, true, false, false, false,
      {16384, 16384}, {4, 1}, mw_global_full, slices_2<swmi_global_full_affine_slices_for>, host_2am<swmi_global_full_affine>,
      dev_2am<swmi_global_full_affine_device>, time_2am<swmi_global_full_affine_time_device>, swmi_global_full_affine_release_workspaces},
-    {"global_long", "launch_global_full", "launch_global_long", SWMI_GLOBAL_LONG_MAX_LEN, false, 4, "steps", 0, 256, false, true, false,
+    {"global_long", "launch_global_full", "launch_global_long", SWMI_GLOBAL_LONG_MAX_LEN, false, 4, "steps", 0, 256, false, true, false, true, false,
      {65536, 65536}, {4, 1}, mw_global_long, slices_2<swmi_global_long_slices_for>, host_2lm<swmi_global_long>,
      dev_2lm<swmi_global_long_device>, time_2lm<swmi_global_long_time_device>, swmi_global_long_release_workspaces},
     {"global_long_affine", "launch_global_full_affine", "launch_global_long_affine", SWMI_GLOBAL_LONG_MAX_LEN, false, 4, "steps", 0, 256,
-     true, true, false, {65536, 65536}, {4, 1}, mw_global_long, slices_2<swmi_global_long_affine_slices_for>,
+     true, true, false, true, false, {65536, 65536}, {4, 1}, mw_global_long, slices_2<swmi_global_long_affine_slices_for>,
      host_2am<swmi_global_long_affine>, dev_2am<swmi_global_long_affine_device>, time_2am<swmi_global_long_affine_time_device>,
      swmi_global_long_affine_release_workspaces},
+    {"local_long", "launch_local_full", "launch_local_long", SWMI_LOCAL_LONG_MAX_LEN, false, 4, "steps", 0, 256, false, false, false,
+     false, false, {64, 16385}, {4, 1}, mw_local_long, slices_2<swmi_local_long_slices_for>, host_2l<swmi_local_long>,
+     dev_2l<swmi_local_long_device>, time_2l<swmi_local_long_time_device>, swmi_local_long_release_workspaces},
+    {"local_long_affine", "launch_local_full_affine", "launch_local_long_affine", SWMI_LOCAL_LONG_MAX_LEN, false, 4, "steps", 0, 256, true,
+     false, false, false, false, {64, 16385}, {4, 1}, mw_local_long, slices_2<swmi_local_long_affine_slices_for>,
+     host_2a<swmi_local_long_affine>, dev_2a<swmi_local_long_affine_device>, time_2a<swmi_local_long_affine_time_device>,
+     swmi_local_long_affine_release_workspaces},
+    {"semiglobal_long", "launch_sgfull", "launch_sgfull_long", SWMI_SEMIGLOBAL_LONG_MAX_LEN, false, 2, "lengths", 1, 256, false, false,
+     false, true, true, {64, 16385}, {4, 1}, mw_semiglobal_long, slices_2<swmi_semiglobal_long_slices_for>, host_2l<swmi_semiglobal_long>,
+     dev_2l<swmi_semiglobal_long_device>, time_2l<swmi_semiglobal_long_time_device>, swmi_semiglobal_long_release_workspaces},
+    {"semiglobal_long_affine", "launch_sgfull_affine", "launch_sgfull_long_affine", SWMI_SEMIGLOBAL_LONG_MAX_LEN, false, 2, "lengths", 1,
+     256, true, false, false, true, true, {64, 16385}, {4, 1}, mw_semiglobal_long, slices_2<swmi_semiglobal_long_affine_slices_for>,
+     host_2a<swmi_semiglobal_long_affine>, dev_2a<swmi_semiglobal_long_affine_device>, time_2a<swmi_semiglobal_long_affine_time_device>,
+     swmi_semiglobal_long_affine_release_workspaces},
 };
 
 static const Family *g_f;
 static size_t mw_of(const Shape &a) { return g_f->move_words(a.len1, a.len2); }
 static size_t carry_words(const Shape &a) { return g_f->striped && a.len2 > kStripe ? a.len1 * (g_f->affine ? 2 : 1) : 0; }
 
-// the parameters of case number c: gaps over the family's whole domain (the striped pair's stay within its domain rule at
+// the parameters of case number c: gaps over the family's whole domain (under the domain rule they stay within it at
 // 65536 x 65536: P <= 64), every mask in turn
 static Call call_of(const Shape &a, unsigned c)
 {
     c &= 15;
-    const int step = g_f->striped ? 4 : 8;
+    const int step = g_f->domain && a.len1 + a.len2 > 65536 ? 4 : 8;
     return {a.len1, a.len2, g_sm, int(c) * step + (c == 15 ? step - 1 : 0), g_f->affine ? (16 * step - 1) - int(c) * step : 0, g_f->mask ? c : 0};
 }
 
@@ -365,20 +390,21 @@ static std::string domain_text(size_t total)
 
 static void refusals()
 {
-    std::vector<uint8_t> seq(2 * g_f->max_len + 2, 0);
-    const uint8_t *s = seq.data();
-    int32_t sc1 = 0, e4[4] = {0, 0, 0, 0};
+    std::vector<uint8_t> seq(2 * g_f->max_len + 64, 0);
+    const uint8_t *s = seq.data() + (16 - (reinterpret_cast<uintptr_t>(seq.data()) & 15)) % 16;     // (a device entry that passes
+    alignas(16) int32_t sc1 = 0, e4[4] = {0, 0, 0, 0};                                              //   its checks wants 16-byte alignment)
     uint64_t mv1[2] = {0, 0};
     uint32_t ct1 = 0;
     float ms = 0.f;
     const size_t max = g_f->max_len;
     const Call good{5, g_f->fixed_len2 ? size_t(SWMI_LOCAL_SEQ2_LEN) : 5, g_sm, 3, g_f->affine ? 2 : 0, 0};
-    const Bufs bufs{s, s + max + 1, 1, &sc1, e4, nullptr, nullptr, nullptr, 2, &ms};
+    const Bufs bufs{s, s + max + 16, 1, &sc1, e4, nullptr, nullptr, nullptr, 2, &ms};
     const auto with = [](Call c, size_t len1, size_t len2) { c.len1 = len1; c.len2 = len2; return c; };
-    int8_t sm64[16], sm65[16], sm128[16];
+    int8_t sm64[16], sm65[16], sm127[16], sm128[16];
     for (int i = 0; i < 16; ++i) {
         sm64[i] = int8_t(i % 5 == 0 ? 64 : -64);
         sm65[i] = int8_t(i % 5 == 0 ? 64 : -65);
+        sm127[i] = int8_t(i % 5 == 0 ? 127 : -127);
         sm128[i] = int8_t(i % 5 == 0 ? 1 : -128);
     }
     for (int e = kHost; e <= kTimer; ++e) {
@@ -425,29 +451,53 @@ static void refusals()
             c.extend = -1;
             args(c, SWMI_ERR_DOMAIN, gaps_text(c.gap, -1), __LINE__);
         }
-        if (g_f->striped) {             // P (len1 + len2) just over 2^23, by the matrix and by each gap
+        if (g_f->domain) {              // P (len1 + len2) just over 2^23, by the matrix and by each gap
             c = with(good, 32769, 32768);
             c.sm = sm128;
             args(c, bad, domain_text(65537), __LINE__);
             c = with(good, 65536, 65536);
             c.sm = sm65;
             args(c, bad, domain_text(131072), __LINE__);
+            c.sm = sm127;               // the int8 extremes
+            c.gap = 127;
+            c.extend = g_f->affine ? 127 : 0;
+            args(c, bad, domain_text(131072), __LINE__);
             c.sm = sm64;
             c.gap = 65;
+            c.extend = g_f->affine ? 64 : 0;
             args(c, bad, domain_text(131072), __LINE__);
             if (g_f->affine) {
                 c.gap = 64;
                 c.extend = 65;
                 args(c, bad, domain_text(131072), __LINE__);
             }
+            c.gap = c.extend = 64;      // one matrix entry of 65
+            if (!g_f->affine) c.extend = 0;
+            sm64[0] = 65;
+            args(c, bad, domain_text(131072), __LINE__);
+            sm64[0] = 64;
             c.gap = -1;                 // the gaps' own domain before the rule
             c.extend = good.extend;
             args(c, SWMI_ERR_DOMAIN, gaps_text(-1, c.extend), __LINE__);
+        }
+        if (g_f->striped && g_pass == 0) {
+            // what passes the check at 65536 x 65536 then finds no device: the edge of the rule (64, -64, 64), or without a
+            // rule the int8 extremes (127, -127, 127)
+            c = with(good, 65536, 65536);
+            c.sm = g_f->domain ? sm64 : sm127;
+            c.gap = g_f->domain ? 64 : 127;
+            c.extend = g_f->affine ? c.gap : 0;
+            refused(entry(c, bufs), SWMI_ERR_NOT_INITIALIZED, kNotInit, __LINE__);
         }
         // the buffers: checked by the pipeline once the arguments have passed, by the timer only with a device
         const bool unbound = e == kTimer && g_pass == 0;
         const auto buffers = [&](Bufs b, const std::string &text, int line) {
             refused(entry(good, b), unbound ? SWMI_ERR_NOT_INITIALIZED : bad, unbound ? kNotInit : text, line);
+        };
+        // one of moves / counts: a timer that checks the pair itself refuses it without a device too
+        const auto pair = [&](Bufs b, const std::string &text, int line) {
+            if (g_f->timer_pair) refused(entry(good, b), bad, text, line);
+            else buffers(b, text, line);
         };
         const std::string null_text = e == kHost ? "NULL buffer with n = 1" : "NULL device buffer with n = 1";
         const std::string pair_text = std::string("moves and ") + g_f->count + " must both be given (traceback) or both be NULL (ends-only)";
@@ -468,12 +518,12 @@ static void refusals()
         buffers(b, null_text, __LINE__);
         b = bufs;
         b.moves = mv1;
-        buffers(b, pair_text, __LINE__);
+        pair(b, pair_text, __LINE__);
         b.s1 = nullptr;                 // the pair before the NULLs
-        buffers(b, pair_text, __LINE__);
+        pair(b, pair_text, __LINE__);
         b = bufs;
         b.counts = &ct1;
-        buffers(b, pair_text, __LINE__);
+        pair(b, pair_text, __LINE__);
         b = Bufs{nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 2, &ms};       // n = 0
         if (e == kTimer) REFUSED(entry(good, b), bad, "n is 0");        // (the timer's own, before the device is looked up)
         else CHECK(entry(good, b) == SWMI_OK);
@@ -503,25 +553,30 @@ static void timer_order()
     CHECK(fake_hip_log_size() == 0);
 }
 
-// the boundary of the striped pair's domain rule from inside: accepted, and launched
-static void domain_boundary()
+// What passes the check at the top of a striped family's range is launched, through the striped launcher with a carry: under
+// the domain rule its boundary from inside, without one the int8 extremes at 65536 x 65536
+static void top_of_range()
 {
     std::vector<uint8_t> big(2 * 65536, 0);
     int32_t sc1 = 0, e4[4] = {0, 0, 0, 0};
-    int8_t sm64[16], sm128[16];
+    int8_t sm64[16], sm127[16], sm128[16];
     for (int i = 0; i < 16; ++i) {
         sm64[i] = int8_t(i % 5 == 0 ? 64 : -64);
+        sm127[i] = int8_t(i % 5 == 0 ? 127 : -127);
         sm128[i] = int8_t(i % 5 == 0 ? 1 : -128);
     }
     fake_hip_log_clear();
     const Call at64{65536, 65536, sm64, 64, g_f->affine ? 64 : 0, 0}, at128{32768, 32768, sm128, 127, g_f->affine ? 127 : 0, 0};
-    for (const Call &c : {at64, at128}) {
+    const Call top{65536, 65536, sm127, 127, g_f->affine ? 127 : 0, 0};
+    const std::vector<Call> calls = g_f->domain ? std::vector<Call>{at64, at128} : std::vector<Call>{top};
+    for (const Call &c : calls) {
         CHECK(g_f->host(c, {big.data(), big.data() + 65536, 1, &sc1, e4, nullptr, nullptr, nullptr, 0, nullptr}) == SWMI_OK);
         const std::vector<Launch> l = launches();
         check_launches({l.back()}, {1}, c, false);
     }
-    CHECK(launches().size() == 2);
-    printf("  domain rule: (65536, 65536) with P = 64 and (32768, 32768) with P = 128 accepted, just over 2^23 refused: ok\n");
+    CHECK(launches().size() == calls.size());
+    if (g_f->domain) printf("  domain rule: (65536, 65536) with P = 64 and (32768, 32768) with P = 128 accepted, just over 2^23 refused: ok\n");
+    else printf("  no domain rule: (127, -127, 127) at 65536 x 65536 accepted and launched: ok\n");
 }
 
 // swmi_*_slices_for, no device: with the kernels' own code sizes against sizes worked out by hand, then with the fake's
@@ -597,9 +652,9 @@ int main(int argc, char **argv)
     }
     printf("  lengths of 0 and %zu, %sgaps outside their domain, NULLs, one of moves / %s, n = 0%s: refused with their texts through the "
            "host entry, the device entry and the timer, without a device and with one, nothing launched: ok\n",
-           g_f->max_len + 1, g_f->mask ? "a mask of 16, " : "", g_f->count, g_f->striped ? ", calls outside the domain rule" : "");
+           g_f->max_len + 1, g_f->mask ? "a mask of 16, " : "", g_f->count, g_f->domain ? ", calls outside the domain rule" : "");
     printf("  the timer checks %s first: ok\n", g_f->timer_first ? "its own arguments" : "the call's arguments");
-    if (g_f->striped) domain_boundary();
+    if (g_f->striped) top_of_range();
 
     // host entry: n = 1, one slice, one slice + 1, two and a half slices; a family with a mask twice, for every mask once
     const Shape &tb_a = g_f->tb, &eo_a = g_f->eo;
@@ -629,13 +684,14 @@ int main(int argc, char **argv)
     CHECK(log.empty());
 
     if (g_f->striped) {
-        // which launcher a shape reaches, and the carry (check_launches); an ends-only call with a carry takes a workspace of
-        // the carry alone, on a fresh stream
-        const Shape wide{40, 16385}, tall{16385, 40}, small{300, 16384};
-        host_case(wide, 7, true, c++);
-        host_case(wide, 7, false, c++);
-        host_case(tall, 7, true, c++);          // the striped launcher, no carry
-        host_case(small, 7, true, c++);         // the fixed-length launcher
+        // which launcher a shape reaches, and the carry (check_launches): the fixed-length launcher, the same across, the
+        // striped launcher without a carry, and with one
+        const Shape wide{64, 16385}, tall{16385, 17}, small{300, 16384}, small2{16384, 300};
+        for (const Shape *a : {&small, &small2, &tall, &wide})
+            for (int tb = 1; tb >= 0; --tb) host_case(*a, 7, tb != 0, c++);
+        CHECK(device_case(wide, 7, false, sa, ida, c++).empty());          // ends-only on a stream that has a workspace: the carry fits
+        CHECK(device_case(tall, 9, false, sa, ida, c++).empty());          // the striped launcher without a carry: no workspace
+        // an ends-only call with a carry takes a workspace of the carry alone, on a fresh stream
         hipStream_t sc;
         CHECK(hipStreamCreateWithFlags(&sc, 0) == hipSuccess);
         fake_hip_log_clear();

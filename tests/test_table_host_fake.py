@@ -1,4 +1,4 @@
-"""The host sides of the ten fixed-shape table aligners (csrc/table_api.cpp through the slice pipeline of csrc/swmi_table.cpp)
+"""The host sides of the fourteen fixed-shape table aligners (csrc/table_api.cpp through the slice pipeline of csrc/swmi_table.cpp)
 on a fake GPU, no device needed: the real host sources (every csrc/swmi_*.cpp and table_api.cpp), compiled once with g++ and
 ASan + UBSan against tests/native/fake_hip.cpp, whose launcher stand-ins write results derived from each alignment's index,
 log what they were handed and abort on any copy or launch that leaves its device block.  tests/native/table_host_fake.cpp runs
@@ -6,7 +6,8 @@ one family per invocation: the refusals with their codes and texts (without a de
 checks, the slice sizes, the host entry (traceback and ends-only at n = 1, one slice, one slice + 1 and two and a half slices:
 every result, the move words each slice copies back, the launches, their streams and parameters), the device entry on two
 streams with a workspace that grows, the timer, the release of the workspaces where there is one, the entries after
-swmi_shutdown, and for the striped pair the domain rule, the launcher a shape reaches and the carry."""
+swmi_shutdown, and for the six striped families the top of their range (the domain rule's edge, or for the long local pair,
+which has no rule, the int8 extremes at 65536 x 65536), the launcher a shape reaches and the carry."""
 import glob
 import os
 import shutil
@@ -17,10 +18,11 @@ import pytest
 from conftest import PKG, ROOT
 
 # ": ok" lines per family: refusals, timer order, slices_for, 8 host and 5 device cases, timer, shutdown = 18; the release
-# adds 3 (a device case, a host case, its own line); a mask runs every host case twice (+ 8); the striped pair adds its
-# domain rule, 4 host and 4 device cases (+ 9)
+# adds 3 (a device case, a host case, its own line); a mask runs every host case twice (+ 8); a striped family adds the top
+# of its range (the domain rule, or that it has none), 8 routing host cases and 6 device cases (+ 15)
 OK_LINES = {"local": 18, "sgfull": 21, "local_affine": 18, "sgfull_affine": 21, "local_full": 21, "local_full_affine": 21,
-            "global_full": 29, "global_full_affine": 29, "global_long": 38, "global_long_affine": 38}
+            "global_full": 29, "global_full_affine": 29, "global_long": 44, "global_long_affine": 44, "local_long": 36,
+            "local_long_affine": 36, "semiglobal_long": 36, "semiglobal_long_affine": 36}
 
 
 @pytest.fixture(scope="module")
