@@ -152,6 +152,16 @@ constexpr int *carry = nullptr;
 constexpr int2 *carry_hf = nullptr;
 constexpr int kStripeCols = 64 * 16 * 16;   // kMaxWaves x 64 lanes x kCols columns (asserted below)
 
+// Where a cell's substitution score comes from (wide_affine_kernels.hip): a kernel that shadows WIDE with
+// true scores over 32 letters.  It names `wide_sm`, the 32 x 32 int8 matrix in device memory, and `wide_prof`, its profile in
+// LDS: per wave 32 letter rows of 64 lanes x 16 bytes, a lane's 16 column scores of letter a at wide_prof[(32 w + a) 64 + l],
+// which the lane itself builds before its sweep and reads back a row at a time (wide_row below), one trip ahead of use.  Such
+// a kernel has no `cols`, so it names an empty one; the walk's staging block takes the profile's place after the sweep's last
+// barrier.  What every other kernel sees (the affine body alone reads these names):
+constexpr bool WIDE = false;
+constexpr const int8_t *wide_sm = nullptr;
+constexpr uint4 *wide_prof = nullptr;
+
 // The end rule (above).  The flags are SWMI_FREE_* of include/swmi.h, which no kernel file includes.
 constexpr unsigned kFreeBegin1 = 1, kFreeBegin2 = 2, kFreeEnd1 = 4, kFreeEnd2 = 8;
 constexpr unsigned free_ends = 0;      // what a kernel without the argument sees
@@ -200,6 +210,16 @@ __device__ __forceinline__ int base_shift(const uint8_t *s1, int idx, int len1)
     const int c = idx < 0 ? 0 : idx >= len1 ? len1 - 1 : idx;
     return 8 * (s1[c] & 3);
 }
+
+// A WIDE kernel's form of it: 64 * (seq1[idx] & 31), the letter's row in the lane's view of the profile (in uint4)
+__device__ __forceinline__ int wide_row(const uint8_t *s1, int idx, int len1)
+{
+    const int c = idx < 0 ? 0 : idx >= len1 ? len1 - 1 : idx;
+    return 64 * (s1[c] & 31);
+}
+
+// dword x (a constant) of a profile row
+__device__ __forceinline__ uint32_t wide_dword(const uint4 &v, int x) { return x == 0 ? v.x : x == 1 ? v.y : x == 2 ? v.z : v.w; }
 
 // The carry entry that a lane of a striped kernel's wave 0 loads for the row `idx` + 1, clamped into the buffer.  Only lane
 // 0's value is used (it is from_left's `edge`), and lane 0 asks for the row it needs; the other lanes' indices run backwards

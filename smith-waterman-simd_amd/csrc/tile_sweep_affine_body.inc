@@ -4,8 +4,10 @@
 // counts, move_words, n_trips and its template parameter TB.  A kernel with a ragged form also names RAGGED and slot, and
 // then len1, len2 and n_trips are the slot's (tile_sweep.h).  A kernel whose variant has the end rule (kEndRule<V>,
 // tile_sweep.h) also names free_ends.  A kernel that sweeps column stripes shadows STRIPED and kEndBias and names `carry_hf`
-// (tile_sweep.h; tile_sweep_body.inc tells the stripe loop, which is the same here with (H, F) pairs in the carry).  Text and
-// not a function on purpose: tile_sweep.h says why.
+// (tile_sweep.h; tile_sweep_body.inc tells the stripe loop, which is the same here with (H, F) pairs in the carry).  A kernel
+// over 32 letters shadows WIDE and names wide_sm and wide_prof (tile_sweep.h, wide_affine_kernels.hip): where a cell's score
+// comes from is the one thing that changes, and every `if constexpr (WIDE)` below is that.  Text and not a function on purpose:
+// tile_sweep.h says why.
 //
 // E runs down a column and stays with the lane; F runs along the row, so what lane l - 1 hands over (and lane 63 through
 // the ring) is its H(i, 16 G) AND its F(i, 16 G): two v_mov_b32_dpp wave_shr:1 per step, (H, F) pairs in the ring.  With a
@@ -24,7 +26,9 @@
     __shared__ int2 ring[(kMaxWaves - 1) * kRing];
     __shared__ unsigned long long red[kMaxWaves];
     __shared__ int walk_at[V::kWalkStops ? 3 : 2];
-    __shared__ unsigned long long stage[TB ? kStageRows * kStageLanes : 1];
+    // (a WIDE kernel stages the walk's blocks where its profile lay: nothing reads the profile after the sweep's last barrier)
+    __shared__ unsigned long long stage_lds[TB && !WIDE ? kStageRows * kStageLanes : 1];
+    unsigned long long *const stage = WIDE ? reinterpret_cast<unsigned long long *>(wide_prof) : stage_lds;
 
     const int W = blockDim.x >> 6;
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
@@ -86,11 +90,30 @@
 #pragma unroll
     for (int jj = 0; jj < kCols; ++jj) {
         const int j = jbase + jj + 1;
-        const uint32_t b = s2[j <= len2 ? j - 1 : 0] & 3u;
-        prof[jj] = j > len2 ? 0x80808080u : b == 0 ? cols.c[0] : b == 1 ? cols.c[1] : b == 2 ? cols.c[2] : cols.c[3];
+        if constexpr (WIDE) {
+            prof[jj] = s2[j <= len2 ? j - 1 : 0] & 31u;     // the column's letter, for the profile below
+        } else {
+            const uint32_t b = s2[j <= len2 ? j - 1 : 0] & 3u;
+            prof[jj] = j > len2 ? 0x80808080u : b == 0 ? cols.c[0] : b == 1 ? cols.c[1] : b == 2 ? cols.c[2] : cols.c[3];
+        }
         key[jj] = V::row0(jj, j, open_row0, ext_row0);
         if constexpr (STRIPED && !kEndRule<V>) key[jj] |= row0_zero;
         e[jj] = kMinusInf;
+    }
+    // WIDE: the lane's 16 bytes of every letter's profile row, from the matrix (columns past len2: -128).  A lane reads back
+    // only what it wrote itself, so the profile needs no barrier.
+    [[maybe_unused]] const uint4 *const prof_lane = wide_prof + (WIDE ? w * (32 * 64) + l : 0);
+    if constexpr (WIDE) {
+#pragma unroll 1
+        for (int a = 0; a < 32; ++a) {
+            uint32_t d[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int jj = 0; jj < kCols; ++jj) {
+                const uint32_t v = jbase + jj + 1 > len2 ? 0x80u : (uint32_t)(uint8_t)wide_sm[a * 32 + (int)prof[jj]];
+                d[jj >> 2] |= v << (8 * (jj & 3));
+            }
+            wide_prof[(w * 32 + a) * 64 + l] = make_uint4(d[0], d[1], d[2], d[3]);
+        }
     }
     // end rule: the border cells (0, len2) and (len1, 0) are closed forms; thread 0 holds them as candidates from here on (in
     // two VGPRs: kept as scalars until after the sweep, the borders' gaps cost SGPRs that the traceback kernel has not got)
@@ -128,7 +151,17 @@
 
     int sh_next[kUnroll];
 #pragma unroll
-    for (int t = 0; t < kUnroll; ++t) sh_next[t] = base_shift(s1, t - l, len1);
+    for (int t = 0; t < kUnroll; ++t) sh_next[t] = WIDE ? wide_row(s1, t - l, len1) : base_shift(s1, t - l, len1);
+    // WIDE: sh_next holds the rows' places in the profile, two trips ahead, and pr_next the profile rows themselves, one trip
+    // ahead: the LDS read of a row is issued a trip before the row's first cell, behind the load of its letter a trip earlier
+    [[maybe_unused]] uint4 pr_next[kUnroll];
+    if constexpr (WIDE) {
+#pragma unroll
+        for (int t = 0; t < kUnroll; ++t) {
+            pr_next[t] = prof_lane[sh_next[t]];
+            sh_next[t] = wide_row(s1, kUnroll + t - l, len1);
+        }
+    }
 
     for (int c = 0; c < total_chunks; ++c) {
         const int lc = c - kDelay * w;
@@ -137,10 +170,17 @@
                 const int s0 = lc * kChunk + q * kUnroll;
                 int sh[kUnroll], bound_h[kUnroll], bound_f[kUnroll], edge_h[kUnroll], edge_f[kUnroll];
                 uint32_t cw[kUnroll], co[kUnroll];
+                [[maybe_unused]] uint4 pr[kUnroll];
 #pragma unroll
                 for (int t = 0; t < kUnroll; ++t) {
-                    sh[t] = sh_next[t];
-                    sh_next[t] = base_shift(s1, s0 + kUnroll + t - l, len1);
+                    if constexpr (WIDE) {
+                        pr[t] = pr_next[t];
+                        pr_next[t] = prof_lane[sh_next[t]];
+                        sh_next[t] = wide_row(s1, s0 + 2 * kUnroll + t - l, len1);
+                    } else {
+                        sh[t] = sh_next[t];
+                        sh_next[t] = base_shift(s1, s0 + kUnroll + t - l, len1);
+                    }
                     // lane 0's left column for row s0 + t + 1: the ring, or the border's H and F = -inf
                     if (w > 0) {
                         const int2 v = ring_in[(s0 + t) & (kRing - 1)];
@@ -200,7 +240,8 @@
                         }
 #pragma unroll
                         for (int jj = 0; jj < kCols; ++jj) {
-                            const int sc = __builtin_amdgcn_sbfe((int)prof[jj], sh[t], 8);
+                            const int sc = WIDE ? __builtin_amdgcn_sbfe((int)wide_dword(pr[t], jj >> 2), 8 * (jj & 3), 8)
+                                                : __builtin_amdgcn_sbfe((int)prof[jj], sh[t], 8);
                             const int ev = imax(key[jj] + g_open, e[jj] + g_ext);
                             const int fv = imax(lft + g_open, f + g_ext);
                             int ec = ev, fc = fv;

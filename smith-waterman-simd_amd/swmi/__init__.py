@@ -1206,3 +1206,4 @@ from . import global_long      # noqa: E402  (the global aligners for lengths up
 from . import local_long       # noqa: E402  (the local aligners for lengths up to 65536, likewise a submodule)
 from . import semiglobal_long  # noqa: E402  (the exact semi-global aligners for lengths up to 65536, likewise a submodule)
 from . import semiglobal_ragged  # noqa: E402  (the exact semi-global aligners on mixed-shape batches, likewise a submodule)
+from . import wide             # noqa: E402  (the wide-alphabet aligners of libswmi_wide.so, likewise a submodule)
