@@ -337,7 +337,8 @@ sw128_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ seq2
 // kernels keep f16 denormals; tools/experiments/pk_max3_probe.hip checks the claim on 1M random triples).  Two cells' max3
 // in one half-rate instruction (v_max3_i32 does one) is what makes 16-bit packing pay on this VALU -- with v_pk_max_i16
 // alone it only ties with the int32 cell.  Every value of the gap-folded recurrence is kept
-// non-negative and below 16 768 by working on values SHIFTED by a bias Q:
+// non-negative and below 16 768 (this biased form; each body's largest value is in DESIGN.md 5.1) by working on values
+// SHIFTED by a bias Q:
 //     sc = s + gap + Q >= 0            (Q = max(0, -(min s + gap)); one byte: s + gap + Q <= 255 for every int8 matrix)
 //     t  = H(i-1,j-1) + sc             (the folded diagonal term + Q: a plain add, never negative)
 //     x  = max3(left + Q, up + Q, t)   (= the unshifted x + Q)

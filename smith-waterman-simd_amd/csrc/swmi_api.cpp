@@ -187,9 +187,9 @@ LaunchConfig make_config(const Context &ctx, const int8_t *sm, int gap, SmRows *
             lowest = int(sm[k]) < lowest ? int(sm[k]) : lowest;
             highest = int(sm[k]) > highest ? int(sm[k]) : highest;
         }
-        // Which cell body (sw_kernels.hip PkVariant; tests/test_gpu_pk_kernels.py restates the rule):
+        // Which cell body (sw_kernels.hip PkVariant; tests/pk_edges.py restates the rule and holds sets on both sides of each bound):
         //   0  every s + gap >= 0: nothing to bias
-        //   2  every s + 2 gap in [0, 255] and the largest value of the vertical-offset form, 128 max(s) + gap * 34 + 255,
+        //   2  every s + 2 gap in [0, 255] and the largest value of the vertical-offset form, 128 max(s) + gap * 34 + 256,
         //      stays a finite half-precision pattern (< 0x7C00): rows carry s + 2 gap
         //   1  anything else: values shifted by Q = -(min s + gap)
         int add = gap;

@@ -49,9 +49,11 @@ while time.time() < t_end:
     elif kind == 2: sm = rng.integers(-128, 128, 16).astype(np.int8); gap = int(rng.integers(0, 128))
     elif kind == 3: sm = rng.integers(-12, 13, 16).astype(np.int8); gap = int(rng.integers(0, 9))
     else:                    # every score + 2 gap in [0, 255], some score + gap < 0: the packed kernel's vertical-offset cell
-        gap = int(rng.integers(1, 61))
+        gap = int(rng.integers(1, 65))   # up to 64, where -128 + 2 gap = 0 and 127 + 2 gap = 255: both ends of the row byte
         sm = rng.integers(-2 * gap, min(127, 255 - 2 * gap) + 1, 16).astype(np.int8)
-        sm[int(rng.integers(0, 16))] = -2 * gap
+        lo_at, hi_at = (int(k) for k in rng.choice(16, 2, replace=False))
+        sm[lo_at] = -2 * gap
+        if 255 - 2 * gap <= 127: sm[hi_at] = 255 - 2 * gap
     L = [4, 4, 8, 4, 16, 2, 4, 32, 64][rounds % 9]      # L = 4 (the packed kernel unless a flag says otherwise) meets every parameter family
     swmi.set_schedule(L, int((0, 0, 1, 8)[int(rng.integers(0, 4))]))
     swmi.generate_pairs_device(d1.data_ptr(), d2.data_ptr(), n, seed, first, st)

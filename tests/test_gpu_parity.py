@@ -89,6 +89,8 @@ def test_packed_kernel_for_non_negative_folded_scores(gpu, oracle, seed):
 
 
 def test_domain_edges(gpu, oracle):
+    """The extreme matrices under the automatic schedule, which at 2 048 pairs runs the int32 kernel sw128_kernel<64,...>;
+    the packed kernel's three cell bodies meet their own domain edges, chosen by name, in test_gpu_pk_edges.py."""
     rng = np.random.default_rng(5)
     a = rng.integers(0, 4, (2048, 128), dtype=np.uint8)
     b = a.copy()

@@ -1,7 +1,7 @@
 """Every shipped instantiation of the packed kernel sw128_pk_kernel<MODE, VARIANT, L> against REFERENCE fixtures, by name.
 
 MODE 0 = pairs, 1 = 2-bit packed input, 2 = one-vs-many; VARIANT = the cell body the host picks from the parameters
-(`expected_variant` below restates the rule of swmi_api.cpp make_config from the header's description, independently);
+(`expected_variant` of pk_edges.py restates the rule of swmi_api.cpp make_config from the header's description, independently);
 L = lanes per pair of alignments (4, 8, 16).  Each test asks the library which instantiation a launch runs
 (swmi_score_kernel_for_batch) and requires it to be the one in the test id, so a change of the dispatch rule cannot
 silently leave an instantiation untested.  Scores: F1 / F4 (the reference's scalar with its SIMD variants agreeing,
@@ -13,29 +13,9 @@ Also here: the exhaustive self-test of the premise the packed kernel rests on (v
 import numpy as np
 import pytest
 
+from pk_edges import MODES, VARIANTS, expected_name, expected_variant      # the dispatch rule, restated there
+
 pytestmark = pytest.mark.gpu
-
-MODES = {"pairs": 0, "packed2bit": 1, "one_vs_many": 2}
-VARIANTS = ("q0", "bias", "vert")      # template argument 0, 1, 2
-
-
-def expected_variant(sm, gap):
-    """The packed cell body for these parameters (include/swmi.h, "schedules"):
-    q0    every sm + gap >= 0: no bias at all
-    vert  some sm + gap < 0 but every sm + 2 gap in [0, 255] and the row offsets fit: vertical-offset form
-    bias  everything else: values shifted by Q = -(min sm + gap)"""
-    sm = np.asarray(sm, np.int32)
-    gap = int(gap)
-    if sm.min() + gap >= 0:
-        return "q0"
-    if sm.min() + 2 * gap >= 0 and sm.max() + 2 * gap <= 255 and 128 * max(0, int(sm.max())) + 34 * gap + 256 < 0x7C00:
-        return "vert"
-    return "bias"
-
-
-def expected_name(mode, variant, lanes):
-    v = VARIANTS.index(variant)
-    return "sw128_pk_kernel<%d,%d>" % (mode, v) if lanes == 4 else "sw128_pk_kernel<%d,%d,%d>" % (mode, v, lanes)
 
 
 def param_sets(f, variant, key_sm="sm", key_gap="gap"):
