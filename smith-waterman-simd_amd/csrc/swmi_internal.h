@@ -168,7 +168,7 @@ struct TileWork {
     uint64_t move_base;     // moves at d_moves + move_base: SWMI_LOCAL_FULL_MOVE_WORDS(len1, len2) words
     uint32_t k;             // results at index k
     uint32_t len1, len2;    // 0 .. 16384 each
-    uint32_t pad;
+    uint32_t pad;           // 0; a ragged STRIPED kernel's slot (wide_long_affine_kernels.hip): its carry block, in units of carry_stride
 };
 
 // The wave count of a slot's workgroup, 1 .. 16: one wavefront per 1024 columns; a slot with a zero length runs (and returns

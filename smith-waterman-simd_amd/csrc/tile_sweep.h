@@ -150,6 +150,9 @@ constexpr TileWork slot{};
 constexpr bool STRIPED = false;
 constexpr int *carry = nullptr;
 constexpr int2 *carry_hf = nullptr;
+// (a kernel that is RAGGED and STRIPED -- wide_long_affine_kernels.hip -- also names `carry_stride`: slot.pad * carry_stride
+// entries into carry_hf lies the slot's carry block, for the slots of one launch differ in len1)
+constexpr uint32_t carry_stride = 0;
 constexpr int kStripeCols = 64 * 16 * 16;   // kMaxWaves x 64 lanes x kCols columns (asserted below)
 
 // Where a cell's substitution score comes from (wide_affine_kernels.hip): a kernel that shadows WIDE with

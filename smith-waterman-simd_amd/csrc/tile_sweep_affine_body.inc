@@ -4,7 +4,8 @@
 // counts, move_words, n_trips and its template parameter TB.  A kernel with a ragged form also names RAGGED and slot, and
 // then len1, len2 and n_trips are the slot's (tile_sweep.h).  A kernel whose variant has the end rule (kEndRule<V>,
 // tile_sweep.h) also names free_ends.  A kernel that sweeps column stripes shadows STRIPED and kEndBias and names `carry_hf`
-// (tile_sweep.h; tile_sweep_body.inc tells the stripe loop, which is the same here with (H, F) pairs in the carry).  A kernel
+// (tile_sweep.h; tile_sweep_body.inc tells the stripe loop, which is the same here with (H, F) pairs in the carry); one that is
+// RAGGED as well names `carry_stride` and finds its carry block through slot.pad (wide_long_affine_kernels.hip).  A kernel
 // over 32 letters shadows WIDE and names wide_sm and wide_prof (tile_sweep.h, wide_affine_kernels.hip): where a cell's score
 // comes from is the one thing that changes, and every `if constexpr (WIDE)` below is that.  Text and not a function on purpose:
 // tile_sweep.h says why.
@@ -57,7 +58,10 @@
     // barriers in every stripe but the last and total_chunks in the last, whatever w and the stripe's valid width); the
     // carry holds the last column's stored key AND its F, so a gap that opened left of the stripe's edge extends across it.
     // A local variant's best cell of each stripe is folded into r as in the linear body.
-    [[maybe_unused]] int2 *const carry_k = STRIPED ? carry_hf + k * (size_t)len1 : nullptr;
+    // (a RAGGED striped kernel's slots differ in len1: each names its carry block, slot.pad, in units of the launch's carry_stride)
+    [[maybe_unused]] int2 *const carry_k = !STRIPED ? nullptr
+                                           : RAGGED ? carry_hf + (size_t)slot.pad * (size_t)carry_stride
+                                                    : carry_hf + k * (size_t)len1;
     unsigned long long r = 0;                           // best cell so far: (H desc, row asc, column asc)
     // A striped kernel without the end rule (a local variant) keeps its best cell so far per wave in red[w], not in r: two VGPRs
     // that it has not got across the sweep.  Only lane 0 of wave w touches red[w] before the last barrier.
@@ -69,7 +73,7 @@
     do {
     // (a striped kernel's per-stripe tid, w and l: opaque_lane, tile_sweep.h; they shadow the workgroup's, which they equal)
     const int tid = opaque_lane<STRIPED>((int)threadIdx.x), w = tid >> 6, l = tid & 63;
-    const int G = STRIPED ? stripe * (64 * kMaxWaves) + tid : tid;
+    const int G = STRIPED ? stripe * (kStripeCols / kCols) + tid : tid;   // (lanes per stripe: not 64 kMaxWaves, which sizes the ring)
     const int gw = STRIPED ? G >> 6 : w;                // the wave of G in the code layout
     // whether another stripe follows (nothing but len2 and `stripe` is kept across the sweep: the kernels have no SGPRs to spare)
     const bool more_stripes = STRIPED && (stripe + 1) * kStripeCols < len2;

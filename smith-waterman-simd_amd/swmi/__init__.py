@@ -1207,3 +1207,4 @@ from . import local_long       # noqa: E402  (the local aligners for lengths up 
 from . import semiglobal_long  # noqa: E402  (the exact semi-global aligners for lengths up to 65536, likewise a submodule)
 from . import semiglobal_ragged  # noqa: E402  (the exact semi-global aligners on mixed-shape batches, likewise a submodule)
 from . import wide             # noqa: E402  (the wide-alphabet aligners of libswmi_wide.so, likewise a submodule)
+from . import wide_long        # noqa: E402  (the wide-alphabet aligners for lengths up to 65536, libswmi_wide_long.so, likewise)
