@@ -1,16 +1,20 @@
-// wide_api.cpp -- the C entries of libswmi_wide.so (include/swmi_wide.h): the wide-alphabet local and
-// global aligners on a batch of mixed (len1, len2).  Self-contained: no Context of libswmi.so, no swmi_init -- every entry runs
-// on the calling thread's current HIP device, with this file's own workspaces per (device, stream), its own two streams and
-// buffer sets per device for the host entries, and its own thread-local error text.  Of libswmi.so it calls one public
-// function, swmi_local_full_ragged_move_offsets (the one move layout).  The planner is DESIGN.md section 19's, as
-// tile_ragged_api.cpp has it: slices contiguous in caller order within a byte budget, inside a slice one launch per wave
-// count, widest first, longest seq1 first, results at caller positions.  This file's name lies outside csrc/swmi_*.cpp, which
-// four host-only test programs glob.
-#include "../../include/swmi_wide.h"
-#include "wide_internal.h"
+// wide_api.cpp -- the C entries of libswmi_wide.so (include/swmi_wide.h) and, compiled a second time
+// with -DSWMI_WIDE_LONG_LIBRARY, of libswmi_wide_long.so (include/swmi_wide_long.h, section 30): the wide-alphabet local and
+// global aligners on a batch of mixed (len1, len2).  Everything in which the two libraries differ stands in the one block
+// below the error text (section 31); nothing after it tests the define.  Self-contained: no Context of libswmi.so, no swmi_init -- every entry runs on the calling thread's
+// current HIP device, with this file's own workspaces per (device, stream), its own two streams and buffer sets per device for
+// the host entries, and its own thread-local error text.  Of libswmi.so, linked for the callers' expander, it calls nothing:
+// the move layout is a sum of SWMI_LOCAL_LONG_MOVE_WORDS that this file makes itself.  The planner is DESIGN.md section 19's,
+// as tile_ragged_api.cpp has it, with a class of slots in front of the wave counts: slices contiguous in caller order within
+// a byte budget; inside a slice the alignments that the striped kernels of wide_long_affine_kernels.hip take
+// (wide_long_internal.h) in one launch of the process's stripe width, then one launch of wide_affine_kernels.hip per wave
+// count, widest first, longest seq1 first, results at caller positions.  A striped slot of more than 1024 columns owns a carry
+// block behind the slice's codes.  This file's name lies outside csrc/swmi_*.cpp, which four host-only test programs glob.
+#include "wide_long_internal.h"
 
 #include <algorithm>
 #include <array>
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -34,6 +38,88 @@ int fail(int code, const char *fmt, ...)
     return code;
 }
 
+int check_both(const uint64_t *off1, const uint64_t *off2, size_t n);
+void fill_move_offsets(const uint64_t *off1, const uint64_t *off2, size_t n, uint64_t *out);
+
+}  // namespace
+}  // namespace wide
+}  // namespace swmi
+
+// ---- what the two libraries differ in: the public header, the prefix of the exported names, the limits on len1 and len2,
+// ---- the traceback budget, and whether there is a striped class of slots with its width rule and its two entries ----
+#ifdef SWMI_WIDE_LONG_LIBRARY
+#include "../../include/swmi_wide_long.h"
+#define WIDE_ENTRY(name) swmi_wide_long_##name
+
+namespace swmi {
+namespace wide {
+namespace {
+constexpr size_t kMaxLen1 = SWMI_WIDE_LONG_MAX_LEN, kMaxLen2 = SWMI_WIDE_LONG_MAX_LEN;
+// a traceback slice: what this many of the largest shape take (section 23's affine figure)
+constexpr size_t kTbSliceAlignments = 16;
+constexpr bool kHasStriped = true;
+static_assert(kWideLongMaxLen == SWMI_WIDE_LONG_MAX_LEN && SWMI_WIDE_LONG_LOCAL == SWMI_WIDE_LOCAL && SWMI_WIDE_LONG_GLOBAL == SWMI_WIDE_GLOBAL);
+
+// the stripe width of the process: 0 = the rule below
+std::atomic<int> g_width{0};
+
+// The stripe width of a launch of n striped slots (DESIGN.md section 30 has the measurement).  Either width keeps four
+// wavefronts on a CU, whose LDS holds four profiles: one workgroup of 4 or four of 1.  4 wavefronts finish an alignment four
+// times sooner and won every row of 256 alignments or fewer, by 3.6 - 3.9x; 1 wavefront has no barrier and no pipeline fill
+// and won the row of 4096, by 1.24 - 1.73x.  Between them nothing was measured: the rule turns where the launch fills every
+// slot of the machine at 1 wavefront, 256 CUs x 4 workgroups, which is supposed from the code.
+constexpr size_t kNarrowFrom = 1024;
+int stripe_width(size_t n)
+{
+    const int w = g_width.load(std::memory_order_relaxed);
+    if (w) return w;
+    return n >= kNarrowFrom ? 1 : 4;
+}
+}  // namespace
+}  // namespace wide
+}  // namespace swmi
+
+extern "C" int swmi_wide_long_set_stripe_waves(int waves)
+{
+    using namespace swmi;
+    bool shipped = waves == 0;
+    for (int w : kWideLongWidths) shipped = shipped || w == waves;
+    if (!shipped) return wide::fail(SWMI_ERR_INVALID_ARGUMENT, "stripe width %d is not shipped (0 = the library's rule, 1 or 4 wavefronts)", waves);
+    wide::g_width.store(waves, std::memory_order_relaxed);
+    return SWMI_OK;
+}
+
+extern "C" int swmi_wide_long_move_offsets(const uint64_t *seq1_offsets, const uint64_t *seq2_offsets, size_t n, uint64_t *move_offsets)
+{
+    using namespace swmi;
+    if (!move_offsets) return wide::fail(SWMI_ERR_INVALID_ARGUMENT, "move_offsets is NULL");
+    const int rc = wide::check_both(seq1_offsets, seq2_offsets, n);
+    if (rc != SWMI_OK) return rc;
+    wide::fill_move_offsets(seq1_offsets, seq2_offsets, n, move_offsets);
+    return SWMI_OK;
+}
+#else
+#include "../../include/swmi_wide.h"
+#define WIDE_ENTRY(name) swmi_wide_##name
+
+namespace swmi {
+namespace wide {
+namespace {
+constexpr size_t kMaxLen1 = SWMI_WIDE_MAX_LEN1, kMaxLen2 = SWMI_WIDE_MAX_LEN2;
+constexpr size_t kTbSliceAlignments = 256;               // a traceback slice: what this many of the largest shape take
+// No striped class: within these limits wide_long_striped is false for every shape, so no slot owns a carry block, and
+// libswmi_wide.so, which does not link wide_long_affine_kernels.o, names nothing of that file.
+constexpr bool kHasStriped = false;
+constexpr int stripe_width(size_t) { return 0; }         // (named in a discarded statement only)
+}  // namespace
+}  // namespace wide
+}  // namespace swmi
+#endif
+
+namespace swmi {
+namespace wide {
+namespace {
+
 #define WIDE_HIP_TRY(expr)                                                                                          \
     do {                                                                                                            \
         hipError_t e_ = (expr);                                                                                     \
@@ -43,22 +129,53 @@ int fail(int code, const char *fmt, ...)
 constexpr size_t kMatrixBytes = SWMI_WIDE_LETTERS * SWMI_WIDE_LETTERS;
 constexpr size_t kSliceBytes = size_t(256) << 20;        // an ends-only slice's device bytes
 constexpr size_t kMaxSlice = size_t(1) << 20;            // alignments per slice (and per launch)
-constexpr size_t kTbSliceAlignments = 256;               // a traceback slice: what this many of the largest shape take
+// classes of a slice's slots: the striped one where the library has it, then the unstriped wave counts 4 .. 1
+constexpr int kClasses = kWideMaxWaves + (kHasStriped ? 1 : 0);
+constexpr uint32_t kCarryUnit = 2;                       // int2 per unit of TileWork::pad: carry blocks start 16-byte aligned
 static_assert(kWideMaxLen1 == SWMI_WIDE_MAX_LEN1 && kWideMaxLen2 == SWMI_WIDE_MAX_LEN2);
+static_assert(kHasStriped || (kMaxLen1 <= size_t(kWideMaxLen1) && kMaxLen2 <= size_t(kWideMaxLen2)),
+              "without the striped class every accepted shape must be the unstriped kernels'");
 static_assert(sizeof(TileWork) == 48 && kMatrixBytes % 16 == 0);
+// one move layout for both libraries: the two macros of swmi.h are the same expression
+static_assert(SWMI_LOCAL_LONG_MOVE_WORDS(0, 0) == SWMI_LOCAL_FULL_MOVE_WORDS(0, 0) &&
+              SWMI_LOCAL_LONG_MOVE_WORDS(1, 0) == SWMI_LOCAL_FULL_MOVE_WORDS(1, 0) &&
+              SWMI_LOCAL_LONG_MOVE_WORDS(31, 2) == SWMI_LOCAL_FULL_MOVE_WORDS(31, 2) &&
+              SWMI_LOCAL_LONG_MOVE_WORDS(300, 1025) == SWMI_LOCAL_FULL_MOVE_WORDS(300, 1025) &&
+              SWMI_LOCAL_LONG_MOVE_WORDS(16384, 4096) == SWMI_LOCAL_FULL_MOVE_WORDS(16384, 4096));
 
 // ---- the planner ----
-size_t code_qwords(size_t len1, size_t len2) { return len1 && len2 ? wide_affine_code_qwords((int)len1, (int)len2) : 0; }
+// whether the striped kernels take the alignment
+bool striped(size_t len1, size_t len2) { return kHasStriped && wide_long_striped(len1, len2); }
 
-// device bytes one alignment of a slice takes: inputs, its slot, results, and with a traceback codes, moves and count
+size_t code_qwords(size_t len1, size_t len2)
+{
+    if (!len1 || !len2) return 0;
+    if constexpr (kHasStriped)
+        if (striped(len1, len2)) return wide_long_code_qwords((int)len1, (int)len2);
+    return wide_affine_code_qwords((int)len1, (int)len2);
+}
+
+// whether the slot owns a carry block: a striped slot of more than one stripe at the narrowest width shipped (at a wider
+// stripe some of these blocks stay unused; the plan does not depend on the width)
+bool has_carry(size_t len1, size_t len2) { return striped(len1, len2) && len2 > size_t(1024 * kWideLongMinWidth); }
+
+// its units of TileWork::pad
+size_t carry_units(size_t len1) { return (len1 + kCarryUnit - 1) / kCarryUnit; }
+
+// the class of a slot: kClasses = striped (kWideMaxWaves + 1), else its unstriped wave count
+int slot_class(size_t len1, size_t len2) { return striped(len1, len2) ? kClasses : wide_ragged_waves((int)len1, (int)len2); }
+
+// device bytes one alignment of a slice takes: inputs, its slot, results, its carry (8 len1) where it has one, and with a
+// traceback codes, moves and count
 size_t ragged_bytes(bool tb, size_t len1, size_t len2)
 {
     size_t b = len1 + len2 + sizeof(TileWork) + 5 * sizeof(int32_t);
-    if (tb) b += code_qwords(len1, len2) * sizeof(uint64_t) + SWMI_LOCAL_FULL_MOVE_WORDS(len1, len2) * sizeof(uint64_t) + sizeof(uint32_t);
+    if (has_carry(len1, len2)) b += len1 * sizeof(int2);
+    if (tb) b += code_qwords(len1, len2) * sizeof(uint64_t) + SWMI_LOCAL_LONG_MOVE_WORDS(len1, len2) * sizeof(uint64_t) + sizeof(uint32_t);
     return b;
 }
 
-size_t budget(bool tb) { return tb ? kTbSliceAlignments * ragged_bytes(true, kWideMaxLen1, kWideMaxLen2) : kSliceBytes; }
+size_t budget(bool tb) { return tb ? kTbSliceAlignments * ragged_bytes(true, kMaxLen1, kMaxLen2) : kSliceBytes; }
 
 int check_offsets(const char *name, const uint64_t *off, size_t n, size_t max_len)
 {
@@ -74,8 +191,14 @@ int check_offsets(const char *name, const uint64_t *off, size_t n, size_t max_le
 
 int check_both(const uint64_t *off1, const uint64_t *off2, size_t n)
 {
-    const int rc = check_offsets("seq1_offsets", off1, n, SWMI_WIDE_MAX_LEN1);
-    return rc != SWMI_OK ? rc : check_offsets("seq2_offsets", off2, n, SWMI_WIDE_MAX_LEN2);
+    const int rc = check_offsets("seq1_offsets", off1, n, kMaxLen1);
+    return rc != SWMI_OK ? rc : check_offsets("seq2_offsets", off2, n, kMaxLen2);
+}
+
+void fill_move_offsets(const uint64_t *off1, const uint64_t *off2, size_t n, uint64_t *out)
+{
+    out[0] = 0;
+    for (size_t k = 0; k < n; ++k) out[k + 1] = out[k] + SWMI_LOCAL_LONG_MOVE_WORDS(off1[k + 1] - off1[k], off2[k + 1] - off2[k]);
 }
 
 // Slices of checked offsets: each the longest run from where the last one ended whose ragged_bytes fit the budget, at most
@@ -103,22 +226,22 @@ struct Plan {
     std::vector<uint64_t> move_offsets;         // n + 1
     std::vector<size_t> first;                  // slice s = alignments [first[s], first[s + 1])
     std::vector<TileWork> tiles;                // [n]: slice s's slots at [first[s], first[s + 1]), everything slice-relative
-    // per slice: the slots of wave count W lie at [start[kWideMaxWaves - W], start[kWideMaxWaves - W + 1]) of the slice's slots
-    std::vector<std::array<uint32_t, kWideMaxWaves + 1>> start;
+    // per slice: the slots of class C lie at [start[kClasses - C], start[kClasses - C + 1]) of the slice's slots
+    std::vector<std::array<uint32_t, kClasses + 1>> start;
     std::vector<size_t> code_qwords;            // per slice
-    size_t max_m = 0, max_seq1 = 0, max_seq2 = 0, max_codes = 0, max_moves = 0;   // the largest slice's
+    size_t max_m = 0, max_seq1 = 0, max_seq2 = 0, max_codes = 0, max_moves = 0, max_carry = 0;   // the largest slice's (carry: in int2)
     size_t slices() const { return first.size() - 1; }
 };
 
 // The plan of a checked batch.  Every TileWork offset and base is a 64-bit running sum relative to its slice; code bases run
-// in caller order.  Inside a slice: wave count descending, then len1 descending, then caller order (a stable sort).
+// in caller order; carry blocks run in slot order, TileWork::pad in units of kCarryUnit.  Inside a slice: class descending
+// (striped first), then len1 descending, then caller order (a stable sort).
 int make_plan(Plan &p, const uint64_t *off1, const uint64_t *off2, size_t n, bool tb)
 {
     p.off1 = off1;
     p.off2 = off2;
     p.move_offsets.assign(n + 1, 0);
-    if (tb && swmi_local_full_ragged_move_offsets(off1, off2, n, p.move_offsets.data()) != SWMI_OK)
-        return fail(SWMI_ERR_INVALID_ARGUMENT, "swmi_local_full_ragged_move_offsets: %s", swmi_last_error());
+    if (tb) fill_move_offsets(off1, off2, n, p.move_offsets.data());
     p.first = cut(off1, off2, n, tb);
     p.tiles.resize(n);
     p.start.resize(p.slices());
@@ -128,7 +251,7 @@ int make_plan(Plan &p, const uint64_t *off1, const uint64_t *off2, size_t n, boo
         const size_t a = p.first[s], b = p.first[s + 1];
         auto len1 = [&](size_t k) { return uint32_t(off1[k + 1] - off1[k]); };
         auto len2 = [&](size_t k) { return uint32_t(off2[k + 1] - off2[k]); };
-        auto waves = [&](size_t k) { return wide_ragged_waves((int)len1(k), (int)len2(k)); };
+        auto waves = [&](size_t k) { return slot_class(len1(k), len2(k)); };
         order.resize(b - a);
         for (size_t x = 0; x < b - a; ++x) order[x] = uint32_t(x);
         std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
@@ -141,15 +264,20 @@ int make_plan(Plan &p, const uint64_t *off1, const uint64_t *off2, size_t n, boo
             code_base[k - a] = codes;
             if (tb) codes += code_qwords(len1(k), len2(k));
         }
-        std::array<uint32_t, kWideMaxWaves + 1> &start = p.start[s];
+        std::array<uint32_t, kClasses + 1> &start = p.start[s];
         start.fill(uint32_t(b - a));
-        int next = kWideMaxWaves;                // the wave count whose start is to be written next
+        int next = kClasses;                     // the class whose start is to be written next
+        size_t carry = 0;                        // units of kCarryUnit
         for (size_t x = 0; x < b - a; ++x) {
             const size_t k = a + order[x];
-            for (; next >= waves(k); --next) start[kWideMaxWaves - next] = uint32_t(x);
+            for (; next >= waves(k); --next) start[kClasses - next] = uint32_t(x);
+            const bool owns = has_carry(len1(k), len2(k));
+            if (owns && carry + carry_units(len1(k)) > size_t(0xFFFFFFFFu)) return fail(SWMI_ERR_INVALID_ARGUMENT, "slice %zu: carry blocks past 2^32 units", s);
             p.tiles[a + x] = {off1[k] - off1[a], off2[k] - off2[a], code_base[k - a], p.move_offsets[k] - p.move_offsets[a],
-                              uint32_t(k - a), len1(k), len2(k), 0};
+                              uint32_t(k - a), len1(k), len2(k), owns ? uint32_t(carry) : 0u};
+            if (owns) carry += carry_units(len1(k));
         }
+        p.max_carry = std::max(p.max_carry, carry * kCarryUnit);
         p.code_qwords[s] = size_t(codes);
         p.max_m = std::max(p.max_m, b - a);
         p.max_seq1 = std::max(p.max_seq1, size_t(off1[b] - off1[a]));
@@ -167,14 +295,23 @@ struct Params {
     unsigned free_ends;
 };
 
-// the launches of slice s: one per wave count present, widest first, on the one stream
+// the launches of slice s on the one stream: the striped slots first, at the process's stripe width, then one launch per
+// unstriped wave count present, widest first
 hipError_t launch_slice(const Plan &p, size_t s, const Params &c, const uint8_t *s1, const uint8_t *s2, const TileWork *work,
                         const int8_t *d_sm, int32_t *scores, int32_t *ends, unsigned long long *codes, unsigned long long *moves,
-                        uint32_t *counts, hipStream_t st)
+                        uint32_t *counts, void *carry, hipStream_t st)
 {
     const auto &start = p.start[s];
+    if constexpr (kHasStriped) {
+        if (start[1] > start[0]) {
+            const size_t m = start[1] - start[0];
+            const hipError_t e = launch_wide_long_affine_ragged(c.kind, s1, s2, work + start[0], m, stripe_width(m), d_sm, c.gap_open, c.gap_extend,
+                                                                c.free_ends, scores, ends, codes, moves, counts, carry, kCarryUnit, st);
+            if (e != hipSuccess) return e;
+        }
+    }
     for (int waves = kWideMaxWaves; waves >= 1; --waves) {
-        const uint32_t a = start[kWideMaxWaves - waves], b = start[kWideMaxWaves - waves + 1];
+        const uint32_t a = start[kClasses - waves], b = start[kClasses - waves + 1];
         if (a == b) continue;
         const hipError_t e = launch_wide_affine_ragged(c.kind, s1, s2, work + a, size_t(b - a), waves, d_sm, c.gap_open, c.gap_extend,
                                                        c.free_ends, scores, ends, codes, moves, counts, st);
@@ -203,20 +340,21 @@ struct HostSet {
     unsigned long long *d_codes = nullptr, *d_moves = nullptr;
     uint32_t *d_counts = nullptr;
     TileWork *d_work = nullptr;
-    struct { size_t d1, d2, sm, scores, ends, codes, moves, counts, work; } have{};
+    int2 *d_carry = nullptr;
+    struct { size_t d1, d2, sm, scores, ends, codes, moves, counts, work, carry; } have{};
     size_t off = 0, m = 0;                          // slice in flight
     void release()
     {
         for (void *q : {(void *)d1, (void *)d2, (void *)d_sm, (void *)d_scores, (void *)d_ends, (void *)d_codes, (void *)d_moves,
-                        (void *)d_counts, (void *)d_work})
+                        (void *)d_counts, (void *)d_work, (void *)d_carry})
             if (q) (void)hipFree(q);
         if (stream) (void)hipStreamDestroy(stream);      // (made again by the next host call)
         *this = HostSet{};
     }
 };
 
-// a stream's workspace of the device entries -- codes of one slice, the matrix, the call's slots -- and the pinned copy of
-// matrix and slots that the upload reads; `done` is recorded behind the upload
+// a stream's workspace of the device entries -- codes of one slice, behind them its carry blocks, the matrix, the call's
+// slots -- and the pinned copy of matrix and slots that the upload reads; `done` is recorded behind the upload
 struct StreamSpace {
     unsigned char *dev = nullptr, *host = nullptr;
     size_t dev_bytes = 0, host_bytes = 0;
@@ -263,7 +401,7 @@ int current(DeviceState **out)
 
 // ---- the entries' bodies ----
 // The checks in the order of the 4-letter ragged entries: the mask, the matrix and the gaps, the moves / steps pair; then
-// n = 0, the buffers, and the lengths, which lie in the offsets.  1 = nothing to do.
+// n = 0, the buffers, the lengths, which lie in the offsets, and last the global kind's domain rule.  1 = nothing to do.
 int check_call(const Params &c, const void *seq1s, const uint64_t *off1, const void *seq2s, const uint64_t *off2, size_t n,
                const void *scores, const void *ends, const void *moves, const void *counts)
 {
@@ -276,7 +414,24 @@ int check_call(const Params &c, const void *seq1s, const uint64_t *off1, const v
         return fail(SWMI_ERR_INVALID_ARGUMENT, "moves and steps must both be given (traceback) or both be NULL (ends-only)");
     if (n == 0) return 1;
     if (!seq1s || !seq2s || !scores || !ends) return fail(SWMI_ERR_INVALID_ARGUMENT, "NULL buffer with n = %zu", n);
-    return check_both(off1, off2, n);
+    const int rc = check_both(off1, off2, n);
+    if (rc != SWMI_OK || c.kind != kWideGlobal) return rc;
+    // the global kind's domain rule (wide_long_affine_kernels.hip): P (len1 + len2) <= 2^23
+    static_assert(kHasStriped || 128 * (kMaxLen1 + kMaxLen2) <= (size_t(1) << 23),
+                  "without the striped class the rule must hold for every int8 matrix at the limits, so that it refuses nothing");
+    int lo = 0, hi = 0;                          // (two reductions the compiler vectorises; the short build pays for them too)
+    for (size_t x = 0; x < kMatrixBytes; ++x) {
+        lo = std::min(lo, int(c.sm[x]));
+        hi = std::max(hi, int(c.sm[x]));
+    }
+    const long P = std::max({1, c.gap_open, c.gap_extend, -lo, hi});
+    for (size_t k = 0; k < n; ++k) {
+        const unsigned long long total = (off1[k + 1] - off1[k]) + (off2[k + 1] - off2[k]);
+        if ((unsigned long long)P * total > (1ull << 23))
+            return fail(SWMI_ERR_INVALID_ARGUMENT, "alignment %zu is outside the domain: P (len1 + len2) = %ld x %llu > 2^23 (P = max(1, max |score_matrix|, gap_open, gap_extend))",
+                        k, P, total);
+    }
+    return SWMI_OK;
 }
 
 int run_device(const Params &c, const void *d_seq1s, const uint64_t *off1, const void *d_seq2s, const uint64_t *off2, size_t n,
@@ -299,7 +454,8 @@ int run_device(const Params &c, const void *d_seq1s, const uint64_t *off1, const
     // stream only: earlier launches on it may still use the old one)
     std::lock_guard<std::mutex> lock(ds->ws_mu);
     StreamSpace &sp = ds->spaces[st];
-    const size_t code_bytes = ((tb ? p.max_codes * sizeof(uint64_t) : 0) + 15) & ~size_t(15);
+    const size_t codes_only = ((tb ? p.max_codes * sizeof(uint64_t) : 0) + 15) & ~size_t(15);
+    const size_t code_bytes = codes_only + p.max_carry * sizeof(int2);       // (the carry: whole units of 16 bytes)
     const size_t up_bytes = kMatrixBytes + n * sizeof(TileWork);
     if (code_bytes + up_bytes > sp.dev_bytes) {
         WIDE_HIP_TRY(hipStreamSynchronize(st));
@@ -332,7 +488,7 @@ int run_device(const Params &c, const void *d_seq1s, const uint64_t *off1, const
         WIDE_HIP_TRY(launch_slice(p, s, c, s1 + off1[a], s2 + off2[a], work + a, d_sm, static_cast<int32_t *>(d_scores) + a,
                                   static_cast<int32_t *>(d_ends) + 4 * a, tb ? reinterpret_cast<unsigned long long *>(sp.dev) : nullptr,
                                   tb ? static_cast<unsigned long long *>(d_moves) + p.move_offsets[a] : nullptr,
-                                  tb ? static_cast<uint32_t *>(d_counts) + a : nullptr, st));
+                                  tb ? static_cast<uint32_t *>(d_counts) + a : nullptr, sp.dev + codes_only, st));
     }
     return SWMI_OK;
 }
@@ -365,6 +521,7 @@ int run_host(const Params &c, const char *entry, const uint8_t *seq1s, const uin
         if (rc == SWMI_OK) rc = grow(s.d_work, s.have.work, p.max_m);
         if (rc == SWMI_OK && tb) rc = grow(s.d_codes, s.have.codes, std::max<size_t>(p.max_codes, 2));
         if (rc == SWMI_OK && tb) rc = grow(s.d_moves, s.have.moves, std::max<size_t>(p.max_moves, 2));
+        if (rc == SWMI_OK && p.max_carry) rc = grow(s.d_carry, s.have.carry, p.max_carry);
         if (rc != SWMI_OK) return rc;
     }
     // results of the slice a set holds -> host, at the caller's positions
@@ -399,7 +556,7 @@ int run_host(const Params &c, const char *entry, const uint8_t *seq1s, const uin
         if (e == hipSuccess) e = hipMemcpyAsync(s.d_work, p.tiles.data() + a, s.m * sizeof(TileWork), hipMemcpyHostToDevice, s.stream);
         if (e == hipSuccess)
             e = launch_slice(p, sc, c, s.d1, s.d2, s.d_work, s.d_sm, s.d_scores, s.d_ends, tb ? s.d_codes : nullptr,
-                             tb ? s.d_moves : nullptr, tb ? s.d_counts : nullptr, s.stream);
+                             tb ? s.d_moves : nullptr, tb ? s.d_counts : nullptr, s.d_carry, s.stream);
         if (e == hipSuccess && n_sets == 2) e = drain(turn ^ 1);         // the previous slice, while this one computes
     }
     for (int k = 0; k < n_sets; ++k) {
@@ -420,11 +577,11 @@ using namespace swmi::wide;
 
 extern "C" {
 
-const char *swmi_wide_last_error(void) { return t_error; }
+const char *WIDE_ENTRY(last_error)(void) { return t_error; }
 
-int swmi_wide_version(void) { return SWMI_VERSION; }
+int WIDE_ENTRY(version)(void) { return SWMI_VERSION; }
 
-int swmi_wide_release_workspaces(void)
+int WIDE_ENTRY(release_workspaces)(void)
 {
     DeviceState *ds = nullptr;
     const int rc = current(&ds);
@@ -436,7 +593,7 @@ int swmi_wide_release_workspaces(void)
     return SWMI_OK;
 }
 
-size_t swmi_wide_slices_for(const uint64_t *seq1_offsets, const uint64_t *seq2_offsets, size_t n, int traceback, size_t *sizes, size_t cap)
+size_t WIDE_ENTRY(slices_for)(const uint64_t *seq1_offsets, const uint64_t *seq2_offsets, size_t n, int traceback, size_t *sizes, size_t cap)
 {
     if (check_both(seq1_offsets, seq2_offsets, n) != SWMI_OK) return 0;
     const std::vector<size_t> first = cut(seq1_offsets, seq2_offsets, n, traceback != 0);
@@ -444,42 +601,42 @@ size_t swmi_wide_slices_for(const uint64_t *seq1_offsets, const uint64_t *seq2_o
     return first.size() - 1;
 }
 
-int swmi_wide_local(const uint8_t *seq1s, const uint64_t *seq1_offsets, const uint8_t *seq2s, const uint64_t *seq2_offsets, size_t n,
-                    const int8_t score_matrix[1024], int gap_open, int gap_extend, int32_t *scores, int32_t *ends, uint64_t *moves,
-                    uint32_t *steps)
+int WIDE_ENTRY(local)(const uint8_t *seq1s, const uint64_t *seq1_offsets, const uint8_t *seq2s, const uint64_t *seq2_offsets, size_t n,
+                      const int8_t score_matrix[1024], int gap_open, int gap_extend, int32_t *scores, int32_t *ends, uint64_t *moves,
+                      uint32_t *steps)
 {
     return run_host({kWideLocal, score_matrix, gap_open, gap_extend, 0}, __func__, seq1s, seq1_offsets, seq2s, seq2_offsets, n, scores,
                     ends, moves, steps);
 }
 
-int swmi_wide_global(const uint8_t *seq1s, const uint64_t *seq1_offsets, const uint8_t *seq2s, const uint64_t *seq2_offsets, size_t n,
-                     const int8_t score_matrix[1024], int gap_open, int gap_extend, unsigned free_ends, int32_t *scores, int32_t *ends,
-                     uint64_t *moves, uint32_t *steps)
+int WIDE_ENTRY(global)(const uint8_t *seq1s, const uint64_t *seq1_offsets, const uint8_t *seq2s, const uint64_t *seq2_offsets, size_t n,
+                       const int8_t score_matrix[1024], int gap_open, int gap_extend, unsigned free_ends, int32_t *scores, int32_t *ends,
+                       uint64_t *moves, uint32_t *steps)
 {
     return run_host({kWideGlobal, score_matrix, gap_open, gap_extend, free_ends}, __func__, seq1s, seq1_offsets, seq2s, seq2_offsets, n,
                     scores, ends, moves, steps);
 }
 
-int swmi_wide_local_device(const void *d_seq1s, const uint64_t *seq1_offsets, const void *d_seq2s, const uint64_t *seq2_offsets,
-                           size_t n, const int8_t score_matrix[1024], int gap_open, int gap_extend, void *d_scores, void *d_ends,
-                           void *d_moves, void *d_steps, void *stream)
+int WIDE_ENTRY(local_device)(const void *d_seq1s, const uint64_t *seq1_offsets, const void *d_seq2s, const uint64_t *seq2_offsets,
+                             size_t n, const int8_t score_matrix[1024], int gap_open, int gap_extend, void *d_scores, void *d_ends,
+                             void *d_moves, void *d_steps, void *stream)
 {
     return run_device({kWideLocal, score_matrix, gap_open, gap_extend, 0}, d_seq1s, seq1_offsets, d_seq2s, seq2_offsets, n, d_scores,
                       d_ends, d_moves, d_steps, stream);
 }
 
-int swmi_wide_global_device(const void *d_seq1s, const uint64_t *seq1_offsets, const void *d_seq2s, const uint64_t *seq2_offsets,
-                            size_t n, const int8_t score_matrix[1024], int gap_open, int gap_extend, unsigned free_ends,
-                            void *d_scores, void *d_ends, void *d_moves, void *d_steps, void *stream)
+int WIDE_ENTRY(global_device)(const void *d_seq1s, const uint64_t *seq1_offsets, const void *d_seq2s, const uint64_t *seq2_offsets,
+                              size_t n, const int8_t score_matrix[1024], int gap_open, int gap_extend, unsigned free_ends,
+                              void *d_scores, void *d_ends, void *d_moves, void *d_steps, void *stream)
 {
     return run_device({kWideGlobal, score_matrix, gap_open, gap_extend, free_ends}, d_seq1s, seq1_offsets, d_seq2s, seq2_offsets, n,
                       d_scores, d_ends, d_moves, d_steps, stream);
 }
 
 // one untimed device call first (it grows the workspace, which synchronises the stream), then HIP events around `iters`
-int swmi_wide_time_device(int kind, const void *d_seq1s, const uint64_t *seq1_offsets, const void *d_seq2s, const uint64_t *seq2_offsets,
-                          size_t n, const int8_t score_matrix[1024], int gap_open, int gap_extend, unsigned free_ends, void *d_scores,
-                          void *d_ends, void *d_moves, void *d_steps, void *stream, int iters, float *avg_ms)
+int WIDE_ENTRY(time_device)(int kind, const void *d_seq1s, const uint64_t *seq1_offsets, const void *d_seq2s, const uint64_t *seq2_offsets,
+                            size_t n, const int8_t score_matrix[1024], int gap_open, int gap_extend, unsigned free_ends, void *d_scores,
+                            void *d_ends, void *d_moves, void *d_steps, void *stream, int iters, float *avg_ms)
 {
     if (kind != SWMI_WIDE_LOCAL && kind != SWMI_WIDE_GLOBAL) return fail(SWMI_ERR_INVALID_ARGUMENT, "kind %d is neither local nor global", kind);
     if (!avg_ms || iters < 1) return fail(SWMI_ERR_INVALID_ARGUMENT, "avg_ms is NULL or iters %d < 1", iters);

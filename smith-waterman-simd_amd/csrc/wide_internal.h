@@ -1,5 +1,5 @@
-// wide_internal.h -- what wide_affine_kernels.hip and wide_api.cpp (libswmi_wide.so, include/swmi_wide.h) share.  Nothing here
-// or in those two files knows the Context of libswmi.so.
+// wide_internal.h -- what wide_affine_kernels.hip and wide_api.cpp (libswmi_wide.so, include/swmi_wide.h, and
+// libswmi_wide_long.so, which links the same kernels) share.  Nothing here or in those two files knows the Context of libswmi.so.
 #pragma once
 #include "swmi_internal.h"
 

@@ -1,6 +1,7 @@
-// wide_long_internal.h -- what wide_long_affine_kernels.hip and wide_long_api.cpp (libswmi_wide_long.so,
-// include/swmi_wide_long.h) share beside wide_internal.h, whose unstriped launcher the library calls
-// for the shapes of libswmi_wide.so.
+// wide_long_internal.h -- what wide_long_affine_kernels.hip and wide_api.cpp as compiled for libswmi_wide_long.so
+// (include/swmi_wide_long.h, DESIGN.md sections 30 and 31) share beside wide_internal.h, whose unstriped launcher the library
+// calls for the shapes of libswmi_wide.so.  libswmi_wide.so's build of wide_api.cpp includes this header too and names
+// neither function declared here.
 #pragma once
 #include "wide_internal.h"
 

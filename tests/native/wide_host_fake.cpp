@@ -1,36 +1,56 @@
-// wide_host_fake.cpp -- the host side of the wide-alphabet aligners (csrc/wide_api.cpp, the whole of libswmi_wide.so's host
-// code) on a fake GPU (fake_hip.cpp), plus the stand-ins for what that file takes from elsewhere: the kernels' launcher, code
-// size and wave count (wide_affine_kernels.hip), hipGetDevice, and libswmi.so's swmi_local_full_ragged_move_offsets.  The code
-// workspaces take a constant 512 qwords per alignment, so a traceback slice is a thousand-odd alignments.  Built and run by
+// wide_host_fake.cpp -- the host side of the wide-alphabet aligners (csrc/wide_api.cpp, the whole host code of libswmi_wide.so
+// and, with -DSWMI_WIDE_LONG_LIBRARY on both files, of libswmi_wide_long.so) on a fake GPU (fake_hip.cpp), plus the stand-ins
+// for what that file takes from elsewhere: the launchers, code sizes and wave count (wide_affine_kernels.hip,
+// wide_long_affine_kernels.hip) and hipGetDevice.  The code workspaces take a constant 512 qwords per alignment, so a
+// traceback slice is a few thousand short alignments or a handful of long ones.  Built and run once per library by
 // tests/test_wide_host_fake.py (g++, ASan + UBSan, no GPU).
 //
 // A stand-in launch checks that the matrix in "device" memory, the gaps and the mask are the call's, and computes every slot's
 // results from ALL bytes of the sequences the slot names (so ASan sees a slot that points outside the buffers): score = 3 len1
 // + 5 len2 + sum(seq1) + 7 sum(seq2) + 1000 mask, ends[e] = score + e + 1, and with a traceback (sum(seq1) + sum(seq2)) %
 // (32 move_words + 1) moves and move word w = 0xC0DE << 48 | score << 16 | w in every word of its row; it writes the first and
-// last qword of the slot's codes (none for a slot with a zero length).  Every slot must have the wave count its launch was
-// given, len1 must not grow inside a launch, and the launches of one slice must come in descending wave count.  After a call
-// the driver checks every result at its caller position, that every alignment was launched once, and the sentinels behind
-// ends and moves.
+// last qword of the slot's codes (none for a slot with a zero length).  The UNSTRIPED stand-in insists that no slot is one the
+// striped kernels take (len1 > 16384 or len2 > 4096, no zero length), on the wave count and on the library's limits.  The
+// STRIPED stand-in, which only the long library's build has, insists on the opposite, that the width is the process's (the
+// rule: 4 below 1024 slots, else 1; or what swmi_wide_long_set_stripe_waves set), that the stride is the unit of 2, and it
+// writes the first and last int2 of the carry block of every slot of more than 1024 columns (ASan: inside the workspace) and
+// checks that the blocks of one launch are disjoint.  In a slice (one score buffer) the striped launch comes first, then the
+// wave counts in descending order; len1 never grows inside a launch.  After a call the driver checks every result at its
+// caller position, that every alignment was launched once, and the sentinels behind ends and moves.
 //
 // Cases: refusals before any device is touched; the host entry, both kinds, with a traceback split by the byte budget into at
-// least 3 slices and ends-only split by the count cap into 2; the device entry on two streams with a growing workspace; the
-// timer; the release, then the host entry again.
+// least 3 slices and ends-only split by the count cap into 2; in the long build a forced stripe width; the device entry on two
+// streams with a growing workspace; the timer; the release, then the host entry again.
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <vector>
 
+#include "../../smith-waterman-simd_amd/csrc/wide_long_internal.h"
+
+// ---- what the two builds differ in: the header, the prefix of the entries, the limits, the closing line ----
+#ifdef SWMI_WIDE_LONG_LIBRARY
+#include "../../include/swmi_wide_long.h"
+#define W(name) swmi_wide_long_##name
+constexpr bool kLong = true;
+constexpr uint32_t kMaxLen1 = swmi::kWideLongMaxLen, kMaxLen2 = swmi::kWideLongMaxLen;
+constexpr const char *kDone = "wide long host fake ok";
+#else
 #include "../../include/swmi_wide.h"
-#include "../../smith-waterman-simd_amd/csrc/wide_internal.h"
+#define W(name) swmi_wide_##name
+constexpr bool kLong = false;
+constexpr uint32_t kMaxLen1 = swmi::kWideMaxLen1, kMaxLen2 = swmi::kWideMaxLen2;
+constexpr const char *kDone = "wide host fake ok";
+#endif
 
 #define CHECK(cond)                                                                                                     \
     do {                                                                                                                \
         if (!(cond)) {                                                                                                  \
-            fprintf(stderr, "CHECK failed at line %d: %s (last error: %s)\n", __LINE__, #cond, swmi_wide_last_error()); \
+            fprintf(stderr, "CHECK failed at line %d: %s (last error: %s)\n", __LINE__, #cond, W(last_error)());      \
             exit(1);                                                                                                    \
         }                                                                                                               \
     } while (0)
@@ -55,7 +75,11 @@ static std::vector<Launch> g_launches;
 static size_t g_slots = 0;
 static bool g_check_order = true;      // off under the timer, whose calls in turn reuse one score buffer
 
-static size_t move_words(size_t a, size_t b) { return SWMI_LOCAL_FULL_MOVE_WORDS(a, b); }
+static size_t move_words(size_t a, size_t b) { return SWMI_LOCAL_LONG_MOVE_WORDS(a, b); }
+#ifdef SWMI_WIDE_LONG_LIBRARY
+static int g_width = 0;                // what swmi_wide_long_set_stripe_waves was given
+static size_t g_striped = 0, g_carried = 0;
+#endif
 
 struct Expected {
     int32_t score, ends[4];
@@ -79,26 +103,19 @@ extern "C" hipError_t hipGetDevice(int *d)
     return hipSuccess;
 }
 
-// libswmi.so's, which the wide library links
-extern "C" const char *swmi_last_error(void) { return "(stand-in)"; }
-extern "C" int swmi_local_full_ragged_move_offsets(const uint64_t *o1, const uint64_t *o2, size_t n, uint64_t *out)
-{
-    out[0] = 0;
-    for (size_t k = 0; k < n; ++k) out[k + 1] = out[k] + move_words(o1[k + 1] - o1[k], o2[k + 1] - o2[k]);
-    return SWMI_OK;
-}
-
 namespace swmi {
 size_t wide_affine_code_qwords(int, int) { return kCodeQwords; }
 int wide_ragged_waves(int len1, int len2) { return len1 == 0 || len2 == 0 ? 1 : (len2 + 1023) / 1024; }
 
-hipError_t launch_wide_affine_ragged(WideKind kind, const uint8_t *s1, const uint8_t *s2, const TileWork *work, size_t n, int waves,
-                                     const int8_t *d_sm, int open, int extend, unsigned free_ends, int32_t *scores, int32_t *ends,
-                                     unsigned long long *codes, unsigned long long *moves, uint32_t *steps, hipStream_t)
+// both stand-ins: `waves` = kWideMaxWaves + 1 names the striped launch
+static hipError_t fake_launch(WideKind kind, const uint8_t *s1, const uint8_t *s2, const TileWork *work, size_t n, int waves,
+                              const int8_t *d_sm, int open, int extend, unsigned free_ends, int32_t *scores, int32_t *ends,
+                              unsigned long long *codes, unsigned long long *moves, uint32_t *steps)
 {
+    const bool striped = waves == kWideMaxWaves + 1;
     CHECK(kind == g_kind && open == g_open && extend == g_extend && free_ends == (g_kind == kWideGlobal ? g_mask : 0u));
     CHECK(memcmp(d_sm, g_sm, sizeof g_sm) == 0);
-    CHECK(n >= 1 && n <= (size_t(1) << 20) && waves >= 1 && waves <= kWideMaxWaves);
+    CHECK(n >= 1 && n <= (size_t(1) << 20) && waves >= 1 && waves <= kWideMaxWaves + 1);
     CHECK((moves != nullptr) == (codes != nullptr) && (moves != nullptr) == (steps != nullptr));
     {
         std::lock_guard<std::mutex> l(g_mu);
@@ -110,8 +127,9 @@ hipError_t launch_wide_affine_ragged(WideKind kind, const uint8_t *s1, const uin
     uint32_t last_len1 = ~0u;
     for (size_t x = 0; x < n; ++x) {
         const TileWork w = work[x];
-        CHECK(wide_ragged_waves(int(w.len1), int(w.len2)) == waves);
-        CHECK(w.len1 <= last_len1 && w.len1 <= uint32_t(kWideMaxLen1) && w.len2 <= uint32_t(kWideMaxLen2));
+        CHECK(wide_long_striped(w.len1, w.len2) == striped);
+        CHECK(striped || (wide_ragged_waves(int(w.len1), int(w.len2)) == waves && w.pad == 0));
+        CHECK(w.len1 <= last_len1 && w.len1 <= kMaxLen1 && w.len2 <= kMaxLen2);
         last_len1 = w.len1;
         const bool empty = w.len1 == 0 || w.len2 == 0;
         // (a slot with a zero length reads neither sequence, as the kernel does)
@@ -125,6 +143,48 @@ hipError_t launch_wide_affine_ragged(WideKind kind, const uint8_t *s1, const uin
     }
     return hipSuccess;
 }
+
+hipError_t launch_wide_affine_ragged(WideKind kind, const uint8_t *s1, const uint8_t *s2, const TileWork *work, size_t n, int waves,
+                                     const int8_t *d_sm, int open, int extend, unsigned free_ends, int32_t *scores, int32_t *ends,
+                                     unsigned long long *codes, unsigned long long *moves, uint32_t *steps, hipStream_t)
+{
+    CHECK(waves <= kWideMaxWaves);
+    return fake_launch(kind, s1, s2, work, n, waves, d_sm, open, extend, free_ends, scores, ends, codes, moves, steps);
+}
+
+#ifdef SWMI_WIDE_LONG_LIBRARY
+size_t wide_long_code_qwords(int, int) { return kCodeQwords; }
+
+hipError_t launch_wide_long_affine_ragged(WideKind kind, const uint8_t *s1, const uint8_t *s2, const TileWork *work, size_t n, int width,
+                                          const int8_t *d_sm, int open, int extend, unsigned free_ends, int32_t *scores, int32_t *ends,
+                                          unsigned long long *codes, unsigned long long *moves, uint32_t *steps, void *d_carry,
+                                          uint32_t stride, hipStream_t)
+{
+    CHECK(width == (g_width ? g_width : n >= 1024 ? 1 : 4) && stride == 2);
+    // the carry blocks of the slots of more than 1024 columns: inside the workspace (ASan), disjoint inside the launch
+    std::vector<std::pair<size_t, size_t>> blocks;
+    int2 *carry = static_cast<int2 *>(d_carry);
+    for (size_t x = 0; x < n; ++x) {
+        const TileWork w = work[x];
+        if (w.len2 <= 1024) {
+            CHECK(w.pad == 0);
+            continue;
+        }
+        CHECK(carry != nullptr);
+        const size_t at = size_t(w.pad) * stride;
+        carry[at] = carry[at + w.len1 - 1] = int2{int(w.k), int(w.len1)};
+        blocks.push_back({at, at + w.len1});
+    }
+    std::sort(blocks.begin(), blocks.end());
+    for (size_t x = 1; x < blocks.size(); ++x) CHECK(blocks[x - 1].second <= blocks[x].first);
+    {
+        std::lock_guard<std::mutex> l(g_mu);
+        g_striped += n;
+        g_carried += blocks.size();
+    }
+    return fake_launch(kind, s1, s2, work, n, kWideMaxWaves + 1, d_sm, open, extend, free_ends, scores, ends, codes, moves, steps);
+}
+#endif
 }  // namespace swmi
 
 // ---- the driver ----
@@ -164,8 +224,8 @@ static int call_host(const Batch &b, bool tb, int32_t *sc, int32_t *en, uint64_t
     const uint8_t *s1 = b.s1.empty() ? reinterpret_cast<const uint8_t *>("") : b.s1.data();
     const uint8_t *s2 = b.s2.empty() ? reinterpret_cast<const uint8_t *>("") : b.s2.data();
     return g_kind == swmi::kWideLocal
-               ? swmi_wide_local(s1, b.o1.data(), s2, b.o2.data(), b.n(), g_sm, g_open, g_extend, sc, en, tb ? mv : nullptr, tb ? st : nullptr)
-               : swmi_wide_global(s1, b.o1.data(), s2, b.o2.data(), b.n(), g_sm, g_open, g_extend, g_mask, sc, en, tb ? mv : nullptr,
+               ? W(local)(s1, b.o1.data(), s2, b.o2.data(), b.n(), g_sm, g_open, g_extend, sc, en, tb ? mv : nullptr, tb ? st : nullptr)
+               : W(global)(s1, b.o1.data(), s2, b.o2.data(), b.n(), g_sm, g_open, g_extend, g_mask, sc, en, tb ? mv : nullptr,
                                   tb ? st : nullptr);
 }
 
@@ -175,7 +235,7 @@ static void host_case(const char *name, const Batch &b, bool tb, size_t min_slic
     std::vector<uint64_t> mv(b.mo.back() + 1, kSentinel);
     std::vector<uint32_t> st(b.n());
     std::vector<size_t> sizes(64);
-    const size_t slices = swmi_wide_slices_for(b.o1.data(), b.o2.data(), b.n(), tb, sizes.data(), sizes.size());
+    const size_t slices = W(slices_for)(b.o1.data(), b.o2.data(), b.n(), tb, sizes.data(), sizes.size());
     CHECK(slices >= min_slices);
     g_launches.clear();
     g_slots = 0;
@@ -205,15 +265,15 @@ static void device_case(const char *name, const Batch &b, bool tb, hipStream_t s
     g_launches.clear();
     g_slots = 0;
     const int rc = g_kind == swmi::kWideLocal
-                       ? swmi_wide_local_device(d1, b.o1.data(), d2, b.o2.data(), b.n(), g_sm, g_open, g_extend, sc, en, tb ? mv : nullptr,
+                       ? W(local_device)(d1, b.o1.data(), d2, b.o2.data(), b.n(), g_sm, g_open, g_extend, sc, en, tb ? mv : nullptr,
                                                 tb ? st : nullptr, stream)
-                       : swmi_wide_global_device(d1, b.o1.data(), d2, b.o2.data(), b.n(), g_sm, g_open, g_extend, g_mask, sc, en,
+                       : W(global_device)(d1, b.o1.data(), d2, b.o2.data(), b.n(), g_sm, g_open, g_extend, g_mask, sc, en,
                                                  tb ? mv : nullptr, tb ? st : nullptr, stream);
     CHECK(rc == SWMI_OK && g_slots == b.n());
     check_results(b, tb, sc, en, mv, st);
     float ms = 0.f;
     g_check_order = false;
-    CHECK(swmi_wide_time_device(g_kind == swmi::kWideLocal ? SWMI_WIDE_LOCAL : SWMI_WIDE_GLOBAL, d1, b.o1.data(), d2, b.o2.data(), b.n(), g_sm,
+    CHECK(W(time_device)(g_kind == swmi::kWideLocal ? SWMI_WIDE_LOCAL : SWMI_WIDE_GLOBAL, d1, b.o1.data(), d2, b.o2.data(), b.n(), g_sm,
                                 g_open, g_extend, g_mask, sc, en, tb ? mv : nullptr, tb ? st : nullptr, stream, 2, &ms) == SWMI_OK);
     CHECK(ms == 0.5f && g_slots == 4 * b.n());      // the fake's 1 ms over 2 calls; one untimed call before them
     g_check_order = true;
@@ -224,34 +284,56 @@ static void device_case(const char *name, const Batch &b, bool tb, hipStream_t s
 int main()
 {
     unsigned seed = 12345;
-    for (int x = 0; x < 1024; ++x) g_sm[x] = int8_t((seed = seed * 1664525u + 1013904223u) >> 24);
+    // (the long build: |entries| <= 60, so that with the gaps below P = 60 and the global kind's domain rule takes the batch's
+    // 65536 x 65536; the short build: every int8, which the rule takes at every shape within its limits)
+    for (int x = 0; x < 1024; ++x) {
+        const unsigned r = (seed = seed * 1664525u + 1013904223u) >> 24;
+        g_sm[x] = kLong ? int8_t(int(r % 121) - 60) : int8_t(r);
+    }
     // ---- refusals, before any device is touched ----
     {
-        const uint64_t good[3] = {0, 3, 8}, dec[3] = {0, 5, 3}, long2[3] = {0, 4097, 4100}, long1[3] = {0, 16385, 16390};
+        const uint64_t good[3] = {0, 3, 8}, dec[3] = {0, 5, 3}, long2[3] = {0, kMaxLen2 + 1, kMaxLen2 + 4}, long1[3] = {0, kMaxLen1 + 1, kMaxLen1 + 6};
         uint8_t s[16] = {0};
         int32_t out[16];
         uint64_t mv[8];
         uint32_t st[2];
-        CHECK(swmi_wide_local(s, dec, s, good, 2, g_sm, 1, 1, out, out, mv, st) == SWMI_ERR_INVALID_ARGUMENT);
-        CHECK(swmi_wide_local(s, good, s, long2, 2, g_sm, 1, 1, out, out, mv, st) == SWMI_ERR_INVALID_ARGUMENT);
-        CHECK(swmi_wide_global(s, long1, s, good, 2, g_sm, 1, 1, 0, out, out, mv, st) == SWMI_ERR_INVALID_ARGUMENT);
-        CHECK(swmi_wide_global(s, good, s, good, 2, g_sm, 1, 1, 16, out, out, mv, st) == SWMI_ERR_INVALID_ARGUMENT);
-        CHECK(swmi_wide_local(s, good, s, good, 2, g_sm, 1, 1, out, out, mv, nullptr) == SWMI_ERR_INVALID_ARGUMENT);
-        CHECK(swmi_wide_local(s, good, s, good, 2, g_sm, 128, 1, out, out, mv, st) == SWMI_ERR_DOMAIN);
-        CHECK(swmi_wide_local(nullptr, nullptr, nullptr, nullptr, 0, g_sm, 1, 1, nullptr, nullptr, nullptr, nullptr) == SWMI_OK);
+        CHECK(W(local)(s, dec, s, good, 2, g_sm, 1, 1, out, out, mv, st) == SWMI_ERR_INVALID_ARGUMENT);
+        CHECK(W(local)(s, good, s, long2, 2, g_sm, 1, 1, out, out, mv, st) == SWMI_ERR_INVALID_ARGUMENT);
+        CHECK(W(global)(s, long1, s, good, 2, g_sm, 1, 1, 0, out, out, mv, st) == SWMI_ERR_INVALID_ARGUMENT);
+        CHECK(W(global)(s, good, s, good, 2, g_sm, 1, 1, 16, out, out, mv, st) == SWMI_ERR_INVALID_ARGUMENT);
+        CHECK(W(local)(s, good, s, good, 2, g_sm, 1, 1, out, out, mv, nullptr) == SWMI_ERR_INVALID_ARGUMENT);
+#ifdef SWMI_WIDE_LONG_LIBRARY
+        // the global kind's domain rule, P = 128: (3, 65534) is outside it -- and the local kind has none (checked below, where it runs)
+        const uint64_t edge_out[3] = {0, 65534, 65540};
+        int8_t low[1024];
+        memset(low, -128, sizeof low);
+        CHECK(W(global)(s, good, s, edge_out, 2, low, 1, 1, 0, out, out, mv, st) == SWMI_ERR_INVALID_ARGUMENT);
+        CHECK(strstr(W(last_error)(), "alignment 0 is outside the domain") != nullptr);
+        CHECK(swmi_wide_long_set_stripe_waves(3) == SWMI_ERR_INVALID_ARGUMENT && swmi_wide_long_set_stripe_waves(2) == SWMI_ERR_INVALID_ARGUMENT && swmi_wide_long_set_stripe_waves(0) == SWMI_OK);
+#endif
+        CHECK(W(local)(s, good, s, good, 2, g_sm, 128, 1, out, out, mv, st) == SWMI_ERR_DOMAIN);
+        CHECK(W(local)(nullptr, nullptr, nullptr, nullptr, 0, g_sm, 1, 1, nullptr, nullptr, nullptr, nullptr) == SWMI_OK);
         CHECK(g_launches.empty());
         printf("refusals: ok\n");
     }
-    // ---- batches ----
-    Batch mixed;        // every wave count, zero lengths, both limits
-    for (int k = 0; k < 5200; ++k) {
+    // ---- batches: per library the recipe it always had ----
+    Batch mixed;        // every wave count, zero lengths, the limits; the long build: striped slots with and without a carry
+    for (int k = 0; k < (kLong ? 9000 : 5200); ++k) {
         const unsigned r = (seed = seed * 1664525u + 1013904223u) >> 8;
         size_t len1 = r % 301, len2 = (r >> 10) % 301;
         if (k % 97 == 0) len2 = 1025 + r % 3072;        // 2 .. 4 wavefronts
+        if (kLong && k % 101 == 0) len2 = 4097 + r % 3000;       // striped, with a carry
         if (k % 211 == 0) len1 = 0;
         if (k % 223 == 0) len2 = 0;
         if (k == 1000) len1 = 16384, len2 = 3;
         if (k == 2000) len1 = 7, len2 = 4096;
+        if (kLong) {
+            if (k == 2500) len1 = 16385, len2 = 3;          // striped because of len1: one stripe, no carry
+            if (k == 3000) len1 = 20000, len2 = 1025;       // ... and with one
+            if (k == 3500) len1 = 65536, len2 = 0;
+            if (k == 4000) len1 = 65536, len2 = 65536;
+            if (k == 4500) len1 = 3, len2 = 65536;
+        }
         mixed.add(len1, len2, seed);
     }
     Batch tiny;         // the count cap
@@ -262,15 +344,41 @@ int main()
     Batch small;
     for (int k = 0; k < 700; ++k) {
         const unsigned r = (seed = seed * 1664525u + 1013904223u) >> 8;
-        small.add(r % 200, k % 50 == 0 ? 2048 + r % 2049 : (r >> 10) % 200, seed);
+        small.add(r % 200, k % 50 == 0 ? 2048 + r % 2049 : kLong && k % 7 == 0 ? 4097 + r % 2000 : (r >> 10) % 200, seed);
     }
     for (int kind = 0; kind < 2; ++kind) {
         g_kind = kind ? swmi::kWideGlobal : swmi::kWideLocal;
         g_mask = kind ? 10u : 0u;
         g_open = 5 + kind;
+#ifdef SWMI_WIDE_LONG_LIBRARY
+        g_striped = g_carried = 0;
+#endif
         host_case(kind ? "global host traceback" : "local host traceback", mixed, true, 3);
         host_case(kind ? "global host ends-only" : "local host ends-only", mixed, false, 1);
+#ifdef SWMI_WIDE_LONG_LIBRARY
+        // two calls: every striped alignment went to the striped launcher, every one of more than 1024 columns with a carry block
+        size_t striped = 0, carried = 0;
+        for (size_t k = 0; k < mixed.n(); ++k) {
+            const size_t len1 = mixed.o1[k + 1] - mixed.o1[k], len2 = mixed.o2[k + 1] - mixed.o2[k];
+            striped += swmi::wide_long_striped(len1, len2);
+            carried += swmi::wide_long_striped(len1, len2) && len2 > 1024;
+        }
+        CHECK(striped >= 90 && carried >= 88 && carried < striped && g_striped == 2 * striped && g_carried == 2 * carried);
+#endif
     }
+#ifdef SWMI_WIDE_LONG_LIBRARY
+    // a forced width: the striped launches of the 700 of `small` would take the rule's 4 (100 striped slots)
+    g_kind = swmi::kWideLocal;
+    g_mask = 0;
+    g_open = 5;
+    for (int w : {1, 4}) {
+        CHECK(swmi_wide_long_set_stripe_waves(w) == SWMI_OK);
+        g_width = w;
+        host_case("local host traceback, forced width", small, true, 1);
+    }
+    CHECK(swmi_wide_long_set_stripe_waves(0) == SWMI_OK);
+    g_width = 0;
+#endif
     g_kind = swmi::kWideGlobal;
     g_mask = 15;
     host_case("global host count cap", tiny, false, 2);
@@ -282,10 +390,10 @@ int main()
     device_case("device mixed traceback, stream a (grown)", mixed, true, a);
     g_kind = swmi::kWideLocal;
     device_case("device mixed ends-only, stream b", mixed, false, b);
-    CHECK(swmi_wide_release_workspaces() == SWMI_OK);
+    CHECK(W(release_workspaces)() == SWMI_OK);
     host_case("local host traceback after the release", small, true, 1);
-    CHECK(swmi_wide_release_workspaces() == SWMI_OK);
+    CHECK(W(release_workspaces)() == SWMI_OK);
     CHECK(hipStreamDestroy(a) == hipSuccess && hipStreamDestroy(b) == hipSuccess);
-    printf("wide host fake ok\n");
+    printf("%s\n", kDone);
     return 0;
 }
