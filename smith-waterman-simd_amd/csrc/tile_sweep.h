@@ -164,6 +164,12 @@ constexpr int kStripeCols = 64 * 16 * 16;   // kMaxWaves x 64 lanes x kCols colu
 constexpr bool WIDE = false;
 constexpr const int8_t *wide_sm = nullptr;
 constexpr uint4 *wide_prof = nullptr;
+// A WIDE kernel whose column scores are the caller's, one column of 32 scores per position of seq2's side and no seq2 at all
+// (wide_profile_kernels.hip), shadows PROFILED with true as well and names `wide_pssm` in place of
+// wide_sm: the profile in device memory in the lane-ready form, letter-major, 32 rows of 64 W uint4, byte jj of entry G of row
+// a the score of letter a in column 16 G + jj + 1 (-128 past len2).  The lane loads its 32 entries where the others build them.
+constexpr bool PROFILED = false;
+constexpr const uint4 *wide_pssm = nullptr;
 
 // The end rule (above).  The flags are SWMI_FREE_* of include/swmi.h, which no kernel file includes.
 constexpr unsigned kFreeBegin1 = 1, kFreeBegin2 = 2, kFreeEnd1 = 4, kFreeEnd2 = 8;

@@ -7,8 +7,9 @@
 // (tile_sweep.h; tile_sweep_body.inc tells the stripe loop, which is the same here with (H, F) pairs in the carry); one that is
 // RAGGED as well names `carry_stride` and finds its carry block through slot.pad (wide_long_affine_kernels.hip).  A kernel
 // over 32 letters shadows WIDE and names wide_sm and wide_prof (tile_sweep.h, wide_affine_kernels.hip): where a cell's score
-// comes from is the one thing that changes, and every `if constexpr (WIDE)` below is that.  Text and not a function on purpose:
-// tile_sweep.h says why.
+// comes from is the one thing that changes, and every `if constexpr (WIDE)` below is that.  One that also shadows PROFILED
+// names wide_pssm and an empty seq2s (tile_sweep.h, wide_profile_kernels.hip): it loads the profile that the others build.
+// Text and not a function on purpose: tile_sweep.h says why.
 //
 // E runs down a column and stays with the lane; F runs along the row, so what lane l - 1 hands over (and lane 63 through
 // the ring) is its H(i, 16 G) AND its F(i, 16 G): two v_mov_b32_dpp wave_shr:1 per step, (H, F) pairs in the ring.  With a
@@ -35,7 +36,8 @@
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
     const size_t k = RAGGED ? (size_t)slot.k : (size_t)blockIdx.x;
     const uint8_t *s1 = seq1s + (RAGGED ? (size_t)slot.s1_off : k * (size_t)len1);
-    const uint8_t *s2 = seq2s + (RAGGED ? (size_t)slot.s2_off : k * (size_t)len2);
+    // (a PROFILED kernel has no seq2: it names an empty seq2s, and nothing below reads s2)
+    [[maybe_unused]] const uint8_t *s2 = PROFILED ? nullptr : seq2s + (RAGGED ? (size_t)slot.s2_off : k * (size_t)len2);
     if constexpr (RAGGED) {
         // a slot with a zero length: the whole workgroup (one wavefront) leaves here, before any barrier and any sequence load
         if (len1 == 0 || len2 == 0) {
@@ -95,7 +97,8 @@
     for (int jj = 0; jj < kCols; ++jj) {
         const int j = jbase + jj + 1;
         if constexpr (WIDE) {
-            prof[jj] = s2[j <= len2 ? j - 1 : 0] & 31u;     // the column's letter, for the profile below
+            // the column's letter, for the profile below (PROFILED: the columns have no letters)
+            if constexpr (!PROFILED) prof[jj] = s2[j <= len2 ? j - 1 : 0] & 31u;
         } else {
             const uint32_t b = s2[j <= len2 ? j - 1 : 0] & 3u;
             prof[jj] = j > len2 ? 0x80808080u : b == 0 ? cols.c[0] : b == 1 ? cols.c[1] : b == 2 ? cols.c[2] : cols.c[3];
@@ -107,7 +110,12 @@
     // WIDE: the lane's 16 bytes of every letter's profile row, from the matrix (columns past len2: -128).  A lane reads back
     // only what it wrote itself, so the profile needs no barrier.
     [[maybe_unused]] const uint4 *const prof_lane = wide_prof + (WIDE ? w * (32 * 64) + l : 0);
-    if constexpr (WIDE) {
+    if constexpr (WIDE && PROFILED) {
+        // ... or, PROFILED, from the launch's profile in device memory, which the host laid out for exactly this: per letter
+        // row one 16-byte load, coalesced over the lanes, and one LDS store; the padding is in the rows already
+#pragma unroll 8
+        for (int a = 0; a < 32; ++a) wide_prof[(w * 32 + a) * 64 + l] = wide_pssm[a * (64 * W) + 64 * w + l];
+    } else if constexpr (WIDE) {
 #pragma unroll 1
         for (int a = 0; a < 32; ++a) {
             uint32_t d[4] = {0u, 0u, 0u, 0u};
