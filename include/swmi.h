@@ -1083,7 +1083,16 @@ SWMI_API int swmi_queue_destroy(swmi_queue *q);
  * alignments per wavefront, 16-bit cells, v_pk_maximum3_f16 as a packed integer max.  VARIANT is the cell body, chosen from
  * the parameters: 0 when every score_matrix entry + gap_penalty is >= 0 (e.g. (1,-1,1), the parameters of the reference's
  * SmithWaterman_8bit111simd, source.cpp:1105-1225: ~1.55x the int32 kernel), 2 when every entry + 2 * gap_penalty lies in
- * [0, 255] (e.g. the harness's (10,-30,15): ~1.4x), 1 otherwise (~1.3x).  DESIGN.md section 5a.) */
+ * [0, 255] (e.g. (120,-120,62): ~1.4x), 1 otherwise (~1.3x).  Variant 2 has a FLAG FORM, which runs variant 0's cell inside
+ * the variant-2 kernel (same reported name) and which the harness's (10,-30,15) gets (~1.55x).  It applies when ALL of:
+ *   - the rule above gives 2;
+ *   - every score_matrix entry is either one common value m with m + gap_penalty > 0, or <= -2 * gap_penalty (such a score
+ *     never decides a cell: H(i,j-1) >= H(i-1,j-1) - gap);
+ *   - (m + gap_penalty) divides 255 * gap_penalty (the recurrence is rescaled by 255 / (m + gap_penalty), exactly);
+ *   - 255 * (128 * m + gap_penalty) / (m + gap_penalty) + 255 < 0x7C00 (the largest rescaled value).
+ * (127,-127,64), (120,-120,62), (7,-30,15), (10,-29,15) do not qualify and keep the vertical-offset cell; (10,-40,15) is
+ * variant 1 as before.  swmi_pk_cell_form (swmi_pk_form.h, libswmi_pk_form.so) reports the form without a device.
+ * DESIGN.md section 5a.) */
 SWMI_API int swmi_set_schedule(int lanes_per_alignment, unsigned flags);
 SWMI_API int swmi_get_schedule(int *lanes_per_alignment, unsigned *flags);
 /* Lanes per alignment a launch of n pairs runs with under the current setting (what 0 = automatic resolves to). */

@@ -22,8 +22,17 @@ Sections (selected with PK_SECTION = 100 * variant + rows per lane before includ
                     diagonal term share one paired add.
                     Per two rows: 2 v_perm, 2 max3, 2 sat-sub, 2 paired adds, 1 max3 (best) = 9 instructions (round 2's
                     bias form: 11).  Pad columns look up 0, i.e. act as score -2 gap: harmless (kernel header).
+  variant 3 "flag"  the q0 cell for parameter sets that the host rescales (swmi_api.cpp make_config): every score
+                    is either one value m (rescaled: m + gap = 255) or <= -2 gap, which never decides a cell.  The looked-up addend
+                    is 0x00FF (enabled) or 0x80FF (disabled: the diagonal term becomes a finite NEGATIVE half, which
+                    v_pk_maximum3_f16 drops against the non-negative `left` and `up`).  The cell is q0's, instruction for
+                    instruction; the sweep is rolled ONE step per trip (q0: two) -- the hand-over value moves into its pair
+                    register with one v_mov_b32 per step, and the next step's tables are fetched behind the step's last lookup:
+                    8 R / 2 + 1 cell instructions per step.  Half the code of the two-step form, and the only loop of the
+                    variant-2 kernels with 2 R lookups stays the vertical-offset one, which the disassembly census
+                    (tools/isa_census.py) finds by that count.  Pad columns look up 0x80FF: disabled.
 The code expects, in the including scope: `col` (per-column table offsets), `tables_at(t, cx, cy)`, `rsel[R]`, `group_mask`,
-`gap` (int), `L` (lanes per pair of alignments) and defines `pk_best` (packed running best) for the epilogue.
+`gap` (int), `L` (lanes per pair of alignments), `lds_tab` (flag sections) and defines `pk_best` (packed running best) for the epilogue.
 
 Run: python3 gen_pk_sweeps.py > pk_sweeps_gen.inc   (the Makefile does; tests/test_generated_sources.py checks the committed
 file is what this script prints)."""
@@ -195,11 +204,85 @@ def section(variant, R):
     return o
 
 
+def flag_step(R):
+    """one anti-diagonal step of the flag cell (q0's cell on fixed registers): tables pk_cx / pk_cy, `up` = pk_up, diagonal
+    hand-over = pk_diag, which sits above row R - 2 in the aligned pair v[H0+R-2 : H0+R-1]"""
+    c = []
+    h = lambda r: "pk_h%d" % r
+    sc = lambda k, half: "pk_sc%d" % (2 * (k % 2) + half)
+    sc_reg = lambda k: SC[k % 2]
+    def P(i):
+        if i >= R - 1:                                     # (the last row is looked up at the start of the step)
+            c.append('    asm volatile("s_nop 0");')
+            return
+        emit(c, "v_perm_b32 %0, %1, %2, %3", [sc((i - 1) // 2, (i - 1) % 2)], ["pk_cy", "pk_cx", "rsel[%d]" % i])
+    emit(c, "v_perm_b32 %0, %1, %2, %3", ["pk_s0"], ["pk_cy", "pk_cx", "rsel[0]"])
+    emit(c, "v_perm_b32 %0, %1, %2, %3", ["pk_sL"], ["pk_cy", "pk_cx", "rsel[%d]" % (R - 1)])
+    P(1)
+    emit(c, "v_lshl_add_u64 v[28:29], v[%d:%d], 0, v[26:27]" % (H0 + R - 2, H0 + R - 1), ["pk_ttL", "pk_t0"], [h(R - 2), "pk_diag", "pk_sL", "pk_s0"])
+    P(2)
+    nblk = R // 2
+    for k in range(nblk):
+        a, b = 2 * k, 2 * k + 1
+        t_a = "pk_t0" if k == 0 else "pk_tt1"
+        last = b + 1 >= R
+        if k == nblk - 2:                                  # every lookup of this step is issued: fetch the next step's tables
+            c.append("    pk_cx = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(lds_tab) + pk_ox);")
+            c.append("    pk_cy = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(lds_tab) + pk_oy);")
+        emit(c, "v_pk_maximum3_f16 %0, %1, %2, %3", ["pk_xa"], [h(a), "pk_up" if k == 0 else h(a - 1), t_a])
+        if not last:
+            emit(c, "v_lshl_add_u64 v[%d:%d], v[%d:%d], 0, v[%d:%d]" % (TT, TT + 1, H0 + a, H0 + b, sc_reg(k), sc_reg(k) + 1),
+                 ["pk_tt0", "pk_tt1"], [h(a), h(b), sc(k, 0), sc(k, 1)])
+        else:
+            c.append('    asm volatile("s_nop 0");')     # (the last row's diagonal term came with row 0's)
+        emit(c, "v_pk_sub_u16 %0, %1, %2 clamp", [h(a)], ["pk_xa"], ["pk_g2"])
+        P(b + 2)
+        emit(c, "v_pk_maximum3_f16 %0, %1, %2, %3", ["pk_xb"], [h(b), h(a), "pk_ttL" if last else "pk_tt0"])
+        P(b + 3)
+        emit(c, "v_pk_sub_u16 %0, %1, %2 clamp", [h(b)], ["pk_xb"], ["pk_g2"])
+        emit(c, "v_pk_maximum3_f16 %0, %1, %2, %3", ["pk_best"], ["pk_best", "pk_xa", "pk_xb"])
+    emit(c, "v_mov_b32 %0, %1", ["pk_diag"], ["pk_up"])    # this step's `up` is the next step's diagonal hand-over
+    c.append('    asm volatile("s_nop 0");            // the DPP below reads a register the asm above wrote: 2 wait states, by hand')
+    c.append("    pk_up = (uint32_t)from_prev_lane<L>((int)%s, group_mask);" % h(R - 1))
+    return c
+
+
+def flag_section(R):
+    o = []
+    o.append("#if PK_SECTION == %d" % (300 + R))
+    o.append("{")
+    o.append("    // ---- generated by gen_pk_sweeps.py: flag cell (q0's cell, one step per trip), %d rows per lane ----" % R)
+    for r in range(R - 1):
+        o.append('    register uint32_t pk_h%d asm("v%d") = 0;' % (r, H0 + r))
+    o.append('    register uint32_t pk_diag asm("v%d") = 0;   // H(last row of the lane before) of the previous column, above row %d' % (H0 + R - 1, R - 2))
+    o.append('    register uint32_t pk_h%d asm("v30") = 0;   // (no pair to sit in: its diagonal term is added with that of row 0)' % (R - 1))
+    for q in range(4):
+        o.append('    register uint32_t pk_sc%d asm("v%d") = 0;' % (q, SC[0] + q))
+    o.append('    register uint32_t pk_tt0 asm("v%d") = 0, pk_tt1 asm("v%d") = 0;' % (TT, TT + 1))
+    o.append("    const uint32_t pk_g2 = (uint32_t)gap | ((uint32_t)gap << 16);")
+    o.append("    uint32_t pk_xa = 0, pk_xb = 0, pk_up = 0;")
+    o.append('    register uint32_t pk_sL asm("v26") = 0, pk_s0 asm("v27") = 0;   // scores of the last row and of row 0')
+    o.append('    register uint32_t pk_ttL asm("v28") = 0, pk_t0 asm("v29") = 0;  // their diagonal terms')
+    o.append("    uint32_t pk_cx, pk_cy;")
+    o.append("    tables_at(0, pk_cx, pk_cy);")
+    o.append("    for (int t = 0; t < 2 * T2 + 1; ++t) {")
+    o.append("        // the next step's table offsets (col[2 T2 + 1] is a pad entry of the column array: read, never used)")
+    o.append("        const uint16_t *pk_next = reinterpret_cast<const uint16_t *>(col + t + 1);")
+    o.append("        const uint32_t pk_ox = pk_next[0], pk_oy = pk_next[1];")
+    o += ["    " + l for l in flag_step(R)]
+    o.append("    }")
+    o.append("}")
+    o.append("#endif")
+    return o
+
+
 def main():
     out = ["// GENERATED by gen_pk_sweeps.py -- do not edit.  Included inside sw128_pk_kernel (sw_kernels.hip) with PK_SECTION set."]
     for variant in (0, 2):
         for R in (32, 16, 8):
             out += section(variant, R)
+    for R in (32, 16, 8):
+        out += flag_section(R)
     sys.stdout.write("\n".join(out) + "\n")
 
 

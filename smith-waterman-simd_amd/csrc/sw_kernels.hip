@@ -368,6 +368,20 @@ sw128_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ seq2
 //            row above's max3 result as it is (chain max3 -> max3), takes the saturating subtraction and the re-biasing add
 //            off the chain and lets both adds pair -- 9 instructions per two rows (the bias form below: 11);
 //   kPkBias  everything else: the form described above.
+// The FLAG FORM of kPkVert (q != 0; the host's rule: swmi_api.cpp make_config, include/swmi.h, derivation in DESIGN.md 5a) runs
+// kPkQ0's 8-instruction cell on parameter sets that kPkQ0 cannot take, when every score is either one value m or <= -2 gap:
+//   * a score s <= -2 gap never decides a cell: H(i,j-1) >= H(i-1,j-1) - gap, hence H(i-1,j-1) + s <= H(i,j-1) - gap (on the
+//     borders too), so the diagonal term of such a cell may be anything that loses the max3;
+//   * v_pk_maximum3_f16 drops a finite NEGATIVE half (bit 15 set, magnitude < 0x7C00) against the non-negative `left` and `up`
+//     (pk_max3_negative_selftest_kernel, pk_form_kernels.hip, checks that exhaustively);
+//   * the host rescales the recurrence by 255 / (m + gap): the folded score of an enabled cell is then exactly 255, and the
+//     lookup writes the column table's flag byte -- 0x00 enabled, 0x80 disabled -- into the HIGH byte of each half and the
+//     constant 0xFF into the low byte (selector 0x0D): the addend is 0x00FF or 0x80FF.  `gap` arrives rescaled, q = m + gap
+//     turns the best value back: score = max(best - gap, 0) * q / 255, an exact division.
+// Pad columns of the flag form fetch 0x80808080, every row DISABLED (a zero flag would be a match).  The pad-column argument
+// of this file's header then reads: before the first column every input of the cell is 0 and the diagonal term loses, so
+// x = max(left, up) = 0 and the state stays all-zero; after the last column x = max(left, up), bounded by a value some real
+// cell already held, feeding only cells that are themselves past the last column.
 // Same anti-diagonal pipeline, DPP hand-over and pad-column argument as sw128_kernel (header of this file).
 __device__ __forceinline__ uint32_t pk_max3(uint32_t a, uint32_t b, uint32_t c)
 {
@@ -492,7 +506,8 @@ enum PkVariant : int { kPkQ0 = 0, kPkBias = 1, kPkVert = 2 };
 template <int MODE, int VARIANT, int L>
 __global__ void __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_per_eu(4)))
 sw128_pk_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ seq2s, int32_t *__restrict__ scores,
-                uint32_t n, SmRows rows /* s + gap + Q (kPkVert: s + 2 gap), every byte in [0, 255] */, int gap, int q)
+                uint32_t n, SmRows rows /* s + gap + Q (kPkVert: s + 2 gap; its flag form: 0x00 / 0x80), every byte in [0, 255] */,
+                int gap, int q /* kPkBias: Q; kPkVert: 0, or m + gap = the flag form (gap is then the rescaled one) */)
 {
     static_assert(L == 4 || L == 8 || L == 16, "lanes per pair of alignments");
     constexpr bool kGenerated = VARIANT == kPkQ0 || VARIANT == kPkVert;
@@ -503,13 +518,14 @@ sw128_pk_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ s
     constexpr int S = kSeqLen + 2 * PAD;
     constexpr int T2 = (kSeqLen + L - 1) / 2;               // T = 128 + L - 1 steps (odd): T2 pairs of steps and one more
     constexpr int NW = R / 4;
-    constexpr uint32_t kPadCode = 16u | (16u << 16);        // both halves point at the all-zero table
+    constexpr uint32_t kPadCode = 16u | (16u << 16);        // both halves point at the pad table, lds_tab[4]
+    const bool flag_form = VARIANT == kPkVert && q != 0;    // wave-uniform (a kernel argument)
 
     // per column of an alignment pair: the LDS byte offsets (into lds_tab) of the column's score table for X (low half) and
     // for Y (high half)
     __shared__ uint32_t lds_col[kWavesPerBlock][G * S];
     // lds_tab[b], b < 4: the scores of column base b against the four row bases, one per byte (the transposed matrix);
-    // lds_tab[4] = 0 for pad columns.  The same for every wavefront of the block, which all write it (identical values).
+    // lds_tab[4] = 0 for pad columns (flag form: 0x80808080, every row disabled).  The same for every wavefront of the block, which all write it (identical values).
     __shared__ uint32_t lds_tab[8];
 
     const int lane = threadIdx.x & 63;
@@ -536,8 +552,9 @@ sw128_pk_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ s
     }
 
     if (lane < 5) {
-        uint32_t c = 0;
+        uint32_t c = flag_form ? 0x80808080u : 0u;
         if (lane < 4) {
+            c = 0;
 #pragma unroll
             for (int a = 0; a < 4; ++a) c |= ((rows.r[a] >> (8 * lane)) & 0xFFu) << (8 * a);
         }
@@ -554,6 +571,9 @@ sw128_pk_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ s
     //   column code  = (4 * base of X's column) | (4 * base of Y's column) << 16   (byte offsets into lds_tab)
     //   row selector = byte 0 <- byte (base of X's row) of X's column table, byte 2 <- byte (base of Y's row) of Y's column
     //                  table (source bytes 4..7), bytes 1 and 3 <- 0x00 (selector 0x0C):  ra | (4 + rb) << 16 | 0x0C000C00
+    //   flag form:     the same two bytes go into bytes 1 and 3 (the HIGH byte of each half), bytes 0 and 2 <- 0xFF
+    //                  (selector 0x0D):  ra << 8 | (4 + rb) << 24 | 0x000D000D
+    const uint32_t sel_shift = flag_form ? 8u : 0u, sel_const = flag_form ? 0x000D000Du : 0x0C000C00u;
     uint32_t rsel[R];
 #pragma unroll
     for (int w = 0; w < NW; ++w) {
@@ -563,7 +583,8 @@ sw128_pk_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ s
         for (int k = 0; k < 4; ++k) {
             const uint32_t pick = (uint32_t)k | 0x0C000C00u | ((uint32_t)(4 + k) << 16);     // byte k of the first, byte k of the second
             prof[PAD + j * R + 4 * w + k] = __builtin_amdgcn_perm(cy4, cx4, pick);
-            rsel[4 * w + k] = __builtin_amdgcn_perm(rb4, ra4, pick) | 0x0C000C00u;
+            if constexpr (VARIANT == kPkVert) rsel[4 * w + k] = (__builtin_amdgcn_perm(rb4, ra4, pick) << sel_shift) | sel_const;
+            else                              rsel[4 * w + k] = __builtin_amdgcn_perm(rb4, ra4, pick) | 0x0C000C00u;
         }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -612,6 +633,20 @@ sw128_pk_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ s
 #define PK_SECTION 8
 #include "pk_sweeps_gen.inc"
 #undef PK_SECTION
+        } else if (flag_form) {             // (kPkVert only) q0's cell on rescaled values, one step per trip
+            if constexpr (R == 32) {
+#define PK_SECTION 332
+#include "pk_sweeps_gen.inc"
+#undef PK_SECTION
+            } else if constexpr (R == 16) {
+#define PK_SECTION 316
+#include "pk_sweeps_gen.inc"
+#undef PK_SECTION
+            } else {
+#define PK_SECTION 308
+#include "pk_sweeps_gen.inc"
+#undef PK_SECTION
+            }
         } else if constexpr (VARIANT == kPkVert && R == 32) {
 #define PK_SECTION 232
 #include "pk_sweeps_gen.inc"
@@ -662,16 +697,22 @@ sw128_pk_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ s
     step(x0, y0, u0, u1);                   // step 128 + L - 2, the last lane's last column
     }
 
-    // reduce over the L lanes of the group (packed), then unfold: the maximum was tracked on x + Q = H + gap + Q (kPkVert: on H)
+    // reduce over the L lanes of the group (packed), then unfold: the maximum was tracked on x + Q = H + gap + Q (kPkVert: on H;
+    // its flag form: on x = 255 / q (H + gap) with the rescaled gap, q = m + gap)
 #pragma unroll
     for (int o = L / 2; o > 0; o >>= 1) {
         const uint32_t other = (uint32_t)__shfl_xor((int)best, o);
         best = pk_max3(best, other, other);
     }
-    const int bx_score = (int)(best & 0xFFFFu), by_score = (int)(best >> 16), gq = VARIANT == kPkVert ? 0 : gap + q;
+    const int bx_score = (int)(best & 0xFFFFu), by_score = (int)(best >> 16), gq = VARIANT != kPkVert ? gap + q : flag_form ? gap : 0;
+    int sx = bx_score > gq ? bx_score - gq : 0, sy = by_score > gq ? by_score - gq : 0;
+    if (flag_form) {                        // back from the rescaled values: a multiple of 255 times q / 255
+        sx = sx * q / 255;
+        sy = sy * q / 255;
+    }
     if (j == 0) {
-        if (live_x) scores[px] = bx_score > gq ? bx_score - gq : 0;
-        if (live_y) scores[py] = by_score > gq ? by_score - gq : 0;
+        if (live_x) scores[px] = sx;
+        if (live_y) scores[py] = sy;
     }
 }
 
@@ -1244,7 +1285,8 @@ hipError_t launch_L(const LaunchConfig &cfg, const uint8_t *s1, const uint8_t *s
             const dim3 grid_pk((unsigned)((waves_pk + kWavesPerBlock - 1) / kWavesPerBlock));
             switch (cfg.pk_variant) {
             case kPkQ0:    hipLaunchKernelGGL((sw128_pk_kernel<MODE, kPkQ0, L>), grid_pk, block, cfg.extra_lds_bytes, stream, s1, s2, out, n32, rows, gap, 0); break;
-            case kPkVert:  hipLaunchKernelGGL((sw128_pk_kernel<MODE, kPkVert, L>), grid_pk, block, cfg.extra_lds_bytes, stream, s1, s2, out, n32, rows, gap, 0); break;
+            case kPkVert:  hipLaunchKernelGGL((sw128_pk_kernel<MODE, kPkVert, L>), grid_pk, block, cfg.extra_lds_bytes, stream, s1, s2, out, n32, rows,
+                                              cfg.pk_flag_unit ? cfg.pk_flag_gap : gap, cfg.pk_flag_unit); break;
             default:       hipLaunchKernelGGL((sw128_pk_kernel<MODE, kPkBias, L>), grid_pk, block, cfg.extra_lds_bytes, stream, s1, s2, out, n32, rows, gap, cfg.pk_bias); break;
             }
             return hipGetLastError();

@@ -5,6 +5,7 @@
 // hipEvent timing.  There is deliberately no CPU implementation of the scoring path in this
 // library: without a usable gfx950 device every scoring entry point returns an error.
 #include "swmi_host.h"
+#include "pk_form.h"
 
 #include <cstdarg>
 #include <cstdio>
@@ -181,28 +182,28 @@ LaunchConfig make_config(const Context &ctx, const int8_t *sm, int gap, SmRows *
                  !(flags & (swmi::kNoPacked | swmi::kNoGapFold | swmi::kUseI16 | swmi::kUseLut));
     cfg.pk_bias = 0;
     cfg.pk_variant = 0;
+    cfg.pk_flag_unit = 0;
+    cfg.pk_flag_gap = 0;
     if (cfg.use_pk) {
-        int lowest = 255, highest = -255;
-        for (int k = 0; k < 16; ++k) {
-            lowest = int(sm[k]) < lowest ? int(sm[k]) : lowest;
-            highest = int(sm[k]) > highest ? int(sm[k]) : highest;
-        }
-        // Which cell body (sw_kernels.hip PkVariant; tests/pk_edges.py restates the rule and holds sets on both sides of each bound):
+        // Which cell body (sw_kernels.hip PkVariant; the rule is pk_form.h's, tests/pk_edges.py and tests/pk_flag_form.py restate it
+        // and hold sets on both sides of each bound):
         //   0  every s + gap >= 0: nothing to bias
-        //   2  every s + 2 gap in [0, 255] and the largest value of the vertical-offset form, 128 max(s) + gap * 34 + 256,
-        //      stays a finite half-precision pattern (< 0x7C00): rows carry s + 2 gap
+        //   2  every s + 2 gap in [0, 255] and the values of the vertical-offset form fit: rows carry s + 2 gap -- or, in its
+        //      flag form (every score one value m or <= -2 gap, and the scale 255 / (m + gap) fits), one flag byte per entry
         //   1  anything else: values shifted by Q = -(min s + gap)
-        int add = gap;
-        if (lowest + gap >= 0) {
-            cfg.pk_variant = 0;
-        } else if (lowest + 2 * gap >= 0 && highest + 2 * gap <= 255 &&
-                   128 * (highest > 0 ? highest : 0) + 34 * gap + 256 < 0x7C00) {
-            cfg.pk_variant = 2;
-            add = 2 * gap;
-        } else {
-            cfg.pk_variant = 1;
-            cfg.pk_bias = -(lowest + gap);
-            add = gap + cfg.pk_bias;
+        const swmi::PkCellForm form = swmi::pk_cell_form(sm, gap);
+        cfg.pk_variant = form.variant;
+        cfg.pk_bias = form.bias;
+        cfg.pk_flag_unit = form.flag_unit;
+        cfg.pk_flag_gap = form.flag_gap;
+        const int add = form.add;
+        if (form.flag_unit) {               // 0x00: the entry is m (enabled); 0x80: it is <= -2 gap and never decides a cell
+            for (int a = 0; a < 4; ++a) {
+                uint32_t r = 0;
+                for (int b = 0; b < 4; ++b) r |= (int(sm[4 * a + b]) <= -2 * gap ? 0x80u : 0u) << (8 * b);
+                rows->r[a] = r;
+            }
+            return cfg;
         }
         for (int a = 0; a < 4; ++a) {
             uint32_t r = 0;

@@ -29,6 +29,8 @@ struct LaunchConfig {
     int pk_bias;               //   rows then hold s + gap + pk_bias (bytes 0..255), pk_bias = max(0, -(min s + gap))
     int pk_variant;            //   cell body: 0 = no bias needed, 1 = biased, 2 = vertical-offset form (rows hold s + 2 gap);
                                //   sw_kernels.hip PkVariant
+    int pk_flag_unit;          //   variant 2 only, 0 = off: m + gap of its flag form (pk_form.h), which runs variant 0's cell on values
+    int pk_flag_gap;           //   rescaled by 255 / (m + gap); rows then hold flag bytes, and this is the rescaled gap
 };
 
 // Score n pairs resident in device memory. packed = 2-bit inputs (32 B per sequence).
