@@ -1092,6 +1092,10 @@ SWMI_API int swmi_queue_destroy(swmi_queue *q);
  *   - 255 * (128 * m + gap_penalty) / (m + gap_penalty) + 255 < 0x7C00 (the largest rescaled value).
  * (127,-127,64), (120,-120,62), (7,-30,15), (10,-29,15) do not qualify and keep the vertical-offset cell; (10,-40,15) is
  * variant 1 as before.  swmi_pk_cell_form (swmi_pk_form.h, libswmi_pk_form.so) reports the form without a device.
+ * Where the flag form's enabled entries are exactly the four diagonal ones (plain match / mismatch scoring) and the largest
+ * rescaled H, 255 * 128 * m / (m + gap_penalty), is at most 16383, it runs as its PRODUCT FORM: lookup and diagonal add of a
+ * row are one 16-bit multiply-add (swmi_pk_product_form reports it; the harness's (10,-30,15) qualifies, same kernel name,
+ * same scores).  The environment variable SWMI_PK_NO_PRODUCT, read at swmi_init, keeps such sets on the flag form's own cell.
  * DESIGN.md section 5a.) */
 SWMI_API int swmi_set_schedule(int lanes_per_alignment, unsigned flags);
 SWMI_API int swmi_get_schedule(int *lanes_per_alignment, unsigned *flags);

@@ -1,4 +1,4 @@
-/* swmi_pk_form.h -- C ABI of libswmi_pk_form.so: two checks of the packed scorer (sw128_pk_kernel, libswmi.so) that tests
+/* swmi_pk_form.h -- C ABI of libswmi_pk_form.so: the checks of the packed scorer (sw128_pk_kernel, libswmi.so) that tests
  * and tools call; scoring needs neither.  A small library of its own beside libswmi.so: it needs NO swmi_init, links only the
  * HIP runtime, and its GPU entry runs on the calling thread's current HIP device.
  *
@@ -28,6 +28,22 @@ SWMI_API int swmi_pk_cell_form(const int8_t score_matrix[16], int gap_penalty, i
  * half in each operand position, in either half of the register.  *checked = comparisons made, *mismatches = those that
  * failed.  SWMI_OK, SWMI_ERR_INVALID_ARGUMENT (NULL) or SWMI_ERR_HIP (a HIP call failed, or there is no device). */
 SWMI_API int swmi_pk_selftest_max3_negative(unsigned long long *checked, unsigned long long *mismatches);
+
+/* The PRODUCT FORM, a sub-form of SWMI_PK_FORM_FLAG for plain match / mismatch scoring: the diagonal term of a
+ * row is one 16-bit multiply-add per half, a[row base] * b[column base] + H modulo 2^16 -- H + 255 where the bases agree, a
+ * finite negative half where they differ.  Returns 1 when (score_matrix, gap_penalty) is eligible -- swmi_pk_cell_form gives
+ * SWMI_PK_FORM_FLAG, the entries above -2 gap are exactly the four diagonal ones, and the largest rescaled H,
+ * 255 * 128 m / (m + gap), is at most the bound below -- else 0.  Needs no device.  When eligible, consts[0..3] = a,
+ * consts[4..7] = b, consts[8] = the largest rescaled H the constants are verified for; otherwise nine zeros (consts may be
+ * NULL).  Errors as swmi_pk_cell_form.  An eligible set runs the product form unless the environment holds
+ * SWMI_PK_NO_PRODUCT at swmi_init, which keeps it on the flag form's own cell (same scores; for A/B runs). */
+SWMI_API int swmi_pk_product_form(const int8_t score_matrix[16], int gap_penalty, int consts[9]);
+
+/* The product form's premise, on the current HIP device: for all 16 (row base, column base), EVERY H in [0, bound] and both
+ * halves of the register, v_pk_mad_i16 gives (a[r] * b[c] + H) mod 65536, and the v_pk_maximum3_f16 that follows against two
+ * non-negative operands p, q gives max(p, q, H + 255) where r = c and max(p, q) where not.  *checked, *mismatches and the
+ * return value as swmi_pk_selftest_max3_negative. */
+SWMI_API int swmi_pk_selftest_product_mad(unsigned long long *checked, unsigned long long *mismatches);
 
 #ifdef __cplusplus
 }

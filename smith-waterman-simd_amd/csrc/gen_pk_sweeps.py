@@ -31,6 +31,12 @@ Sections (selected with PK_SECTION = 100 * variant + rows per lane before includ
                     8 R / 2 + 1 cell instructions per step.  Half the code of the two-step form, and the only loop of the
                     variant-2 kernels with 2 R lookups stays the vertical-offset one, which the disassembly census
                     (tools/isa_census.py) finds by that count.  Pad columns look up 0x80FF: disabled.
+  variant 4 "product"  the flag cell for plain match / mismatch sets (pk_form.h): lookup and diagonal add of a row
+                    are ONE v_pk_mad_i16 (row multiplier * column multiplier + H of the row above, modulo 2^16 per half: H + 255
+                    where the bases agree, a finite negative half where they differ).  Per two rows: 2 v_pk_mad_i16, 2 max3,
+                    2 sat-sub, 1 max3 (best) = 7 instructions.  No register pairs, no lookup table: the column operand is one
+                    dword of `col`, rsel[] holds the row multipliers.  Two steps per trip: the hand-over values alternate between
+                    two registers and need no move.  Pad columns carry the multiplier 0 (kernel header).
 The code expects, in the including scope: `col` (per-column table offsets), `tables_at(t, cx, cy)`, `rsel[R]`, `group_mask`,
 `gap` (int), `L` (lanes per pair of alignments), `lds_tab` (flag sections) and defines `pk_best` (packed running best) for the epilogue.
 
@@ -276,6 +282,71 @@ def flag_section(R):
     return o
 
 
+def product_step(R, cm, up, diag, out):
+    """one anti-diagonal step of the product cell: column multiplier cm, `up` / `diag` from the lane before, hand-over -> out.
+    Row i: D (v_pk_mad_i16, the diagonal term, issued two rows ahead: it reads H of row i - 1 BEFORE that row's subtraction
+    overwrites it), M (max3), S (saturating subtraction); per two rows one B (running best, on x, one pair late).  The chain
+    M -> S -> M -> S is 4 of the 7 slots of a row pair, so ONE dependent pair per two rows is adjacent, S of the odd row and M
+    of the next even one; every other consumer is one instruction behind its producer.  hipcc reads the operand lists and adds
+    the wait states a packed result needs before its consumer (s_nop 0, here as in the flag sweep); an s_nop written by hand
+    at the adjacent pair changed the stream's rate by under 1 % (profiles/pk_product_cell_stream.txt)."""
+    c = []
+    h = lambda r: "pk_h%d" % r
+    t = lambda i: "pk_t%d" % (i % 4)
+    x = lambda i: "pk_x%d" % (i % 4)
+    def D(i):
+        if i >= R:
+            c.append('    asm volatile("s_nop 0");')
+            return
+        emit(c, "v_pk_mad_i16 %0, %1, %2, %3", [t(i)], ["rsel[%d]" % i, cm, h(i - 1) if i else diag])
+    def B(k):
+        emit(c, "v_pk_maximum3_f16 %0, %1, %2, %3", ["pk_best"], ["pk_best", x(2 * k), x(2 * k + 1)])
+    D(0)
+    D(1)
+    for k in range(R // 2):
+        a, b = 2 * k, 2 * k + 1
+        emit(c, "v_pk_maximum3_f16 %0, %1, %2, %3", [x(a)], [h(a), h(a - 1) if k else up, t(a)])
+        D(a + 2)
+        emit(c, "v_pk_sub_u16 %0, %1, %2 clamp", [h(a)], [x(a)], ["pk_g2"])
+        if k:
+            B(k - 1)
+        emit(c, "v_pk_maximum3_f16 %0, %1, %2, %3", [x(b)], [h(b), h(a), t(b)])
+        D(b + 2)
+        emit(c, "v_pk_sub_u16 %0, %1, %2 clamp", [h(b)], [x(b)], ["pk_g2"])
+    B(R // 2 - 1)
+    c.append('    asm volatile("s_nop 1");            // the DPP below reads a register the asm above wrote: 2 wait states, by hand')
+    c.append("    %s = (uint32_t)from_prev_lane<L>((int)%s, group_mask);" % (out, h(R - 1)))
+    return c
+
+
+def product_section(R):
+    o = []
+    o.append("#if PK_SECTION == %d" % (400 + R))
+    o.append("{")
+    o.append("    // ---- generated by gen_pk_sweeps.py: product cell (the flag form with one v_pk_mad_i16 per row), %d rows per lane ----" % R)
+    for r in range(R):
+        o.append('    register uint32_t pk_h%d asm("v%d") = 0;' % (r, H0 + r))
+    o.append("    const uint32_t pk_g2 = (uint32_t)gap | ((uint32_t)gap << 16);")
+    o.append("    uint32_t pk_t0 = 0, pk_t1 = 0, pk_t2 = 0, pk_t3 = 0, pk_x0 = 0, pk_x1 = 0, pk_x2 = 0, pk_x3 = 0;")
+    o.append("    uint32_t pk_u0 = 0, pk_u1 = 0;   // H(last row of the lane before): this step's column / the previous one, alternating")
+    o.append("    uint32_t pk_c0 = col[0];        // the column multipliers of the step's column: one dword, no table")
+    o.append("    for (int t2 = 0; t2 < T2; ++t2) {")
+    o.append("        const uint32_t pk_c1 = col[2 * t2 + 1];")
+    o += ["    " + l for l in product_step(R, "pk_c0", "pk_u0", "pk_u1", "pk_u1")]
+    o.append("        const uint32_t pk_c2 = col[2 * t2 + 2];")
+    o += ["    " + l for l in product_step(R, "pk_c1", "pk_u1", "pk_u0", "pk_u0")]
+    o.append("        pk_c0 = pk_c2;")
+    o.append("    }")
+    o.append("    {   // step 128 + L - 2, the last lane's last column")
+    o.append("        uint32_t pk_last;")
+    o += ["    " + l for l in product_step(R, "pk_c0", "pk_u0", "pk_u1", "pk_last")]
+    o.append("        (void)pk_last;")
+    o.append("    }")
+    o.append("}")
+    o.append("#endif")
+    return o
+
+
 def main():
     out = ["// GENERATED by gen_pk_sweeps.py -- do not edit.  Included inside sw128_pk_kernel (sw_kernels.hip) with PK_SECTION set."]
     for variant in (0, 2):
@@ -283,6 +354,8 @@ def main():
             out += section(variant, R)
     for R in (32, 16, 8):
         out += flag_section(R)
+    for R in (32, 16, 8):
+        out += product_section(R)
     sys.stdout.write("\n".join(out) + "\n")
 
 

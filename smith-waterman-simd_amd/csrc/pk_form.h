@@ -1,10 +1,17 @@
 // pk_form.h -- which cell body the packed scorer sw128_pk_kernel runs for a parameter set (sw_kernels.hip PkVariant), as one
 // inline rule without a device: make_config (swmi_api.cpp) launches by it, swmi_pk_cell_form (pk_form_kernels.hip,
-// include/swmi_pk_form.h) reports it.  tests/pk_edges.py and tests/pk_flag_form.py restate it.
+// include/swmi_pk_form.h) reports it.  tests/pk_edges.py, tests/pk_flag_form.py and tests/pk_product_form.py restate it.
 #pragma once
 #include <cstdint>
 
+#include "pk_product_consts_gen.inc"
+
 namespace swmi {
+
+// The product form's multipliers and the largest rescaled H they were verified for (gen_pk_product_consts.py)
+constexpr uint16_t kPkProductRowMul[4] = SWMI_PK_PRODUCT_ROW_MUL;
+constexpr uint16_t kPkProductColMul[4] = SWMI_PK_PRODUCT_COL_MUL;
+constexpr int kPkProductBound = SWMI_PK_PRODUCT_BOUND;
 
 struct PkCellForm {
     int variant;        // 0 = no bias needed, 1 = biased, 2 = vertical-offset form
@@ -13,6 +20,7 @@ struct PkCellForm {
     int flag_unit;      // variant 2 only, 0 = off: m + gap of the FLAG FORM -- q0's cell on values rescaled by 255 / (m + gap);
                         // the row bytes are then 0x00 (score = m) or 0x80 (score <= -2 gap)
     int flag_gap;       // ... and the rescaled gap, 255 gap / (m + gap)
+    bool product;       // flag form only: its PRODUCT FORM -- lookup and diagonal add of a row are one v_pk_mad_i16
 };
 
 //   0  every s + gap >= 0: nothing to bias
@@ -25,9 +33,14 @@ struct PkCellForm {
 //   * every entry is either m, with m + gap > 0, or <= -2 gap,
 //   * (m + gap) divides 255 gap: the rescaled gap is an integer (and with it every rescaled H),
 //   * 255 (128 m + gap) / (m + gap) + 255 < 0x7C00: the largest rescaled value, 128 matches + gap + one more folded score.
+// The product form of the flag form: the diagonal term is  a[row base] * b[column base] + H(i-1,j-1)  modulo 2^16,
+// which is H + 255 where the bases agree and a finite negative half where they differ.  It applies when
+//   * the flag form applies,
+//   * the enabled entries are exactly the four diagonal ones (plain match / mismatch scoring),
+//   * the largest rescaled H, 255 * 128 m / (m + gap), is at most kPkProductBound.
 inline PkCellForm pk_cell_form(const int8_t *sm, int gap)
 {
-    PkCellForm f = {0, gap, 0, 0, 0};
+    PkCellForm f = {0, gap, 0, 0, 0, false};
     int lowest = 255, highest = -255;
     for (int k = 0; k < 16; ++k) {
         lowest = int(sm[k]) < lowest ? int(sm[k]) : lowest;
@@ -56,6 +69,9 @@ inline PkCellForm pk_cell_form(const int8_t *sm, int gap)
         255 * (128 * m + gap) + 255 * unit < 0x7C00 * unit) {       // (the bound of the comment above, times m + gap > 0)
         f.flag_unit = unit;
         f.flag_gap = 255 * gap / unit;
+        bool diagonal = true;
+        for (int k = 0; k < 16; ++k) diagonal = diagonal && (int(sm[k]) > -2 * gap) == (k / 4 == k % 4);
+        f.product = diagonal && 255 * 128 * m <= kPkProductBound * unit;
     }
     return f;
 }

@@ -382,6 +382,19 @@ sw128_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ seq2
 // of this file's header then reads: before the first column every input of the cell is 0 and the diagonal term loses, so
 // x = max(left, up) = 0 and the state stays all-zero; after the last column x = max(left, up), bounded by a value some real
 // cell already held, feeding only cells that are themselves past the last column.
+// The PRODUCT FORM of the flag form (q carries kPkProductBit; the host's rule: pk_form.h, derivation in DESIGN.md 5a) is for plain
+// match / mismatch sets, where an entry is enabled exactly when row base = column base.  Lookup and diagonal add of a row are
+// then ONE instruction,  v_pk_mad_i16 t, rowmul, colmul, H(i-1,j-1):  per half a 16-bit multiply-add modulo 2^16 with
+//   rowmul = a[base of X's row] | a[base of Y's row] << 16     (a per-row register, where the flag form keeps its selector)
+//   colmul = b[base of X's column] | b[base of Y's column] << 16    (ONE dword per column in lds_col; no table fetch)
+// and eight constants (gen_pk_product_consts.py, in `rows`) with  a[r] b[r] = 255  and  a[r] b[c], r != c, in the window where
+// a[r] b[c] + H is a finite negative half for every H the set can reach -- the flag form's two addends, 0x00FF and 0x80xx, out
+// of a multiplier.  Halves of a packed instruction do not carry into each other.  7 instructions per two rows (flag form: 8).
+// Pad columns carry colmul = 0, so t = H(i-1,j-1): a folded score of 0, where the flag form disables the cell.  The pad-column
+// argument then reads: before the first column every input of the cell is 0, so t = 0 and x = max3(0, 0, 0) = 0 and the state
+// stays all-zero; after the last column x = max3(left, up, H(i-1,j-1)), three values of H that real cells (or, by induction,
+// pad cells bounded by them) already held -- none above the x it came from, so the running best does not move --
+// feeding only cells that are themselves past the last column.
 // Same anti-diagonal pipeline, DPP hand-over and pad-column argument as sw128_kernel (header of this file).
 __device__ __forceinline__ uint32_t pk_max3(uint32_t a, uint32_t b, uint32_t c)
 {
@@ -502,13 +515,18 @@ __device__ __forceinline__ void pk_two_rows(uint32_t &hq0, uint32_t &hq1, uint32
 //   kPkVert  every s + 2 gap >= 0 (and the row offsets fit): vertical-offset form (generated sweep, gen_pk_sweeps.py)
 // (round 2's unbiased form, pk_two_rows<false>, ran 2-3 % slower than kPkQ0 and is gone: profiles/r03_pk_variants_timing.txt)
 enum PkVariant : int { kPkQ0 = 0, kPkBias = 1, kPkVert = 2 };
+constexpr int kPkProductBit = 1 << 16;      // in the flag form's q: run its product form (`rows` then holds the multipliers)
 
 template <int MODE, int VARIANT, int L>
 __global__ void __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_per_eu(4)))
 sw128_pk_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ seq2s, int32_t *__restrict__ scores,
-                uint32_t n, SmRows rows /* s + gap + Q (kPkVert: s + 2 gap; its flag form: 0x00 / 0x80), every byte in [0, 255] */,
-                int gap, int q /* kPkBias: Q; kPkVert: 0, or m + gap = the flag form (gap is then the rescaled one) */)
+                uint32_t n, SmRows rows /* s + gap + Q (kPkVert: s + 2 gap; its flag form: 0x00 / 0x80), every byte in [0, 255];
+                                           product form: the row multipliers in r[0..1], the column multipliers in r[2..3], 16 bits each */,
+                int gap, int q_arg /* kPkBias: Q; kPkVert: 0, or m + gap = the flag form (gap is then the rescaled one), with
+                                      kPkProductBit = its product form */)
 {
+    const int q = VARIANT == kPkVert ? q_arg & (kPkProductBit - 1) : q_arg;
+    const bool product = VARIANT == kPkVert && (q_arg & kPkProductBit) != 0;      // wave-uniform (a kernel argument)
     static_assert(L == 4 || L == 8 || L == 16, "lanes per pair of alignments");
     constexpr bool kGenerated = VARIANT == kPkQ0 || VARIANT == kPkVert;
     constexpr int R = kSeqLen / L;          // rows per lane (L = lanes per pair of alignments)
@@ -522,7 +540,7 @@ sw128_pk_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ s
     const bool flag_form = VARIANT == kPkVert && q != 0;    // wave-uniform (a kernel argument)
 
     // per column of an alignment pair: the LDS byte offsets (into lds_tab) of the column's score table for X (low half) and
-    // for Y (high half)
+    // for Y (high half); product form: the column's two 16-bit multipliers, X's in the low half and Y's in the high one
     __shared__ uint32_t lds_col[kWavesPerBlock][G * S];
     // lds_tab[b], b < 4: the scores of column base b against the four row bases, one per byte (the transposed matrix);
     // lds_tab[4] = 0 for pad columns (flag form: 0x80808080, every row disabled).  The same for every wavefront of the block, which all write it (identical values).
@@ -561,9 +579,10 @@ sw128_pk_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ s
         lds_tab[lane] = c;
     }
     uint32_t *prof = &lds_col[wv][g * S];
+    const uint32_t pad_code = product ? 0u : kPadCode;      // product form: the column multiplier 0
     for (int k = j; k < PAD; k += L) {
-        prof[k] = kPadCode;
-        prof[PAD + kSeqLen + k] = kPadCode;
+        prof[k] = pad_code;
+        prof[PAD + kSeqLen + k] = pad_code;
     }
     // Column codes and row selectors, four at a time: the bases of four rows / columns sit in the four bytes of a dword, so
     // one mask (and one shift / or) per DWORD prepares all four, and one v_perm_b32 per entry then puts X's byte into byte 0
@@ -574,7 +593,24 @@ sw128_pk_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ s
     //   flag form:     the same two bytes go into bytes 1 and 3 (the HIGH byte of each half), bytes 0 and 2 <- 0xFF
     //                  (selector 0x0D):  ra << 8 | (4 + rb) << 24 | 0x000D000D
     const uint32_t sel_shift = flag_form ? 8u : 0u, sel_const = flag_form ? 0x000D000Du : 0x0C000C00u;
+    //   product form:  bases e = (base of X) | (base of Y) << 16 of a row / column pick their two 16-bit multipliers out of the four
+    //                  in a dword pair with one more v_perm_b32: selector bytes (2 bx, 2 bx + 1, 2 by, 2 by + 1) = 2 * 0x101 e + 0x01000100.
+    //                  The column entry is the column multiplier dword, the row register the row multiplier dword.
     uint32_t rsel[R];
+    if (product) {
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            const uint32_t cx4 = bx[w] & 0x03030303u, cy4 = by[w] & 0x03030303u;
+            const uint32_t ra4 = ax[w] & 0x03030303u, rb4 = ay[w] & 0x03030303u;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t pick = (uint32_t)k | 0x0C000C00u | ((uint32_t)(4 + k) << 16);
+                const uint32_t ce = __builtin_amdgcn_perm(cy4, cx4, pick), re = __builtin_amdgcn_perm(rb4, ra4, pick);
+                prof[PAD + j * R + 4 * w + k] = __builtin_amdgcn_perm(rows.r[3], rows.r[2], ((ce * 0x101u) << 1) + 0x01000100u);
+                rsel[4 * w + k] = __builtin_amdgcn_perm(rows.r[1], rows.r[0], ((re * 0x101u) << 1) + 0x01000100u);
+            }
+        }
+    } else {
 #pragma unroll
     for (int w = 0; w < NW; ++w) {
         const uint32_t cx4 = (bx[w] & 0x03030303u) << 2, cy4 = (by[w] & 0x03030303u) << 2;
@@ -586,6 +622,7 @@ sw128_pk_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ s
             if constexpr (VARIANT == kPkVert) rsel[4 * w + k] = (__builtin_amdgcn_perm(rb4, ra4, pick) << sel_shift) | sel_const;
             else                              rsel[4 * w + k] = __builtin_amdgcn_perm(rb4, ra4, pick) | 0x0C000C00u;
         }
+    }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -633,6 +670,20 @@ sw128_pk_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ s
 #define PK_SECTION 8
 #include "pk_sweeps_gen.inc"
 #undef PK_SECTION
+        } else if (product) {               // (kPkVert only) the flag form with one multiply-add for lookup and diagonal add
+            if constexpr (R == 32) {
+#define PK_SECTION 432
+#include "pk_sweeps_gen.inc"
+#undef PK_SECTION
+            } else if constexpr (R == 16) {
+#define PK_SECTION 416
+#include "pk_sweeps_gen.inc"
+#undef PK_SECTION
+            } else {
+#define PK_SECTION 408
+#include "pk_sweeps_gen.inc"
+#undef PK_SECTION
+            }
         } else if (flag_form) {             // (kPkVert only) q0's cell on rescaled values, one step per trip
             if constexpr (R == 32) {
 #define PK_SECTION 332
@@ -1286,7 +1337,7 @@ hipError_t launch_L(const LaunchConfig &cfg, const uint8_t *s1, const uint8_t *s
             switch (cfg.pk_variant) {
             case kPkQ0:    hipLaunchKernelGGL((sw128_pk_kernel<MODE, kPkQ0, L>), grid_pk, block, cfg.extra_lds_bytes, stream, s1, s2, out, n32, rows, gap, 0); break;
             case kPkVert:  hipLaunchKernelGGL((sw128_pk_kernel<MODE, kPkVert, L>), grid_pk, block, cfg.extra_lds_bytes, stream, s1, s2, out, n32, rows,
-                                              cfg.pk_flag_unit ? cfg.pk_flag_gap : gap, cfg.pk_flag_unit); break;
+                                              cfg.pk_flag_unit ? cfg.pk_flag_gap : gap, cfg.pk_flag_unit | (cfg.pk_product ? kPkProductBit : 0)); break;
             default:       hipLaunchKernelGGL((sw128_pk_kernel<MODE, kPkBias, L>), grid_pk, block, cfg.extra_lds_bytes, stream, s1, s2, out, n32, rows, gap, cfg.pk_bias); break;
             }
             return hipGetLastError();

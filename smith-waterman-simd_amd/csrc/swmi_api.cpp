@@ -91,6 +91,7 @@ void read_knobs()
     k.lanes = (int)num("SWMI_LANES", 0, 64, 0);
     k.banded_no_i16 = getenv("SWMI_BANDED_NO_I16") != nullptr;
     k.banded_no_pk = getenv("SWMI_BANDED_NO_PK") != nullptr;
+    k.pk_no_product = getenv("SWMI_PK_NO_PRODUCT") != nullptr;
     k.sg_sweep = (int)num("SWMI_SG_SWEEP", 1, 44, -1);
     k.sg_exact = (int)num("SWMI_SG_EXACT", 0, 1, -1);
     const char *gb = getenv("SWMI_GATHER_BACKEND");
@@ -184,6 +185,7 @@ LaunchConfig make_config(const Context &ctx, const int8_t *sm, int gap, SmRows *
     cfg.pk_variant = 0;
     cfg.pk_flag_unit = 0;
     cfg.pk_flag_gap = 0;
+    cfg.pk_product = false;
     if (cfg.use_pk) {
         // Which cell body (sw_kernels.hip PkVariant; the rule is pk_form.h's, tests/pk_edges.py and tests/pk_flag_form.py restate it
         // and hold sets on both sides of each bound):
@@ -197,6 +199,16 @@ LaunchConfig make_config(const Context &ctx, const int8_t *sm, int gap, SmRows *
         cfg.pk_flag_unit = form.flag_unit;
         cfg.pk_flag_gap = form.flag_gap;
         const int add = form.add;
+        if (form.product && !knobs().pk_no_product) {
+            // the product form of the flag form: rows.r[0..1] = the four row multipliers, rows.r[2..3] = the four column
+            // multipliers, 16 bits each
+            cfg.pk_product = true;
+            for (int k = 0; k < 2; ++k) {
+                rows->r[k] = uint32_t(swmi::kPkProductRowMul[2 * k]) | uint32_t(swmi::kPkProductRowMul[2 * k + 1]) << 16;
+                rows->r[2 + k] = uint32_t(swmi::kPkProductColMul[2 * k]) | uint32_t(swmi::kPkProductColMul[2 * k + 1]) << 16;
+            }
+            return cfg;
+        }
         if (form.flag_unit) {               // 0x00: the entry is m (enabled); 0x80: it is <= -2 gap and never decides a cell
             for (int a = 0; a < 4; ++a) {
                 uint32_t r = 0;

@@ -31,6 +31,7 @@ struct LaunchConfig {
                                //   sw_kernels.hip PkVariant
     int pk_flag_unit;          //   variant 2 only, 0 = off: m + gap of its flag form (pk_form.h), which runs variant 0's cell on values
     int pk_flag_gap;           //   rescaled by 255 / (m + gap); rows then hold flag bytes, and this is the rescaled gap
+    bool pk_product;           //   the flag form runs as its product form: rows hold the eight 16-bit multipliers (pk_form.h)
 };
 
 // Score n pairs resident in device memory. packed = 2-bit inputs (32 B per sequence).

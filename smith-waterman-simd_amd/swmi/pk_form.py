@@ -27,6 +27,8 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     lib.swmi_pk_cell_form.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
     lib.swmi_pk_selftest_max3_negative.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]
+    lib.swmi_pk_product_form.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+    lib.swmi_pk_selftest_product_mad.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]
     _lib = lib
     return lib
 
@@ -43,6 +45,31 @@ def cell_form(score_matrix, gap_penalty):
     if rc < 0:
         raise SwmiError(rc, "swmi_pk_cell_form: gap_penalty %d outside [0, 127]" % int(gap_penalty))
     return rc, scale[0], scale[1]
+
+
+def product_form(score_matrix, gap_penalty):
+    """swmi_pk_product_form: (eligible, row multipliers a[4], column multipliers b[4], verified bound) -- eligible is True when the
+    set's flag form runs as the product form (one 16-bit multiply-add per row for lookup and diagonal add); the constants are
+    zeros when it is not."""
+    sm = np.ascontiguousarray(np.asarray(score_matrix).reshape(16))
+    if sm.min() < -128 or sm.max() > 127:
+        raise SwmiError(ERR_DOMAIN, "score_matrix entries must fit int8")
+    sm = sm.astype(np.int8)
+    consts = (ctypes.c_int * 9)()
+    rc = load().swmi_pk_product_form(sm.ctypes.data, int(gap_penalty), consts)
+    if rc < 0:
+        raise SwmiError(rc, "swmi_pk_product_form: gap_penalty %d outside [0, 127]" % int(gap_penalty))
+    return bool(rc), tuple(consts[0:4]), tuple(consts[4:8]), consts[8]
+
+
+def selftest_product_mad():
+    """(comparisons made, mismatches) of swmi_pk_selftest_product_mad: v_pk_mad_i16 with the product form's constants, every
+    (row base, column base), every H up to the verified bound, both halves, and the max3 behind it."""
+    checked, bad = ctypes.c_ulonglong(), ctypes.c_ulonglong()
+    rc = load().swmi_pk_selftest_product_mad(ctypes.byref(checked), ctypes.byref(bad))
+    if rc < 0:
+        raise SwmiError(rc, "swmi_pk_selftest_product_mad failed (HIP error or no device)")
+    return checked.value, bad.value
 
 
 def selftest_max3_negative():

@@ -8,6 +8,9 @@ wavefronts per SIMD.  Streams:
   bias_t64   bias form with the same pairing of T (A stays on the dependency chain, 32-bit)
   vert       "vertical offset" bias form: row r works in domain g * (r + 1), so `up` is the row above's max3 result as it is
              (chain = max3 -> max3), the saturating subtraction and the re-biasing add leave the chain, and both adds pair
+  prod       "product" Q = 0 form for match/mismatch sets: lookup and diagonal add of a row as ONE v_pk_mad_i16 (row multiplier
+             times column multiplier plus H of the row above), 7 instructions per two rows
+  prod_nop   the same with an s_nop in front of the one max3 that follows the subtraction it depends on
 Run: python gen_cell_v3.py > cell_v3.hip && make cell_v3 && ./cell_v3"""
 R = 32
 LO = 32                  # v32..v63: the column (h / hq / L), even-aligned pairs
@@ -91,10 +94,29 @@ def stream(name):
             o += ([B(k - 1)] if k else []) + [Pn(b + 2), M(b), Pn(b + 3), S(b)]
         o += ["s_nop 0", A64(R // 2 - 1), B(R // 2 - 1)]
         return o
+    if name in ("prod", "prod_nop"):
+        # product form: t_i = rowmul_i * colmul + H(i-1) per half, ONE v_pk_mad_i16 per row in place of the perm and the paired add.
+        # colmul in v1; rowmul_i in v64..v95; t in v24..v27 by i % 4 (the mad of row i + 2 issues while t_i, t_(i+1) are live);
+        # x in v6..v9 by i % 4 (the best of pair k - 1 folds in during pair k).  mad_(i+1) reads H(i) before S(i) overwrites it.
+        # Chain M -> S -> M -> S is 4 of the 7 slots per two rows, so one dependent pair is adjacent: S(b) -> M(a + 2); prod_nop
+        # pays an s_nop there instead.
+        t4 = lambda i: v(24 + i % 4)
+        x4 = lambda i: v(6 + i % 4)
+        MAD = lambda i: "v_pk_mad_i16 %s, %s, v1, %s" % (t4(i), v(RSEL + i), v(LO + i - 1) if i else "v11") if i < R else "s_nop 0"
+        M = lambda i: "v_pk_maximum3_f16 %s, %s, %s, %s" % (x4(i), v(LO + i), v(LO + i - 1) if i else "v12", t4(i))
+        S = lambda i: "v_pk_sub_u16 %s, %s, s40 clamp" % (v(LO + i), x4(i))
+        B = lambda k: "v_pk_maximum3_f16 v10, v10, %s, %s" % (x4(2 * k), x4(2 * k + 1))
+        o += [MAD(0), MAD(1)]
+        for k in range(R // 2):
+            a, b = 2 * k, 2 * k + 1
+            o += [M(a), MAD(a + 2), S(a)] + ([B(k - 1)] if k else []) + [M(b), MAD(b + 2), S(b)]
+            o += ["s_nop 0"] if name == "prod_nop" and k + 1 < R // 2 else []
+        o += [B(R // 2 - 1)]
+        return o
     raise SystemExit(name)
 
 
-VARIANTS = ["cur_bias", "cur_q0", "q0_t64", "bias_t64", "vert"]
+VARIANTS = ["cur_bias", "cur_q0", "q0_t64", "bias_t64", "vert", "prod", "prod_nop"]
 
 print('''// GENERATED by gen_cell_v3.py -- do not edit.  Candidate instruction streams for the packed cell (DESIGN.md 5a, round 3).
 #include <hip/hip_runtime.h>
