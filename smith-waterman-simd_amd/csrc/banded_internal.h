@@ -1,0 +1,33 @@
+// banded_internal.h -- what banded_api.cpp (host compiler) and banded_align_kernels.hip (hipcc) of libswmi_banded.so share:
+// the launcher and the size of an alignment's traceback codes (include/swmi_banded.h).
+#ifndef SWMI_BANDED_INTERNAL_H
+#define SWMI_BANDED_INTERNAL_H
+
+#include <hip/hip_runtime_api.h>
+
+#include <cstddef>
+#include <cstdint>
+
+namespace swmi {
+namespace banded {
+
+constexpr int kBandMaxLen = 16384;
+constexpr int kBandWidth = 128;             // diagonals -64 .. 63 around diagonals[k]
+constexpr int kBandTrip = 4;                // iterations per loop trip: one code dword per lane
+constexpr int kBandWalkTrips = 16;          // trips of codes a wavefront's walk window holds in LDS (64 iterations, 4 KiB)
+
+// Bytes of codes per alignment of a traceback launch: one byte per lane and iteration (two cells of 4 bits), a dword per lane
+// and trip, len1 + 63 iterations at the most (lane 0 on row 1 .. lane 63 on row len1) rounded up to whole trips.
+constexpr size_t band_code_bytes(size_t len1) { return 64 * kBandTrip * ((len1 + 63 + kBandTrip - 1) / kBandTrip); }
+
+// n alignments of one (len1, len2) on `stream`; every pointer is device memory but sm (int8[16], host).  diagonals may be
+// NULL (all 0).  codes: n * band_code_bytes(len1) bytes, 16-byte aligned, with moves and steps or NULL with both (ends-only).
+// moves rows are move_words uint64.  Checks nothing: the callers have.
+hipError_t launch_banded_local(const uint8_t *d_seq1s, int len1, const uint8_t *d_seq2s, int len2, const int32_t *d_diagonals, size_t n,
+                               const int8_t *sm, int gap_open, int gap_extend, int32_t *d_scores, int32_t *d_ends, unsigned char *d_codes,
+                               unsigned long long *d_moves, size_t move_words, uint32_t *d_steps, hipStream_t stream);
+
+}  // namespace banded
+}  // namespace swmi
+
+#endif

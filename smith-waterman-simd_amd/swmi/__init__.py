@@ -1210,3 +1210,4 @@ from . import wide             # noqa: E402  (the wide-alphabet aligners of libs
 from . import wide_long        # noqa: E402  (the wide-alphabet aligners for lengths up to 65536, libswmi_wide_long.so, likewise)
 from . import wide_profile     # noqa: E402  (a batch against one position-specific profile, libswmi_wide_profile.so, likewise)
 from . import pk_form          # noqa: E402  (the packed scorer's cell-form rule and flag-form self-test, libswmi_pk_form.so, likewise)
+from . import banded           # noqa: E402  (banded local alignment with end cells and traceback, libswmi_banded.so, likewise)
