@@ -5,7 +5,25 @@
 // text.  Of libswmi.so, linked for the callers' expander, it calls nothing.  The slices are swmi_table.cpp's for one shape:
 // equal runs in caller order within a byte budget.  This file's name lies outside csrc/swmi_*.cpp, which four host-only test
 // programs glob.
+//
+// Compiled a second time with -DSWMI_BANDED_GLOBAL_LIBRARY it is the host side of libswmi_banded_global.so
+// (include/swmi_banded_global.h).  Three things differ there: the entries' names, free_ends in Call with
+// its check, and the launcher and code-size function taken from banded_internal.h.
+#ifdef SWMI_BANDED_GLOBAL_LIBRARY
+#include "../../include/swmi_banded_global.h"
+#define BANDED_ENTRY(name) swmi_banded_global##name
+#define BANDED_ALIGN swmi_banded_global
+#define BANDED_ALIGN_DEVICE swmi_banded_global_device
+#define BANDED_MASK_PARAM unsigned free_ends,          // behind gap_extend in the three aligning entries
+#define BANDED_MASK_ARG , free_ends                    // ... and behind it in their Call
+#else
 #include "../../include/swmi_banded.h"
+#define BANDED_ENTRY(name) swmi_banded##name
+#define BANDED_ALIGN swmi_banded_local
+#define BANDED_ALIGN_DEVICE swmi_banded_local_device
+#define BANDED_MASK_PARAM
+#define BANDED_MASK_ARG
+#endif
 #include "banded_internal.h"
 
 #include <algorithm>
@@ -37,7 +55,13 @@ int fail(int code, const char *fmt, ...)
         if (e_ != hipSuccess) return fail(SWMI_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
+#ifdef SWMI_BANDED_GLOBAL_LIBRARY
+static_assert(kBandMaxLen == SWMI_BANDED_GLOBAL_MAX_LEN && kBandWidth == SWMI_BANDED_GLOBAL_WIDTH);
+constexpr size_t code_bytes(size_t len1) { return band_global_code_bytes(len1); }
+#else
 static_assert(kBandMaxLen == SWMI_BANDED_MAX_LEN && kBandWidth == SWMI_BANDED_WIDTH);
+constexpr size_t code_bytes(size_t len1) { return band_code_bytes(len1); }
+#endif
 constexpr size_t kSliceBytes = size_t(256) << 20;        // an ends-only slice's device bytes
 constexpr size_t kMaxSlice = size_t(1) << 20;            // alignments per slice (and per launch)
 // A traceback slice's device bytes: swmi_local_affine_slices_for's budget, 4096 alignments of its largest shape (len1 = 16384
@@ -49,6 +73,9 @@ struct Call {
     size_t len1, len2, n;
     const int8_t *sm;
     int gap_open, gap_extend;
+#ifdef SWMI_BANDED_GLOBAL_LIBRARY
+    unsigned free_ends;
+#endif
     size_t move_words() const { return SWMI_LOCAL_FULL_MOVE_WORDS(len1, len2); }
 };
 
@@ -56,7 +83,7 @@ struct Call {
 size_t alignment_bytes(const Call &c, bool tb)
 {
     size_t b = c.len1 + c.len2 + sizeof(int32_t) + 5 * sizeof(int32_t);
-    if (tb) b += band_code_bytes(c.len1) + c.move_words() * sizeof(uint64_t) + sizeof(uint32_t);
+    if (tb) b += code_bytes(c.len1) + c.move_words() * sizeof(uint64_t) + sizeof(uint32_t);
     return b;
 }
 
@@ -71,7 +98,8 @@ size_t slice_size(const Call &c, bool tb)
     return std::min(s, c.n);
 }
 
-// The checks in swmi_wide.h's order: the matrix and the gaps, the moves / steps pair; then n = 0, the buffers, the lengths.
+// The checks in swmi_wide.h's order: the matrix and the gaps (and the mask), the moves / steps pair; then n = 0, the buffers,
+// the lengths.
 // 1 = nothing to do.
 int check_call(const Call &c, const void *seq1s, const void *seq2s, const void *scores, const void *ends, const void *moves,
                const void *steps)
@@ -79,6 +107,10 @@ int check_call(const Call &c, const void *seq1s, const void *seq2s, const void *
     if (!c.sm) return fail(SWMI_ERR_INVALID_ARGUMENT, "score_matrix is NULL");
     if (c.gap_open < 0 || c.gap_open > 127 || c.gap_extend < 0 || c.gap_extend > 127)
         return fail(SWMI_ERR_DOMAIN, "gap_open %d / gap_extend %d outside [0,127]", c.gap_open, c.gap_extend);
+#ifdef SWMI_BANDED_GLOBAL_LIBRARY
+    if (c.free_ends > SWMI_BANDED_MAX_FREE_ENDS)
+        return fail(SWMI_ERR_INVALID_ARGUMENT, "free_ends %u is not a mask of SWMI_FREE_* (0..15) or SWMI_BANDED_END_ANYWHERE with SWMI_FREE_BEGIN* (16..19)", c.free_ends);
+#endif
     if (!moves != !steps)
         return fail(SWMI_ERR_INVALID_ARGUMENT, "moves and steps must both be given (traceback) or both be NULL (ends-only)");
     if (c.n == 0) return 1;
@@ -157,8 +189,13 @@ int current(DeviceState **out)
 hipError_t launch(const Call &c, const uint8_t *s1, const uint8_t *s2, const int32_t *diag, size_t m, int32_t *scores, int32_t *ends,
                   unsigned char *codes, unsigned long long *moves, uint32_t *steps, hipStream_t st)
 {
+#ifdef SWMI_BANDED_GLOBAL_LIBRARY
+    return launch_banded_global(s1, (int)c.len1, s2, (int)c.len2, diag, m, c.sm, c.gap_open, c.gap_extend, c.free_ends, scores, ends, codes,
+                                moves, c.move_words(), steps, st);
+#else
     return launch_banded_local(s1, (int)c.len1, s2, (int)c.len2, diag, m, c.sm, c.gap_open, c.gap_extend, scores, ends, codes, moves,
                                c.move_words(), steps, st);
+#endif
 }
 
 int run_device(const Call &c, const void *d_seq1s, const void *d_seq2s, const void *d_diagonals, void *d_scores, void *d_ends,
@@ -182,7 +219,7 @@ int run_device(const Call &c, const void *d_seq1s, const void *d_seq2s, const vo
     unsigned char *codes = nullptr;
     if (tb) {
         auto &sp = ds->spaces[st];
-        const size_t need = slice * band_code_bytes(c.len1);
+        const size_t need = slice * code_bytes(c.len1);
         if (need > sp.second) {
             BANDED_HIP_TRY(hipStreamSynchronize(st));
             if (sp.first) (void)hipFree(sp.first);
@@ -227,7 +264,7 @@ int run_host(const Call &c, const char *entry, const uint8_t *seq1s, const uint8
         if (rc == SWMI_OK) rc = grow(s.d_scores, s.have.scores, std::max<size_t>(slice, 4));
         if (rc == SWMI_OK) rc = grow(s.d_ends, s.have.ends, slice * 4);
         if (rc == SWMI_OK && tb) rc = grow(s.d_steps, s.have.steps, std::max<size_t>(slice, 4));
-        if (rc == SWMI_OK && tb) rc = grow(s.d_codes, s.have.codes, slice * band_code_bytes(c.len1));
+        if (rc == SWMI_OK && tb) rc = grow(s.d_codes, s.have.codes, slice * code_bytes(c.len1));
         if (rc == SWMI_OK && tb) rc = grow(s.d_moves, s.have.moves, slice * mw);
         if (rc != SWMI_OK) return rc;
     }
@@ -279,11 +316,11 @@ using namespace swmi::banded;
 
 extern "C" {
 
-const char *swmi_banded_last_error(void) { return t_error; }
+const char *BANDED_ENTRY(_last_error)(void) { return t_error; }
 
-int swmi_banded_version(void) { return SWMI_VERSION; }
+int BANDED_ENTRY(_version)(void) { return SWMI_VERSION; }
 
-int swmi_banded_release_workspaces(void)
+int BANDED_ENTRY(_release_workspaces)(void)
 {
     DeviceState *ds = nullptr;
     const int rc = current(&ds);
@@ -295,43 +332,48 @@ int swmi_banded_release_workspaces(void)
     return SWMI_OK;
 }
 
-size_t swmi_banded_slices_for(size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap)
+size_t BANDED_ENTRY(_slices_for)(size_t n, size_t len1, size_t len2, int traceback, size_t *sizes, size_t cap)
 {
     if (!lengths_ok(len1, len2)) {
         (void)fail(SWMI_ERR_INVALID_ARGUMENT, "len1 %zu / len2 %zu outside [1,%d]", len1, len2, kBandMaxLen);
         return 0;
     }
     if (n == 0) return 0;
-    const size_t s = slice_size(Call{len1, len2, n, nullptr, 0, 0}, traceback != 0);
+    Call c{};
+    c.len1 = len1;
+    c.len2 = len2;
+    c.n = n;
+    const size_t s = slice_size(c, traceback != 0);
     size_t count = 0;
     for (size_t off = 0; off < n; off += s, ++count)
         if (sizes && count < cap) sizes[count] = std::min(s, n - off);
     return count;
 }
 
-int swmi_banded_local(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t len2, size_t n, const int32_t *diagonals,
-                      const int8_t score_matrix[16], int gap_open, int gap_extend, int32_t *scores, int32_t *ends, uint64_t *moves,
-                      uint32_t *steps)
+int BANDED_ALIGN(const uint8_t *seq1s, size_t len1, const uint8_t *seq2s, size_t len2, size_t n, const int32_t *diagonals,
+                 const int8_t score_matrix[16], int gap_open, int gap_extend, BANDED_MASK_PARAM int32_t *scores, int32_t *ends,
+                 uint64_t *moves, uint32_t *steps)
 {
-    return run_host(Call{len1, len2, n, score_matrix, gap_open, gap_extend}, __func__, seq1s, seq2s, diagonals, scores, ends, moves, steps);
+    return run_host(Call{len1, len2, n, score_matrix, gap_open, gap_extend BANDED_MASK_ARG}, __func__, seq1s, seq2s, diagonals, scores, ends,
+                    moves, steps);
 }
 
-int swmi_banded_local_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n, const void *d_diagonals,
-                             const int8_t score_matrix[16], int gap_open, int gap_extend, void *d_scores, void *d_ends, void *d_moves,
-                             void *d_steps, void *stream)
+int BANDED_ALIGN_DEVICE(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n, const void *d_diagonals,
+                        const int8_t score_matrix[16], int gap_open, int gap_extend, BANDED_MASK_PARAM void *d_scores, void *d_ends,
+                        void *d_moves, void *d_steps, void *stream)
 {
-    return run_device(Call{len1, len2, n, score_matrix, gap_open, gap_extend}, d_seq1s, d_seq2s, d_diagonals, d_scores, d_ends, d_moves,
-                      d_steps, stream);
+    return run_device(Call{len1, len2, n, score_matrix, gap_open, gap_extend BANDED_MASK_ARG}, d_seq1s, d_seq2s, d_diagonals, d_scores,
+                      d_ends, d_moves, d_steps, stream);
 }
 
 // one untimed device call first (it grows the workspace, which synchronises the stream), then HIP events around `iters`
-int swmi_banded_time_device(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n, const void *d_diagonals,
-                            const int8_t score_matrix[16], int gap_open, int gap_extend, void *d_scores, void *d_ends, void *d_moves,
-                            void *d_steps, void *stream, int iters, float *avg_ms)
+int BANDED_ENTRY(_time_device)(const void *d_seq1s, size_t len1, const void *d_seq2s, size_t len2, size_t n, const void *d_diagonals,
+                               const int8_t score_matrix[16], int gap_open, int gap_extend, BANDED_MASK_PARAM void *d_scores, void *d_ends,
+                               void *d_moves, void *d_steps, void *stream, int iters, float *avg_ms)
 {
     if (!avg_ms || iters < 1) return fail(SWMI_ERR_INVALID_ARGUMENT, "avg_ms is NULL or iters %d < 1", iters);
     if (n == 0) return fail(SWMI_ERR_INVALID_ARGUMENT, "n is 0");
-    const Call c{len1, len2, n, score_matrix, gap_open, gap_extend};
+    const Call c{len1, len2, n, score_matrix, gap_open, gap_extend BANDED_MASK_ARG};
     hipStream_t st = static_cast<hipStream_t>(stream);
     int rc = run_device(c, d_seq1s, d_seq2s, d_diagonals, d_scores, d_ends, d_moves, d_steps, stream);
     if (rc != SWMI_OK) return rc;

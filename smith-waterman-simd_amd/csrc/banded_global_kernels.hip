@@ -1,0 +1,348 @@
+// banded_global_kernels.hip -- the kernels of libswmi_banded_global.so (include/swmi_banded_global.h):
+// global, fit, overlap and extension alignment with affine gaps on the 128 diagonals -64 <= (j - i) - d0 <= 63 of a
+// len1 x len2 table, with end cell, start cell and traceback or ends-only.  No zero floor; the mask is a runtime argument.
+//
+// The mapping, the loads, the gap folding, the codes and the walk window are banded_align_kernels.hip's (section 33); that file
+// stays as it is, and the small helpers (lane shifts, max, clamp, Rows) are a second copy here.  What differs:
+//
+// MINUS INFINITY IS A VALUE: kNeg = -2^29 on plain int32.  Every finite H, E or F lies in [-127 (len1 + len2), 127 min(len1,
+// len2)], above -4.2e6.  A value computed from kNeg moves away from it by at most 128 a step of a path of at most len1 + len2
+// steps (a diagonal step adds a matrix entry in [-128, 127], a gap step takes at most 127 + 127 once), so it stays within
+// [kNeg - 4.3e6, kNeg + 2.1e6] -- int32 never wraps -- and "below kInfeasible = -2^28" tells the two apart.  A cell outside the
+// table is reset to kNeg itself, so nothing drifts along the sweep outside the table.  A finite H never equals a value made
+// from kNeg, so H's source code never points at an out-of-band or off-table neighbour.
+//
+// ROWS AND ITERATIONS.  Row 0 and column 0 are real cells, so the sweep starts one row earlier than the local one: in
+// iteration tt (absolute) lane m sits on row i = tt - m, its even cell on column j = i + 2m - 64 + d0, its odd cell on j + 1.
+// Rows that meet the band: i_lo = max(0, -63 - d0) .. i_hi = min(len1, len2 + 64 - d0); iterations i_lo .. i_hi + 63 in whole
+// trips of kBandTrip.  Every cell is computed by the recurrence and then replaced unless it is an interior cell (1 <= i <= len1,
+// 1 <= j <= len2): a border cell of the table takes its closed form (0, the gap from (0,0), or kNeg when (0,0) is not in the
+// band) and hands over what a cell with that H and E = F = -infinity hands over; a cell off the table takes kNeg.  Lane 0's
+// left and lane 63's upper neighbour lie outside the band: the lane shift runs unconditionally and a select puts kNeg there.
+//
+// BEST.  A cell competes only if it is a candidate under the mask: (len1, len2); column len2 with END1; row len1 with END2;
+// every cell of the table with END_ANYWHERE.  The running best starts at kNeg; within a lane a strict > in arrival order keeps
+// the first cell in row-major order, across lanes the key is (H biased by 2^31) : ~(i << 15 | j), compared unsigned.  A best
+// below kInfeasible writes the NO_ALIGNMENT closed form.  A band that misses the table or every candidate writes it before any
+// other access.  d0 is clamped to +-65536 first.
+//
+// WALK.  No "stop" code: the loop runs while i >= 1 and j >= 1 and the border rule then appends the forced steps (at most 64:
+// they occur only with (0,0) in the band).  The two "never" bounds checks of the local walk are kept.
+#include "banded_internal.h"
+
+#include <hip/hip_runtime.h>
+
+namespace swmi {
+namespace banded {
+namespace {
+
+constexpr int kWaves = 4;                   // wavefronts (alignments) per workgroup
+constexpr int kNeg = -(1 << 29);            // minus infinity
+constexpr int kInfeasible = -(1 << 28);     // every finite value is above, every value made from kNeg below
+constexpr unsigned kBegin1 = 1u, kBegin2 = 2u, kEnd1 = 4u, kEnd2 = 8u, kAnywhere = 16u;
+constexpr int kNoAlignment = -2147483647 - 1;
+
+struct Rows {
+    uint32_t r[4];                          // r[a] = sm[4a .. 4a + 3], one byte per column base
+};
+
+// lane m - 1's / lane m + 1's v; 0 where there is no such lane (the callers select)
+__device__ __forceinline__ int from_below(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138 /* wave_shr:1 */, 0xf, 0xf, true); }
+__device__ __forceinline__ int from_above(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x130 /* wave_shl:1 */, 0xf, 0xf, true); }
+
+__device__ __forceinline__ int max_i(int a, int b) { return a > b ? a : b; }
+__device__ __forceinline__ int min_i(int a, int b) { return a < b ? a : b; }
+__device__ __forceinline__ int clamp_i(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
+
+struct Cell {
+    int h, me, mf;
+};
+
+// One cell from its diagonal H, the values handed to it and its substitution row / column one-hot.  `interior`: the
+// recurrence's value stands; else the cell holds `fixed` (a border's closed form, or kNeg) with E = F = -infinity.
+template <bool kOge, bool kTb>
+__device__ __forceinline__ Cell cell(int arow, int boh, int h_diag, int me_up, int mf_left, int cost, int fold, bool interior, int fixed,
+                                     uint32_t &code)
+{
+    const int e = me_up - cost, f = mf_left - cost;
+    const int d = __builtin_amdgcn_sdot4(arow, boh, h_diag, false);
+    const int h = max_i(d, max_i(e, f));
+    const int a = kOge ? h - fold : h;
+    const int eb = kOge ? e : e - fold, fb = kOge ? f : f - fold;
+    if constexpr (kTb) {
+        const uint32_t src = h == d ? 3u : h == e ? 2u : 1u;
+        code = src | (a >= eb ? 4u : 0u) | (a >= fb ? 8u : 0u);      // (a cell that is not interior: never read by the walk)
+    }
+    const int fa = kOge ? fixed - fold : fixed;
+    Cell out;
+    out.h = interior ? h : fixed;
+    out.me = interior ? max_i(a, eb) : fa;
+    out.mf = interior ? max_i(a, fb) : fa;
+    return out;
+}
+
+template <bool kOge, bool kTb>
+__global__ void __launch_bounds__(64 * kWaves)
+banded_global_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ seq2s, const int32_t *__restrict__ diagonals,
+                     uint32_t n, int len1, int len2, Rows rows, int gap_open, int gap_extend, uint32_t free_ends,
+                     int32_t *__restrict__ scores, int32_t *__restrict__ ends, uint32_t *__restrict__ codes,
+                     unsigned long long *__restrict__ moves, uint32_t move_words, uint32_t *__restrict__ steps)
+{
+    const int lane = threadIdx.x & 63;
+    const int wv = threadIdx.x >> 6;
+    const uint32_t pair = blockIdx.x * kWaves + wv;
+    if (pair >= n) return;                  // wave-uniform; only wave-level synchronisation below
+
+    int d0 = diagonals ? diagonals[pair] : 0;
+    d0 = clamp_i(d0, -65536, 65536);        // before any arithmetic: every int32 is legal
+    d0 = __builtin_amdgcn_readfirstlane(d0);
+    const bool begin1 = free_ends & kBegin1, begin2 = free_ends & kBegin2, end1 = free_ends & kEnd1, end2 = free_ends & kEnd2;
+    const bool anywhere = free_ends & kAnywhere;
+    int32_t *e_out = ends + 4 * (size_t)pair;
+    auto no_alignment = [&]() {
+        if (lane == 0) {
+            scores[pair] = kNoAlignment;
+            e_out[0] = e_out[1] = 0;
+            e_out[2] = e_out[3] = kTb ? 0 : -1;
+            if constexpr (kTb) steps[pair] = 0;
+        }
+    };
+    const int i_lo = max_i(0, -63 - d0), i_hi = min_i(len1, len2 + 64 - d0);
+    {
+        // the candidates in the band: the corner; column len2's rows with END1; row len1's columns with END2; any cell
+        const int dc = len2 - len1 - d0;
+        const bool corner = dc >= -64 && dc <= 63;
+        const bool col = end1 && max_i(0, len2 - d0 - 63) <= min_i(len1, len2 - d0 + 64);
+        const bool row = end2 && max_i(0, len1 + d0 - 64) <= min_i(len2, len1 + d0 + 63);
+        if (i_lo > i_hi || !(corner || col || row || anywhere)) {
+            no_alignment();
+            return;
+        }
+    }
+    const int n_trips = (i_hi - i_lo + 64 + kBandTrip - 1) / kBandTrip;
+
+    const uint8_t *s1 = seq1s + (size_t)pair * (size_t)len1;
+    const uint8_t *s2 = seq2s + (size_t)pair * (size_t)len2;
+    uint32_t *cd = nullptr;
+    if constexpr (kTb) cd = codes + (size_t)pair * (band_global_code_bytes((size_t)len1) / 4);
+
+    const int cost = kOge ? gap_extend : gap_open;
+    const int fold = kOge ? gap_open - gap_extend : gap_extend - gap_open;
+    // the borders' closed forms: H(0, j) = row0_at - (j - 1) row0_step, H(i, 0) = col0_at - (i - 1) col0_step
+    const bool origin = d0 >= -63 && d0 <= 64;                 // (0,0) is in the band
+    const int row0_at = begin2 ? 0 : origin ? -gap_open : kNeg, row0_step = !begin2 && origin ? gap_extend : 0;
+    const int col0_at = begin1 ? 0 : origin ? -gap_open : kNeg, col0_step = !begin1 && origin ? gap_extend : 0;
+
+    // row scores of a seq1 byte, one-hot of a seq2 byte
+    auto row_of = [&](uint32_t a) {
+        const uint32_t lo = (a & 1u) ? rows.r[1] : rows.r[0], hi = (a & 1u) ? rows.r[3] : rows.r[2];
+        return (int)((a & 2u) ? hi : lo);
+    };
+    auto hot_of = [](uint32_t b) { return (int)(1u << (8u * (b & 3u))); };
+    auto load1 = [&](int idx) { return (uint32_t)s1[clamp_i(idx, 0, len1 - 1)]; };
+    auto load2 = [&](int idx) { return (uint32_t)s2[clamp_i(idx, 0, len2 - 1)]; };
+
+    // 0-based: r = i - 1 of the lane at the trip's first iteration (-1 on row 0), ce = j - 1 of its even cell there
+    int r = i_lo - 1 - lane, ce = i_lo - 1 + lane - 64 + d0;
+    int b_even = hot_of(load2(ce));
+    uint32_t a_nxt[kBandTrip], b_nxt[kBandTrip];
+#pragma unroll
+    for (int k = 0; k < kBandTrip; ++k) {
+        a_nxt[k] = load1(r + k);
+        b_nxt[k] = load2(ce + 1 + k);
+    }
+
+    Cell c0{kNeg, kNeg, kNeg}, c1{kNeg, kNeg, kNeg};    // the lane's last even and odd cell: off the table
+    int best = kNeg;
+    uint32_t best_pos = 0;                               // i << 15 | j
+
+#pragma unroll 1
+    for (int trip = 0; trip < n_trips; ++trip) {
+        int a_row[kBandTrip], b_hot[kBandTrip];
+#pragma unroll
+        for (int k = 0; k < kBandTrip; ++k) {
+            a_row[k] = row_of(a_nxt[k]);
+            b_hot[k] = hot_of(b_nxt[k]);
+        }
+        // the next trip's bytes (clamped indices: behind the last trip they are loaded and not used)
+#pragma unroll
+        for (int k = 0; k < kBandTrip; ++k) {
+            a_nxt[k] = load1(r + kBandTrip + k);
+            b_nxt[k] = load2(ce + 1 + kBandTrip + k);
+        }
+        uint32_t word = 0;
+#pragma unroll
+        for (int k = 0; k < kBandTrip; ++k) {
+            const int i = r + k + 1, j0 = ce + k + 1, j1 = j0 + 1;
+            const bool row_in = (uint32_t)i <= (uint32_t)len1;
+            const bool in0 = row_in && (uint32_t)j0 <= (uint32_t)len2, in1 = row_in && (uint32_t)j1 <= (uint32_t)len2;
+            const bool int0 = in0 && i >= 1 && j0 >= 1, int1 = in1 && i >= 1 && j1 >= 1;
+            // what a cell that is not interior holds: off the table kNeg, (0,0) 0, else its border's closed form
+            const int col0 = i == 0 ? 0 : col0_at - (i - 1) * col0_step;
+            const int row0_0 = row0_at - (j0 - 1) * row0_step;
+            const int fix0 = !in0 ? kNeg : j0 == 0 ? col0 : row0_0;
+            const int fix1 = !in1 ? kNeg : j1 == 0 ? col0 : row0_0 - row0_step;
+            const bool last_row = i == len1;
+            const bool cand_row = anywhere || (end2 && last_row);
+            const bool cand0 = in0 && (cand_row || (j0 == len2 && (end1 || last_row)));
+            const bool cand1 = in1 && (cand_row || (j1 == len2 && (end1 || last_row)));
+            const uint32_t pos = ((uint32_t)i << 15) + (uint32_t)j0;
+            uint32_t code0 = 0, code1 = 0;
+            // even cell: left = lane m - 1's odd cell of the last iteration.  The shift stands outside the select: under a
+            // branch on the lane it would run with lane 0 switched off, and lane 1 would read 0 from it
+            const int left_in = from_below(c1.mf);
+            const int left = lane == 0 ? kNeg : left_in;
+            c0 = cell<kOge, kTb>(a_row[k], b_even, c0.h, c1.me, left, cost, fold, int0, fix0, code0);
+            if (cand0 && c0.h > best) {
+                best = c0.h;
+                best_pos = pos;
+            }
+            // odd cell: up = lane m + 1's even cell of this iteration
+            const int up_in = from_above(c0.me);
+            const int up = lane == 63 ? kNeg : up_in;
+            c1 = cell<kOge, kTb>(a_row[k], b_hot[k], c1.h, up, c0.mf, cost, fold, int1, fix1, code1);
+            if (cand1 && c1.h > best) {
+                best = c1.h;
+                best_pos = pos + 1;
+            }
+            b_even = b_hot[k];
+            if constexpr (kTb) word |= (code0 | (code1 << 4)) << (8 * k);
+        }
+        if constexpr (kTb) cd[(size_t)trip * 64 + lane] = word;
+        r += kBandTrip;
+        ce += kBandTrip;
+    }
+
+    // the first cell in row-major order among the lanes' bests; H is signed, so it is biased before the unsigned compare
+    uint32_t key_hi = (uint32_t)best ^ 0x80000000u, key_lo = ~best_pos;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t hi = (uint32_t)__shfl_xor((int)key_hi, o), lo = (uint32_t)__shfl_xor((int)key_lo, o);
+        const bool take = hi > key_hi || (hi == key_hi && lo > key_lo);
+        key_hi = take ? hi : key_hi;
+        key_lo = take ? lo : key_lo;
+    }
+    best = (int)(key_hi ^ 0x80000000u);
+    best_pos = ~key_lo;
+    if (best < kInfeasible) {               // wave-uniform: no candidate, or every candidate holds -infinity
+        no_alignment();
+        return;
+    }
+    const int bi = (int)(best_pos >> 15), bj = (int)(best_pos & 32767u);
+    if constexpr (!kTb) {
+        if (lane == 0) {
+            scores[pair] = best;
+            e_out[0] = bi;
+            e_out[1] = bj;
+            e_out[2] = e_out[3] = -1;
+        }
+        return;
+    } else {
+        __shared__ uint32_t window[kWaves][kBandWalkTrips * 64];
+        uint32_t *win = window[wv];
+        const unsigned char *win8 = reinterpret_cast<const unsigned char *>(win);
+        // this wave's code stores have reached L2, and the window's loads do not take them from the L1
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        unsigned long long *mv = moves + (size_t)pair * (size_t)move_words;
+        int i = bi, j = bj, state = 0;      // state: 0 = H, 2 = in a vertical gap (E), 1 = in a horizontal gap (F)
+        int w_lo = n_trips;                 // the window holds trips [w_lo, w_lo + kBandWalkTrips): nothing yet
+        uint32_t t = 0;
+        unsigned long long word = 0;
+        auto step = [&](int dir) {
+            word |= (unsigned long long)dir << (2 * (t & 31u));
+            ++t;
+            if ((t & 31u) == 0) {
+                if (lane == 0) mv[(t >> 5) - 1] = word;
+                word = 0;
+            }
+        };
+        bool lost = false;
+        while (i >= 1 && j >= 1) {          // E(1, j) and F(i, 1) always open: the border is reached in state H
+            const int dl = j - i - d0 + 64; // the band diagonal, 0 .. 127
+            if ((uint32_t)dl > 127u) { lost = true; break; }                    // (never: the walk cannot leave the band)
+            const int ln = dl >> 1, rel = i + ln - i_lo;                        // the lane and iteration that hold the cell
+            if (rel < 0 || rel >= n_trips * kBandTrip) { lost = true; break; }  // (never: every cell of the table in the band was swept)
+            const int q = rel >> 2;
+            if (q < w_lo || q >= w_lo + kBandWalkTrips) {
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();            // every lane is past its reads of the old window
+                w_lo = max_i(q - (kBandWalkTrips - 1), 0);
+                const int cnt = n_trips - w_lo < kBandWalkTrips ? n_trips - w_lo : kBandWalkTrips;
+                for (int x = 0; x < cnt; ++x) win[x * 64 + lane] = __builtin_nontemporal_load(cd + (size_t)(w_lo + x) * 64 + lane);
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            }
+            const uint32_t byte = win8[((q - w_lo) * 64 + ln) * 4 + (rel & 3)];
+            const uint32_t c = (byte >> (4 * (dl & 1))) & 15u;
+            // arrived in a gap: it ends here if the value this cell handed over opened it
+            if (state == 2 && (c & 4u)) state = 0;
+            if (state == 1 && (c & 8u)) state = 0;
+            int dir = state;
+            if (state == 0) dir = (int)(c & 3u);
+            if (dir == 0) { lost = true; break; }                               // (never: an interior cell's source is 1, 2 or 3)
+            step(dir);
+            if (dir == 3) {
+                --i;
+                --j;
+                state = 0;
+            } else if (dir == 2) {
+                --i;
+                state = 2;
+            } else {
+                --j;
+                state = 1;
+            }
+        }
+        // the border rule: a border that is not free is walked to (0,0) by forced steps
+        if (!lost) {
+            if (i == 0 && !begin2)
+                for (; j > 0; --j) step(1);
+            if (j == 0 && !begin1)
+                for (; i > 0; --i) step(2);
+        }
+        if (lane == 0) {
+            if (t & 31u) mv[t >> 5] = word;
+            scores[pair] = best;
+            e_out[0] = bi;
+            e_out[1] = bj;
+            e_out[2] = i;
+            e_out[3] = j;
+            steps[pair] = t;
+        }
+    }
+}
+
+}  // namespace
+
+hipError_t launch_banded_global(const uint8_t *d_seq1s, int len1, const uint8_t *d_seq2s, int len2, const int32_t *d_diagonals, size_t n,
+                                const int8_t *sm, int gap_open, int gap_extend, unsigned free_ends, int32_t *d_scores, int32_t *d_ends,
+                                unsigned char *d_codes, unsigned long long *d_moves, size_t move_words, uint32_t *d_steps,
+                                hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    Rows rows;
+    for (int a = 0; a < 4; ++a) {
+        rows.r[a] = 0;
+        for (int b = 0; b < 4; ++b) rows.r[a] |= (uint32_t)(uint8_t)sm[4 * a + b] << (8 * b);
+    }
+    const dim3 grid((unsigned)((n + kWaves - 1) / kWaves)), block(64 * kWaves);
+    const bool tb = d_moves != nullptr, oge = gap_open >= gap_extend;
+    uint32_t *codes = reinterpret_cast<uint32_t *>(d_codes);
+#define BANDED_LAUNCH(OGE, TB)                                                                                                        \
+    hipLaunchKernelGGL((banded_global_kernel<OGE, TB>), grid, block, 0, stream, d_seq1s, d_seq2s, d_diagonals, (uint32_t)n, len1, len2, rows, \
+                       gap_open, gap_extend, (uint32_t)free_ends, d_scores, d_ends, codes, d_moves, (uint32_t)move_words, d_steps)
+    if (tb) {
+        if (oge) BANDED_LAUNCH(true, true);
+        else BANDED_LAUNCH(false, true);
+    } else {
+        if (oge) BANDED_LAUNCH(true, false);
+        else BANDED_LAUNCH(false, false);
+    }
+#undef BANDED_LAUNCH
+    return hipGetLastError();
+}
+
+}  // namespace banded
+}  // namespace swmi

@@ -27,6 +27,18 @@ hipError_t launch_banded_local(const uint8_t *d_seq1s, int len1, const uint8_t *
                                const int8_t *sm, int gap_open, int gap_extend, int32_t *d_scores, int32_t *d_ends, unsigned char *d_codes,
                                unsigned long long *d_moves, size_t move_words, uint32_t *d_steps, hipStream_t stream);
 
+// ---- libswmi_banded_global.so (banded_global_kernels.hip, include/swmi_banded_global.h) ----
+// Bytes of codes per alignment of a traceback launch of the global kernels: the same layout, but row 0 is swept too (its
+// cells are real cells there), so there is one iteration more: lane 0 on row 0 .. lane 63 on row len1, len1 + 64 at the most.
+constexpr size_t band_global_code_bytes(size_t len1) { return 64 * kBandTrip * ((len1 + 64 + kBandTrip - 1) / kBandTrip); }
+
+// As launch_banded_local, with free_ends (SWMI_FREE_* | SWMI_BANDED_END_ANYWHERE, checked by the caller) and codes of
+// n * band_global_code_bytes(len1) bytes.
+hipError_t launch_banded_global(const uint8_t *d_seq1s, int len1, const uint8_t *d_seq2s, int len2, const int32_t *d_diagonals, size_t n,
+                                const int8_t *sm, int gap_open, int gap_extend, unsigned free_ends, int32_t *d_scores, int32_t *d_ends,
+                                unsigned char *d_codes, unsigned long long *d_moves, size_t move_words, uint32_t *d_steps,
+                                hipStream_t stream);
+
 }  // namespace banded
 }  // namespace swmi
 
