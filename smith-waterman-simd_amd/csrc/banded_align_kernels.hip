@@ -2,89 +2,30 @@
 // with affine gaps on the 128 diagonals -64 <= (j - i) - d0 <= 63 of a len1 x len2 table, with end cell, start cell and
 // traceback or ends-only.
 //
-// MAPPING (section 9's, with the int32 cell).  One wavefront sweeps ONE alignment's anti-diagonals; lane m owns band diagonals
-// 2m (its even cell) and 2m + 1 (its odd cell).  In iteration t lane m sits on row i = 1 - m + t; its even cell is column
-// j = i + 2m - 64 + d0 and its odd cell column j + 1 (section 9's u is t - 32).  Neighbours:
-//   even cell: diagonal = own even cell of t - 1, up = own odd cell of t - 1, left = lane m - 1's odd cell of t - 1
-//   odd cell:  diagonal = own odd cell of t - 1,  left = own even cell of t,  up = lane m + 1's even cell of t
-// Only rows that meet the band are swept: i_lo = max(1, -62 - d0) .. i_hi = min(len1, len2 + 64 - d0), that is iterations
-// t0 = i_lo - 1 .. i_hi + 62 in whole trips of kBandTrip = 4.  A band that misses the table (i_lo > i_hi) writes its closed form
-// and returns before any other load or store.  d0 is clamped to +-65536 first: beyond +-(16384 + 64) every band misses.
+// The lane mapping, the loads, the gap folding, the codes and the walk window are banded_sweep.h's.  What is this file's:
 //
-// SEQUENCES: no LDS stage.  Every lane loads its own row base (seq1[t - m]) and column base (seq2[t + m - 63 + d0], the odd
-// cell's: the even cell's is last iteration's odd one) one trip ahead, four bytes of each per trip, from indices clamped into
-// the sequence.  A wavefront's 64 bytes of one load are consecutive, so they cost one or two cache lines; the LDS a wavefront
-// takes does not depend on the lengths (the traceback kernels hold the walk window there, the ends-only kernels nothing).
+// ROWS AND ITERATIONS.  In iteration t lane m sits on row i = 1 - m + t; its even cell is column j = i + 2m - 64 + d0 and its
+// odd cell column j + 1 (section 9's u is t - 32).  Only rows that meet the band are swept: i_lo = max(1, -62 - d0) ..
+// i_hi = min(len1, len2 + 64 - d0), that is iterations t0 = i_lo - 1 .. i_hi + 62 in whole trips of kBandTrip = 4.  A lane loads
+// its row base seq1[t - m] and its column base seq2[t + m - 63 + d0].  A band that misses the table (i_lo > i_hi) writes its
+// closed form and returns before any other load or store.  d0 is clamped to +-65536 first: beyond +-(16384 + 64) every band
+// misses.
 //
-// CELLS OUTSIDE THE TABLE (row < 1 or > len1, column < 1 or > len2) are computed like any other and then replaced by what the
-// contract gives them: H = 0, E = F = -infinity, that is the hand-over values of a cell holding H = 0, and code "stop".  They
-// never reach the best (0 is never greater) and never a code that the walk reads.  Outside the BAND lie lane 0's left and
-// lane 63's upper neighbour; the lane shift delivers nothing there and a select puts the same hand-over value in its place.
-//
-// GAPS are folded as in section 9, on signed int32 without saturation.  A cell hands ONE value down (me) and one to the right
-// (mf); with fold = |open - extend| and cost = min(open, extend):
-//   open >= extend:  a = H - fold, me = max(a, E), mf = max(a, F)            and the receiver takes  E' = me - extend
-//   open <  extend:  a = H,        me = max(a, E - fold), mf = max(a, F - fold)   and                E' = me - open
-// E' opened (came from H) iff a >= its partner: the tie goes to the opening.  That bit is known where the value is made, so it
-// is stored in the code of the cell that HANDS OVER, and the walk reads it after its up or left move, in the cell it arrives
-// at, which it has to read anyway.  A cell that hands over H = 0, E = F = -infinity hands over base = (open >= extend ? -fold : 0).
+// THE FLOOR AND CELLS OUTSIDE THE TABLE (row < 1 or > len1, column < 1 or > len2).  H has a floor at 0.  A cell outside the
+// table is computed like any other and then replaced by what the contract gives it: H = 0, E = F = -infinity, that is the
+// hand-over values of a cell holding H = 0, base = (open >= extend ? -fold : 0), and code "stop".  They never reach the best (0
+// is never greater) and never a code that the walk reads.  Lane 0's left and lane 63's upper neighbour take base as well.
 // Every value is at least -127 - 127 and at most 127 * 16384: int32 never wraps.
-//
-// CODES: 4 bits per cell: bits 0-1 H's source (0 stop, 3 diagonal, 2 E, 1 F, tested in that order), bit 2 "the E handed down
-// opens", bit 3 "the F handed right opens".  A lane's two cells of an iteration are one byte, its four iterations of a trip one
-// dword: dword (trip * 64 + lane) of the alignment's codes, a 256-byte store per wavefront and trip.
 //
 // BEST: within a lane rows grow with t and the even cell lies left of the odd one, so a strict > in arrival order keeps the
 // lane's first cell in row-major order.  Across lanes the 64 (H, i, j) are reduced as a 64-bit key H : ~(i << 15 | j).
 //
-// WALK: all 64 lanes walk the same cell (wave-uniform; lane 0 stores).  The codes of kBandWalkTrips trips ending at the walk's
-// trip are loaded into LDS by the whole wavefront; every move goes to iteration t or t - 1, so a window serves at least 64 steps.
-#include "banded_internal.h"
-
-#include <hip/hip_runtime.h>
+// WALK: it stops in state H at a cell whose source is "stop" (H = 0: the start cell); a border cell holds 0.
+#include "banded_sweep.h"
 
 namespace swmi {
 namespace banded {
 namespace {
-
-constexpr int kWaves = 4;                   // wavefronts (alignments) per workgroup
-
-struct Rows {
-    uint32_t r[4];                          // r[a] = sm[4a .. 4a + 3], one byte per column base
-};
-
-// lane m - 1's / lane m + 1's v; 0 where there is no such lane (the callers select)
-__device__ __forceinline__ int from_below(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138 /* wave_shr:1 */, 0xf, 0xf, true); }
-__device__ __forceinline__ int from_above(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x130 /* wave_shl:1 */, 0xf, 0xf, true); }
-
-__device__ __forceinline__ int max_i(int a, int b) { return a > b ? a : b; }
-__device__ __forceinline__ int clamp_i(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
-
-struct Cell {
-    int h, me, mf;
-};
-
-// One cell from its diagonal H, the values handed to it and its substitution row / column one-hot.
-template <bool kOge, bool kTb>
-__device__ __forceinline__ Cell cell(int arow, int boh, int h_diag, int me_up, int mf_left, int cost, int fold, int base, bool valid,
-                                     uint32_t &code)
-{
-    const int e = me_up - cost, f = mf_left - cost;
-    const int d = __builtin_amdgcn_sdot4(arow, boh, h_diag, false);
-    const int h = max_i(max_i(d, e), max_i(f, 0));
-    const int a = kOge ? h - fold : h;
-    const int eb = kOge ? e : e - fold, fb = kOge ? f : f - fold;
-    if constexpr (kTb) {
-        const uint32_t src = h == 0 ? 0u : h == d ? 3u : h == e ? 2u : 1u;
-        const uint32_t c = src | (a >= eb ? 4u : 0u) | (a >= fb ? 8u : 0u);
-        code = valid ? c : 12u;
-    }
-    Cell out;
-    out.h = valid ? h : 0;
-    out.me = valid ? max_i(a, eb) : base;
-    out.mf = valid ? max_i(a, fb) : base;
-    return out;
-}
 
 template <bool kOge, bool kTb>
 __global__ void __launch_bounds__(64 * kWaves)
@@ -173,7 +114,7 @@ banded_local_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict
             // branch on the lane it would run with lane 0 switched off, and lane 1 would read 0 from it
             const int left_in = from_below(c1.mf);
             const int left = lane == 0 ? base : left_in;
-            c0 = cell<kOge, kTb>(a_row[k], b_even, c0.h, c1.me, left, cost, fold, base, ok0, code0);
+            c0 = cell<true, kOge, kTb>(a_row[k], b_even, c0.h, c1.me, left, cost, fold, ok0, 0, code0);
             if (c0.h > best) {
                 best = c0.h;
                 best_pos = pos;
@@ -181,7 +122,7 @@ banded_local_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict
             // odd cell: up = lane m + 1's even cell of this iteration
             const int up_in = from_above(c0.me);
             const int up = lane == 63 ? base : up_in;
-            c1 = cell<kOge, kTb>(a_row[k], b_hot[k], c1.h, up, c0.mf, cost, fold, base, ok1, code1);
+            c1 = cell<true, kOge, kTb>(a_row[k], b_hot[k], c1.h, up, c0.mf, cost, fold, ok1, 0, code1);
             if (c1.h > best) {
                 best = c1.h;
                 best_pos = pos + 1;
@@ -290,26 +231,13 @@ hipError_t launch_banded_local(const uint8_t *d_seq1s, int len1, const uint8_t *
                                unsigned long long *d_moves, size_t move_words, uint32_t *d_steps, hipStream_t stream)
 {
     if (n == 0) return hipSuccess;
-    Rows rows;
-    for (int a = 0; a < 4; ++a) {
-        rows.r[a] = 0;
-        for (int b = 0; b < 4; ++b) rows.r[a] |= (uint32_t)(uint8_t)sm[4 * a + b] << (8 * b);
-    }
-    const dim3 grid((unsigned)((n + kWaves - 1) / kWaves)), block(64 * kWaves);
-    const bool tb = d_moves != nullptr, oge = gap_open >= gap_extend;
+    const Rows rows = pack_rows(sm);
     uint32_t *codes = reinterpret_cast<uint32_t *>(d_codes);
-#define BANDED_LAUNCH(OGE, TB)                                                                                                       \
-    hipLaunchKernelGGL((banded_local_kernel<OGE, TB>), grid, block, 0, stream, d_seq1s, d_seq2s, d_diagonals, (uint32_t)n, len1, len2, rows, \
-                       gap_open, gap_extend, d_scores, d_ends, codes, d_moves, (uint32_t)move_words, d_steps)
-    if (tb) {
-        if (oge) BANDED_LAUNCH(true, true);
-        else BANDED_LAUNCH(false, true);
-    } else {
-        if (oge) BANDED_LAUNCH(true, false);
-        else BANDED_LAUNCH(false, false);
-    }
-#undef BANDED_LAUNCH
-    return hipGetLastError();
+    return launch_variant(gap_open >= gap_extend, d_moves != nullptr, n, [&](auto oge, auto tb, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL((banded_local_kernel<decltype(oge)::value, decltype(tb)::value>), grid, block, 0, stream, d_seq1s, d_seq2s,
+                           d_diagonals, (uint32_t)n, len1, len2, rows, gap_open, gap_extend, d_scores, d_ends, codes, d_moves,
+                           (uint32_t)move_words, d_steps);
+    });
 }
 
 }  // namespace banded

@@ -2,8 +2,7 @@
 // global, fit, overlap and extension alignment with affine gaps on the 128 diagonals -64 <= (j - i) - d0 <= 63 of a
 // len1 x len2 table, with end cell, start cell and traceback or ends-only.  No zero floor; the mask is a runtime argument.
 //
-// The mapping, the loads, the gap folding, the codes and the walk window are banded_align_kernels.hip's (section 33); that file
-// stays as it is, and the small helpers (lane shifts, max, clamp, Rows) are a second copy here.  What differs:
+// The lane mapping, the loads, the gap folding, the codes and the walk window are banded_sweep.h's.  What is this file's:
 //
 // MINUS INFINITY IS A VALUE: kNeg = -2^29 on plain int32.  Every finite H, E or F lies in [-127 (len1 + len2), 127 min(len1,
 // len2)], above -4.2e6.  A value computed from kNeg moves away from it by at most 128 a step of a path of at most len1 + len2
@@ -28,58 +27,16 @@
 //
 // WALK.  No "stop" code: the loop runs while i >= 1 and j >= 1 and the border rule then appends the forced steps (at most 64:
 // they occur only with (0,0) in the band).  The two "never" bounds checks of the local walk are kept.
-#include "banded_internal.h"
-
-#include <hip/hip_runtime.h>
+#include "banded_sweep.h"
 
 namespace swmi {
 namespace banded {
 namespace {
 
-constexpr int kWaves = 4;                   // wavefronts (alignments) per workgroup
 constexpr int kNeg = -(1 << 29);            // minus infinity
 constexpr int kInfeasible = -(1 << 28);     // every finite value is above, every value made from kNeg below
 constexpr unsigned kBegin1 = 1u, kBegin2 = 2u, kEnd1 = 4u, kEnd2 = 8u, kAnywhere = 16u;
 constexpr int kNoAlignment = -2147483647 - 1;
-
-struct Rows {
-    uint32_t r[4];                          // r[a] = sm[4a .. 4a + 3], one byte per column base
-};
-
-// lane m - 1's / lane m + 1's v; 0 where there is no such lane (the callers select)
-__device__ __forceinline__ int from_below(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138 /* wave_shr:1 */, 0xf, 0xf, true); }
-__device__ __forceinline__ int from_above(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x130 /* wave_shl:1 */, 0xf, 0xf, true); }
-
-__device__ __forceinline__ int max_i(int a, int b) { return a > b ? a : b; }
-__device__ __forceinline__ int min_i(int a, int b) { return a < b ? a : b; }
-__device__ __forceinline__ int clamp_i(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
-
-struct Cell {
-    int h, me, mf;
-};
-
-// One cell from its diagonal H, the values handed to it and its substitution row / column one-hot.  `interior`: the
-// recurrence's value stands; else the cell holds `fixed` (a border's closed form, or kNeg) with E = F = -infinity.
-template <bool kOge, bool kTb>
-__device__ __forceinline__ Cell cell(int arow, int boh, int h_diag, int me_up, int mf_left, int cost, int fold, bool interior, int fixed,
-                                     uint32_t &code)
-{
-    const int e = me_up - cost, f = mf_left - cost;
-    const int d = __builtin_amdgcn_sdot4(arow, boh, h_diag, false);
-    const int h = max_i(d, max_i(e, f));
-    const int a = kOge ? h - fold : h;
-    const int eb = kOge ? e : e - fold, fb = kOge ? f : f - fold;
-    if constexpr (kTb) {
-        const uint32_t src = h == d ? 3u : h == e ? 2u : 1u;
-        code = src | (a >= eb ? 4u : 0u) | (a >= fb ? 8u : 0u);      // (a cell that is not interior: never read by the walk)
-    }
-    const int fa = kOge ? fixed - fold : fixed;
-    Cell out;
-    out.h = interior ? h : fixed;
-    out.me = interior ? max_i(a, eb) : fa;
-    out.mf = interior ? max_i(a, fb) : fa;
-    return out;
-}
 
 template <bool kOge, bool kTb>
 __global__ void __launch_bounds__(64 * kWaves)
@@ -192,7 +149,7 @@ banded_global_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restric
             // branch on the lane it would run with lane 0 switched off, and lane 1 would read 0 from it
             const int left_in = from_below(c1.mf);
             const int left = lane == 0 ? kNeg : left_in;
-            c0 = cell<kOge, kTb>(a_row[k], b_even, c0.h, c1.me, left, cost, fold, int0, fix0, code0);
+            c0 = cell<false, kOge, kTb>(a_row[k], b_even, c0.h, c1.me, left, cost, fold, int0, fix0, code0);
             if (cand0 && c0.h > best) {
                 best = c0.h;
                 best_pos = pos;
@@ -200,7 +157,7 @@ banded_global_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restric
             // odd cell: up = lane m + 1's even cell of this iteration
             const int up_in = from_above(c0.me);
             const int up = lane == 63 ? kNeg : up_in;
-            c1 = cell<kOge, kTb>(a_row[k], b_hot[k], c1.h, up, c0.mf, cost, fold, int1, fix1, code1);
+            c1 = cell<false, kOge, kTb>(a_row[k], b_hot[k], c1.h, up, c0.mf, cost, fold, int1, fix1, code1);
             if (cand1 && c1.h > best) {
                 best = c1.h;
                 best_pos = pos + 1;
@@ -322,26 +279,13 @@ hipError_t launch_banded_global(const uint8_t *d_seq1s, int len1, const uint8_t 
                                 hipStream_t stream)
 {
     if (n == 0) return hipSuccess;
-    Rows rows;
-    for (int a = 0; a < 4; ++a) {
-        rows.r[a] = 0;
-        for (int b = 0; b < 4; ++b) rows.r[a] |= (uint32_t)(uint8_t)sm[4 * a + b] << (8 * b);
-    }
-    const dim3 grid((unsigned)((n + kWaves - 1) / kWaves)), block(64 * kWaves);
-    const bool tb = d_moves != nullptr, oge = gap_open >= gap_extend;
+    const Rows rows = pack_rows(sm);
     uint32_t *codes = reinterpret_cast<uint32_t *>(d_codes);
-#define BANDED_LAUNCH(OGE, TB)                                                                                                        \
-    hipLaunchKernelGGL((banded_global_kernel<OGE, TB>), grid, block, 0, stream, d_seq1s, d_seq2s, d_diagonals, (uint32_t)n, len1, len2, rows, \
-                       gap_open, gap_extend, (uint32_t)free_ends, d_scores, d_ends, codes, d_moves, (uint32_t)move_words, d_steps)
-    if (tb) {
-        if (oge) BANDED_LAUNCH(true, true);
-        else BANDED_LAUNCH(false, true);
-    } else {
-        if (oge) BANDED_LAUNCH(true, false);
-        else BANDED_LAUNCH(false, false);
-    }
-#undef BANDED_LAUNCH
-    return hipGetLastError();
+    return launch_variant(gap_open >= gap_extend, d_moves != nullptr, n, [&](auto oge, auto tb, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL((banded_global_kernel<decltype(oge)::value, decltype(tb)::value>), grid, block, 0, stream, d_seq1s, d_seq2s,
+                           d_diagonals, (uint32_t)n, len1, len2, rows, gap_open, gap_extend, (uint32_t)free_ends, d_scores, d_ends, codes,
+                           d_moves, (uint32_t)move_words, d_steps);
+    });
 }
 
 }  // namespace banded
