@@ -126,8 +126,12 @@ def _run_pair(rng, x, r, y, up):
     return (long_, short) if up else (short, long_)
 
 
-def carried_cases():
-    """(2, -3), extend 1: the score 2 (x + y) - (open + (r - 1)) pins the path to one gap run (2 x and 2 y > open + r, so each side pays
+CARRIED_F_RUNS = ((700, 520, 600, 10), (1800, 600, 400, 10), (2300, 2100, 1300, 10))
+
+
+def carried_cases(f_runs=CARRIED_F_RUNS):
+    """f_runs: the (x, r, y, open) of the left runs (a caller whose seq2 is shorter than 1 + x + r + y passes its own).
+    (2, -3), extend 1: the score 2 (x + y) - (open + (r - 1)) pins the path to one gap run (2 x and 2 y > open + r, so each side pays
     for the gap; a lone match inside R cannot pay for a second gap), the walk passes through the run's cells in state E / F
     whatever their H codes say, returns to H where the gap opened and goes on diagonally to (1, 1)."""
     out = []
@@ -136,7 +140,7 @@ def carried_cases():
         a, b = _run_pair(rng, x, r, y, True)
         out.append(Hand("carried_E/r=%d" % r, a, b, K23, go, 1, 2 * (x + y) - (go + r - 1), (1 + x + r + y, 1 + x + y, 1, 1),
                         [DIAG] * y + [UP] * r + [DIAG] * x, ("carried_E_decides", "exit_top_in_E", "one_gap_run", "E_run_over_128")))
-    for x, r, y, go in ((700, 520, 600, 10), (1800, 600, 400, 10), (2300, 2100, 1300, 10)):
+    for x, r, y, go in f_runs:
         a, b = _run_pair(rng, x, r, y, False)
         out.append(Hand("carried_F/r=%d/x=%d" % (r, x), a, b, K23, go, 1, 2 * (x + y) - (go + r - 1), (1 + x + y, 1 + x + r + y, 1, 1),
                         [DIAG] * y + [LEFT] * r + [DIAG] * x,
@@ -144,8 +148,9 @@ def carried_cases():
     return out
 
 
-def long_run_cases():
-    """seq1 = X + Y, seq2 = X + R + Y, |X| = |Y| = 900 and |R| = 300 random over four letters, (5, -4).  All 1800 bases of
+def long_run_cases(waves=KC["kMaxWaves"]):
+    """waves: the wave count whose last boundary the last case crosses (the kernel's own by default).
+    seq1 = X + Y, seq2 = X + R + Y, |X| = |Y| = 900 and |R| = 300 random over four letters, (5, -4).  All 1800 bases of
     seq1 match, and seq2's 300 more cost at least one gap of 300, so for extend <= open the score is
     5 * 1800 - (open + 299 extend), first reached at (1800, 2100): (12, 1) -> 8689, (6, 6) -> 7200, (12, 0) -> 8988; the same
     with the sequences swapped (an up run of 300 rows, more than the ring's 256; end cell (2100, 1800)).  At (0, 3) one-base
@@ -159,11 +164,12 @@ def long_run_cases():
         assert go < ge or score == 5 * 1800 - (go + 299 * ge)
         out.append(Hand("long_left/%d,%d" % (go, ge), a, b, K54, go, ge, score, (1800, 2100, 0, 0), None))
         out.append(Hand("long_up/%d,%d" % (go, ge), b, a, K54, go, ge, score, (2100, 1800, 0, 0), None))
-    last = WAVE_COLS * (KC["kMaxWaves"] - 1)
+    last = WAVE_COLS * (waves - 1)
     x, r, y = last - 150, 300, 450
     X, Y, R = te._lo(rng, x), te._lo(rng, y), te._hi(rng, r)
     out.append(Hand("long_left/last_wave", np.concatenate([X, Y]), np.concatenate([X, R, Y]), K23, 12, 1, 2 * (x + y) - (12 + r - 1),
-                    (x + y, x + r + y, 0, 0), [DIAG] * y + [LEFT] * r + [DIAG] * x, ("F_across_last_wave_of_16", "one_gap_run")))
+                    (x + y, x + r + y, 0, 0), [DIAG] * y + [LEFT] * r + [DIAG] * x,
+                    ("F_across_last_wave_of_16" if waves == KC["kMaxWaves"] else "F_extends_across_wave", "one_gap_run")))
     return out
 
 
@@ -189,7 +195,9 @@ def border_cases():
 
 # ---- best-cell ties and padded columns ------------------------------------------------------------------------------------
 
-def best_cell_cases():
+def best_cell_cases(waves=KC["kMaxWaves"], handover_waves=(1,)):
+    """waves: the wave count whose last wavefront holds the one valid column of the second last_column case; handover_waves:
+    the wave edges 1024 w / 1024 w + 1 of the hand-over cases."""
     out = []
     L = 20
     # two blocks of 20 matches, one in wavefront 0 (bases 2) and one in wavefront 1 (bases 3), rows and columns disjoint:
@@ -205,13 +213,14 @@ def best_cell_cases():
         if rows1 < rows0:                               # at open 0 the first block's 100 spreads right and down, not to the left
             out.append(Hand("two_waves/open0/%d,%d" % (rows0, rows1), a, b, K54, 0, 2, 5 * L, (r + L, c + L, r, c), [DIAG] * L))
     # open 0: the block's corner at column 1024 (lane 63 of wave 0) hands its score to column 1025 (lane 0 of wave 1)
-    a, b = _background(90, 1300)
-    a[50:50 + L] = 2
-    b[WAVE_COLS - L:WAVE_COLS] = 2
-    for ge in (0, 4):
-        out.append(Hand("columns_1024_1025/0,%d" % ge, a, b, K54, 0, ge, 5 * L, (50 + L, WAVE_COLS, 50, WAVE_COLS - L), [DIAG] * L))
+    for edge in (WAVE_COLS * w for w in handover_waves):
+        a, b = _background(90, edge + 276)
+        a[50:50 + L] = 2
+        b[edge - L:edge] = 2
+        for ge in (0, 4):
+            out.append(Hand("columns_%d_%d/0,%d" % (edge, edge + 1, ge), a, b, K54, 0, ge, 5 * L, (50 + L, edge, 50, edge - L), [DIAG] * L))
     # the end cell in the last valid column; the columns right of it are padding and, at open 0, hold its score too
-    for len2 in (WAVE_COLS + 1, WAVE_COLS * (KC["kMaxWaves"] - 1) + 1):
+    for len2 in (WAVE_COLS + 1, WAVE_COLS * (waves - 1) + 1):
         a, b = _background(60, len2)
         a[30:30 + L] = 2
         b[len2 - L:] = 2

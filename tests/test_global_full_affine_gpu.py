@@ -19,6 +19,8 @@ import torch
 from conftest import PKG, ROOT, match_matrix
 from global_full_affine_support import (ALL_MASKS, BEGIN1, BEGIN2, END1, END2, FIT, GLOBAL, OVERLAP, GlobalFullAffineOracle, assert_same,
                                         check_path, gap_runs, moves_of, path_from)
+from global_full_affine_edges import END_CELL_TIE_SHAPES, end_cell_tie_case, one_long_gap_case, padding_case
+from global_full_affine_edges import background as _background, column_fit_case as _column_fit_case, fit_case as _fit_case
 from global_full_support import inputs
 from local_support import random_matrix
 
@@ -107,10 +109,8 @@ def test_open_equal_extend_is_the_linear_gpu_entry(gpu, ga, len1, len2):
 
 
 # ---- 3. hand-built cases ----------------------------------------------------------------------------------------------------
-# Background: seq1 all 0, seq2 all 1, so nothing matches but what a test plants with bases 2 and 3.
-
-def _background(len1, len2, n=1):
-    return np.zeros((n, len1), np.uint8), np.ones((n, len2), np.uint8)
+# The inputs come from global_full_affine_edges.py (the wide-alphabet edge tests relabel them).  Background: seq1 all 0, seq2 all
+# 1, so nothing matches but what a case plants with bases 2 and 3.
 
 
 def _expect(ga, oracle, a, b, sm, go, ge, mask, score, ends, codes, what):
@@ -122,15 +122,6 @@ def _expect(ga, oracle, a, b, sm, go, ge, mask, score, ends, codes, what):
         assert np.array_equal(moves_of(mv[0], st[0]), np.asarray(codes, np.int64)), (what, name)
     sc, e, _, _ = ga.global_full_affine(a, b, sm, go, ge, mask, traceback=False)
     assert sc[0] == score and tuple(e[0]) == (ends[0], ends[1], -1, -1), what
-
-
-def _fit_case():
-    L, off, len2 = 150, 1000, 2100
-    P = np.random.default_rng(6).integers(2, 4, L).astype(np.uint8)
-    a = P[None, :].copy()
-    _, b = _background(L, len2)
-    b[0, off:off + L] = P
-    return L, off, len2, a, b
 
 
 def test_fit(ga, oracle):
@@ -159,14 +150,6 @@ def test_fit_inputs_where_a_mismatch_costs_127(ga, oracle):
     _expect(ga, oracle, a, b, sm, 3, 1, END2, -(3 + 149), (L, 0, 0, 0), [UP] * L, "border end cell, forced walk")
 
 
-def _column_fit_case():
-    L, off, len1 = 1025, 200, 1500
-    P = np.random.default_rng(9).integers(2, 4, L).astype(np.uint8)
-    a, _ = _background(len1, L)
-    a[0, off:off + L] = P
-    return L, off, len1, a, P[None, :].copy()
-
-
 def test_column_fit(ga, oracle):
     """seq2 = P of 1025 bases inside a longer seq1: column 1025 is the only valid column of wavefront 1."""
     L, off, len1, a, b = _column_fit_case()
@@ -179,11 +162,10 @@ def test_column_fit(ga, oracle):
 def test_one_long_gap_beats_many(ga, oracle):
     """seq2 = seq1 without bases 100..139 at open 10, extend 1: 260 matches and one gap of 40, exactly one UP run; where it
     sits among equal bases follows the restatement."""
-    x = np.random.default_rng(11).integers(0, 4, 300, dtype=np.uint8)
-    y = np.concatenate([x[:100], x[140:]])
-    sm = match_matrix(2, -3)
-    want = _both(ga, oracle, x[None], y[None], sm, 10, 1, GLOBAL, "one long gap")
-    sc, ends, mv, st = ga.global_full_affine(x[None], y[None], sm, 10, 1, GLOBAL)
+    x, y, sm = one_long_gap_case()
+    assert x.shape == (1, 300) and y.shape == (1, 260) and np.array_equal(sm, match_matrix(2, -3))
+    want = _both(ga, oracle, x, y, sm, 10, 1, GLOBAL, "one long gap")
+    sc, ends, mv, st = ga.global_full_affine(x, y, sm, 10, 1, GLOBAL)
     assert sc[0] == 2 * 260 - (10 + 39) == 471 and tuple(ends[0]) == (300, 260, 0, 0)
     gaps = [(code, k) for code, k in gap_runs(moves_of(mv[0], st[0])) if code != DIAG]
     assert gaps == [(UP, 40)], gaps
@@ -193,11 +175,8 @@ def test_one_long_gap_beats_many(ga, oracle):
 def test_padding_columns_never_win_at_zero_gap_costs(ga, oracle):
     """(5, -4), open = extend = 0, len2 = 1025, the last 20 bases of both sequences match: at no gap cost the padding columns
     right of column 1025 hold the corner's score too.  The linear test's inputs and results."""
-    L, len1, len2 = 20, 100, 1025
-    P = np.random.default_rng(10).integers(2, 4, L).astype(np.uint8)
-    a, b = _background(len1, len2)
-    a[0, len1 - L:] = P
-    b[0, len2 - L:] = P
+    L, len1, len2, a, b = padding_case()
+    assert (L, len1, len2) == (20, 100, 1025)
     _expect(ga, oracle, a, b, K54, 0, 0, END2, 5 * L, (len1, len2, 0, 0), [DIAG] * L + [UP] * (len1 - L) + [LEFT] * (len2 - L), "pad, END2")
     _expect(ga, oracle, a, b, K54, 0, 0, FIT, 5 * L, (len1, len2, 0, len2 - L), [DIAG] * L + [UP] * (len1 - L), "pad, FIT")
 
@@ -205,9 +184,9 @@ def test_padding_columns_never_win_at_zero_gap_costs(ga, oracle):
 def test_end_cell_ties(ga, oracle):
     """Homopolymer against homopolymer with every end free: H(i, j) = min(i, j).  The last column and the last row hold m =
     min(len1, len2) in many cells; the first of them in row-major order is (m, m)."""
-    for len1, len2 in ((40, 1100), (1100, 40)):
-        a = np.full((1, len1), 2, np.uint8)
-        b = np.full((1, len2), 2, np.uint8)
+    assert END_CELL_TIE_SHAPES == ((40, 1100), (1100, 40))
+    for len1, len2 in END_CELL_TIE_SHAPES:
+        a, b = end_cell_tie_case(len1, len2)
         m = min(len1, len2)
         _expect(ga, oracle, a, b, K111, 3, 1, OVERLAP, m, (m, m, 0, 0), [DIAG] * m, ("homopolymer", len1, len2))
 
