@@ -39,6 +39,37 @@ hipError_t launch_banded_global(const uint8_t *d_seq1s, int len1, const uint8_t 
                                 unsigned char *d_codes, unsigned long long *d_moves, size_t move_words, uint32_t *d_steps,
                                 hipStream_t stream);
 
+// ---- libswmi_banded_ragged.so (banded_ragged_kernels.hip, include/swmi_banded_ragged.h) ----
+// One alignment of a mixed-shape launch.  off1 / off2: bytes from the launch's seq1s / seq2s; code_off: dwords from its codes;
+// move_off: words from its moves; d0: the caller's diagonal clamped to +-kRaggedDiagClamp; index: where its results go in the
+// launch's scores / ends / steps.  48 bytes, so a slot is three 16-byte loads.
+struct RaggedSlot {
+    uint64_t off1, off2, code_off, move_off;
+    int32_t len1, len2, d0;
+    uint32_t index;
+};
+static_assert(sizeof(RaggedSlot) == 48);
+constexpr int kRaggedLocal = 0, kRaggedGlobal = 1;
+constexpr int kRaggedDiagClamp = 65536;
+
+constexpr size_t ragged_code_bytes(int kind, size_t len1) { return kind == kRaggedGlobal ? band_global_code_bytes(len1) : band_code_bytes(len1); }
+
+// The planner's key: i_hi - i_lo of the kind's kernel for a clamped diagonal, 0 for a band that misses the table or an empty
+// sequence.
+constexpr int ragged_swept_rows(int kind, int len1, int len2, int d0)
+{
+    if (len1 == 0 || len2 == 0) return 0;
+    const int lo_min = kind == kRaggedGlobal ? 0 : 1, lo_band = (kind == kRaggedGlobal ? -63 : -62) - d0;
+    const int i_lo = lo_min > lo_band ? lo_min : lo_band, i_hi = len1 < len2 + 64 - d0 ? len1 : len2 + 64 - d0;
+    return i_lo > i_hi ? 0 : i_hi - i_lo;
+}
+
+// n slots on `stream`; every pointer is device memory but sm (int8[16], host).  codes: 16-byte aligned, with moves and steps
+// or NULL with both (ends-only).  free_ends is the global kind's.  Checks nothing: the callers have.
+hipError_t launch_banded_ragged(int kind, const uint8_t *d_seq1s, const uint8_t *d_seq2s, const RaggedSlot *d_slots, size_t n,
+                                const int8_t *sm, int gap_open, int gap_extend, unsigned free_ends, int32_t *d_scores, int32_t *d_ends,
+                                unsigned char *d_codes, unsigned long long *d_moves, uint32_t *d_steps, hipStream_t stream);
+
 }  // namespace banded
 }  // namespace swmi
 

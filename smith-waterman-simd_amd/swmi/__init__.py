@@ -1212,3 +1212,4 @@ from . import wide_profile     # noqa: E402  (a batch against one position-speci
 from . import pk_form          # noqa: E402  (the packed scorer's cell-form rule and flag-form self-test, libswmi_pk_form.so, likewise)
 from . import banded           # noqa: E402  (banded local alignment with end cells and traceback, libswmi_banded.so, likewise)
 from . import banded_global    # noqa: E402  (the band's global, fit, overlap and extension kinds, libswmi_banded_global.so, likewise)
+from . import banded_ragged    # noqa: E402  (both banded kinds on mixed-shape batches, libswmi_banded_ragged.so, likewise)
