@@ -70,6 +70,34 @@ hipError_t launch_banded_ragged(int kind, const uint8_t *d_seq1s, const uint8_t 
                                 const int8_t *sm, int gap_open, int gap_extend, unsigned free_ends, int32_t *d_scores, int32_t *d_ends,
                                 unsigned char *d_codes, unsigned long long *d_moves, uint32_t *d_steps, hipStream_t stream);
 
+// ---- libswmi_banded_width.so (banded_width_kernels.hip, include/swmi_banded_width.h) ----
+// A band of `band` diagonals, -band / 2 .. band / 2 - 1 around the alignment's, one width per launch.  A lane owns band / 64
+// diagonals, so an iteration of a lane is band / 128 code bytes where the 128-wide kernels store one.
+constexpr bool width_is_legal(int band) { return band == 128 || band == 256 || band == 512 || band == 1024; }
+
+constexpr size_t width_code_bytes(int kind, size_t len1, int band) { return size_t(band / kBandWidth) * ragged_code_bytes(kind, len1); }
+
+// The planner's key at a width: i_hi - i_lo of the kind's kernel.  From -band/2 <= j - i - d0 <= band/2 - 1 with
+// 1 <= j <= len2 (local: interior cells) or 0 <= j <= len2 (global: row 0 and column 0 are cells):
+//   i >= j - d0 - band/2 + 1  at the smallest j:  local  i_lo = max(1, 2 - band/2 - d0),  global  i_lo = max(0, 1 - band/2 - d0)
+//   i <= j - d0 + band/2      at j = len2:        i_hi = min(len1, len2 + band/2 - d0)
+constexpr int width_swept_rows(int kind, int len1, int len2, int d0, int band)
+{
+    if (len1 == 0 || len2 == 0) return 0;
+    const int half = band / 2;
+    const int lo_min = kind == kRaggedGlobal ? 0 : 1, lo_band = (kind == kRaggedGlobal ? 1 : 2) - half - d0;
+    const int i_lo = lo_min > lo_band ? lo_min : lo_band, i_hi = len1 < len2 + half - d0 ? len1 : len2 + half - d0;
+    return i_lo > i_hi ? 0 : i_hi - i_lo;
+}
+static_assert(width_swept_rows(kRaggedLocal, 900, 700, -40, 128) == ragged_swept_rows(kRaggedLocal, 900, 700, -40) &&
+              width_swept_rows(kRaggedGlobal, 900, 700, 90, 128) == ragged_swept_rows(kRaggedGlobal, 900, 700, 90));
+
+// As launch_banded_ragged, with the band's width (checked by the caller) and an alignment's codes at code_off dwords taking
+// width_code_bytes(kind, len1, band).
+hipError_t launch_banded_width(int kind, int band, const uint8_t *d_seq1s, const uint8_t *d_seq2s, const RaggedSlot *d_slots, size_t n,
+                               const int8_t *sm, int gap_open, int gap_extend, unsigned free_ends, int32_t *d_scores, int32_t *d_ends,
+                               unsigned char *d_codes, unsigned long long *d_moves, uint32_t *d_steps, hipStream_t stream);
+
 }  // namespace banded
 }  // namespace swmi
 

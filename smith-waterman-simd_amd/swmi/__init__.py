@@ -1213,3 +1213,4 @@ from . import pk_form          # noqa: E402  (the packed scorer's cell-form rule
 from . import banded           # noqa: E402  (banded local alignment with end cells and traceback, libswmi_banded.so, likewise)
 from . import banded_global    # noqa: E402  (the band's global, fit, overlap and extension kinds, libswmi_banded_global.so, likewise)
 from . import banded_ragged    # noqa: E402  (both banded kinds on mixed-shape batches, libswmi_banded_ragged.so, likewise)
+from . import banded_width     # noqa: E402  (the same with a band of 128 .. 1024 diagonals per call, libswmi_banded_width.so, likewise)
