@@ -54,16 +54,6 @@ constexpr int kRaggedDiagClamp = 65536;
 
 constexpr size_t ragged_code_bytes(int kind, size_t len1) { return kind == kRaggedGlobal ? band_global_code_bytes(len1) : band_code_bytes(len1); }
 
-// The planner's key: i_hi - i_lo of the kind's kernel for a clamped diagonal, 0 for a band that misses the table or an empty
-// sequence.
-constexpr int ragged_swept_rows(int kind, int len1, int len2, int d0)
-{
-    if (len1 == 0 || len2 == 0) return 0;
-    const int lo_min = kind == kRaggedGlobal ? 0 : 1, lo_band = (kind == kRaggedGlobal ? -63 : -62) - d0;
-    const int i_lo = lo_min > lo_band ? lo_min : lo_band, i_hi = len1 < len2 + 64 - d0 ? len1 : len2 + 64 - d0;
-    return i_lo > i_hi ? 0 : i_hi - i_lo;
-}
-
 // n slots on `stream`; every pointer is device memory but sm (int8[16], host).  codes: 16-byte aligned, with moves and steps
 // or NULL with both (ends-only).  free_ends is the global kind's.  Checks nothing: the callers have.
 hipError_t launch_banded_ragged(int kind, const uint8_t *d_seq1s, const uint8_t *d_seq2s, const RaggedSlot *d_slots, size_t n,
@@ -77,7 +67,8 @@ constexpr bool width_is_legal(int band) { return band == 128 || band == 256 || b
 
 constexpr size_t width_code_bytes(int kind, size_t len1, int band) { return size_t(band / kBandWidth) * ragged_code_bytes(kind, len1); }
 
-// The planner's key at a width: i_hi - i_lo of the kind's kernel.  From -band/2 <= j - i - d0 <= band/2 - 1 with
+// The planner's key at a width, of both libraries (the ragged one's at kBandWidth): i_hi - i_lo of the kind's kernel for a
+// clamped diagonal, 0 for a band that misses the table or an empty sequence.  From -band/2 <= j - i - d0 <= band/2 - 1 with
 // 1 <= j <= len2 (local: interior cells) or 0 <= j <= len2 (global: row 0 and column 0 are cells):
 //   i >= j - d0 - band/2 + 1  at the smallest j:  local  i_lo = max(1, 2 - band/2 - d0),  global  i_lo = max(0, 1 - band/2 - d0)
 //   i <= j - d0 + band/2      at j = len2:        i_hi = min(len1, len2 + band/2 - d0)
@@ -89,8 +80,6 @@ constexpr int width_swept_rows(int kind, int len1, int len2, int d0, int band)
     const int i_lo = lo_min > lo_band ? lo_min : lo_band, i_hi = len1 < len2 + half - d0 ? len1 : len2 + half - d0;
     return i_lo > i_hi ? 0 : i_hi - i_lo;
 }
-static_assert(width_swept_rows(kRaggedLocal, 900, 700, -40, 128) == ragged_swept_rows(kRaggedLocal, 900, 700, -40) &&
-              width_swept_rows(kRaggedGlobal, 900, 700, 90, 128) == ragged_swept_rows(kRaggedGlobal, 900, 700, 90));
 
 // As launch_banded_ragged, with the band's width (checked by the caller) and an alignment's codes at code_off dwords taking
 // width_code_bytes(kind, len1, band).

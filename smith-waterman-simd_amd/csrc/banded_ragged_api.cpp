@@ -1,16 +1,19 @@
 // banded_ragged_api.cpp -- the C entries of libswmi_banded_ragged.so (include/swmi_banded_ragged.h): the
 // banded local and the banded global / fit / overlap / extension aligner on a batch of mixed (len1, len2) with a diagonal per
-// alignment.  Its structure is banded_api.cpp's: no Context of libswmi.so, no swmi_init -- every entry runs on the calling
-// thread's current HIP device, with this file's own workspaces per (device, stream), its own two streams and buffer sets per
-// device for the host entries, and its own thread-local error text.  Of libswmi.so, linked for the callers' move_offsets and
-// expander, it calls nothing.  Both kinds are in this one object: the kind is a field of Call.  This file's name lies outside
-// csrc/swmi_*.cpp, which four host-only test programs glob.
+// alignment; and, compiled a second time with -DSWMI_BANDED_WIDTH_LIBRARY, of libswmi_banded_width.so
+// (include/swmi_banded_width.h, section 38): the same with ONE BAND WIDTH PER CALL, 128 .. 1024.  Everything in which the two
+// libraries differ stands in the one block below the error text (section 39); nothing after it tests the define.  Its
+// structure is banded_api.cpp's: no Context of libswmi.so, no swmi_init -- every entry runs on the calling thread's current
+// HIP device, with this file's own workspaces per (device, stream), its own two streams and buffer sets per device for the
+// host entries, and its own thread-local error text.  Of libswmi.so, linked for the callers' move_offsets and expander, it
+// calls nothing.  Both kinds are in this one object: the kind is a field of Call, and so is the band, which is kBandWidth
+// throughout in the ragged library.  This file's name lies outside csrc/swmi_*.cpp, which four host-only test programs glob.
 //
 // THE PLAN.  A checked batch is cut into slices (contiguous in caller order, the header's arithmetic), and each slice's
-// alignments become slots in the order the kernels take them: by swept rows (ragged_swept_rows, banded_internal.h)
-// descending, ties in caller order, so that the four wavefronts of a workgroup carry similar work and the longest alignments
-// start first.  Every offset of a slot is relative to its slice; code offsets are a running sum in plan order.
-#include "../../include/swmi_banded_ragged.h"
+// alignments become slots in the order the kernels take them: by swept rows at the call's width (width_swept_rows,
+// banded_internal.h) descending, ties in caller order, so that the four wavefronts of a workgroup carry similar work and the
+// longest alignments start first.  Every offset of a slot is relative to its slice; code offsets are a running sum in plan
+// order, an alignment's codes taking band / 128 times the bytes they take at 128.
 #include "banded_internal.h"
 
 #include <algorithm>
@@ -38,20 +41,66 @@ int fail(int code, const char *fmt, ...)
     return code;
 }
 
-#define RAGGED_HIP_TRY(expr)                                                                                        \
-    do {                                                                                                            \
-        hipError_t e_ = (expr);                                                                                     \
-        if (e_ != hipSuccess) return fail(SWMI_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
+}  // namespace
+}  // namespace banded
+}  // namespace swmi
 
+// ---- what the libraries differ in: the public header, the prefix of the exported names, the spelling of the two kinds in an
+// ---- error text, whether a call carries a band (and with it the BAND parameter of seven entries and the launcher), and a
+// ---- test-only switch of the ragged library's ----
+#ifdef SWMI_BANDED_WIDTH_LIBRARY
+#include "../../include/swmi_banded_width.h"
+#define BANDED_ENTRY(name) swmi_banded_width_##name
+#define BANDED_BAND_PARAM int band,
+#define BANDED_BAND_ARG band
+
+namespace swmi {
+namespace banded {
+namespace {
+constexpr bool kHasBand = true;
+constexpr const char *kLocalName = "SWMI_BANDED_WIDTH_LOCAL", *kGlobalName = "SWMI_BANDED_WIDTH_GLOBAL";
+static_assert(kBandMaxLen == SWMI_BANDED_WIDTH_MAX_LEN && sizeof(RaggedSlot) == SWMI_BANDED_WIDTH_SLOT_BYTES);
+static_assert(kRaggedLocal == SWMI_BANDED_WIDTH_LOCAL && kRaggedGlobal == SWMI_BANDED_WIDTH_GLOBAL);
+static_assert(width_is_legal(SWMI_BANDED_WIDTH_MIN) && width_is_legal(SWMI_BANDED_WIDTH_MAX) && kBandWidth == SWMI_BANDED_WIDTH_MIN);
+constexpr bool sort_enabled() { return true; }
+#else
+#include "../../include/swmi_banded_ragged.h"
+#define BANDED_ENTRY(name) swmi_banded_ragged_##name
+#define BANDED_BAND_PARAM
+#define BANDED_BAND_ARG kBandWidth
+
+namespace swmi {
+namespace banded {
+namespace {
+constexpr bool kHasBand = false;
+constexpr const char *kLocalName = "SWMI_BANDED_RAGGED_LOCAL", *kGlobalName = "SWMI_BANDED_RAGGED_GLOBAL";
 static_assert(kBandMaxLen == SWMI_BANDED_RAGGED_MAX_LEN && sizeof(RaggedSlot) == SWMI_BANDED_RAGGED_SLOT_BYTES);
 static_assert(kRaggedLocal == SWMI_BANDED_RAGGED_LOCAL && kRaggedGlobal == SWMI_BANDED_RAGGED_GLOBAL);
+// test-only: SWMI_BANDED_RAGGED_NO_SORT=1 leaves the slots of a slice in caller order (read once)
+bool sort_enabled()
+{
+    static const bool on = [] {
+        const char *e = getenv("SWMI_BANDED_RAGGED_NO_SORT");
+        return !(e && e[0] == '1');
+    }();
+    return on;
+}
+#endif
+// ---- below this line the two builds are one text ----
+
+// (no line number: the text is the same wherever the call stands, so that a line added here moves neither library's texts)
+#define BANDED_HIP_TRY(expr)                                                                                        \
+    do {                                                                                                            \
+        hipError_t e_ = (expr);                                                                                     \
+        if (e_ != hipSuccess) return fail(SWMI_ERR_HIP, "%s failed: %s (%s)", #expr, hipGetErrorString(e_), __FILE__); \
+    } while (0)
+
 constexpr size_t kSliceBytes = size_t(256) << 20;        // an ends-only slice's device bytes
 constexpr size_t kMaxSlice = size_t(1) << 20;            // alignments per slice (and per launch)
 constexpr size_t kTbSliceBytes = 4383801344ull;          // a traceback slice's device bytes: banded_api.cpp's
 
 struct Call {
-    int kind;
+    int kind, band;                             // (the band: kBandWidth in the ragged library)
     const uint64_t *off1, *off2;
     size_t n;
     const int32_t *diagonals;                   // host memory, or NULL
@@ -63,11 +112,24 @@ struct Call {
 };
 
 // device bytes one alignment of a slice takes: its sequences, its slot, its results, and with a traceback codes, moves, count
-size_t alignment_bytes(int kind, size_t len1, size_t len2, bool tb)
+size_t alignment_bytes(int kind, int band, size_t len1, size_t len2, bool tb)
 {
     size_t b = len1 + len2 + sizeof(RaggedSlot) + 5 * sizeof(int32_t);
-    if (tb) b += ragged_code_bytes(kind, len1) + SWMI_LOCAL_FULL_MOVE_WORDS(len1, len2) * sizeof(uint64_t) + sizeof(uint32_t);
+    if (tb) b += width_code_bytes(kind, len1, band) + SWMI_LOCAL_FULL_MOVE_WORDS(len1, len2) * sizeof(uint64_t) + sizeof(uint32_t);
     return b;
+}
+
+int check_kind(int kind)
+{
+    if (kind != kRaggedLocal && kind != kRaggedGlobal)
+        return fail(SWMI_ERR_INVALID_ARGUMENT, "kind %d is neither %s nor %s", kind, kLocalName, kGlobalName);
+    return SWMI_OK;
+}
+
+int check_band(int band)
+{
+    if (kHasBand && !width_is_legal(band)) return fail(SWMI_ERR_INVALID_ARGUMENT, "band %d is not one of 128, 256, 512, 1024", band);
+    return SWMI_OK;
 }
 
 int check_offsets(const uint64_t *off1, const uint64_t *off2, size_t n)
@@ -81,11 +143,12 @@ int check_offsets(const uint64_t *off1, const uint64_t *off2, size_t n)
     return SWMI_OK;
 }
 
-// The checks in the header's order: the mask, the matrix, the gaps, the moves / steps pair; then n = 0, the buffers, the
-// offsets.  1 = nothing to do.
+// The checks in the header's order: the band where the call has one; the mask, the matrix, the gaps, the moves / steps pair;
+// then n = 0, the buffers, the offsets.  1 = nothing to do.
 int check_call(const Call &c, const void *seq1s, const void *seq2s, const void *scores, const void *ends, const void *moves,
                const void *steps)
 {
+    if (check_band(c.band) != SWMI_OK) return SWMI_ERR_INVALID_ARGUMENT;
     if (c.kind == kRaggedGlobal && c.free_ends > SWMI_BANDED_MAX_FREE_ENDS)
         return fail(SWMI_ERR_INVALID_ARGUMENT, "free_ends %u is not a mask of SWMI_FREE_* (0..15) or SWMI_BANDED_END_ANYWHERE with SWMI_FREE_BEGIN* (16..19)", c.free_ends);
     if (!c.sm) return fail(SWMI_ERR_INVALID_ARGUMENT, "score_matrix is NULL");
@@ -99,13 +162,13 @@ int check_call(const Call &c, const void *seq1s, const void *seq2s, const void *
 }
 
 // slices of checked offsets: first = {0, ..., n}
-std::vector<size_t> cut(int kind, const uint64_t *off1, const uint64_t *off2, size_t n, bool tb)
+std::vector<size_t> cut(int kind, int band, const uint64_t *off1, const uint64_t *off2, size_t n, bool tb)
 {
     const size_t cap = tb ? kTbSliceBytes : kSliceBytes;
     std::vector<size_t> first{0};
     size_t bytes = 0, m = 0;
     for (size_t k = 0; k < n; ++k) {
-        const size_t b = alignment_bytes(kind, size_t(off1[k + 1] - off1[k]), size_t(off2[k + 1] - off2[k]), tb);
+        const size_t b = alignment_bytes(kind, band, size_t(off1[k + 1] - off1[k]), size_t(off2[k + 1] - off2[k]), tb);
         if (m && (bytes + b > cap || m == kMaxSlice)) {
             first.push_back(k);
             bytes = 0;
@@ -116,16 +179,6 @@ std::vector<size_t> cut(int kind, const uint64_t *off1, const uint64_t *off2, si
     }
     if (n) first.push_back(n);
     return first;
-}
-
-// test-only: SWMI_BANDED_RAGGED_NO_SORT=1 leaves the slots of a slice in caller order (read once)
-bool sort_enabled()
-{
-    static const bool on = [] {
-        const char *e = getenv("SWMI_BANDED_RAGGED_NO_SORT");
-        return !(e && e[0] == '1');
-    }();
-    return on;
 }
 
 // A call's plan.  It lives in thread-local storage, so that a device call of some ten thousand alignments -- a few
@@ -160,7 +213,7 @@ void make_plan(Plan &p, const Call &c, bool tb, RaggedSlot *slots)
     p.move_offsets.assign(n + 1, 0);
     if (tb)
         for (size_t k = 0; k < n; ++k) p.move_offsets[k + 1] = p.move_offsets[k] + SWMI_LOCAL_FULL_MOVE_WORDS(c.len1(k), c.len2(k));
-    p.first = cut(c.kind, c.off1, c.off2, n, tb);
+    p.first = cut(c.kind, c.band, c.off1, c.off2, n, tb);
     std::vector<uint32_t> &order = p.order;
     std::vector<int32_t> &rows = p.rows, &diag = p.diag;
     for (size_t s = 0; s < p.slices(); ++s) {
@@ -172,7 +225,7 @@ void make_plan(Plan &p, const Call &c, bool tb, RaggedSlot *slots)
         for (size_t x = 0; x < m; ++x) {
             const int32_t d = c.diagonals ? c.diagonals[a + x] : 0;
             diag[x] = std::max(-kRaggedDiagClamp, std::min(kRaggedDiagClamp, d));
-            rows[x] = ragged_swept_rows(c.kind, int(c.len1(a + x)), int(c.len2(a + x)), diag[x]);
+            rows[x] = width_swept_rows(c.kind, int(c.len1(a + x)), int(c.len2(a + x)), diag[x], c.band);
             order[x] = uint32_t(x);
             if (x && rows[x] > rows[x - 1]) sorted = false;
         }
@@ -190,7 +243,7 @@ void make_plan(Plan &p, const Call &c, bool tb, RaggedSlot *slots)
             t.len2 = int32_t(c.len2(k));
             t.d0 = diag[order[x]];
             t.index = order[x];
-            if (tb) codes += ragged_code_bytes(c.kind, c.len1(k)) / 4;
+            if (tb) codes += width_code_bytes(c.kind, c.len1(k), c.band) / 4;
         }
         p.max_m = std::max(p.max_m, m);
         p.max_seq1 = std::max(p.max_seq1, size_t(c.off1[b] - c.off1[a]));
@@ -207,7 +260,7 @@ template <class T> int grow(T *&p, size_t &have, size_t need)
     if (p) (void)hipFree(p);
     p = nullptr;
     have = 0;
-    RAGGED_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&p), need * sizeof(T)));
+    BANDED_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&p), need * sizeof(T)));
     have = need;
     return SWMI_OK;
 }
@@ -269,13 +322,25 @@ int current(DeviceState **out)
     auto it = g_devices.find(dev);
     if (it == g_devices.end()) {
         hipDeviceProp_t prop{};
-        RAGGED_HIP_TRY(hipGetDeviceProperties(&prop, dev));
+        BANDED_HIP_TRY(hipGetDeviceProperties(&prop, dev));
         if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
             return fail(SWMI_ERR_UNSUPPORTED_ARCH, "device %d is %s, not gfx950", dev, prop.gcnArchName);
         it = g_devices.emplace(std::piecewise_construct, std::forward_as_tuple(dev), std::forward_as_tuple()).first;
     }
     *out = &it->second;
     return SWMI_OK;
+}
+
+// one slice's launch, by the launcher of the kernel object the library links
+hipError_t launch(const Call &c, const uint8_t *d_seq1s, const uint8_t *d_seq2s, const RaggedSlot *d_slots, size_t m, int32_t *d_scores,
+                  int32_t *d_ends, unsigned char *d_codes, unsigned long long *d_moves, uint32_t *d_steps, hipStream_t stream)
+{
+    if constexpr (kHasBand)
+        return launch_banded_width(c.kind, c.band, d_seq1s, d_seq2s, d_slots, m, c.sm, c.gap_open, c.gap_extend, c.free_ends, d_scores, d_ends,
+                                   d_codes, d_moves, d_steps, stream);
+    else
+        return launch_banded_ragged(c.kind, d_seq1s, d_seq2s, d_slots, m, c.sm, c.gap_open, c.gap_extend, c.free_ends, d_scores, d_ends, d_codes,
+                                    d_moves, d_steps, stream);
 }
 
 int run_device(const Call &c, const void *d_seq1s, const void *d_seq2s, void *d_scores, void *d_ends, void *d_moves, void *d_steps,
@@ -297,13 +362,13 @@ int run_device(const Call &c, const void *d_seq1s, const void *d_seq2s, void *d_
     StreamSpace &sp = ds->spaces[st];
     const size_t up_bytes = c.n * sizeof(RaggedSlot);
     // the slots are planned straight into pinned memory, once the stream's last upload has finished reading it
-    if (sp.done) RAGGED_HIP_TRY(hipEventSynchronize(sp.done));
-    else RAGGED_HIP_TRY(hipEventCreateWithFlags(&sp.done, hipEventDisableTiming));
+    if (sp.done) BANDED_HIP_TRY(hipEventSynchronize(sp.done));
+    else BANDED_HIP_TRY(hipEventCreateWithFlags(&sp.done, hipEventDisableTiming));
     if (sp.host_bytes < up_bytes) {
         if (sp.host) (void)hipHostFree(sp.host);
         sp.host = nullptr;
         sp.host_bytes = 0;
-        RAGGED_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&sp.host), up_bytes, 0));
+        BANDED_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&sp.host), up_bytes, 0));
         sp.host_bytes = up_bytes;
     }
     PlanUse use;
@@ -311,26 +376,26 @@ int run_device(const Call &c, const void *d_seq1s, const void *d_seq2s, void *d_
     make_plan(p, c, tb, reinterpret_cast<RaggedSlot *>(sp.host));
     const size_t code_bytes = (p.max_codes + 15) & ~size_t(15);
     if (code_bytes + up_bytes > sp.dev_bytes) {
-        RAGGED_HIP_TRY(hipStreamSynchronize(st));
+        BANDED_HIP_TRY(hipStreamSynchronize(st));
         if (sp.dev) (void)hipFree(sp.dev);
         sp.dev = nullptr;
         sp.dev_bytes = 0;
-        RAGGED_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sp.dev), code_bytes + up_bytes));
+        BANDED_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sp.dev), code_bytes + up_bytes));
         sp.dev_bytes = code_bytes + up_bytes;
     }
     // (behind whatever codes this call's slices need: an earlier call's launches on this stream read their slots in stream
     // order before this upload overwrites them)
     unsigned char *up = sp.dev + sp.dev_bytes - up_bytes;
-    RAGGED_HIP_TRY(hipMemcpyAsync(up, sp.host, up_bytes, hipMemcpyHostToDevice, st));
-    RAGGED_HIP_TRY(hipEventRecord(sp.done, st));
+    BANDED_HIP_TRY(hipMemcpyAsync(up, sp.host, up_bytes, hipMemcpyHostToDevice, st));
+    BANDED_HIP_TRY(hipEventRecord(sp.done, st));
     const RaggedSlot *slots = reinterpret_cast<const RaggedSlot *>(up);
     const uint8_t *s1 = static_cast<const uint8_t *>(d_seq1s), *s2 = static_cast<const uint8_t *>(d_seq2s);
     for (size_t s = 0; s < p.slices(); ++s) {
         const size_t a = p.first[s], m = p.first[s + 1] - a;
-        RAGGED_HIP_TRY(launch_banded_ragged(c.kind, s1 + c.off1[a], s2 + c.off2[a], slots + a, m, c.sm, c.gap_open, c.gap_extend, c.free_ends,
-                                            static_cast<int32_t *>(d_scores) + a, static_cast<int32_t *>(d_ends) + 4 * a, tb ? sp.dev : nullptr,
-                                            tb ? static_cast<unsigned long long *>(d_moves) + p.move_offsets[a] : nullptr,
-                                            tb ? static_cast<uint32_t *>(d_steps) + a : nullptr, st));
+        BANDED_HIP_TRY(launch(c, s1 + c.off1[a], s2 + c.off2[a], slots + a, m, static_cast<int32_t *>(d_scores) + a,
+                              static_cast<int32_t *>(d_ends) + 4 * a, tb ? sp.dev : nullptr,
+                              tb ? static_cast<unsigned long long *>(d_moves) + p.move_offsets[a] : nullptr,
+                              tb ? static_cast<uint32_t *>(d_steps) + a : nullptr, st));
     }
     return SWMI_OK;
 }
@@ -354,7 +419,7 @@ int run_host(const Call &c, const char *entry, const uint8_t *seq1s, const uint8
     for (int k = 0; k < n_sets; ++k) {
         HostSet &s = sets[k];
         s.off = s.m = 0;
-        if (!s.stream) RAGGED_HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+        if (!s.stream) BANDED_HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
         rc = grow(s.d1, s.have.d1, std::max<size_t>(p.max_seq1, 16));
         if (rc == SWMI_OK) rc = grow(s.d2, s.have.d2, std::max<size_t>(p.max_seq2, 16));
         if (rc == SWMI_OK) rc = grow(s.d_slots, s.have.slots, p.max_m);
@@ -392,8 +457,8 @@ int run_host(const Call &c, const char *entry, const uint8_t *seq1s, const uint8
         if (e == hipSuccess && b2) e = hipMemcpyAsync(s.d2, seq2s + c.off2[s.off], b2, hipMemcpyHostToDevice, s.stream);
         if (e == hipSuccess) e = hipMemcpyAsync(s.d_slots, p.slots + s.off, s.m * sizeof(RaggedSlot), hipMemcpyHostToDevice, s.stream);
         if (e == hipSuccess)
-            e = launch_banded_ragged(c.kind, s.d1, s.d2, s.d_slots, s.m, c.sm, c.gap_open, c.gap_extend, c.free_ends, s.d_scores, s.d_ends,
-                                     tb ? s.d_codes : nullptr, tb ? s.d_moves : nullptr, tb ? s.d_steps : nullptr, s.stream);
+            e = launch(c, s.d1, s.d2, s.d_slots, s.m, s.d_scores, s.d_ends, tb ? s.d_codes : nullptr, tb ? s.d_moves : nullptr,
+                       tb ? s.d_steps : nullptr, s.stream);
         if (e == hipSuccess && n_sets == 2) e = drain(turn ^ 1);         // the previous slice, while this one computes
     }
     for (int k = 0; k < n_sets; ++k) {
@@ -414,78 +479,75 @@ using namespace swmi::banded;
 
 extern "C" {
 
-const char *swmi_banded_ragged_last_error(void) { return t_error; }
+const char *BANDED_ENTRY(last_error)(void) { return t_error; }
 
-int swmi_banded_ragged_version(void) { return SWMI_VERSION; }
+int BANDED_ENTRY(version)(void) { return SWMI_VERSION; }
 
-int swmi_banded_ragged_release_workspaces(void)
+int BANDED_ENTRY(release_workspaces)(void)
 {
     DeviceState *ds = nullptr;
     const int rc = current(&ds);
     if (rc != SWMI_OK) return rc;
-    RAGGED_HIP_TRY(hipDeviceSynchronize());
+    BANDED_HIP_TRY(hipDeviceSynchronize());
     std::lock_guard<std::mutex> host_lock(ds->host_mu);
     std::lock_guard<std::mutex> lock(ds->ws_mu);
     ds->release();
     return SWMI_OK;
 }
 
-size_t swmi_banded_ragged_slices_for(int kind, const uint64_t *seq1_offsets, const uint64_t *seq2_offsets, size_t n, int traceback,
-                                     size_t *sizes, size_t cap)
+size_t BANDED_ENTRY(slices_for)(int kind, BANDED_BAND_PARAM const uint64_t *seq1_offsets, const uint64_t *seq2_offsets, size_t n, int traceback,
+                                size_t *sizes, size_t cap)
 {
-    if (kind != kRaggedLocal && kind != kRaggedGlobal) {
-        (void)fail(SWMI_ERR_INVALID_ARGUMENT, "kind %d is neither SWMI_BANDED_RAGGED_LOCAL nor SWMI_BANDED_RAGGED_GLOBAL", kind);
-        return 0;
-    }
+    if (check_kind(kind) != SWMI_OK || check_band(BANDED_BAND_ARG) != SWMI_OK) return 0;      // (here the kind first)
     if (n == 0 || check_offsets(seq1_offsets, seq2_offsets, n) != SWMI_OK) return 0;
-    const std::vector<size_t> first = cut(kind, seq1_offsets, seq2_offsets, n, traceback != 0);
+    const std::vector<size_t> first = cut(kind, BANDED_BAND_ARG, seq1_offsets, seq2_offsets, n, traceback != 0);
     for (size_t s = 0; s + 1 < first.size(); ++s)
         if (sizes && s < cap) sizes[s] = first[s + 1] - first[s];
     return first.size() - 1;
 }
 
-int swmi_banded_ragged_local(const uint8_t *seq1s, const uint64_t *seq1_offsets, const uint8_t *seq2s, const uint64_t *seq2_offsets, size_t n,
-                             const int32_t *diagonals, const int8_t score_matrix[16], int gap_open, int gap_extend, int32_t *scores,
-                             int32_t *ends, uint64_t *moves, uint32_t *steps)
+int BANDED_ENTRY(local)(const uint8_t *seq1s, const uint64_t *seq1_offsets, const uint8_t *seq2s, const uint64_t *seq2_offsets, size_t n,
+                        const int32_t *diagonals, BANDED_BAND_PARAM const int8_t score_matrix[16], int gap_open, int gap_extend,
+                        int32_t *scores, int32_t *ends, uint64_t *moves, uint32_t *steps)
 {
-    return run_host(Call{kRaggedLocal, seq1_offsets, seq2_offsets, n, diagonals, score_matrix, gap_open, gap_extend, 0u}, __func__, seq1s, seq2s,
-                    scores, ends, moves, steps);
+    return run_host(Call{kRaggedLocal, BANDED_BAND_ARG, seq1_offsets, seq2_offsets, n, diagonals, score_matrix, gap_open, gap_extend, 0u},
+                    __func__, seq1s, seq2s, scores, ends, moves, steps);
 }
 
-int swmi_banded_ragged_global(const uint8_t *seq1s, const uint64_t *seq1_offsets, const uint8_t *seq2s, const uint64_t *seq2_offsets, size_t n,
-                              const int32_t *diagonals, const int8_t score_matrix[16], int gap_open, int gap_extend, unsigned free_ends,
-                              int32_t *scores, int32_t *ends, uint64_t *moves, uint32_t *steps)
+int BANDED_ENTRY(global)(const uint8_t *seq1s, const uint64_t *seq1_offsets, const uint8_t *seq2s, const uint64_t *seq2_offsets, size_t n,
+                         const int32_t *diagonals, BANDED_BAND_PARAM const int8_t score_matrix[16], int gap_open, int gap_extend,
+                         unsigned free_ends, int32_t *scores, int32_t *ends, uint64_t *moves, uint32_t *steps)
 {
-    return run_host(Call{kRaggedGlobal, seq1_offsets, seq2_offsets, n, diagonals, score_matrix, gap_open, gap_extend, free_ends}, __func__, seq1s,
-                    seq2s, scores, ends, moves, steps);
+    return run_host(Call{kRaggedGlobal, BANDED_BAND_ARG, seq1_offsets, seq2_offsets, n, diagonals, score_matrix, gap_open, gap_extend, free_ends},
+                    __func__, seq1s, seq2s, scores, ends, moves, steps);
 }
 
-int swmi_banded_ragged_local_device(const void *d_seq1s, const uint64_t *seq1_offsets, const void *d_seq2s, const uint64_t *seq2_offsets,
-                                    size_t n, const int32_t *diagonals, const int8_t score_matrix[16], int gap_open, int gap_extend,
-                                    void *d_scores, void *d_ends, void *d_moves, void *d_steps, void *stream)
+int BANDED_ENTRY(local_device)(const void *d_seq1s, const uint64_t *seq1_offsets, const void *d_seq2s, const uint64_t *seq2_offsets, size_t n,
+                               const int32_t *diagonals, BANDED_BAND_PARAM const int8_t score_matrix[16], int gap_open, int gap_extend,
+                               void *d_scores, void *d_ends, void *d_moves, void *d_steps, void *stream)
 {
-    return run_device(Call{kRaggedLocal, seq1_offsets, seq2_offsets, n, diagonals, score_matrix, gap_open, gap_extend, 0u}, d_seq1s, d_seq2s,
-                      d_scores, d_ends, d_moves, d_steps, stream);
+    return run_device(Call{kRaggedLocal, BANDED_BAND_ARG, seq1_offsets, seq2_offsets, n, diagonals, score_matrix, gap_open, gap_extend, 0u},
+                      d_seq1s, d_seq2s, d_scores, d_ends, d_moves, d_steps, stream);
 }
 
-int swmi_banded_ragged_global_device(const void *d_seq1s, const uint64_t *seq1_offsets, const void *d_seq2s, const uint64_t *seq2_offsets,
-                                     size_t n, const int32_t *diagonals, const int8_t score_matrix[16], int gap_open, int gap_extend,
-                                     unsigned free_ends, void *d_scores, void *d_ends, void *d_moves, void *d_steps, void *stream)
+int BANDED_ENTRY(global_device)(const void *d_seq1s, const uint64_t *seq1_offsets, const void *d_seq2s, const uint64_t *seq2_offsets, size_t n,
+                                const int32_t *diagonals, BANDED_BAND_PARAM const int8_t score_matrix[16], int gap_open, int gap_extend,
+                                unsigned free_ends, void *d_scores, void *d_ends, void *d_moves, void *d_steps, void *stream)
 {
-    return run_device(Call{kRaggedGlobal, seq1_offsets, seq2_offsets, n, diagonals, score_matrix, gap_open, gap_extend, free_ends}, d_seq1s,
-                      d_seq2s, d_scores, d_ends, d_moves, d_steps, stream);
+    return run_device(Call{kRaggedGlobal, BANDED_BAND_ARG, seq1_offsets, seq2_offsets, n, diagonals, score_matrix, gap_open, gap_extend, free_ends},
+                      d_seq1s, d_seq2s, d_scores, d_ends, d_moves, d_steps, stream);
 }
 
 // one untimed device call first (it grows the workspace, which synchronises the stream), then HIP events around `iters`
-int swmi_banded_ragged_time_device(int kind, const void *d_seq1s, const uint64_t *seq1_offsets, const void *d_seq2s,
-                                   const uint64_t *seq2_offsets, size_t n, const int32_t *diagonals, const int8_t score_matrix[16],
-                                   int gap_open, int gap_extend, unsigned free_ends, void *d_scores, void *d_ends, void *d_moves, void *d_steps,
-                                   void *stream, int iters, float *avg_ms)
+int BANDED_ENTRY(time_device)(int kind, const void *d_seq1s, const uint64_t *seq1_offsets, const void *d_seq2s, const uint64_t *seq2_offsets,
+                              size_t n, const int32_t *diagonals, BANDED_BAND_PARAM const int8_t score_matrix[16], int gap_open, int gap_extend,
+                              unsigned free_ends, void *d_scores, void *d_ends, void *d_moves, void *d_steps, void *stream, int iters,
+                              float *avg_ms)
 {
-    if (kind != kRaggedLocal && kind != kRaggedGlobal)
-        return fail(SWMI_ERR_INVALID_ARGUMENT, "kind %d is neither SWMI_BANDED_RAGGED_LOCAL nor SWMI_BANDED_RAGGED_GLOBAL", kind);
+    if (check_band(BANDED_BAND_ARG) != SWMI_OK || check_kind(kind) != SWMI_OK) return SWMI_ERR_INVALID_ARGUMENT;     // the band first
     if (!avg_ms || iters < 1) return fail(SWMI_ERR_INVALID_ARGUMENT, "avg_ms is NULL or iters %d < 1", iters);
-    const Call c{kind, seq1_offsets, seq2_offsets, n, diagonals, score_matrix, gap_open, gap_extend, kind == kRaggedGlobal ? free_ends : 0u};
+    const Call c{kind, BANDED_BAND_ARG, seq1_offsets, seq2_offsets, n, diagonals, score_matrix, gap_open, gap_extend,
+                 kind == kRaggedGlobal ? free_ends : 0u};
     hipStream_t st = static_cast<hipStream_t>(stream);
     int rc = run_device(c, d_seq1s, d_seq2s, d_scores, d_ends, d_moves, d_steps, stream);
     if (rc != SWMI_OK) return rc;

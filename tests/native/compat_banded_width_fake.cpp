@@ -1,5 +1,5 @@
 // compat_banded_width_fake.cpp -- TEST ONLY: include/swmi_banded_width_compat.hpp run without a device, as a stand-alone
-// program under ASan + UBSan: the two overloads over the real host source (csrc/banded_width_api.cpp) on the fake GPU of
+// program under ASan + UBSan: the two overloads over the real host source (csrc/banded_ragged_api.cpp with -DSWMI_BANDED_WIDTH_LIBRARY) on the fake GPU of
 // fake_hip.cpp.  This file holds the stand-in for the launcher, hipGetDevice, and plain stand-ins for the three functions the
 // header takes from libswmi.so (swmi_last_error, swmi_local_full_ragged_move_offsets, swmi_local_full_expand_moves: the
 // layout and the expander as swmi.h states them).  The launcher's stand-in gives every slot a result made from the slot and

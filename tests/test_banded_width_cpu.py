@@ -1,8 +1,9 @@
 """libswmi_banded_width.so (include/swmi_banded_width.h) without a device: the restatements' identities
 at a width (a band that holds the table equals the full-table affine restatements; local scores never fall as the band doubles;
 the drift family binds at 128 and 256 and is free at 512 and 1024), its nine exports, every refusal with the band first,
-slices_for at every width, the 32 kernels' resources from the compiler's remarks, the compat header, the host source on the
-fake GPU as a stand-alone ASan + UBSan program, and the module's signatures."""
+slices_for at every width, the 32 kernels' resources from the compiler's remarks, the compat header (over the host source on the
+fake GPU as a stand-alone ASan + UBSan program; the host source's own driver runs from tests/test_banded_ragged_host_fake.py),
+and the module's signatures."""
 import ctypes
 import inspect
 import os
@@ -288,8 +289,9 @@ def test_the_compat_header_runs_on_the_fake_gpu(tmp_path):
     exe = str(tmp_path / "compat_banded_width_fake")
     flags = ["-O1", "-g", "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I", os.path.join(ROOT, "include"),
              "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    b = subprocess.run(["g++"] + flags + ["-o", exe, os.path.join(NATIVE, "compat_banded_width_fake.cpp"), os.path.join(NATIVE, "fake_hip.cpp"),
-                                          os.path.join(PKG, "csrc", "banded_width_api.cpp"), "-ldl", "-lpthread"],
+    b = subprocess.run(["g++"] + flags + ["-DSWMI_BANDED_WIDTH_LIBRARY", "-o", exe, os.path.join(NATIVE, "compat_banded_width_fake.cpp"),
+                                          os.path.join(NATIVE, "fake_hip.cpp"), os.path.join(PKG, "csrc", "banded_ragged_api.cpp"), "-ldl",
+                                          "-lpthread"],
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert b.returncode == 0, b.stdout[-3000:]
     clean = {k: v for k, v in os.environ.items() if not k.startswith("SWMI_")}
@@ -298,25 +300,6 @@ def test_the_compat_header_runs_on_the_fake_gpu(tmp_path):
     assert r.returncode == 0, r.stdout[-4000:]
     assert "banded width compat fake ok\n" in r.stdout
     assert r.stdout.count(": ok") == 6, r.stdout
-
-
-def test_banded_width_host_paths_on_the_fake_gpu(tmp_path):
-    """csrc/banded_width_api.cpp, all of the library's host code, compiled with g++ and ASan + UBSan as a stand-alone program
-    against the unchanged tests/native/fake_hip.cpp and tests/native/banded_width_host_fake.cpp; nothing is loaded into Python."""
-    assert shutil.which("g++") is not None
-    exe = str(tmp_path / "banded_width_host_fake")
-    flags = ["-O1", "-g", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-fsanitize=address,undefined",
-             "-fno-sanitize-recover=all"]
-    b = subprocess.run(["g++"] + flags + ["-o", exe, os.path.join(NATIVE, "banded_width_host_fake.cpp"), os.path.join(NATIVE, "fake_hip.cpp"),
-                                          os.path.join(PKG, "csrc", "banded_width_api.cpp"), "-ldl", "-lpthread"],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert b.returncode == 0, b.stdout[-3000:]
-    clean = {k: v for k, v in os.environ.items() if not k.startswith("SWMI_")}
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
-                       env=dict(clean, ASAN_OPTIONS="detect_leaks=1", FAKE_HIP_DEVICES="1"))
-    assert r.returncode == 0, r.stdout[-4000:]
-    assert "banded width host fake ok\n" in r.stdout
-    assert r.stdout.count(": ok") == 19, r.stdout
 
 
 def test_the_module_has_the_ragged_modules_functions_with_band_before_the_matrix(swmi_mod):
