@@ -2,14 +2,11 @@
 swmi.banded_global (libswmi_banded_global.so) each hold a Binding and their public functions call it.  The libraries' entries
 differ by their prefix, the name of the aligning entry and one argument: the global library's take free_ends behind the gaps."""
 import ctypes
-import os
 
 import numpy as np
 
-from . import ERR_NOT_INITIALIZED, SwmiError, _affine, _free_ends, _move_words, _pair_batch, _ptr, _slices
-from . import load as _load_swmi
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
+from . import _affine, _free_ends, _move_words, _pair_batch, _ptr, _slices
+from ._library import Library
 
 
 def _diagonals(diagonals, n):
@@ -57,47 +54,22 @@ def _stream_handle(stream, tensor):
     return getattr(stream, "cuda_stream", stream)
 
 
-class Binding:
+class Binding(Library):
     """One banded library: its entries are `prefix`_<name> and `align_name` (host) / `align_name`_device; `masked`: the aligning
     and timing entries take free_ends.  The library file is `lib_file` beside libswmi.so, or what the variable `env` names."""
 
     def __init__(self, prefix, align_name, lib_file, env, masked):
-        self.prefix, self.align_name, self.masked = prefix, align_name, masked
-        self.lib_path = os.environ.get(env, os.path.join(os.path.dirname(_HERE), "lib", lib_file))
-        self._lib = None
+        super().__init__(prefix, lib_file, env, self._declare)
+        self.align_name, self.masked = align_name, masked
 
-    def load(self):
-        if self._lib is not None:
-            return self._lib
-        _load_swmi()            # libswmi.so, which the library links
-        if not os.path.exists(self.lib_path):
-            raise SwmiError(ERR_NOT_INITIALIZED,
-                            "%s not built: run __graft_entry__.build() or make -C smith-waterman-simd_amd/csrc" % self.lib_path)
-        lib = ctypes.CDLL(self.lib_path)
+    def _declare(self, lib):
         vp, sz, ci = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
         call = [vp, sz, vp, sz, sz, vp, vp, ci, ci] + ([ctypes.c_uint] if self.masked else []) + [vp, vp, vp, vp]
-        getattr(lib, self.prefix + "_last_error").restype = ctypes.c_char_p
         getattr(lib, self.align_name).argtypes = call
         getattr(lib, self.align_name + "_device").argtypes = call + [vp]
         getattr(lib, self.prefix + "_slices_for").argtypes = [sz, sz, sz, ci, ctypes.POINTER(sz), sz]
         getattr(lib, self.prefix + "_slices_for").restype = sz
         getattr(lib, self.prefix + "_time_device").argtypes = call + [vp, ci, ctypes.POINTER(ctypes.c_float)]
-        self._lib = lib
-        return lib
-
-    def entry(self, name):
-        return getattr(self.load(), self.prefix + "_" + name)
-
-    def last_error(self):
-        return self.entry("last_error")().decode()
-
-    def version(self):
-        return int(self.entry("version")())
-
-    def check(self, rc):
-        if rc < 0:
-            raise SwmiError(rc, self.last_error())
-        return rc
 
     def _call(self, entry, shape, score_matrix, gap_open, gap_extend, free_ends, *tail):
         """entry(*shape, matrix address, gaps, the mask where the entries take it, *tail), checked."""

@@ -3,16 +3,15 @@
 call it.  The libraries' entries differ by their prefix and one argument: the width library's take `band` directly before
 score_matrix (slices_for: directly behind kind)."""
 import ctypes
-import os
 
 import numpy as np
 
-from . import ERR_NOT_INITIALIZED, SwmiError, _affine, _free_ends, _offsets_pair, _ptr, _ragged_pair, _slices, local_full_ragged_move_offsets
-from . import load as _load_swmi
+from . import _affine, _free_ends, _offsets_pair, _ptr, _ragged_pair, _slices, local_full_ragged_move_offsets
 from ._banded_binding import _diagonals
+from ._library import Library
+from ._wide_binding import results
 
 LOCAL, GLOBAL = 0, 1
-_HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def _dev(x):
@@ -20,29 +19,20 @@ def _dev(x):
     return x.data_ptr() if hasattr(x, "data_ptr") else x
 
 
-class RaggedBinding:
+class RaggedBinding(Library):
     """One library: its entries are `prefix`_<name>; `has_band`: they take a band, and the methods below pass the one they are
     given (the ragged library's wrappers give None).  The library file is `lib_file` beside libswmi.so, or what the variable
     `env` names."""
 
     def __init__(self, prefix, lib_file, env, has_band):
-        self.prefix, self.has_band = prefix, has_band
-        self.lib_path = os.environ.get(env, os.path.join(os.path.dirname(_HERE), "lib", lib_file))
-        self._lib = None
+        super().__init__(prefix, lib_file, env, self._declare)
+        self.has_band = has_band
 
-    def load(self):
-        if self._lib is not None:
-            return self._lib
-        _load_swmi()            # libswmi.so, which the library links
-        if not os.path.exists(self.lib_path):
-            raise SwmiError(ERR_NOT_INITIALIZED,
-                            "%s not built: run __graft_entry__.build() or make -C smith-waterman-simd_amd/csrc" % self.lib_path)
-        lib = ctypes.CDLL(self.lib_path)
+    def _declare(self, lib):
         vp, sz, ci, cu = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint
         band = [ci] if self.has_band else []
         head, tail = [vp, vp, vp, vp, sz, vp] + band + [vp, ci, ci], [vp, vp, vp, vp]
         entry = lambda name: getattr(lib, self.prefix + "_" + name)  # noqa: E731
-        entry("last_error").restype = ctypes.c_char_p
         entry("local").argtypes = head + tail
         entry("global").argtypes = head + [cu] + tail
         entry("local_device").argtypes = head + tail + [vp]
@@ -50,22 +40,6 @@ class RaggedBinding:
         entry("slices_for").argtypes = [ci] + band + [vp, vp, sz, ci, ctypes.POINTER(sz), sz]
         entry("slices_for").restype = sz
         entry("time_device").argtypes = [ci] + head + [cu] + tail + [vp, ci, ctypes.POINTER(ctypes.c_float)]
-        self._lib = lib
-        return lib
-
-    def entry(self, name):
-        return getattr(self.load(), self.prefix + "_" + name)
-
-    def last_error(self):
-        return self.entry("last_error")().decode()
-
-    def version(self):
-        return int(self.entry("version")())
-
-    def check(self, rc):
-        if rc < 0:
-            raise SwmiError(rc, self.last_error())
-        return rc
 
     def _band(self, band):
         return (int(band),) if self.has_band else ()
@@ -79,10 +53,7 @@ class RaggedBinding:
             cat1 = np.zeros(16, np.uint8)       # every seq1 is empty: a valid pointer the library never reads
         if len(cat2) == 0:
             cat2 = np.zeros(16, np.uint8)
-        scores = np.zeros(n, np.int32)
-        ends = np.zeros((n, 4), np.int32)
-        moves = np.zeros(int(mo[-1]), np.uint64) if traceback else None
-        steps = np.zeros(n, np.uint32) if traceback else None
+        scores, ends, moves, steps = results(n, mo)
         sm, go, ge = _affine(score_matrix, gap_open, gap_extend)
         head = (cat1.ctypes.data, off1.ctypes.data, cat2.ctypes.data, off2.ctypes.data, n, _ptr(d), *self._band(band), sm.ctypes.data, go, ge)
         tail = (scores.ctypes.data, ends.ctypes.data, _ptr(moves), _ptr(steps))

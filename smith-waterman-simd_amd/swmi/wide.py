@@ -8,62 +8,34 @@ swmi.global_ragged.global_full_affine_ragged's, with the score of cell (i, j) = 
 (seq2[j-1] & 31)].  0 <= len1 <= 16384, 0 <= len2 <= 4096: put the shorter sequence second.  The masks (swmi.ENDS_*,
 swmi.FREE_*), the layout of the moves (swmi.local_full_ragged_move_offsets) and the expander (swmi.local_full_expand_moves)
 are the package's.  No substitution table is shipped: pass your own."""
-import ctypes
-import os
-
 import numpy as np
 
-from . import (ENDS_GLOBAL, ERR_DOMAIN, ERR_NOT_INITIALIZED, SwmiError, _affine_gap, _free_ends, _offsets_pair, _ptr, _ragged_pair,
-               _slices, local_full_ragged_move_offsets)
-from . import load as _load_swmi
+from . import (ENDS_GLOBAL, ERR_DOMAIN, ERR_NOT_INITIALIZED, SwmiError, _affine_gap, _free_ends,  # noqa: F401  (reachable here as before)
+               local_full_ragged_move_offsets)
+from ._wide_binding import WideBinding
 
 LETTERS = 32
 MAX_LEN1 = 16384
 MAX_LEN2 = 4096
 LOCAL, GLOBAL = 0, 1
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("SWMI_WIDE_LIB", os.path.join(os.path.dirname(_HERE), "lib", "libswmi_wide.so"))
-
-_lib = None
+_binding = WideBinding("swmi_wide", "libswmi_wide.so", "SWMI_WIDE_LIB", local_full_ragged_move_offsets)
+LIB_PATH = _binding.lib_path
 
 
 def load():
     """dlopen libswmi_wide.so (built by smith-waterman-simd_amd/csrc/Makefile). Fails loudly when it is missing."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    _load_swmi()            # libswmi.so, which the library links
-    if not os.path.exists(LIB_PATH):
-        raise SwmiError(ERR_NOT_INITIALIZED, "%s not built: run __graft_entry__.build() or make -C smith-waterman-simd_amd/csrc" % LIB_PATH)
-    lib = ctypes.CDLL(LIB_PATH)
-    vp, sz, ci, cu = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint
-    lib.swmi_wide_last_error.restype = ctypes.c_char_p
-    lib.swmi_wide_local.argtypes = [vp, vp, vp, vp, sz, vp, ci, ci, vp, vp, vp, vp]
-    lib.swmi_wide_global.argtypes = [vp, vp, vp, vp, sz, vp, ci, ci, cu, vp, vp, vp, vp]
-    lib.swmi_wide_local_device.argtypes = [vp, vp, vp, vp, sz, vp, ci, ci, vp, vp, vp, vp, vp]
-    lib.swmi_wide_global_device.argtypes = [vp, vp, vp, vp, sz, vp, ci, ci, cu, vp, vp, vp, vp, vp]
-    lib.swmi_wide_slices_for.argtypes = [vp, vp, sz, ci, ctypes.POINTER(sz), sz]
-    lib.swmi_wide_slices_for.restype = sz
-    lib.swmi_wide_time_device.argtypes = [ci, vp, vp, vp, vp, sz, vp, ci, ci, cu, vp, vp, vp, vp, vp, ci, ctypes.POINTER(ctypes.c_float)]
-    _lib = lib
-    return lib
+    return _binding.load()
 
 
 def last_error():
     """swmi_wide_last_error: the text of the calling thread's last failed swmi.wide call."""
-    return load().swmi_wide_last_error().decode()
+    return _binding.last_error()
 
 
 def version():
     """swmi_wide_version."""
-    return int(load().swmi_wide_version())
-
-
-def _check(rc):
-    if rc < 0:
-        raise SwmiError(rc, last_error())
-    return rc
+    return _binding.version()
 
 
 def _sm(score_matrix):
@@ -100,23 +72,6 @@ def embed_dna(sm16):
     return sm.reshape(-1)
 
 
-def _host(entry, seq1s, seq2s, params, traceback):
-    cat1, off1, cat2, off2 = _ragged_pair(seq1s, seq2s)
-    n = len(off1) - 1
-    mo = local_full_ragged_move_offsets(off1, off2) if traceback else None
-    if len(cat1) == 0:
-        cat1 = np.zeros(16, np.uint8)       # every seq1 is empty: a valid pointer the library never reads
-    if len(cat2) == 0:
-        cat2 = np.zeros(16, np.uint8)
-    scores = np.zeros(n, np.int32)
-    ends = np.zeros((n, 4), np.int32)
-    moves = np.zeros(int(mo[-1]), np.uint64) if traceback else None
-    steps = np.zeros(n, np.uint32) if traceback else None
-    _check(entry(cat1.ctypes.data, off1.ctypes.data, cat2.ctypes.data, off2.ctypes.data, n, params[0].ctypes.data, *params[1:],
-                 scores.ctypes.data, ends.ctypes.data, _ptr(moves), _ptr(steps)))
-    return scores, ends, moves, mo, steps
-
-
 def local(seq1s, seq2s, score_matrix, gap_open, gap_extend, traceback=True):
     """swmi_wide_local: local alignment (Smith-Waterman / Gotoh, zero floor) over 32 letters.  seq1s and seq2s: each a list of
     1-D uint8 arrays, or a (concatenated, offsets[n + 1]) pair; score_matrix: 1024 int8, row = seq1's letter.
@@ -124,52 +79,43 @@ def local(seq1s, seq2s, score_matrix, gap_open, gap_extend, traceback=True):
     Returns (scores[n] int32, ends[n, 4] int32 = (end_i, end_j, start_i, start_j), moves uint64 (flat: alignment k's at
     move_offsets[k] ..), move_offsets[n + 1], steps[n] uint32); traceback=False: moves, move_offsets and steps are None and the
     start cell is (-1, -1)."""
-    return _host(load().swmi_wide_local, seq1s, seq2s, _params(score_matrix, gap_open, gap_extend), traceback)
+    return _binding.host("local", seq1s, seq2s, _params(score_matrix, gap_open, gap_extend), traceback)
 
 
 def global_(seq1s, seq2s, score_matrix, gap_open, gap_extend, free_ends=ENDS_GLOBAL, traceback=True):
     """swmi_wide_global: global / fit / overlap alignment (free_ends: a mask of swmi.FREE_*) over 32 letters; arguments and
     result as local(), with scores that may be negative."""
-    return _host(load().swmi_wide_global, seq1s, seq2s, _params(score_matrix, gap_open, gap_extend, _free_ends(free_ends)), traceback)
-
-
-def _device(entry, d_seq1s, seq1_offsets, d_seq2s, seq2_offsets, params, *tail):
-    off1, off2 = _offsets_pair(seq1_offsets, seq2_offsets)
-    return _check(entry(d_seq1s, off1.ctypes.data, d_seq2s, off2.ctypes.data, len(off1) - 1, params[0].ctypes.data, *params[1:], *tail))
+    return _binding.host("global", seq1s, seq2s, _params(score_matrix, gap_open, gap_extend, _free_ends(free_ends)), traceback)
 
 
 def local_device(d_seq1s, seq1_offsets, d_seq2s, seq2_offsets, score_matrix, gap_open, gap_extend, d_scores, d_ends, d_moves=None,
                  d_steps=None, stream=0):
     """swmi_wide_local_device: device pointers of the current device, both offset arrays host arrays of n + 1 (asynchronous on
     `stream`); d_moves = d_steps = None: ends-only."""
-    _device(load().swmi_wide_local_device, d_seq1s, seq1_offsets, d_seq2s, seq2_offsets, _params(score_matrix, gap_open, gap_extend),
-            d_scores, d_ends, d_moves, d_steps, stream)
+    _binding.device("local_device", d_seq1s, seq1_offsets, d_seq2s, seq2_offsets, _params(score_matrix, gap_open, gap_extend),
+                    d_scores, d_ends, d_moves, d_steps, stream)
 
 
 def global_device(d_seq1s, seq1_offsets, d_seq2s, seq2_offsets, score_matrix, gap_open, gap_extend, free_ends, d_scores, d_ends,
                   d_moves=None, d_steps=None, stream=0):
     """swmi_wide_global_device: as local_device with the mask."""
-    _device(load().swmi_wide_global_device, d_seq1s, seq1_offsets, d_seq2s, seq2_offsets,
-            _params(score_matrix, gap_open, gap_extend, _free_ends(free_ends)), d_scores, d_ends, d_moves, d_steps, stream)
+    _binding.device("global_device", d_seq1s, seq1_offsets, d_seq2s, seq2_offsets,
+                    _params(score_matrix, gap_open, gap_extend, _free_ends(free_ends)), d_scores, d_ends, d_moves, d_steps, stream)
 
 
 def slices_for(seq1_offsets, seq2_offsets, traceback=True):
     """The slices a call cuts its batch into (swmi_wide_slices_for; needs no device)."""
-    off1, off2 = _offsets_pair(seq1_offsets, seq2_offsets)
-    return _slices(load().swmi_wide_slices_for, off1.ctypes.data, off2.ctypes.data, len(off1) - 1, 1 if traceback else 0)
+    return _binding.slices_for(seq1_offsets, seq2_offsets, traceback)
 
 
 def time_device(kind, d_seq1s, seq1_offsets, d_seq2s, seq2_offsets, score_matrix, gap_open, gap_extend, free_ends, d_scores, d_ends,
                 d_moves=None, d_steps=None, stream=0, iters=10):
     """swmi_wide_time_device: average ms of `iters` device calls of kind LOCAL or GLOBAL, after one untimed call."""
-    ms = ctypes.c_float()
-    entry = load().swmi_wide_time_device
-    _device(lambda *args: entry(int(kind), *args), d_seq1s, seq1_offsets, d_seq2s, seq2_offsets,
-            _params(score_matrix, gap_open, gap_extend, _free_ends(free_ends)), d_scores, d_ends, d_moves, d_steps, stream, int(iters),
-            ctypes.byref(ms))
-    return float(ms.value)
+    return _binding.time_device(kind, d_seq1s, seq1_offsets, d_seq2s, seq2_offsets,
+                                _params(score_matrix, gap_open, gap_extend, _free_ends(free_ends)), d_scores, d_ends, d_moves, d_steps,
+                                stream, iters=iters)
 
 
 def release_workspaces():
     """swmi_wide_release_workspaces: free the current device's workspaces and host-entry buffers."""
-    _check(load().swmi_wide_release_workspaces())
+    _binding.release_workspaces()

@@ -9,13 +9,13 @@ profile[(j - 1) * 32 + (seq1[i-1] & 31)]; profile is an int8 array of len2 * 32 
 in host memory.  0 <= len1 <= 16384 per sequence, 0 <= len2 <= 4096.  The masks (swmi.ENDS_*, swmi.FREE_*) and the expander
 (swmi.local_full_expand_moves) are the package's."""
 import ctypes
-import os
 
 import numpy as np
 
-from . import (ENDS_GLOBAL, ERR_DOMAIN, ERR_NOT_INITIALIZED, SwmiError, _affine_gap, _free_ends, _ptr, _ragged_seq1s, _slices,
+from . import (ENDS_GLOBAL, ERR_DOMAIN, ERR_NOT_INITIALIZED, SwmiError, _affine_gap, _free_ends, _ptr, _ragged_seq1s, _slices,  # noqa: F401
                local_full_expand_moves)
-from . import load as _load_swmi
+from ._library import Library
+from ._wide_binding import results
 from .wide import _sm
 
 LETTERS = 32
@@ -23,23 +23,9 @@ MAX_LEN1 = 16384
 MAX_LEN2 = 4096
 LOCAL, GLOBAL = 0, 1
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("SWMI_WIDE_PROFILE_LIB", os.path.join(os.path.dirname(_HERE), "lib", "libswmi_wide_profile.so"))
 
-_lib = None
-
-
-def load():
-    """dlopen libswmi_wide_profile.so (built by smith-waterman-simd_amd/csrc/Makefile). Fails loudly when it is missing."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    _load_swmi()            # libswmi.so, which the library links
-    if not os.path.exists(LIB_PATH):
-        raise SwmiError(ERR_NOT_INITIALIZED, "%s not built: run __graft_entry__.build() or make -C smith-waterman-simd_amd/csrc" % LIB_PATH)
-    lib = ctypes.CDLL(LIB_PATH)
+def _declare(lib):
     vp, sz, ci, cu = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint
-    lib.swmi_wide_profile_last_error.restype = ctypes.c_char_p
     lib.swmi_wide_profile_from_sequence.argtypes = [vp, sz, vp, vp]
     lib.swmi_wide_profile_move_offsets.argtypes = [vp, sz, sz, vp]
     lib.swmi_wide_profile_local.argtypes = [vp, vp, sz, vp, sz, ci, ci, vp, vp, vp, vp]
@@ -49,24 +35,26 @@ def load():
     lib.swmi_wide_profile_slices_for.argtypes = [vp, sz, sz, ci, ctypes.POINTER(sz), sz]
     lib.swmi_wide_profile_slices_for.restype = sz
     lib.swmi_wide_profile_time_device.argtypes = [ci, vp, vp, sz, vp, sz, ci, ci, cu, vp, vp, vp, vp, vp, ci, ctypes.POINTER(ctypes.c_float)]
-    _lib = lib
-    return lib
+
+
+_library = Library("swmi_wide_profile", "libswmi_wide_profile.so", "SWMI_WIDE_PROFILE_LIB", _declare)
+LIB_PATH = _library.lib_path
+_check = _library.check
+
+
+def load():
+    """dlopen libswmi_wide_profile.so (built by smith-waterman-simd_amd/csrc/Makefile). Fails loudly when it is missing."""
+    return _library.load()
 
 
 def last_error():
     """swmi_wide_profile_last_error: the text of the calling thread's last failed swmi.wide_profile call."""
-    return load().swmi_wide_profile_last_error().decode()
+    return _library.last_error()
 
 
 def version():
     """swmi_wide_profile_version."""
-    return int(load().swmi_wide_profile_version())
-
-
-def _check(rc):
-    if rc < 0:
-        raise SwmiError(rc, last_error())
-    return rc
+    return _library.version()
 
 
 def _profile(profile):
@@ -115,10 +103,7 @@ def _host(entry, seqs, params, traceback):
     mo = move_offsets(off, params[1]) if traceback else None
     if len(cat) == 0:
         cat = np.zeros(16, np.uint8)        # every sequence is empty: a valid pointer the library never reads
-    scores = np.zeros(n, np.int32)
-    ends = np.zeros((n, 4), np.int32)
-    moves = np.zeros(int(mo[-1]), np.uint64) if traceback else None
-    steps = np.zeros(n, np.uint32) if traceback else None
+    scores, ends, moves, steps = results(n, mo)
     _check(entry(cat.ctypes.data, off.ctypes.data, n, _ptr(params[0]), *params[1:], scores.ctypes.data, ends.ctypes.data, _ptr(moves),
                  _ptr(steps)))
     return scores, ends, moves, mo, steps
