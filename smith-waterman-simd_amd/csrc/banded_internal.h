@@ -87,6 +87,17 @@ hipError_t launch_banded_width(int kind, int band, const uint8_t *d_seq1s, const
                                const int8_t *sm, int gap_open, int gap_extend, unsigned free_ends, int32_t *d_scores, int32_t *d_ends,
                                unsigned char *d_codes, unsigned long long *d_moves, uint32_t *d_steps, hipStream_t stream);
 
+// ---- libswmi_banded_long.so (banded_long_kernels.hip, include/swmi_banded_long.h) ----
+// The width library's slots, codes and key for lengths up to kBandLongMaxLen.  Beyond +-(65536 + 512) no band touches a table,
+// so a diagonal clamped at +-kLongDiagClamp gives what the caller's gives.
+constexpr int kBandLongMaxLen = 65536;
+constexpr int kLongDiagClamp = 131072;
+
+// As launch_banded_width.
+hipError_t launch_banded_long(int kind, int band, const uint8_t *d_seq1s, const uint8_t *d_seq2s, const RaggedSlot *d_slots, size_t n,
+                              const int8_t *sm, int gap_open, int gap_extend, unsigned free_ends, int32_t *d_scores, int32_t *d_ends,
+                              unsigned char *d_codes, unsigned long long *d_moves, uint32_t *d_steps, hipStream_t stream);
+
 }  // namespace banded
 }  // namespace swmi
 

@@ -1,8 +1,10 @@
 // banded_ragged_api.cpp -- the C entries of libswmi_banded_ragged.so (include/swmi_banded_ragged.h): the
 // banded local and the banded global / fit / overlap / extension aligner on a batch of mixed (len1, len2) with a diagonal per
 // alignment; and, compiled a second time with -DSWMI_BANDED_WIDTH_LIBRARY, of libswmi_banded_width.so
-// (include/swmi_banded_width.h, section 38): the same with ONE BAND WIDTH PER CALL, 128 .. 1024.  Everything in which the two
-// libraries differ stands in the one block below the error text (section 39); nothing after it tests the define.  Its
+// (include/swmi_banded_width.h, section 38): the same with ONE BAND WIDTH PER CALL, 128 .. 1024; and a third time with
+// -DSWMI_BANDED_LONG_LIBRARY, of libswmi_banded_long.so (include/swmi_banded_long.h, section 41): the width library's entries
+// for lengths up to 65536.  Everything in which the libraries differ stands in the one block below the error text (section
+// 39); nothing after it tests a define.  Its
 // structure is banded_api.cpp's: no Context of libswmi.so, no swmi_init -- every entry runs on the calling thread's current
 // HIP device, with this file's own workspaces per (device, stream), its own two streams and buffer sets per device for the
 // host entries, and its own thread-local error text.  Of libswmi.so, linked for the callers' move_offsets and expander, it
@@ -46,18 +48,69 @@ int fail(int code, const char *fmt, ...)
 }  // namespace swmi
 
 // ---- what the libraries differ in: the public header, the prefix of the exported names, the spelling of the two kinds in an
-// ---- error text, whether a call carries a band (and with it the BAND parameter of seven entries and the launcher), and a
-// ---- test-only switch of the ragged library's ----
-#ifdef SWMI_BANDED_WIDTH_LIBRARY
-#include "../../include/swmi_banded_width.h"
-#define BANDED_ENTRY(name) swmi_banded_width_##name
+// ---- error text, whether a call carries a band (and with it the BAND parameter of seven entries and the launcher), the
+// ---- longest sequence, the clamp of a diagonal and the macro of an alignment's move words, a test-only switch of the ragged
+// ---- library's, and the long library's tenth export ----
+#ifdef SWMI_BANDED_LONG_LIBRARY
+#include "../../include/swmi_banded_long.h"
+#define BANDED_ENTRY(name) swmi_banded_long_##name
 #define BANDED_BAND_PARAM int band,
 #define BANDED_BAND_ARG band
+#define BANDED_MOVE_WORDS(len1, len2) SWMI_LOCAL_LONG_MOVE_WORDS(len1, len2)
+#define BANDED_LAUNCH_WIDTH launch_banded_long
 
 namespace swmi {
 namespace banded {
 namespace {
 constexpr bool kHasBand = true;
+constexpr int kMaxLen = kBandLongMaxLen, kDiagClamp = kLongDiagClamp;
+constexpr const char *kLocalName = "SWMI_BANDED_LONG_LOCAL", *kGlobalName = "SWMI_BANDED_LONG_GLOBAL";
+static_assert(kMaxLen == SWMI_BANDED_LONG_MAX_LEN && sizeof(RaggedSlot) == SWMI_BANDED_LONG_SLOT_BYTES);
+static_assert(kRaggedLocal == SWMI_BANDED_LONG_LOCAL && kRaggedGlobal == SWMI_BANDED_LONG_GLOBAL);
+static_assert(width_is_legal(SWMI_BANDED_LONG_MIN) && width_is_legal(SWMI_BANDED_LONG_MAX) && kBandWidth == SWMI_BANDED_LONG_MIN);
+// every band beyond the clamp misses every table, and the launcher's arithmetic on a clamped diagonal stays in int32
+static_assert(kDiagClamp > kMaxLen + SWMI_BANDED_LONG_MAX / 2 && kDiagClamp + 2 * kMaxLen < (1 << 30));
+// one move layout with the 16384 libraries: the two macros of swmi.h are the same expression
+static_assert(SWMI_LOCAL_LONG_MOVE_WORDS(0, 0) == SWMI_LOCAL_FULL_MOVE_WORDS(0, 0) &&
+              SWMI_LOCAL_LONG_MOVE_WORDS(31, 2) == SWMI_LOCAL_FULL_MOVE_WORDS(31, 2) &&
+              SWMI_LOCAL_LONG_MOVE_WORDS(300, 1025) == SWMI_LOCAL_FULL_MOVE_WORDS(300, 1025) &&
+              SWMI_LOCAL_LONG_MOVE_WORDS(16384, 16384) == SWMI_LOCAL_FULL_MOVE_WORDS(16384, 16384) &&
+              SWMI_LOCAL_LONG_MOVE_WORDS(65536, 65536) == 4096);
+constexpr bool sort_enabled() { return true; }
+int check_offsets(const uint64_t *off1, const uint64_t *off2, size_t n);
+}  // namespace
+}  // namespace banded
+}  // namespace swmi
+
+// move_offsets[0 .. n]: the running sum of SWMI_LOCAL_LONG_MOVE_WORDS over offsets that the aligning entries accept
+extern "C" int swmi_banded_long_move_offsets(const uint64_t *seq1_offsets, const uint64_t *seq2_offsets, size_t n, uint64_t *move_offsets)
+{
+    using namespace swmi::banded;
+    if (!move_offsets) return fail(SWMI_ERR_INVALID_ARGUMENT, "move_offsets is NULL");
+    const int rc = check_offsets(seq1_offsets, seq2_offsets, n);
+    if (rc != SWMI_OK) return rc;
+    move_offsets[0] = 0;
+    for (size_t k = 0; k < n; ++k)
+        move_offsets[k + 1] = move_offsets[k] + BANDED_MOVE_WORDS(seq1_offsets[k + 1] - seq1_offsets[k], seq2_offsets[k + 1] - seq2_offsets[k]);
+    return SWMI_OK;
+}
+
+namespace swmi {
+namespace banded {
+namespace {
+#elif defined(SWMI_BANDED_WIDTH_LIBRARY)
+#include "../../include/swmi_banded_width.h"
+#define BANDED_ENTRY(name) swmi_banded_width_##name
+#define BANDED_BAND_PARAM int band,
+#define BANDED_BAND_ARG band
+#define BANDED_MOVE_WORDS(len1, len2) SWMI_LOCAL_FULL_MOVE_WORDS(len1, len2)
+#define BANDED_LAUNCH_WIDTH launch_banded_width
+
+namespace swmi {
+namespace banded {
+namespace {
+constexpr bool kHasBand = true;
+constexpr int kMaxLen = kBandMaxLen, kDiagClamp = kRaggedDiagClamp;
 constexpr const char *kLocalName = "SWMI_BANDED_WIDTH_LOCAL", *kGlobalName = "SWMI_BANDED_WIDTH_GLOBAL";
 static_assert(kBandMaxLen == SWMI_BANDED_WIDTH_MAX_LEN && sizeof(RaggedSlot) == SWMI_BANDED_WIDTH_SLOT_BYTES);
 static_assert(kRaggedLocal == SWMI_BANDED_WIDTH_LOCAL && kRaggedGlobal == SWMI_BANDED_WIDTH_GLOBAL);
@@ -68,11 +121,14 @@ constexpr bool sort_enabled() { return true; }
 #define BANDED_ENTRY(name) swmi_banded_ragged_##name
 #define BANDED_BAND_PARAM
 #define BANDED_BAND_ARG kBandWidth
+#define BANDED_MOVE_WORDS(len1, len2) SWMI_LOCAL_FULL_MOVE_WORDS(len1, len2)
+#define BANDED_LAUNCH_WIDTH launch_banded_width      // (named in a discarded statement only)
 
 namespace swmi {
 namespace banded {
 namespace {
 constexpr bool kHasBand = false;
+constexpr int kMaxLen = kBandMaxLen, kDiagClamp = kRaggedDiagClamp;
 constexpr const char *kLocalName = "SWMI_BANDED_RAGGED_LOCAL", *kGlobalName = "SWMI_BANDED_RAGGED_GLOBAL";
 static_assert(kBandMaxLen == SWMI_BANDED_RAGGED_MAX_LEN && sizeof(RaggedSlot) == SWMI_BANDED_RAGGED_SLOT_BYTES);
 static_assert(kRaggedLocal == SWMI_BANDED_RAGGED_LOCAL && kRaggedGlobal == SWMI_BANDED_RAGGED_GLOBAL);
@@ -86,7 +142,7 @@ bool sort_enabled()
     return on;
 }
 #endif
-// ---- below this line the two builds are one text ----
+// ---- below this line the three builds are one text ----
 
 // (no line number: the text is the same wherever the call stands, so that a line added here moves neither library's texts)
 #define BANDED_HIP_TRY(expr)                                                                                        \
@@ -115,7 +171,7 @@ struct Call {
 size_t alignment_bytes(int kind, int band, size_t len1, size_t len2, bool tb)
 {
     size_t b = len1 + len2 + sizeof(RaggedSlot) + 5 * sizeof(int32_t);
-    if (tb) b += width_code_bytes(kind, len1, band) + SWMI_LOCAL_FULL_MOVE_WORDS(len1, len2) * sizeof(uint64_t) + sizeof(uint32_t);
+    if (tb) b += width_code_bytes(kind, len1, band) + BANDED_MOVE_WORDS(len1, len2) * sizeof(uint64_t) + sizeof(uint32_t);
     return b;
 }
 
@@ -137,8 +193,8 @@ int check_offsets(const uint64_t *off1, const uint64_t *off2, size_t n)
     if (!off1 || !off2) return fail(SWMI_ERR_INVALID_ARGUMENT, "seq1_offsets or seq2_offsets is NULL");
     for (size_t k = 0; k < n; ++k) {
         if (off1[k + 1] < off1[k] || off2[k + 1] < off2[k]) return fail(SWMI_ERR_INVALID_ARGUMENT, "offsets decrease at alignment %zu", k);
-        if (off1[k + 1] - off1[k] > uint64_t(kBandMaxLen) || off2[k + 1] - off2[k] > uint64_t(kBandMaxLen))
-            return fail(SWMI_ERR_INVALID_ARGUMENT, "alignment %zu: a length above %d", k, kBandMaxLen);
+        if (off1[k + 1] - off1[k] > uint64_t(kMaxLen) || off2[k + 1] - off2[k] > uint64_t(kMaxLen))
+            return fail(SWMI_ERR_INVALID_ARGUMENT, "alignment %zu: a length above %d", k, kMaxLen);
     }
     return SWMI_OK;
 }
@@ -212,7 +268,7 @@ void make_plan(Plan &p, const Call &c, bool tb, RaggedSlot *slots)
     p.max_m = p.max_seq1 = p.max_seq2 = p.max_codes = p.max_moves = 0;
     p.move_offsets.assign(n + 1, 0);
     if (tb)
-        for (size_t k = 0; k < n; ++k) p.move_offsets[k + 1] = p.move_offsets[k] + SWMI_LOCAL_FULL_MOVE_WORDS(c.len1(k), c.len2(k));
+        for (size_t k = 0; k < n; ++k) p.move_offsets[k + 1] = p.move_offsets[k] + BANDED_MOVE_WORDS(c.len1(k), c.len2(k));
     p.first = cut(c.kind, c.band, c.off1, c.off2, n, tb);
     std::vector<uint32_t> &order = p.order;
     std::vector<int32_t> &rows = p.rows, &diag = p.diag;
@@ -224,7 +280,7 @@ void make_plan(Plan &p, const Call &c, bool tb, RaggedSlot *slots)
         bool sorted = true;
         for (size_t x = 0; x < m; ++x) {
             const int32_t d = c.diagonals ? c.diagonals[a + x] : 0;
-            diag[x] = std::max(-kRaggedDiagClamp, std::min(kRaggedDiagClamp, d));
+            diag[x] = std::max(-kDiagClamp, std::min(kDiagClamp, d));
             rows[x] = width_swept_rows(c.kind, int(c.len1(a + x)), int(c.len2(a + x)), diag[x], c.band);
             order[x] = uint32_t(x);
             if (x && rows[x] > rows[x - 1]) sorted = false;
@@ -336,7 +392,7 @@ hipError_t launch(const Call &c, const uint8_t *d_seq1s, const uint8_t *d_seq2s,
                   int32_t *d_ends, unsigned char *d_codes, unsigned long long *d_moves, uint32_t *d_steps, hipStream_t stream)
 {
     if constexpr (kHasBand)
-        return launch_banded_width(c.kind, c.band, d_seq1s, d_seq2s, d_slots, m, c.sm, c.gap_open, c.gap_extend, c.free_ends, d_scores, d_ends,
+        return BANDED_LAUNCH_WIDTH(c.kind, c.band, d_seq1s, d_seq2s, d_slots, m, c.sm, c.gap_open, c.gap_extend, c.free_ends, d_scores, d_ends,
                                    d_codes, d_moves, d_steps, stream);
     else
         return launch_banded_ragged(c.kind, d_seq1s, d_seq2s, d_slots, m, c.sm, c.gap_open, c.gap_extend, c.free_ends, d_scores, d_ends, d_codes,

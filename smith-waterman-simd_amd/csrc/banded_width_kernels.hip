@@ -35,6 +35,19 @@
 //
 // THE TRAPS of sections 33, 34 and 37 apply unchanged: the lane shifts run unconditionally with a select behind them, -2^29 is
 // a value, a slot is read once into SGPRs, no byte of an empty sequence is read, the two "never" checks of the walk stay.
+//
+// TWO OBJECTS.  banded_long_kernels.hip compiles this text a second time with SWMI_BANDED_LONG_KERNELS for
+// libswmi_banded_long.so (include/swmi_banded_long.h, section 41): lengths up to 65536.  Everything in which the two objects
+// differ stands in the one block below the constants; the body tests kLong and nothing else.  There the best cell's position is
+// i << 10 | delta (27 bits at i = 65536; within a row delta order is column order, so "first in row-major order" is kept),
+// made behind the loop from the lane's iteration and cell (within a lane arrival order is row-major order, and the strict >
+// keeps the first), where the 16384 kernels pack i << 15 | j, and the diagonal is clamped at +-131072, beyond +-(65536 + 512) of which no band
+// touches a table.  INT32 RANGE at len1 = len2 = 65536, band 1024 (kHalf = 512), |d0| <= 131072: i_lo, i_hi and len2 + kHalf -
+// d0 lie within +-197 122; r and ce within +-(65536 + 15 * 63 + 512 + 131072) < 2^18; the border closed forms reach 127 rows or
+// columns of that size, below 2^25; rel = i - i_lo + lane < 65536 + 64 and n_trips <= 16400; the position is below 2^27; an
+// alignment's codes are n_trips * 64 * K <= 8 396 800 dwords, indexed in size_t from a 64-bit code_off.  The values: with int8
+// scores, gaps in [0, 127] and 65536 rows every finite H, E, F lies in [-127 * 131072 - 254, 127 * 65536], above kInfeasible;
+// every value made from kNeg lies in [kNeg - 127 * 131072 - 254, kNeg + 127 * 65536], below kInfeasible and above INT32_MIN.
 #include "banded_sweep.h"
 
 namespace swmi {
@@ -52,9 +65,34 @@ typedef uint32_t Dwords4 __attribute__((ext_vector_type(4)));
 // wavefronts per SIMD the kernels are compiled for: section 37's six at K = 1, and what the lane's 2 K cells leave above it
 constexpr int width_waves_per_simd(int k) { return k == 1 ? 6 : k == 2 ? 4 : 3; }
 
+// ---- what the two objects differ in: the kernel's and the launcher's name, the clamp of a diagonal, how a position is packed ----
+#ifdef SWMI_BANDED_LONG_KERNELS
+#define BANDED_KERNEL banded_long_kernel
+#define BANDED_LAUNCHER launch_banded_long
+constexpr bool kLong = true;
+constexpr int kDiagClamp = kLongDiagClamp, kPosShift = 10;      // i << 10 | delta, delta < 1024
+// The wavefronts per SIMD a kernel is compiled for: no fewer than the 16384 kernel of the same instantiation reaches.  Left at
+// width_waves_per_simd, some local kernels come out a wavefront or two below theirs -- the ends-only ones (theirs: 8, 8 and 7, 7,
+// 5 and 6 at K = 1, 2, 4, 8) and the K = 1 traceback one with open >= extend (7); every other instantiation reaches its
+// sibling's or more on its own.
+constexpr int kernel_waves(int k, bool global, bool oge, bool tb)
+{
+    if (global) return width_waves_per_simd(k);
+    if (tb) return k == 1 && oge ? 7 : width_waves_per_simd(k);
+    return k == 1 ? 8 : k == 2 ? (oge ? 8 : 7) : k == 4 ? 7 : oge ? 6 : 5;
+}
+#else
+#define BANDED_KERNEL banded_width_kernel
+#define BANDED_LAUNCHER launch_banded_width
+constexpr bool kLong = false;
+constexpr int kDiagClamp = kRaggedDiagClamp, kPosShift = 15;    // i << 15 | j, j < 32768
+constexpr int kernel_waves(int k, bool, bool, bool) { return width_waves_per_simd(k); }
+#endif
+// ---- below this line the two objects are one text ----
+
 template <int K, bool kGlobal, bool kOge, bool kTb>
-__global__ void __launch_bounds__(64 * kWaves, width_waves_per_simd(K))
-banded_width_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ seq2s, const RaggedSlot *__restrict__ slots, uint32_t n,
+__global__ void __launch_bounds__(64 * kWaves, kernel_waves(K, kGlobal, kOge, kTb))
+BANDED_KERNEL(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict__ seq2s, const RaggedSlot *__restrict__ slots, uint32_t n,
                     Rows rows, int gap_open, int gap_extend, uint32_t free_ends, int32_t *__restrict__ scores, int32_t *__restrict__ ends,
                     uint32_t *__restrict__ codes, unsigned long long *__restrict__ moves, uint32_t *__restrict__ steps)
 {
@@ -68,7 +106,7 @@ banded_width_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict
     // the wavefront's slot, wave-uniform
     const RaggedSlot slot = slots[at];
     const int len1 = __builtin_amdgcn_readfirstlane(slot.len1), len2 = __builtin_amdgcn_readfirstlane(slot.len2);
-    const int d0 = __builtin_amdgcn_readfirstlane(clamp_i(slot.d0, -kRaggedDiagClamp, kRaggedDiagClamp));   // before any arithmetic
+    const int d0 = __builtin_amdgcn_readfirstlane(clamp_i(slot.d0, -kDiagClamp, kDiagClamp));   // before any arithmetic
     const uint32_t pair = (uint32_t)__builtin_amdgcn_readfirstlane((int)slot.index);
     const bool begin1 = free_ends & kBegin1, begin2 = free_ends & kBegin2, end1 = free_ends & kEnd1, end2 = free_ends & kEnd2;
     const bool anywhere = free_ends & kAnywhere;
@@ -152,7 +190,7 @@ banded_width_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict
         me[c] = out_m;
     }
     int best = kGlobal ? kNeg : 0;
-    uint32_t best_pos = 0;                  // i << 15 | j
+    uint32_t best_pos = 0;                  // i << 15 | j; kLong: (iteration, cell), behind the loop i << 10 | delta
 
 #pragma unroll 1
     for (int trip = 0; trip < n_trips; ++trip) {
@@ -188,7 +226,11 @@ banded_width_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict
             const bool cand_all = row_in && (anywhere || (end2 && last_row)), cand_end = row_in && (end1 || last_row);
             const int cand_lo = cand_all ? 0 : len2;
             const uint32_t cand_n = cand_all ? (uint32_t)len2 + 1u : cand_end ? 1u : 0u;
-            const uint32_t pos = ((uint32_t)i << 15) + (uint32_t)j0;
+            // (kLong: inside the loop a position is the lane's iteration and cell, which is wave-uniform and takes no VGPR; the
+            // lane turns its best one into i << 10 | delta behind the loop)
+            uint32_t pos = kLong ? (uint32_t)((trip * kBandTrip + k) * C) : ((uint32_t)i << kPosShift) + (uint32_t)j0;
+            // (... and is made per iteration: left alone the compiler keeps a trip's 8 K positions in SGPRs and spills three at K = 8)
+            if constexpr (kLong) asm volatile("" : "+s"(pos));
             // cell 0's left = lane m - 1's last cell of the last iteration.  The shift stands outside the select: under a
             // branch on the lane it would run with lane 0 switched off, and lane 1 would read 0 from it
             const int left_in = from_below(mf_last);
@@ -244,6 +286,9 @@ banded_width_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict
         ce += kBandTrip;
     }
 
+    // kLong: iteration t of lane m is row i_lo - m + t, and its cell c is band diagonal C m + c (a lane that took no cell makes
+    // a position of no meaning here: it loses below, or no lane took one and no position is used)
+    if constexpr (kLong) best_pos = ((uint32_t)(i_lo - lane + (int)(best_pos / C)) << kPosShift) + (uint32_t)(C * lane) + best_pos % C;
     // the first cell in row-major order among the lanes' bests; H is signed, so it is biased before the unsigned compare
     uint32_t key_hi = (uint32_t)best ^ 0x80000000u, key_lo = ~best_pos;
 #pragma unroll
@@ -261,7 +306,10 @@ banded_width_kernel(const uint8_t *__restrict__ seq1s, const uint8_t *__restrict
             return;
         }
     }
-    const int bi = (int)(best_pos >> 15), bj = (int)(best_pos & 32767u);
+    // (kLong, local kind: a best of 0 is no cell, reported as (0, 0) as the other packing's position 0 is)
+    const bool no_cell = kLong && !kGlobal && best == 0;
+    const int b_hi = (int)(best_pos >> kPosShift), b_lo = (int)(best_pos & ((1u << kPosShift) - 1u));
+    const int bi = no_cell ? 0 : b_hi, bj = !kLong ? b_lo : no_cell ? 0 : b_hi + d0 + b_lo - kHalf;
     if constexpr (!kTb) {
         if (lane == 0) {
             scores[pair] = best;
@@ -365,18 +413,18 @@ hipError_t launch_width(int kind, const uint8_t *d_seq1s, const uint8_t *d_seq2s
 {
     return launch_variant(gap_open >= gap_extend, d_moves != nullptr, n, [&](auto oge, auto tb, dim3 grid, dim3 block) {
         if (kind == kRaggedGlobal)
-            hipLaunchKernelGGL((banded_width_kernel<K, true, decltype(oge)::value, decltype(tb)::value>), grid, block, 0, stream, d_seq1s,
+            hipLaunchKernelGGL((BANDED_KERNEL<K, true, decltype(oge)::value, decltype(tb)::value>), grid, block, 0, stream, d_seq1s,
                                d_seq2s, d_slots, (uint32_t)n, rows, gap_open, gap_extend, (uint32_t)free_ends, d_scores, d_ends, codes, d_moves,
                                d_steps);
         else
-            hipLaunchKernelGGL((banded_width_kernel<K, false, decltype(oge)::value, decltype(tb)::value>), grid, block, 0, stream, d_seq1s,
+            hipLaunchKernelGGL((BANDED_KERNEL<K, false, decltype(oge)::value, decltype(tb)::value>), grid, block, 0, stream, d_seq1s,
                                d_seq2s, d_slots, (uint32_t)n, rows, gap_open, gap_extend, 0u, d_scores, d_ends, codes, d_moves, d_steps);
     });
 }
 
 }  // namespace
 
-hipError_t launch_banded_width(int kind, int band, const uint8_t *d_seq1s, const uint8_t *d_seq2s, const RaggedSlot *d_slots, size_t n,
+hipError_t BANDED_LAUNCHER(int kind, int band, const uint8_t *d_seq1s, const uint8_t *d_seq2s, const RaggedSlot *d_slots, size_t n,
                                const int8_t *sm, int gap_open, int gap_extend, unsigned free_ends, int32_t *d_scores, int32_t *d_ends,
                                unsigned char *d_codes, unsigned long long *d_moves, uint32_t *d_steps, hipStream_t stream)
 {

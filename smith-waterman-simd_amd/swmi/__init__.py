@@ -1214,3 +1214,4 @@ from . import banded           # noqa: E402  (banded local alignment with end ce
 from . import banded_global    # noqa: E402  (the band's global, fit, overlap and extension kinds, libswmi_banded_global.so, likewise)
 from . import banded_ragged    # noqa: E402  (both banded kinds on mixed-shape batches, libswmi_banded_ragged.so, likewise)
 from . import banded_width     # noqa: E402  (the same with a band of 128 .. 1024 diagonals per call, libswmi_banded_width.so, likewise)
+from . import banded_long      # noqa: E402  (the same for sequences up to 65536 long, libswmi_banded_long.so, likewise)

@@ -1,12 +1,13 @@
-"""The one ctypes binding body of the two mixed-shape banded libraries: swmi.banded_ragged
-(libswmi_banded_ragged.so) and swmi.banded_width (libswmi_banded_width.so) each hold a RaggedBinding and their public functions
-call it.  The libraries' entries differ by their prefix and one argument: the width library's take `band` directly before
-score_matrix (slices_for: directly behind kind)."""
+"""The one ctypes binding body of the three mixed-shape banded libraries (DESIGN.md sections 39 and 41): swmi.banded_ragged
+(libswmi_banded_ragged.so), swmi.banded_width (libswmi_banded_width.so) and swmi.banded_long (libswmi_banded_long.so) each hold a
+RaggedBinding and their public functions call it.  The libraries' entries differ by their prefix, by one argument -- the width
+and the long library's take `band` directly before score_matrix (slices_for: directly behind kind) -- and by the function that
+lays out the moves, which the module gives."""
 import ctypes
 
 import numpy as np
 
-from . import _affine, _free_ends, _offsets_pair, _ptr, _ragged_pair, _slices, local_full_ragged_move_offsets
+from . import _affine, _free_ends, _offsets_pair, _ptr, _ragged_pair, _slices
 from ._banded_binding import _diagonals
 from ._library import Library
 from ._wide_binding import results
@@ -22,11 +23,12 @@ def _dev(x):
 class RaggedBinding(Library):
     """One library: its entries are `prefix`_<name>; `has_band`: they take a band, and the methods below pass the one they are
     given (the ragged library's wrappers give None).  The library file is `lib_file` beside libswmi.so, or what the variable
-    `env` names."""
+    `env` names.  `move_offsets(seq1_offsets, seq2_offsets)` is the library's layout of the moves; `extra`: {entry: argtypes} of entries
+    that only this library has."""
 
-    def __init__(self, prefix, lib_file, env, has_band):
+    def __init__(self, prefix, lib_file, env, has_band, move_offsets, extra=None):
         super().__init__(prefix, lib_file, env, self._declare)
-        self.has_band = has_band
+        self.has_band, self.move_offsets, self.extra = has_band, move_offsets, extra or {}
 
     def _declare(self, lib):
         vp, sz, ci, cu = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint
@@ -40,6 +42,8 @@ class RaggedBinding(Library):
         entry("slices_for").argtypes = [ci] + band + [vp, vp, sz, ci, ctypes.POINTER(sz), sz]
         entry("slices_for").restype = sz
         entry("time_device").argtypes = [ci] + head + [cu] + tail + [vp, ci, ctypes.POINTER(ctypes.c_float)]
+        for name, argtypes in self.extra.items():
+            entry(name).argtypes = argtypes
 
     def _band(self, band):
         return (int(band),) if self.has_band else ()
@@ -48,7 +52,7 @@ class RaggedBinding(Library):
         cat1, off1, cat2, off2 = _ragged_pair(seq1s, seq2s)
         n = len(off1) - 1
         d = _diagonals(diagonals, n)
-        mo = local_full_ragged_move_offsets(off1, off2) if traceback else None
+        mo = self.move_offsets(off1, off2) if traceback else None
         if len(cat1) == 0:
             cat1 = np.zeros(16, np.uint8)       # every seq1 is empty: a valid pointer the library never reads
         if len(cat2) == 0:

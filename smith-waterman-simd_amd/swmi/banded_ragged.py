@@ -20,7 +20,8 @@ SLOT_BYTES = 48               # SWMI_BANDED_RAGGED_SLOT_BYTES
 END_ANYWHERE = 16             # SWMI_BANDED_END_ANYWHERE
 NO_ALIGNMENT = -2**31         # SWMI_BANDED_NO_ALIGNMENT: the score of an infeasible alignment (global kind)
 
-_binding = RaggedBinding("swmi_banded_ragged", "libswmi_banded_ragged.so", "SWMI_BANDED_RAGGED_LIB", has_band=False)
+_binding = RaggedBinding("swmi_banded_ragged", "libswmi_banded_ragged.so", "SWMI_BANDED_RAGGED_LIB", has_band=False,
+                         move_offsets=local_full_ragged_move_offsets)
 LIB_PATH = _binding.lib_path
 
 

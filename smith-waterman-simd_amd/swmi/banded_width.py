@@ -15,7 +15,8 @@ SLOT_BYTES = 48               # SWMI_BANDED_WIDTH_SLOT_BYTES
 END_ANYWHERE = 16             # SWMI_BANDED_END_ANYWHERE
 NO_ALIGNMENT = -2**31         # SWMI_BANDED_NO_ALIGNMENT: the score of an infeasible alignment (global kind)
 
-_binding = RaggedBinding("swmi_banded_width", "libswmi_banded_width.so", "SWMI_BANDED_WIDTH_LIB", has_band=True)
+_binding = RaggedBinding("swmi_banded_width", "libswmi_banded_width.so", "SWMI_BANDED_WIDTH_LIB", has_band=True,
+                         move_offsets=local_full_ragged_move_offsets)
 LIB_PATH = _binding.lib_path
 
 
